@@ -70,7 +70,15 @@ def parse():
     ap.add_argument("--timing-interval", type=int, default=3,
                     help="record the kernel timing events on one launch in N (msd_set_timing_interval); 3 is coprime "
                          "to the four batches of a pass, so the timed launch rotates over all of them")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step delivered (rank 0: its ordered message list, "
+                         "and the decoded fields with --fields) as DIR/<name>.npy, one float32/float64 array per record "
+                         "field, at most 64 MB in all (a fixed, seeded sample of the rows beyond that, their indices in "
+                         "DIR/sample_rows.npy)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def pin_to_gpu_local_cpus(torch, local_rank, world, gpu_of=None):
@@ -142,6 +150,74 @@ def diff_against_oracle(got, gstats, want, wstats):
         differs |= got[f][:m] != want[f][:m]
     differs |= (got["msg"][:m] != want["msg"][:m]).any(axis=1)
     return ndiff + int(differs.sum()) + sum(1 for k in COUNTERS if gstats[k] != wstats[k])
+
+
+class LastPass:
+    """The message records (and decoded fields) of one pass, collected straight into arrays of their own: each collect
+    of that pass gets the free tail of these arrays as the context's message buffer, so the timed step copies nothing."""
+
+    def __init__(self, dem, capacity, expected, fields):
+        capi = graft.load_package().capi
+        self.dem, self.n = dem, 0
+        self.msgs = np.empty(capacity, dtype=capi.MESSAGE_DTYPE)
+        self.fields = np.empty(capacity, dtype=capi.FIELDS_DTYPE) if fields else None
+        for a in (self.msgs, self.fields):  # fault in the pages a pass fills before the clock starts
+            if a is not None:
+                a[:expected].view(np.uint8)[:] = 0
+
+    def before_collect(self):
+        d = self.dem
+        self.saved = (d._buf, getattr(d, "_fbuf", None))
+        d._buf = self.msgs[self.n:]
+        if self.fields is not None:
+            d._fbuf = self.fields[self.n:]
+
+    def after_collect(self, count):
+        d, (d._buf, fbuf) = self.dem, self.saved
+        if self.fields is not None:
+            if fbuf is None:
+                del d._fbuf
+            else:
+                d._fbuf = fbuf
+        self.n += count
+
+
+DUMP_BYTES = 64_000_000 - (1 << 16)  # 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(path, keep):
+    """Write the records `keep` holds as path/<name>.npy, one array per record field with one row per message (the
+    message bytes as (rows, 14)); the decoded fields, when there are any, as path/fields_<name>.npy.  An integer or
+    float64 field wider than 16 bits is written as float64, everything else as float32: every value exactly.  Beyond
+    DUMP_BYTES in all, a fixed, seeded sample of the rows (the same one for the same message count), whose indices go
+    to path/sample_rows.npy."""
+    cols = {}
+    for prefix, rec in (("", keep.msgs[:keep.n]), ("fields_", None if keep.fields is None else keep.fields[:keep.n])):
+        if rec is None:
+            continue
+        for name in rec.dtype.names:
+            if name.startswith("pad"):
+                continue
+            a = np.ascontiguousarray(rec[name])
+            if a.dtype.kind == "S":  # the callsign's eight characters
+                a = a.view(np.uint8).reshape(len(rec), -1)
+            wide = a.dtype.itemsize > 2 and not (a.dtype.kind == "f" and a.dtype.itemsize == 4)
+            cols[prefix + name] = (a, np.float64 if wide else np.float32)
+    n = keep.n
+    row_bytes = sum(np.dtype(t).itemsize * (a[0].size if n else 1) for a, t in cols.values())
+    rows = None
+    if n * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(1090).choice(n, size=DUMP_BYTES // (row_bytes + 8), replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, (a, t) in cols.items():
+        a = a if rows is None else a[rows]
+        out = a.astype(t)
+        if a.dtype.kind in "iu" and not np.array_equal(out.astype(a.dtype), a):
+            raise SystemExit("bench: %s does not convert to %s exactly" % (name, np.dtype(t).name))
+        np.save(os.path.join(path, name + ".npy"), out)
+    if rows is not None:
+        np.save(os.path.join(path, "sample_rows.npy"), rows.astype(np.float64))
+    return {"dir": path, "messages": n, "rows_written": n if rows is None else len(rows), "arrays": len(cols) + (rows is not None)}
 
 
 def cpu_model():
@@ -274,8 +350,9 @@ def main():
     # pass while the last batches of the current one are still in flight (every pass still begins with an
     # empty ICAO filter, a zero clock and zero counters, and all K passes are complete before the clock stops).
     nctx = 1
+    message_capacity = 1 << 21
     dems = [pkg.Demodulator(fmt=fmt, preamble_threshold=args.threshold, nfix_crc=args.fix, mode_ac=int(args.mode_ac), device=device_index, dc_filter=args.dcfilter,
-                            max_batch_samples=batch, stream=stream.cuda_stream, message_capacity=1 << 21,
+                            max_batch_samples=batch, stream=stream.cuda_stream, message_capacity=message_capacity,
                             decode_fields=args.fields, **({"sc16q11_table_bits": args.sc16q11_table_bits} if args.sc16q11_table_bits else {}))
             for _ in range(nctx)]
     for d in dems:
@@ -284,14 +361,20 @@ def main():
 
     DEPTH = int(os.environ.get("MSD_BENCH_DEPTH", pkg.capi.PIPELINE_DEPTH))
 
-    def run_steps(k, collect_timing=None):
+    def run_steps(k, collect_timing=None, keep=None):
         """k passes over the capture on one context, back to back: msd_restart() lets the first batches of the
-        next pass queue up behind the last ones of the current pass.  Returns the messages of the last pass."""
+        next pass queue up behind the last ones of the current pass.  Returns the messages of the last pass, whose
+        records `keep` (a LastPass) receives when given."""
         d, inflight, counts = dems[0], [], {}
 
         def collect_one():
             cap_id, bidx = inflight.pop(0)
+            last = keep is not None and cap_id == k - 1
+            if last:
+                keep.before_collect()
             got = d.collect_fields(copy=False)[0] if args.fields else d.collect(copy=False)
+            if last:
+                keep.after_collect(len(got))
             counts[cap_id] = counts.get(cap_id, 0) + len(got)
             if collect_timing is not None:
                 t = d.timing()
@@ -334,13 +417,18 @@ def main():
         if len(settle_log) >= 3 and max(settle_log[-3:]) <= 1.01 * min(settle_log):
             break  # three half seconds in a row within 1 % of the best so far: nothing is settling any more
     settle_log = [round(x, 3) for x in settle_log]
-    run_steps(args.warmup)
+    nmsg_warmup = run_steps(args.warmup) if args.warmup else 0
+    keep = None
+    if args.dump_outputs and rank == 0:
+        keep = LastPass(dem, ((n + batch - 1) // batch) * message_capacity, nmsg_warmup, args.fields)
     timings = []
     barrier()
     t0 = time.perf_counter()
-    nmsg = run_steps(args.steps, timings)
+    nmsg = run_steps(args.steps, timings, keep)
     barrier()
     elapsed = time.perf_counter() - t0
+    if keep is not None:
+        dumped = dump_outputs(args.dump_outputs, keep)
     my_ms_per_step = elapsed * 1e3 / max(1, args.steps)
     per_rank = [{"rank": rank, "ms_per_step": my_ms_per_step, "seed": seed, "device": device_index, "messages": nmsg,
                  "cpus": (pinned or {}).get("cpu_list")}]
@@ -480,6 +568,8 @@ def main():
                           else "host threads (%s)" % os.environ["MSD_RESOLVE_THREADS"]),
     }
 
+    if keep is not None:
+        out["dumped_outputs"] = dumped
     if args.dcfilter:
         # how the DC block of the last batch was computed (msd_dc_filter_status): by the exact parallel-in-time kernels, in how many passes
         ex, passes, guessed, blocks = dems[0].dc_filter_status()

@@ -1,13 +1,16 @@
 """The mag_buf FIFO of the host boundary (fifo.h:34-120), against its contract and against the
-reference's own fifo.c (oracle/_ref/libref_fifo.so, compiled unmodified from /root/reference)."""
+reference's own fifo.c.  What that fifo.c hands its consumer on the two feeds below is recorded in
+tests/golden/reference_fifo.json (tests/golden/make_reference_records.py); wherever build() has compiled it
+into oracle/_ref/libref_fifo.so, the record is checked against the live library as well."""
 import ctypes as C
+import hashlib
+import json
 import os
 import shutil
 import threading
 import time
 
 import numpy as np
-import pytest
 
 
 class MagBuf(C.Structure):
@@ -44,9 +47,10 @@ def ours(pkg):
 
 
 def reference(oracle, tmp_path):
+    """The reference's fifo.c, or None where build() could not compile it (no reference tree beside the checkout)."""
     path = oracle.build_ref()
     if path is None:
-        pytest.skip("oracle/_ref/libref_fifo.so is not there and /root/reference is not available to build it")
+        return None
     # a private copy per test: the reference keeps its state in file statics and fifo_create does not
     # clear fifo_halted, so one loaded instance serves one create .. halt cycle
     mine = tmp_path / "libref_fifo_instance.so"
@@ -89,6 +93,47 @@ def make_blocks(rng, n, new):
     return [rng.integers(1, 65535, size=new).astype(np.uint16) for _ in range(n)]
 
 
+RECORDS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_fifo.json")
+OVERLAP = 326
+
+
+def record(got):
+    """[sampleTimestamp, validLength, sha256 of data[0:validLength]] of every buffer the consumer saw, in order."""
+    return [[int(ts), int(len(d)), hashlib.sha256(d.astype("<u2").tobytes()).hexdigest()] for ts, d in got]
+
+
+def recorded(name):
+    with open(RECORDS) as f:
+        return json.load(f)[name]
+
+
+def depth_one_feed(q):
+    """The feed under which the reference is lossless (SURVEY.md 8(b)): every buffer is consumed before the
+    next one is enqueued.  Ragged last block, a discontinuity in the middle, a block shorter than the overlap."""
+    new = 4096
+    blocks = make_blocks(np.random.default_rng(7), 7, new)
+    blocks[3] = blocks[3][:100]      # shorter than the overlap: the carried tail then spans two blocks
+    blocks[6] = blocks[6][:1234]     # ragged end of the capture
+    flags = [0, 0, DISCONTINUOUS, 0, 0, 0, 0]
+    assert q.create(12, OVERLAP + new, OVERLAP)
+    try:
+        return feed(q, blocks, OVERLAP, OVERLAP + new, depth_one=True, flags=flags)
+    finally:
+        q.halt()
+        q.destroy()
+
+
+def three_queued_feed(q):
+    """Three buffers enqueued before the consumer takes any of them."""
+    new = 1000
+    assert q.create(4, OVERLAP + new, OVERLAP)
+    try:
+        return feed(q, make_blocks(np.random.default_rng(2), 3, new), OVERLAP, OVERLAP + new, depth_one=False)
+    finally:
+        q.halt()
+        q.destroy()
+
+
 def test_queue_deeper_than_one_keeps_every_buffer_and_overlap_rule(pkg):
     q = ours(pkg)
     overlap, new = 326, 1000
@@ -107,40 +152,26 @@ def test_queue_deeper_than_one_keeps_every_buffer_and_overlap_rule(pkg):
 
 
 def test_same_stream_as_the_reference_fifo_on_a_depth_one_feed(pkg, oracle, tmp_path):
-    """The feed under which the reference is lossless (SURVEY.md 8(b)): every buffer is consumed before the
-    next one is enqueued.  Ragged last block, a discontinuity in the middle, a block shorter than the overlap."""
-    overlap, new = 326, 4096
-    rng = np.random.default_rng(7)
-    blocks = make_blocks(rng, 7, new)
-    blocks[3] = blocks[3][:100]      # shorter than the overlap: the carried tail then spans two blocks
-    blocks[6] = blocks[6][:1234]     # ragged end of the capture
-    flags = [0, 0, DISCONTINUOUS, 0, 0, 0, 0]
-    seen = {}
-    for name, q in (("ref", reference(oracle, tmp_path)), ("ours", ours(pkg))):
-        assert q.create(12, overlap + new, overlap)
-        try:
-            seen[name] = feed(q, blocks, overlap, overlap + new, depth_one=True, flags=flags)
-        finally:
-            q.halt()
-            q.destroy()
-    assert len(seen["ref"]) == len(seen["ours"]) == len(blocks)
-    for (ts_r, d_r), (ts_o, d_o) in zip(seen["ref"], seen["ours"]):
-        assert ts_r == ts_o and np.array_equal(d_r, d_o)
-    assert (seen["ours"][2][1][:overlap] == 0).all()  # behind the gap: silence (fifo.c:179-182)
+    """depth_one_feed through this build's FIFO: buffer for buffer (timestamp, length, every sample) what the
+    reference's fifo.c hands its consumer on the same feed."""
+    want = recorded("depth_one_feed")
+    live = reference(oracle, tmp_path)
+    if live is not None:
+        assert record(depth_one_feed(live)) == want  # the record still is what the reference does
+    got = depth_one_feed(ours(pkg))
+    assert len(got) == len(want) == 7
+    assert record(got) == want
+    assert (got[2][1][:OVERLAP] == 0).all()  # behind the gap: silence (fifo.c:179-182)
 
 
 def test_the_reference_fifo_loses_buffers_once_two_are_queued(oracle, tmp_path):
     """The defect this build does not reproduce, shown on the reference's own code: with three buffers
     queued only the first is ever dequeued (fifo.c:192-197 never advances the tail pointer)."""
-    q = reference(oracle, tmp_path)
-    overlap, new = 326, 1000
-    assert q.create(4, overlap + new, overlap)
-    try:
-        got = feed(q, make_blocks(np.random.default_rng(2), 3, new), overlap, overlap + new, depth_one=False)
-        assert len(got) < 3
-    finally:
-        q.halt()
-        q.destroy()
+    want = recorded("three_queued_feed")
+    live = reference(oracle, tmp_path)
+    if live is not None:
+        assert record(three_queued_feed(live)) == want
+    assert len(want) < 3
 
 
 def test_timeouts_and_nonblocking_calls(pkg):
