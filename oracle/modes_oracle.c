@@ -189,6 +189,18 @@ void orc_set_dc_filter(orc_ctx *ctx, int on)
     ctx->dc_a = 1.0 - ctx->dc_b;
 }
 
+void orc_set_dc_state(orc_ctx *ctx, float zi, float zq)
+{
+    ctx->dc_z1_i = zi;
+    ctx->dc_z1_q = zq;
+}
+
+void orc_get_dc_state(const orc_ctx *ctx, float out[2])
+{
+    out[0] = ctx->dc_z1_i;
+    out[1] = ctx->dc_z1_q;
+}
+
 /* convert.c:264-328, a build with -DSC16Q11_TABLE_BITS=bits (debian/rules:19 sets 8 on armhf): init_sc16q11_lookup ... */
 void orc_set_sc16q11_table_bits(orc_ctx *ctx, int bits)
 {

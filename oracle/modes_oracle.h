@@ -80,6 +80,10 @@ orc_ctx *orc_create(int format, int preamble_threshold, int nfix_crc, int mode_a
  * (stats.c); for --ifile input it never holds anything. */
 void orc_set_recently_dropped(orc_ctx *ctx, int on);
 void orc_set_dc_filter(orc_ctx *ctx, int on);
+/* the converter state of --dcfilter (struct converter_state's z1_I, z1_Q, convert.c:137-138), set and read as it is:
+ * a start state for tests of the filter from anywhere (subnormal, -0, beyond full scale) */
+void orc_set_dc_state(orc_ctx *ctx, float zi, float zq);
+void orc_get_dc_state(const orc_ctx *ctx, float out[2]);
 /* restate a reference built with -DSC16Q11_TABLE_BITS=bits (1..11; anything else: the float path, as without the define) */
 void orc_set_sc16q11_table_bits(orc_ctx *ctx, int bits);
 const uint16_t *orc_sc16q11_table(const orc_ctx *ctx);

@@ -125,6 +125,10 @@ def lib():
         L.orc_create.argtypes = [C.c_int] * 4
         L.orc_set_dc_filter.restype = None
         L.orc_set_dc_filter.argtypes = [C.c_void_p, C.c_int]
+        L.orc_set_dc_state.restype = None
+        L.orc_set_dc_state.argtypes = [C.c_void_p, C.c_float, C.c_float]
+        L.orc_get_dc_state.restype = None
+        L.orc_get_dc_state.argtypes = [C.c_void_p, C.POINTER(C.c_float * 2)]
         L.orc_set_recently_dropped.restype = None
         L.orc_set_recently_dropped.argtypes = [C.c_void_p, C.c_int]
         L.orc_set_sc16q11_table_bits.restype = None
@@ -209,6 +213,18 @@ class Oracle:
     @property
     def bytes_per_sample(self):
         return 2 if self.fmt == FMT_UC8 else 4
+
+    @property
+    def dc_state(self):
+        """The --dcfilter state (z1_I, z1_Q) as the two float32 bit patterns (uint32), so that -0 and NaN survive."""
+        out = (C.c_float * 2)()
+        lib().orc_get_dc_state(self._h, C.byref(out))
+        return tuple(int(v) for v in np.frombuffer(bytes(out), dtype="<u4"))
+
+    @dc_state.setter
+    def dc_state(self, bits):
+        zi, zq = (C.c_float.from_buffer_copy(np.uint32(b).tobytes()) for b in bits)  # the bits as they are, not via a double
+        lib().orc_set_dc_state(self._h, zi, zq)
 
     def set_recently_dropped(self, on):
         """Modes.stats_15min.samples_dropped != 0 (demod_2400.c:285-290) for the buffers demodulated from now on."""

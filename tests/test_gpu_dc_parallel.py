@@ -32,6 +32,8 @@ def content(kind, fmt, n, seed):
         v = rng.uniform(-1, 1, (n, 2))
     elif kind == "step":         # the offset jumps in the middle of the stream
         v = rng.standard_normal((n, 2)) * 0.05 + np.where(np.arange(n)[:, None] < n // 2, 0.01, -0.3)
+    elif kind == "zero":         # a muted front end (SC16 / SC16Q11: the samples are exactly zero)
+        v = np.zeros((n, 2))
     else:
         raise ValueError(kind)
     if fmt == "uc8":
@@ -152,6 +154,19 @@ def test_every_block_table_is_monotone(pkg, torch_cuda, fmt, kind):
     (every step z -> fl(t + fl(z b)) is), so the table values ascend with the candidates -- every block's table after two passes,
     read back from the workspace of msd_launch_dcfilter_parallel (white box: the layout of msd_dc_kernels.hip's dcp_launch).  Also
     the brackets tile the line (a lane's upper end is the next lane's candidate) and a flat mark sits on equal table values only."""
+    check_block_tables(pkg, torch_cuda, fmt, kind, np.array([0.003, -0.0007], dtype=np.float32))
+
+
+@pytest.mark.parametrize("start", ["+0", "floor"])
+def test_every_block_table_of_silence_is_monotone_and_finite(pkg, torch_cuda, start):
+    """The same on SC16 zero content from the state +0 (a fresh context) and from the subnormal floor 190650 * 2^-149 (where
+    seconds of silence leave it): there the block's map is the identity on the candidates near the state, 2^-149 apart, so a
+    secant divides by a subnormal -- it must still come out finite."""
+    bits = {"+0": 0, "floor": 190650}[start]
+    check_block_tables(pkg, torch_cuda, "sc16", "zero", np.array([bits, bits | 0x80000000], dtype=np.uint32).view(np.float32))
+
+
+def check_block_tables(pkg, torch_cuda, fmt, kind, start):
     import ctypes as C
     L = C.CDLL(pkg.capi.LIB_PATH)
     L.msd_dcp_work_bytes.restype = C.c_size_t
@@ -168,7 +183,7 @@ def test_every_block_table_is_monotone(pkg, torch_cuda, fmt, kind):
     work = torch_cuda.zeros(L.msd_dcp_work_bytes(n, blk), dtype=torch_cuda.uint8, device="cuda")
     mag = torch_cuda.zeros(n, dtype=torch_cuda.int16, device="cuda")
     sq = torch_cuda.zeros(n, dtype=torch_cuda.float32, device="cuda")
-    state = torch_cuda.tensor([0.003, -0.0007], dtype=torch_cuda.float32, device="cuda")
+    state = torch_cuda.from_numpy(start.copy()).cuda()
     b = np.float32(np.exp(-2 * np.pi / 2.4e6))
     a = np.float32(1.0 - float(b))
     assert len(iq) == n * bps
@@ -183,6 +198,9 @@ def test_every_block_table_is_monotone(pkg, torch_cuda, fmt, kind):
     assert (np.diff(y0, axis=1) >= 0).all()                       # ... and so do the block's values at them: F is monotone
     assert np.array_equal(x_up[:, :62], x0[:, 1:63])              # lane j's bracket ends where lane j + 1's begins
     flat = w[:, :63].view(np.uint32) == 0x80000000
-    assert flat.any() and (y0[:, :63][flat] == y0[:, 1:][flat]).all()
+    if kind != "zero":  # (silence from +0: the map is strictly increasing on the candidates, no bracket is flat)
+        assert flat.any()
+    assert (y0[:, :63][flat] == y0[:, 1:][flat]).all()
     assert (w[:, :63][~flat] >= 0).all()                          # a secant of a monotone map is not negative
-
+    assert np.isfinite(w[:, :63][~flat]).all(), np.argwhere(~np.isfinite(w[:, :63]) & ~flat)[:4]   # ... and a finite one
+    assert np.isfinite(T[:, 63, 3]).all() and np.isfinite(T[:, 63, 1]).all()   # lane 63: the slopes above c_63 and below c_0
