@@ -30,7 +30,12 @@ extern "C" {
 #define MSD_OVERLAP 326u          /* Modes.trailing_samples, readsb.c:198 */
 
 /* input_format_t, convert.h:29-31 (same numbering); MSD_FMT_MAG16 = already-converted u16
- * magnitudes, i.e. the contents of struct mag_buf.data (fifo.h:57-73). */
+ * magnitudes, i.e. the contents of struct mag_buf.data (fifo.h:57-73).  The reference has no
+ * converter for this input, so the convention is the library's: the conversion is the identity,
+ * and a buffer of n samples gets the integer converters' means (convert.c:104-110),
+ *   mean_level = sum(m) / 65536.0 / n,   mean_power = sum(m * m) / 65535.0 / 65535.0 / n,
+ * both sums exact 64-bit integers, each division in double (an empty last buffer: 0 / 0 as for
+ * UC8).  It does not take MSD_CFG_DC_FILTER (-EINVAL). */
 enum { MSD_FMT_UC8 = 0, MSD_FMT_SC16 = 1, MSD_FMT_SC16Q11 = 2, MSD_FMT_MAG16 = 3 };
 
 /* The receiver options that reach the hot path ("Config / flags"). */

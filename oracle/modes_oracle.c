@@ -12,6 +12,7 @@
  */
 #include "modes_oracle.h"
 
+#include <errno.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -181,12 +182,15 @@ void orc_set_recently_dropped(orc_ctx *ctx, int on)
     ctx->recently_dropped = on != 0;
 }
 
-void orc_set_dc_filter(orc_ctx *ctx, int on)
+int orc_set_dc_filter(orc_ctx *ctx, int on)
 {
+    if (on && ctx->format == ORC_FMT_MAG16)
+        return -EINVAL; /* magnitudes carry no IQ to filter (msd_create rejects the same configuration) */
     ctx->dc_filter = on;
     ctx->dc_z1_i = ctx->dc_z1_q = 0;
     ctx->dc_b = exp(-2.0 * M_PI * 1.0 / 2400000.0);
     ctx->dc_a = 1.0 - ctx->dc_b;
+    return 0;
 }
 
 void orc_set_dc_state(orc_ctx *ctx, float zi, float zq)
@@ -251,8 +255,30 @@ static void convert_q11_table(const orc_ctx *ctx, const uint8_t *iq, uint16_t *m
         *mp = sum_power / 65535.0 / 65535.0 / n;
 }
 
+/* ORC_FMT_MAG16: the input is the magnitude buffer itself (struct mag_buf.data, fifo.h:57-73).  No reference
+ * converter exists for it; the means are those of the integer converters, from the integer level / power sums
+ * (convert.c:104-110), which is what a MAG16 context of the product derives (modes_hip.h, MSD_FMT_MAG16). */
+static void convert_mag16(const uint8_t *in, uint16_t *mag, unsigned n, double *ml, double *mp)
+{
+    uint64_t sum_level = 0, sum_power = 0;
+    for (unsigned k = 0; k < n; ++k) {
+        uint16_t v = (uint16_t)((unsigned)in[2 * k] | ((unsigned)in[2 * k + 1] << 8));
+        mag[k] = v;
+        sum_level += v;
+        sum_power += (uint32_t)v * (uint32_t)v;
+    }
+    if (ml)
+        *ml = sum_level / 65536.0 / n;
+    if (mp)
+        *mp = sum_power / 65535.0 / 65535.0 / n;
+}
+
 void orc_convert(orc_ctx *ctx, const void *iq, uint16_t *mag, unsigned n, double *ml, double *mp)
 {
+    if (ctx->format == ORC_FMT_MAG16) {
+        convert_mag16(iq, mag, n, ml, mp);
+        return;
+    }
     if (ctx->dc_filter) {
         convert_dc(ctx, iq, mag, n, ml, mp);
         return;
@@ -2016,7 +2042,7 @@ void orc_demod_buffer(orc_ctx *ctx, const uint16_t *data, unsigned valid_length,
 uint64_t orc_replay(orc_ctx *ctx, const void *iq, uint64_t nsamples, orc_message *out, size_t cap,
                     size_t *nout, double *chunk_means, size_t means_cap)
 {
-    const unsigned bps = (ctx->format == ORC_FMT_UC8) ? 2u : 4u; /* sdr_ifile.c:130-141 */
+    const unsigned bps = (ctx->format == ORC_FMT_UC8 || ctx->format == ORC_FMT_MAG16) ? 2u : 4u; /* sdr_ifile.c:130-141 */
     const uint8_t *src = iq;
     uint64_t sample_counter = 0, nbuf = 0;
     int eof = 0;
@@ -2057,7 +2083,7 @@ uint64_t orc_replay(orc_ctx *ctx, const void *iq, uint64_t nsamples, orc_message
 
 orc_ctx *orc_create(int format, int preamble_threshold, int nfix_crc, int mode_ac)
 {
-    if (format < ORC_FMT_UC8 || format > ORC_FMT_SC16Q11 || nfix_crc < 0 || nfix_crc > 2)
+    if (format < ORC_FMT_UC8 || format > ORC_FMT_MAG16 || nfix_crc < 0 || nfix_crc > 2)
         return NULL; /* MODES_MAX_BITERRORS, crc.h:30 */
     orc_ctx *ctx = calloc(1, sizeof *ctx);
     if (!ctx)

@@ -32,8 +32,9 @@ extern "C" {
 #define ORC_CHUNK_SAMPLES 131072u
 #define ORC_OVERLAP 326u
 
-/* convert.h:29-31 */
-enum { ORC_FMT_UC8 = 0, ORC_FMT_SC16 = 1, ORC_FMT_SC16Q11 = 2 };
+/* convert.h:29-31; ORC_FMT_MAG16 = u16 magnitudes in (MSD_FMT_MAG16 of modes_hip.h): converted as the identity, means
+ * from the integer sums as for UC8 */
+enum { ORC_FMT_UC8 = 0, ORC_FMT_SC16 = 1, ORC_FMT_SC16Q11 = 2, ORC_FMT_MAG16 = 3 };
 
 /* The subset of struct modesMessage (readsb.h:340-547) that the demodulator itself determines. */
 typedef struct orc_message {
@@ -79,7 +80,8 @@ orc_ctx *orc_create(int format, int preamble_threshold, int nfix_crc, int mode_a
  * max(PREAMBLE_THRESHOLD_PIZERO = 75, threshold) (demod_2400.c:285-290).  The 15-minute window belongs to the host program
  * (stats.c); for --ifile input it never holds anything. */
 void orc_set_recently_dropped(orc_ctx *ctx, int on);
-void orc_set_dc_filter(orc_ctx *ctx, int on);
+/* returns 0, or -EINVAL for on != 0 in an ORC_FMT_MAG16 context (no IQ to filter) */
+int orc_set_dc_filter(orc_ctx *ctx, int on);
 /* the converter state of --dcfilter (struct converter_state's z1_I, z1_Q, convert.c:137-138), set and read as it is:
  * a start state for tests of the filter from anywhere (subnormal, -0, beyond full scale) */
 void orc_set_dc_state(orc_ctx *ctx, float zi, float zq);

@@ -12,7 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libmodes_oracle.so")
 
-FMT_UC8, FMT_SC16, FMT_SC16Q11 = 0, 1, 2
+FMT_UC8, FMT_SC16, FMT_SC16Q11, FMT_MAG16 = 0, 1, 2, 3  # MAG16: u16 magnitudes in, as a mag_buf holds them
 CHUNK = 131072
 OVERLAP = 326
 
@@ -123,7 +123,7 @@ def lib():
         L = C.CDLL(_LIB)
         L.orc_create.restype = C.c_void_p
         L.orc_create.argtypes = [C.c_int] * 4
-        L.orc_set_dc_filter.restype = None
+        L.orc_set_dc_filter.restype = C.c_int
         L.orc_set_dc_filter.argtypes = [C.c_void_p, C.c_int]
         L.orc_set_dc_state.restype = None
         L.orc_set_dc_state.argtypes = [C.c_void_p, C.c_float, C.c_float]
@@ -192,11 +192,12 @@ class Oracle:
     """One receiver context (its own ICAO filter, clock and counters)."""
 
     def __init__(self, fmt=FMT_UC8, preamble_threshold=58, nfix_crc=1, mode_ac=0, dc_filter=False, sc16q11_table_bits=0):
+        self._h = None
         self._h = lib().orc_create(fmt, preamble_threshold, nfix_crc, mode_ac)
         if not self._h:
             raise ValueError("orc_create rejected the configuration")
-        if dc_filter:
-            lib().orc_set_dc_filter(self._h, 1)
+        if dc_filter and lib().orc_set_dc_filter(self._h, 1) != 0:
+            raise ValueError("orc_set_dc_filter rejected the configuration")  # MAG16: no IQ to filter, as msd_create (-EINVAL)
         self.sc16q11_table_bits = sc16q11_table_bits
         if sc16q11_table_bits: # a reference built with -DSC16Q11_TABLE_BITS=n (convert.c:264-328)
             lib().orc_set_sc16q11_table_bits(self._h, sc16q11_table_bits)
@@ -212,7 +213,7 @@ class Oracle:
 
     @property
     def bytes_per_sample(self):
-        return 2 if self.fmt == FMT_UC8 else 4
+        return 2 if self.fmt in (FMT_UC8, FMT_MAG16) else 4
 
     @property
     def dc_state(self):
