@@ -469,6 +469,43 @@ typedef struct msd_magbuf_view {
 } msd_magbuf_view;
 int msd_demodulate_magbufs(msd_ctx *ctx, const msd_magbuf_view *bufs, unsigned n, msd_message_fn sink, void *user);
 
+/* ---- remote input: frames read from a Beast stream (--net-bi-port, --net-connector, a Beast device) or from AVR lines
+ * (--net-ri-port), decided as readsb decides them: the READ_MODE_BEAST scanner (net_io.c:2504-2569), decodeBinMessage
+ * (net_io.c:1486-1627) / decodeHexMessage (net_io.c:1656-1764) and decodeModesMessage (mode_s.c:424-555,717-726),
+ * against the context's own ICAO filter -- the one the demodulator entries read and write, so that addresses learnt
+ * from either source make the other's address/parity replies acceptable.  On the GPU.
+ *
+ * Within a call every frame sees the adds of the frames before it; after the call, icaoFilterExpire with mstime() =
+ * now_ms (readsb.c:331).  Accepted messages go to `sink` in stream order with sysTimestampMsg = now_ms, score and
+ * bestphase 0, signalLevel = (signal byte / 255)^2 and timestampMsg from the frame (AVR: as parsed).  Type '1' frames /
+ * Mode A/C records are delivered as Mode A/C records with msd_config.mode_ac and only counted without it; '4', '5' and
+ * 'H' frames are framed and counted (other_frames), not acted on.  Divergence: a 56-bit frame whose DF implies 112 bits
+ * is rejected as bad (the reference computes its CRC over seven uninitialised bytes, net_io.c:1490, mode_s.c:439-440);
+ * a 112-bit frame with a short DF is checked over its first 56 bits, as the reference does.
+ * -EBUSY while msd_launch_* batches are outstanding; msd_reset also clears these counters, the kept frame and the
+ * pending gap. ---- */
+typedef struct msd_remote_stats {
+    uint64_t remote_received_modes;        /* stats.h: the counters net_io.c:1500-1620 updates */
+    uint64_t remote_received_modeac;
+    uint64_t remote_rejected_bad;          /* bad frames, plus floor(gap / 15) per run of bytes in front of a 0x1A */
+    uint64_t remote_rejected_unknown_icao;
+    uint64_t remote_accepted[3];
+    uint64_t frames;        /* as msd_beast_reader: Mode S frames, and type '1' frames with mode_ac, handed to decoding */
+    uint64_t other_frames;  /* well-formed '4', '5', 'H' frames */
+    uint64_t garbage_bytes; /* bytes skipped in front of a 0x1A or behind an unknown type */
+    uint64_t tile_rewalks;  /* diagnostics: tiles the chain walk had to walk again from their true entry */
+} msd_remote_stats;
+/* A Beast byte stream, in order over calls: an incomplete frame at the end is kept and completed by the next call, and
+ * bytes in front of the next 0x1A are charged when it arrives.  bytes: device memory (on_device = 1; it must stay
+ * valid until the call returns) or host memory (copied in; page-locked memory from msd_host_alloc is faster). */
+int msd_accept_beast(msd_ctx *ctx, const void *bytes, size_t n, int on_device, uint64_t now_ms, msd_message_fn sink,
+                     void *user);
+/* Records framed on the host (msd_avr_parse_line, msd_beast_reader_feed): msg, msgbits (16 / 56 / 112), timestampMsg
+ * and signalLevel are read, the rest is decided again.  frames: device or host memory as above. */
+int msd_accept_frames(msd_ctx *ctx, const msd_message *frames, size_t n, int on_device, uint64_t now_ms,
+                      msd_message_fn sink, void *user);
+int msd_get_remote_stats(const msd_ctx *ctx, msd_remote_stats *st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,27 @@ class Timing(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RemoteStats(C.Structure):
+    _fields_ = [
+        ("remote_received_modes", C.c_uint64),
+        ("remote_received_modeac", C.c_uint64),
+        ("remote_rejected_bad", C.c_uint64),
+        ("remote_rejected_unknown_icao", C.c_uint64),
+        ("remote_accepted", C.c_uint64 * 3),
+        ("frames", C.c_uint64),
+        ("other_frames", C.c_uint64),
+        ("garbage_bytes", C.c_uint64),
+        ("tile_rewalks", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        out = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            out[name] = list(v) if hasattr(v, "__len__") else v
+        return out
+
+
 class _SinkState(C.Structure):
     _fields_ = [("out", C.c_void_p), ("cap", C.c_size_t), ("count", C.c_size_t)]
 
@@ -194,6 +215,7 @@ EXPORTS = [
     "msd_note_dropped", "msd_set_preamble_threshold", "msd_set_timing_interval", "msd_restart", "msd_decode_fields_device",
     "msd_arena_permille", "msd_host_register", "msd_host_unregister", "msd_demodulate_magbufs",
     "msd_convert_begin", "msd_convert_end", "msd_thread_attach", "msd_dc_filter_status",
+    "msd_accept_beast", "msd_accept_frames", "msd_get_remote_stats",
 ]
 
 _lib = None
@@ -269,6 +291,12 @@ def lib():
         L.msd_host_register.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.msd_host_unregister.restype = None
         L.msd_host_unregister.argtypes = [C.c_void_p, C.c_void_p]
+        for name in ("msd_accept_beast", "msd_accept_frames"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p,
+                                         C.c_void_p]
+        L.msd_get_remote_stats.restype = C.c_int
+        L.msd_get_remote_stats.argtypes = [C.c_void_p, C.POINTER(RemoteStats)]
         _lib = L
     return _lib
 
@@ -463,6 +491,31 @@ class Demodulator:
         return self._run(lambda fn, st: lib().msd_demodulate_magbuf(
             self._h, data.ctypes.data, valid_length, overlap, sample_timestamp, sys_timestamp, mean_level,
             mean_power, fn, st))
+
+
+    # --- remote input: Beast streams and framed records (net_io.c decodeBinMessage / decodeHexMessage) ------------
+    def accept_beast(self, data, now_ms):
+        """msd_accept_beast: the messages readsb accepts from these bytes of a Beast stream.  `data`: bytes, a numpy
+        array, or a torch tensor on the GPU (read in place through its device pointer)."""
+        if hasattr(data, "data_ptr") and getattr(data, "is_cuda", False):
+            if not data.is_contiguous():
+                raise ValueError("accept_beast needs a contiguous tensor")
+            ptr, n = data.data_ptr(), data.numel() * data.element_size()
+            return self._run(lambda fn, st: lib().msd_accept_beast(self._h, C.c_void_p(ptr), n, 1, now_ms, fn, st))
+        arr = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        return self._run(lambda fn, st: lib().msd_accept_beast(self._h, arr.ctypes.data, arr.size, 0, now_ms, fn, st))
+
+    def accept_frames(self, records, now_ms):
+        """msd_accept_frames: records framed on the host (msd_avr_parse_line, msd_beast_reader_feed)."""
+        records = np.ascontiguousarray(records, dtype=MESSAGE_DTYPE)
+        return self._run(lambda fn, st: lib().msd_accept_frames(self._h, records.ctypes.data, records.size, 0, now_ms,
+                                                                fn, st))
+
+    def remote_stats(self):
+        st = RemoteStats()
+        self._check(lib().msd_get_remote_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
 
 class MagbufView(C.Structure):

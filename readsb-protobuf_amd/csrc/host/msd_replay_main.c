@@ -8,6 +8,11 @@
  * follow modesQueueOutput's forwarding rule (net_io.c:1263-1290: two-bit repairs only with --net-verbatim,
  * which also sends the bytes as received).
  * Counters go to stderr with --stats.
+ *
+ * `--beast-in F` replays a Beast byte stream instead of a capture: the file is read in pieces of --beast-chunk bytes
+ * (default 65536) and each piece goes through msd_accept_beast (decodeBinMessage behind the READ_MODE_BEAST scanner,
+ * net_io.c:1486-1627,2504-2569) with mstime() = --now-ms (default 0); the same outputs, and --stats prints the remote
+ * counters (stats.h remote_*).
  */
 #define _GNU_SOURCE
 #include <inttypes.h>
@@ -68,6 +73,65 @@ static void write_beast(const msd_message *mm, void *user)
  * and the hooks that stand for Modes.exit / sdrMonitor() (sdr_ifile.c:178-184,236). */
 enum { OptIfileName = 615, OptIfileFormat, OptIfileThrottle, OptIfilePath };
 static volatile int g_exit; /* Modes.exit */
+
+/* --beast-in: a Beast stream through msd_accept_beast on a context of its own */
+static int run_beast_in(const char *path, size_t chunk, uint64_t now_ms, const msd_receiver_options *rx, int want_stats)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 1;
+    }
+    msd_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.device = rx->device;
+    cfg.format = MSD_FMT_UC8;
+    cfg.preamble_threshold = rx->preamble_threshold;
+    cfg.nfix_crc = rx->nfix_crc;
+    cfg.mode_ac = rx->mode_ac;
+    msd_ctx *ctx = NULL;
+    int rc = msd_create(&cfg, &ctx);
+    if (rc) {
+        fprintf(stderr, "msd_create: %s (%d)\n", msd_last_error(NULL), rc);
+        fclose(f);
+        return 1;
+    }
+    uint8_t *buf = malloc(chunk);
+    if (!buf) {
+        fprintf(stderr, "out of memory\n");
+        msd_destroy(ctx);
+        fclose(f);
+        return 1;
+    }
+    size_t got;
+    while ((got = fread(buf, 1, chunk, f)) > 0) {
+        rc = msd_accept_beast(ctx, buf, got, 0, now_ms, rx->sink, rx->sink_user);
+        if (rc) {
+            fprintf(stderr, "msd_accept_beast: %s (%d)\n", msd_last_error(ctx), rc);
+            break;
+        }
+    }
+    const int read_error = ferror(f);
+    fclose(f);
+    free(buf);
+    if (!rc && read_error) {
+        fprintf(stderr, "cannot read %s\n", path);
+        rc = -1;
+    }
+    if (!rc && want_stats) {
+        msd_remote_stats st;
+        if (msd_get_remote_stats(ctx, &st) == 0)
+            fprintf(stderr, "messages %" PRIu64 "\nremote_received_modes %" PRIu64 "\nremote_received_modeac %" PRIu64
+                            "\nremote_rejected_bad %" PRIu64 "\nremote_rejected_unknown_icao %" PRIu64
+                            "\nremote_accepted %" PRIu64 " %" PRIu64 " %" PRIu64 "\nframes %" PRIu64 "\nother_frames %" PRIu64
+                            "\ngarbage_bytes %" PRIu64 "\n",
+                    g_count, st.remote_received_modes, st.remote_received_modeac, st.remote_rejected_bad,
+                    st.remote_rejected_unknown_icao, st.remote_accepted[0], st.remote_accepted[1], st.remote_accepted[2],
+                    st.frames, st.other_frames, st.garbage_bytes);
+    }
+    msd_destroy(ctx);
+    return rc ? 1 : 0;
+}
 static int host_should_exit(void) { return g_exit; }
 static void host_at_eof(void) { g_exit = 1; }
 
@@ -81,6 +145,9 @@ int main(int argc, char **argv)
     rx.sink = print_raw;
     rx.sink_user = stdout;
     int want_stats = 0, want_timing = 0;
+    const char *beast_in = NULL;
+    size_t beast_chunk = 65536;
+    uint64_t now_ms = 0;
 
     const msd_ifile_hooks hooks = {host_should_exit, NULL, host_at_eof, NULL};
     msd_ifileSetOptionKeys(OptIfileName, OptIfileFormat, OptIfileThrottle, OptIfilePath);
@@ -104,6 +171,9 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--mlat")) g_mlat = 1;
         else if (!strcmp(a, "--net-verbatim")) g_net_verbatim = 1; /* readsb.c: Modes.net_verbatim */
         else if (!strcmp(a, "--stats")) want_stats = 1;
+        else if (!strcmp(a, "--beast-in") && next) { beast_in = next; ++i; }
+        else if (!strcmp(a, "--beast-chunk") && next && strtoull(next, NULL, 10) > 0) { beast_chunk = (size_t)strtoull(next, NULL, 10); ++i; }
+        else if (!strcmp(a, "--now-ms") && next) { now_ms = strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--timing")) want_timing = 1; /* one JSON line on stderr: what the run cost (msd_ifileGetTiming) */
         else if (!strcmp(a, "--no-output")) rx.sink = count_only;
         else if (!strcmp(a, "--net-raw")) rx.sink = print_net_raw;
@@ -120,10 +190,14 @@ int main(int argc, char **argv)
         } else {
             fprintf(stderr, "usage: msd_replay --ifile F [--iformat uc8|sc16|sc16q11] [--fix|--no-fix|--aggressive] [--dcfilter] "
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
-                            "[--device N] [--sc16q11-table-bits N]\n");
+                            "[--device N] [--sc16q11-table-bits N]\n"
+                            "       msd_replay --beast-in F [--beast-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
+                            "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n");
             return 2;
         }
     }
+    if (beast_in)
+        return run_beast_in(beast_in, beast_chunk, now_ms, &rx, want_stats);
     msd_ifileSetReceiver(&rx);
     if (!msd_ifileOpen()) {
         fprintf(stderr, "%s\n", msd_ifileLastError());

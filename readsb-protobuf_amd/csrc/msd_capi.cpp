@@ -32,6 +32,7 @@
 
 #include "modes_hip.h"
 #include "msd_internal.h"
+#include "msd_frames.h"
 #include "msd_kernels.h"
 
 extern "C" int msd_tables_selftest(const msd_tables *t);
@@ -364,6 +365,7 @@ struct msd_ctx {
     bool failed = false;    /* a batch could not be finished: only msd_reset() / msd_destroy() are accepted */
     bool scan_queued = false; /* enqueue(): its scan kernel is on the stream (a later failure cannot be undone) */
     bool no_helper = false; /* MSD_NO_HELPER: everything on the calling thread */
+    void *frames = nullptr; /* Beast / AVR input (msd_frames.cpp) */
     char err[256] = {0};
 };
 
@@ -2070,6 +2072,8 @@ void destroy(msd_ctx *c)
     (void)hipSetDevice(c->cfg.device);
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
+    msd_frames_free(c->frames);
+    c->frames = nullptr;
     if (c->copy_stream)
         (void)hipStreamSynchronize(c->copy_stream);
     if (c->aux_stream)
@@ -2522,7 +2526,34 @@ int msd_reset(msd_ctx *c)
         HIPCHK(c, hipMemset(c->d_dcstate, 0, 2 * sizeof(float)));
     c->helper.wait();
     msd_resolver_reset(&c->resolver);
+    msd_frames_reset(c->frames);
     memset(&c->timing, 0, sizeof c->timing);
+    return 0;
+}
+
+int msd_frames_get_view(msd_ctx *c, msd_frames_view *v)
+{
+    if (!c || !v)
+        return -EINVAL;
+    memset(v, 0, sizeof *v);
+    v->stream = c->stream;
+    v->device = c->cfg.device;
+    v->busy = c->outstanding != 0;
+    v->failed = c->failed;
+    v->tables.crc_byte = c->d_crc;
+    v->tables.synhash = c->cfg.nfix_crc >= 1 ? c->d_synhash : nullptr;
+    v->tables.synh_mul56 = c->tables->synhash_mul[0];
+    v->tables.synh_mul112 = c->tables->synhash_mul[1];
+    v->tables.fix2[0] = c->d_fix2[0];
+    v->tables.fix2[1] = c->d_fix2[1];
+    v->tables.fix2_lg[0] = c->fix2_lg[0];
+    v->tables.fix2_lg[1] = c->fix2_lg[1];
+    v->tables.nfix = c->cfg.nfix_crc;
+    v->tables.mode_ac = c->cfg.mode_ac;
+    v->filter = &c->resolver.filter;
+    v->state = &c->frames;
+    v->err = c->err;
+    v->errlen = sizeof c->err;
     return 0;
 }
 

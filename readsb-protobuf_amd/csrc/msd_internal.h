@@ -235,6 +235,12 @@ typedef struct msd_filter {
     uint32_t active_used; /* occupied slots of the active table: icaoFilterAdd gives up when it is full */
 } msd_filter;
 
+/* the same filter operations for the Beast / AVR input (msd_frames.cpp): icaoFilterAdd, icaoFilterTest,
+ * icaoFilterExpire(now) */
+int msd_filter_add(msd_filter *f, uint32_t addr);
+int msd_filter_test(const msd_filter *f, uint32_t addr);
+void msd_filter_expire(msd_filter *f, uint64_t now);
+
 /* ---- resolve stage (msd_resolve.c) ---- */
 struct msd_message;
 struct msd_stats;

@@ -184,6 +184,21 @@ static int filter_expire(msd_filter *f, uint64_t now)
     return dropped;
 }
 
+int msd_filter_add(msd_filter *f, uint32_t addr)
+{
+    return filter_add(f, addr);
+}
+
+int msd_filter_test(const msd_filter *f, uint32_t addr)
+{
+    return filter_test(f, addr);
+}
+
+void msd_filter_expire(msd_filter *f, uint64_t now)
+{
+    (void)filter_expire(f, now);
+}
+
 /* ---------------------------------------------------------------------------------------- */
 /* the addresses one buffer has added so far (consulted on top of the snapshot)             */
 /* ---------------------------------------------------------------------------------------- */
