@@ -506,6 +506,63 @@ int msd_accept_frames(msd_ctx *ctx, const msd_message *frames, size_t n, int on_
                       msd_message_fn sink, void *user);
 int msd_get_remote_stats(const msd_ctx *ctx, msd_remote_stats *st);
 
+/* ---- receiver groups: many independent live receivers of one configuration decoded in one launch.
+ * A group holds up to max_receivers receivers.  Each call takes exactly one full MSD_CHUNK_SAMPLES buffer from each
+ * of any subset of them, runs one scan over all of them and delivers each receiver's messages.  For every receiver the
+ * results are exactly those of a context of its own fed the same buffers (msd_launch_* without `last`, msd_note_dropped
+ * for drops).
+ *
+ * Per-receiver state -- nothing of one receiver is visible to another; an address learnt by receiver A never makes
+ * receiver B's address/parity replies acceptable:
+ *   - the 326-sample look-behind: the end of its previous buffer, or zeros for its first buffer and after dropped > 0
+ *     (fifo.c:176-184);
+ *   - its sample counter, which also counts dropped samples, and from it sampleTimestamp, sysTimestamp and the filter
+ *     clock, by the rule of the stream entries (sdr_ifile.c:187-190, sdr_rtlsdr.c:281-300);
+ *   - its ICAO filter, with the 60 s flip on its own clock (demod, then expire: readsb.c:331);
+ *   - every msd_stats counter, the order-sensitive signal and noise power sums summed in its own message order.
+ * Delivery: before the call returns, by entry in the order of the call's entries, then in stream order within an entry.
+ * -EINVAL, with the group's state untouched: a receiver id out of range, the same receiver twice in one call,
+ * n > max_receivers, nonzero entry flags.  msd_group_create refuses (-EINVAL) msd_config.mode_ac -- the Mode A/C pass
+ * reads the batch's magnitudes across buffer boundaries (MsdScanParams.mag_out), which in a group belong to other
+ * receivers --, MSD_CFG_DC_FILTER -- the DC block's state runs through the batch in order and would have to be kept
+ * per receiver --, MSD_FMT_MAG16 -- its buffers arrive as mag_bufs with their own overlap (msd_demodulate_magbufs),
+ * not as a stream -- and sc16q11_table_bits -- that converter writes the batch's magnitudes to an array of its own in
+ * front of the scan, and the tails and the power kernels would then have to read that array instead of the IQ.
+ * Resolve: by default on the GPU -- one pass of the resolve kernel with every buffer against its own receiver's filter
+ * snapshot, kept on the device (MSD_SNAP_WORDS words per receiver) and updated there after the pass by the buffer's
+ * adds and its receiver's flip; only those adds (a few bytes each) cross PCIe, besides the records.  A buffer the
+ * kernel hands back, a receiver whose active table is nearly full, and every buffer of a call whose candidate arenas
+ * overflowed (it is rescanned in pieces) are resolved on host threads against the receiver's host copy of the filter,
+ * and that receiver's snapshot is uploaded afterwards.  MSD_CFG_HOST_RESOLVE resolves every buffer on host threads
+ * (msd_config.resolve_threads of them; 0 = an eighth of the CPUs, at most 16).
+ * Device memory: the group wraps a context of max_batch_samples = max_receivers x MSD_CHUNK_SAMPLES in the dense
+ * layout, about 60 bytes per sample (dense candidate lists and their region arenas, as estimated for max_batch_samples
+ * above): about 7.9 MB per receiver, plus its filter snapshot (65.6 KB), the resolve stage's per-buffer records
+ * (about 0.1 MB) and its tail slot (656 bytes UC8, 1312 bytes SC16 / SC16Q11); about 8.2 GB for 1024 receivers. ---- */
+typedef struct msd_group msd_group;
+typedef struct msd_group_entry {
+    uint32_t receiver; /* 0 .. max_receivers-1 */
+    uint32_t flags;    /* reserved, 0 */
+    uint64_t dropped;  /* samples this receiver lost in front of this buffer (msd_note_dropped semantics) */
+} msd_group_entry;
+typedef void (*msd_group_message_fn)(uint32_t receiver, const msd_message *mm, void *user);
+
+int msd_group_create(const msd_config *cfg, uint32_t max_receivers, msd_group **out);
+void msd_group_destroy(msd_group *g);
+const char *msd_group_last_error(const msd_group *g);
+/* entry i's IQ is iq[i * MSD_CHUNK_SAMPLES * bytes_per_sample ...], exactly MSD_CHUNK_SAMPLES samples; d_iq 16-byte
+ * aligned.  A call that fails after its scan was queued (-EIO) leaves the group accepting msd_group_destroy only. */
+int msd_group_submit_device(msd_group *g, const void *d_iq, const msd_group_entry *e, uint32_t n,
+                            msd_group_message_fn sink, void *user);
+int msd_group_submit_host(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n,
+                          msd_group_message_fn sink, void *user);
+int msd_group_reset_receiver(msd_group *g, uint32_t receiver); /* filter, clock, counters, tail */
+int msd_group_get_stats(const msd_group *g, uint32_t receiver, msd_stats *st);
+int msd_group_set_preamble_threshold(msd_group *g, int threshold); /* group-wide */
+/* of the most recent call: hits, tries, resolve_passes (1: the GPU resolve ran; 0: all on the host); since creation:
+ * reruns (calls rescanned in pieces) and resolve_fallback (buffers resolved on the host); the kernel times are not kept */
+int msd_group_get_timing(const msd_group *g, msd_timing *t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,8 @@ EXPORTS = [
     "msd_arena_permille", "msd_host_register", "msd_host_unregister", "msd_demodulate_magbufs",
     "msd_convert_begin", "msd_convert_end", "msd_thread_attach", "msd_dc_filter_status",
     "msd_accept_beast", "msd_accept_frames", "msd_get_remote_stats",
+    "msd_group_create", "msd_group_destroy", "msd_group_last_error", "msd_group_submit_device", "msd_group_submit_host",
+    "msd_group_reset_receiver", "msd_group_get_stats", "msd_group_set_preamble_threshold", "msd_group_get_timing",
 ]
 
 _lib = None
@@ -582,3 +584,130 @@ def decode_fields(message, carry=None):
     cp = np.ascontiguousarray(carry).reshape(1).ctypes.data if carry is not None else None
     lib().msd_decode_fields(rec.ctypes.data, cp, out.ctypes.data)
     return out[0]
+
+
+class GroupEntry(C.Structure):
+    _fields_ = [("receiver", C.c_uint32), ("flags", C.c_uint32), ("dropped", C.c_uint64)]
+
+
+GROUP_MESSAGE_DTYPE = np.dtype([("receiver", "<u4"), ("m", MESSAGE_DTYPE)])
+_GROUP_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_void_p)
+
+
+def _group_lib():
+    L = lib()
+    if not getattr(L, "_group_bound", False):
+        L.msd_group_create.restype = C.c_int
+        L.msd_group_create.argtypes = [C.POINTER(Config), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.msd_group_destroy.restype = None
+        L.msd_group_destroy.argtypes = [C.c_void_p]
+        L.msd_group_last_error.restype = C.c_char_p
+        L.msd_group_last_error.argtypes = [C.c_void_p]
+        for f in (L.msd_group_submit_device, L.msd_group_submit_host):
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.msd_group_reset_receiver.restype = C.c_int
+        L.msd_group_reset_receiver.argtypes = [C.c_void_p, C.c_uint32]
+        L.msd_group_get_stats.restype = C.c_int
+        L.msd_group_get_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Stats)]
+        L.msd_group_set_preamble_threshold.restype = C.c_int
+        L.msd_group_set_preamble_threshold.argtypes = [C.c_void_p, C.c_int]
+        L.msd_group_get_timing.restype = C.c_int
+        L.msd_group_get_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
+        L._group_bound = True
+    return L
+
+
+class ReceiverGroup:
+    """msd_group: up to max_receivers independent live receivers of one configuration, one buffer of each of any
+    subset of them decoded per call.  Every receiver has its own look-behind, clock, ICAO filter and counters."""
+
+    def __init__(self, max_receivers, fmt=FMT_UC8, preamble_threshold=58, nfix_crc=1, device=0, flags=0, mode_ac=0,
+                 **fields):
+        self._h = C.c_void_p()
+        self.fmt = fmt
+        self.max_receivers = max_receivers
+        cfg = Config(device=device, format=fmt, preamble_threshold=preamble_threshold, nfix_crc=nfix_crc,
+                     mode_ac=mode_ac, flags=flags, **fields)
+        rc = _group_lib().msd_group_create(C.byref(cfg), max_receivers, C.byref(self._h))
+        if rc != 0:
+            self._h = C.c_void_p()
+            raise MsdError(f"msd_group_create failed: {os.strerror(-rc)} ({rc})")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            _group_lib().msd_group_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def bytes_per_sample(self):
+        return 2 if self.fmt == FMT_UC8 else 4
+
+    def _check(self, rc):
+        if rc != 0:
+            raise MsdError(f"{_group_lib().msd_group_last_error(self._h).decode()} ({os.strerror(-rc)}, {rc})")
+
+    def submit(self, iq, receivers, dropped=None, as_dict=False, deliver=True):
+        """One buffer of CHUNK samples for each of `receivers`, entry i at iq[i * CHUNK * bytes_per_sample ...].
+        iq: bytes, a numpy array, or a torch tensor on the GPU (read in place, after torch's current stream is done).  dropped[i]: samples receiver i lost
+        in front of its buffer.  Returns a GROUP_MESSAGE_DTYPE array (receiver, m) in delivery order, or with
+        as_dict=True {receiver: MESSAGE_DTYPE array} for the receivers of the call.  deliver=False passes no sink (the
+        counters still advance; for timing the library without the per-message Python callback)."""
+        receivers = [int(r) for r in receivers]
+        n = len(receivers)
+        entries = (GroupEntry * max(n, 1))()
+        for i, r in enumerate(receivers):
+            entries[i] = GroupEntry(r, 0, int(dropped[i]) if dropped is not None else 0)
+        rx, raw = [], []
+
+        def sink(receiver, mm, _user):
+            rx.append(receiver)
+            raw.append(C.string_at(mm, MESSAGE_DTYPE.itemsize))
+
+        fn = _GROUP_SINK(sink)  # (kept alive until the call returns)
+        cb = C.cast(fn, C.c_void_p) if deliver else None
+        need = n * CHUNK * self.bytes_per_sample
+        L = _group_lib()
+        if hasattr(iq, "data_ptr") and getattr(iq, "is_cuda", False):
+            if not iq.is_contiguous():
+                raise ValueError("submit needs a contiguous tensor")
+            if iq.numel() * iq.element_size() < need:
+                raise ValueError(f"{n} buffers need {need} bytes")
+            import torch
+            torch.cuda.current_stream(iq.device).synchronize()  # the group reads it on its own stream
+            self._check(L.msd_group_submit_device(self._h, C.c_void_p(iq.data_ptr()), entries, n, cb, None))
+        else:
+            arr = np.frombuffer(iq, dtype=np.uint8) if isinstance(iq, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(iq).view(np.uint8).reshape(-1)
+            if arr.size < need:
+                raise ValueError(f"{n} buffers need {need} bytes")
+            self._check(L.msd_group_submit_host(self._h, arr.ctypes.data, entries, n, cb, None))
+        res = np.zeros(len(rx), dtype=GROUP_MESSAGE_DTYPE)
+        if rx:
+            res["receiver"] = rx
+            res["m"] = np.frombuffer(b"".join(raw), dtype=MESSAGE_DTYPE)
+        if not as_dict:
+            return res
+        return {r: _raw_copy(np.ascontiguousarray(res["m"][res["receiver"] == r])) for r in receivers}
+
+    def stats(self, receiver):
+        st = Stats()
+        self._check(_group_lib().msd_group_get_stats(self._h, receiver, C.byref(st)))
+        return st.as_dict()
+
+    def timing(self):
+        t = Timing()
+        self._check(_group_lib().msd_group_get_timing(self._h, C.byref(t)))
+        return t.as_dict()
+
+    def reset_receiver(self, receiver):
+        self._check(_group_lib().msd_group_reset_receiver(self._h, receiver))
+
+    def set_preamble_threshold(self, threshold):
+        self._check(_group_lib().msd_group_set_preamble_threshold(self._h, threshold))

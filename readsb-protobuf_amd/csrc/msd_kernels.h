@@ -84,7 +84,14 @@ typedef struct MsdScanParams {
     int debug_flags;      /* MSD_DEBUG_FLAGS env, perf experiments only: 1 = stop after the scan,
                              2 = stop after the conversion (results are then incomplete) */
     MsdEmitJob emit;      /* the previous batch's records, or nbuffers == 0 */
+    /* ---- receiver group (msd_group.cpp): the buffers of a batch belong to different receivers ----
+     * group_lb != NULL: the look-behind of buffer b is not the end of buffer b - 1 but tail slot group_lb[b] of
+     * group_tails (MSD_HALO_FRONT raw samples each), or zeros when group_lb[b] == MSD_GROUP_NO_TAIL.  Selects the
+     * group instantiation of the scan kernel; have_prev must be 0. */
+    const uint8_t *group_tails;
+    const uint32_t *group_lb;
 } MsdScanParams;
+#define MSD_GROUP_NO_TAIL 0xFFFFFFFFu
 
 typedef struct MsdResolveParams {
     const msd_hit *hits; /* the batch's ordered candidate lists, as the gather kernel left them */
@@ -176,6 +183,23 @@ int msd_launch_gather(const msd_region_counts *counts, const msd_wg_totals *wg_t
                       uint32_t tail_bytes, uint32_t region_len, uint32_t *buf_first, uint32_t try_abs, hipStream_t stream);
 int msd_launch_power(const MsdScanParams *p, int format, const uint64_t *d_req, uint32_t nreq,
                      unsigned long long *d_out, hipStream_t stream);
+/* receiver groups: the same signal power with every buffer's look-behind from its tail slot (p->group_lb);
+ * req = batch-relative scan position << 16 | samples */
+int msd_launch_group_power(const MsdScanParams *p, int format, const uint64_t *d_req, uint32_t nreq,
+                           unsigned long long *d_out, hipStream_t stream);
+/* receiver groups: tails[dst_slot[i]] = the last MSD_HALO_FRONT raw samples of buffer i of iq (n buffers of
+ * MSD_CHUNK_SAMPLES), bps bytes per sample */
+/* receiver groups, GPU resolve: out[b][m] = signal power of accepted message m < nmsgs[b] of buffer b = todo[w], from
+ * acc[b][m] (MSD_RB_MSG_CAP per buffer), the look-behind from the tail slots as above */
+int msd_launch_group_power_buffers(const MsdScanParams *p, int format, const msd_acc *acc, const uint32_t *nmsgs,
+                                   const uint32_t *todo, uint32_t ntodo, unsigned long long *out, hipStream_t stream);
+/* receiver groups, GPU resolve: entry i applies its adds add_list[add_first[i] .. add_first[i + 1]) to snapshot
+ * snaps[slot[i]] (MSD_SNAP_WORDS each) with icao_filter.c's probing (icaoFilterAdd, the active table), then, if flip[i],
+ * icaoFilterExpire's flip: the other table emptied and made the active one.  The arrays may be pinned host memory. */
+int msd_launch_group_filter_apply(uint32_t *snaps, uint32_t n, const uint32_t *slot, const uint32_t *add_first,
+                                  const uint32_t *add_list, const uint32_t *flip, hipStream_t stream);
+int msd_launch_group_tails(const uint8_t *iq, uint32_t n, const uint32_t *dst_slot, uint8_t *tails, uint32_t bps,
+                           hipStream_t stream);
 /* Mode A/C candidate stage: noise levels (unless noise_ready), candidate kernel, ordered gather.
  * d_totals[0] receives the number of candidates, d_totals[2] an overflow flag.  phase 0: both kernels; 1: the candidate
  * kernel; 2: the gather of what phase 1 left in d_regions / d_counts (10 us of latency that the pipeline moves to the head of

@@ -213,6 +213,30 @@ __device__ __forceinline__ uint32_t fetch_group(const MsdScanParams &P, int64_t 
     return valid;
 }
 
+/* Receiver groups (MsdScanParams.group_lb): samples [pos - FRONT + 8 lane, + 8) as the look-behind of the tile at
+ * batch-relative scan position pos.  A tile that starts a buffer reads the buffer's own look-behind -- its receiver's
+ * tail slot, or zeros -- instead of the end of the batch's previous buffer, which belongs to another receiver; any
+ * other tile reads the batch.  One selected address per load, as in fetch_group. */
+template <int FMT>
+__device__ __forceinline__ uint32_t fetch_lookbehind(const MsdScanParams &P, uint64_t pos, int lane, RawGroup<FMT> &r)
+{
+    constexpr int BPS = RawGroup<FMT>::WORDS / 2;
+    if (pos % MSD_CHUNK_SAMPLES != 0) /* wave-uniform */
+        return fetch_group<FMT>(P, (int64_t)(P.batch_first + pos) - FRONT + 8 * lane, r);
+    const uint32_t slot = P.group_lb[pos / MSD_CHUNK_SAMPLES];
+    const bool have = slot != MSD_GROUP_NO_TAIL;
+    const uint8_t *src = have ? P.group_tails + ((size_t)slot * FRONT + 8u * (uint32_t)lane) * BPS
+                              : reinterpret_cast<const uint8_t *>(P.lut);
+    const uint4 a = *reinterpret_cast<const uint4 *>(src);
+    r.w[0] = a.x; r.w[1] = a.y; r.w[2] = a.z; r.w[3] = a.w;
+    if (BPS == 4) {
+        const uint4 b = *reinterpret_cast<const uint4 *>(src + 16);
+        r.w[4 % RawGroup<FMT>::WORDS] = b.x; r.w[5 % RawGroup<FMT>::WORDS] = b.y;
+        r.w[6 % RawGroup<FMT>::WORDS] = b.z; r.w[7 % RawGroup<FMT>::WORDS] = b.w;
+    }
+    return have ? 0xffu : 0u;
+}
+
 template <int FMT, bool MASK = true /* false: the caller masks (mask_group) once all its groups' loads are out */,
           bool SCAN_TABLE = false /* lut is the context's device table: use the 256-pitch copy behind it (msd_internal.h) */>
 __device__ __forceinline__ void convert_group(const RawGroup<FMT> &r, uint32_t valid, const uint16_t *lut,
@@ -758,8 +782,9 @@ template <int FMT>
 __device__ inline void msd_emit_slice(const MsdEmitJob &J, const uint16_t *lut_g, uint32_t w, int lane, unsigned char *lds,
                                       bool dbg_no_store = false);
 
-/* One wavefront's share of the batch: the tiles [tile_lo, tile_hi) of 1024 * tile_runs(FMT) scan positions each. */
-template <int FMT, bool FIX2, bool EMIT>
+/* One wavefront's share of the batch: the tiles [tile_lo, tile_hi) of 1024 * tile_runs(FMT) scan positions each.
+ * GROUP: the buffers belong to different receivers (MsdScanParams.group_lb). */
+template <int FMT, bool FIX2, bool EMIT, bool GROUP>
 __device__ __forceinline__ void scan_region(const MsdScanParams &P, const WaveCtx &X, const uint16_t *lut,
                                             uint32_t region, uint32_t tile_lo, uint32_t tile_hi, uint32_t &hits_total,
                                             uint32_t &tries_total)
@@ -836,7 +861,11 @@ __device__ __forceinline__ void scan_region(const MsdScanParams &P, const WaveCt
         const uint64_t a0 = P.batch_first + (uint64_t)tile_lo * WT;
         if (lane < FRONT / 8) {
             RawGroup<FMT> r;
-            const uint32_t valid = fetch_group<FMT>(P, (int64_t)a0 - FRONT + 8 * lane, r);
+            uint32_t valid;
+            if constexpr (GROUP)
+                valid = fetch_lookbehind<FMT>(P, (uint64_t)tile_lo * WT, lane, r);
+            else
+                valid = fetch_group<FMT>(P, (int64_t)a0 - FRONT + 8 * lane, r);
             uint32_t mg[8];
             convert_group<FMT, true, SCAN_LUT>(r, valid, lut, mg);
             *reinterpret_cast<uint4 *>(mags + 8 * lane) = pack8(mg);
@@ -1143,12 +1172,26 @@ __device__ __forceinline__ void scan_region(const MsdScanParams &P, const WaveCt
         TMARK(9)
 
         /* ---- carry the last 328 magnitudes over as the next tile's look-behind ---- */
-        uint4 carry = make_uint4(0, 0, 0, 0);
-        if (lane < FRONT / 8)
-            carry = *reinterpret_cast<const uint4 *>(mags + WT + 8 * lane);
-        wave_lds_sync();
-        if (lane < FRONT / 8)
-            *reinterpret_cast<uint4 *>(mags + 8 * lane) = carry;
+        if (GROUP && tile + 1 < tile_hi && (tile_pos0 + WT) % MSD_CHUNK_SAMPLES == 0) { /* wave-uniform: the next tile starts another receiver's buffer */
+            uint4 lb = make_uint4(0, 0, 0, 0);
+            if (lane < FRONT / 8) {
+                RawGroup<FMT> r;
+                const uint32_t valid = fetch_lookbehind<FMT>(P, tile_pos0 + WT, lane, r);
+                uint32_t mg[8];
+                convert_group<FMT, true, SCAN_LUT>(r, valid, lut, mg);
+                lb = pack8(mg);
+            }
+            wave_lds_sync();
+            if (lane < FRONT / 8)
+                *reinterpret_cast<uint4 *>(mags + 8 * lane) = lb;
+        } else {
+            uint4 carry = make_uint4(0, 0, 0, 0);
+            if (lane < FRONT / 8)
+                carry = *reinterpret_cast<const uint4 *>(mags + WT + 8 * lane);
+            wave_lds_sync();
+            if (lane < FRONT / 8)
+                *reinterpret_cast<uint4 *>(mags + 8 * lane) = carry;
+        }
 #pragma unroll
         for (int k = 0; k < GPT; ++k) {
             cur[k] = nxt[k];
@@ -1165,7 +1208,8 @@ __device__ __forceinline__ void scan_region(const MsdScanParams &P, const WaveCt
 
 template <int FMT, bool FIX2 /* --aggressive: two-bit correction tables in global memory */,
           bool EMIT /* the wavefronts also write the previous batch's message records (P.emit): an instantiation of its
-                       own, because the call alone costs the tile loop 7 us per launch in spills */>
+                       own, because the call alone costs the tile loop 7 us per launch in spills */,
+          bool GROUP = false /* receiver groups: every buffer's look-behind from P.group_lb (fetch_lookbehind) */>
 #ifndef MSD_SCAN_OCC
 #define MSD_SCAN_OCC ((MSD_SCAN_WAVES * MSD_SCAN_WGS_PER_CU + 3) / 4) /* wavefronts per SIMD the register budget is held to */
 #endif
@@ -1221,7 +1265,7 @@ __global__ void __launch_bounds__(NT, MSD_SCAN_OCC) msd_scan_kernel(const MsdSca
         X.syn = syn;
         X.sl = sl;
         X.lane = lane;
-        scan_region<FMT, FIX2, EMIT>(P, X, lut, region, tile_lo, tile_hi, nhits, ntries);
+        scan_region<FMT, FIX2, EMIT, GROUP>(P, X, lut, region, tile_lo, tile_hi, nhits, ntries);
     } else if (EMIT && P.emit.nbuffers && region / P.emit.stride < P.emit.nbuffers && !(P.debug_flags & 128)) {
         /* a region without tiles (lean layout: the pieces of a short last buffer) still owes its share of the
          * previous batch's records */
@@ -1543,6 +1587,151 @@ __global__ void __launch_bounds__(256) msd_power_kernel(const MsdScanParams P, c
         acc += __shfl_down(acc, o);
     if (lane == 0)
         out[i] = acc;
+}
+
+/* Receiver groups: the same sums, with the samples in front of a buffer from its receiver's tail slot
+ * (P.group_lb) instead of the batch's previous buffer.  A message never reaches into the next buffer
+ * (j + 19 + 268 < 131072 + 326), so a buffer and its look-behind are all it reads. */
+template <int FMT>
+__global__ void __launch_bounds__(256) msd_group_power_kernel(const MsdScanParams P, const uint64_t *req, uint32_t nreq,
+                                                              unsigned long long *out)
+{
+    constexpr int BPS = (FMT == MSD_FMT_SC16 || FMT == MSD_FMT_SC16Q11) ? 4 : 2;
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= nreq)
+        return;
+    const uint64_t rq = req[i];
+    const int len = (int)(rq & 0xffffu);
+    const uint64_t pos = rq >> 16, b = pos / MSD_CHUNK_SAMPLES;
+    const uint32_t slot = P.group_lb[b];
+    MsdSampleSource S;
+    S.iq = P.iq + b * MSD_CHUNK_SAMPLES * BPS;
+    S.have_prev = slot != MSD_GROUP_NO_TAIL;
+    S.prev_tail = S.have_prev ? P.group_tails + (size_t)slot * FRONT * BPS : nullptr;
+    S.batch_first = 0;
+    S.nsamples = min((uint64_t)MSD_CHUNK_SAMPLES, P.nsamples - b * MSD_CHUNK_SAMPLES);
+    const int64_t n0 = (int64_t)(pos - b * MSD_CHUNK_SAMPLES) - (int64_t)MSD_OVERLAP + 19;
+    unsigned long long acc = 0;
+    for (int k = lane; k < len; k += 64) {
+        const uint32_t x = msd_stream_mag<FMT>(S, n0 + k, P.lut);
+        acc += (unsigned long long)(x * x);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        acc += __shfl_down(acc, o);
+    if (lane == 0)
+        out[i] = acc;
+}
+
+/* Receiver groups, GPU resolve: the signal power of every accepted message the resolve kernel left in acc[], one
+ * wavefront per message, buffer todo[blockIdx.x], messages blockIdx.y * 4 + wave, + 4 * gridDim.y, ... */
+template <int FMT>
+__global__ void __launch_bounds__(256) msd_group_power_buffers_kernel(const MsdScanParams P, const msd_acc *acc,
+                                                                      const uint32_t *nmsgs, const uint32_t *todo,
+                                                                      unsigned long long *out)
+{
+    constexpr int BPS = (FMT == MSD_FMT_SC16 || FMT == MSD_FMT_SC16Q11) ? 4 : 2;
+    const uint32_t b = todo[blockIdx.x];
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = min(nmsgs[b], MSD_RB_MSG_CAP);
+    const uint32_t slot = P.group_lb[b];
+    MsdSampleSource S;
+    S.iq = P.iq + (size_t)b * MSD_CHUNK_SAMPLES * BPS;
+    S.have_prev = slot != MSD_GROUP_NO_TAIL;
+    S.prev_tail = S.have_prev ? P.group_tails + (size_t)slot * FRONT * BPS : nullptr;
+    S.batch_first = 0;
+    S.nsamples = MSD_CHUNK_SAMPLES;
+    for (uint32_t m = blockIdx.y * 4 + (threadIdx.x >> 6); m < n; m += 4 * gridDim.y) {
+        const msd_acc a = acc[(size_t)b * MSD_RB_MSG_CAP + m];
+        const int64_t n0 = (int64_t)a.pos - (int64_t)b * MSD_CHUNK_SAMPLES - (int64_t)MSD_OVERLAP + 19;
+        unsigned long long sum = 0;
+        for (int k = lane; k < (int)a.len; k += 64) {
+            const uint32_t x = msd_stream_mag<FMT>(S, n0 + k, P.lut);
+            sum += (unsigned long long)(x * x);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+            sum += __shfl_down(sum, o);
+        if (lane == 0)
+            out[(size_t)b * MSD_RB_MSG_CAP + m] = sum;
+    }
+}
+
+/* icao_filter.c:44-65 */
+__device__ __forceinline__ uint32_t group_hash24(uint32_t a)
+{
+    uint32_t h = 0;
+    h += a & 0xff;         h += h << 10; h ^= h >> 6;
+    h += (a >> 8) & 0xff;  h += h << 10; h ^= h >> 6;
+    h += (a >> 16) & 0xff; h += h << 10; h ^= h >> 6;
+    h += h << 3;
+    h ^= h >> 11;
+    h += h << 15;
+    return h & 8191u;
+}
+
+/* Receiver groups, GPU resolve: one workgroup per entry keeps its receiver's device snapshot equal to the host's filter
+ * after the buffer -- the adds in order (icaoFilterAdd, icao_filter.c:76-97: the address keyed by its hash, a second
+ * copy keyed by its low 16 bits, giving up where the table is full), then the flip.  A snapshot interleaves the two
+ * tables: slot h of table t is word 2 h + t; word 16384 is the active table. */
+__global__ void __launch_bounds__(256) msd_group_filter_apply_kernel(uint32_t *snaps, const uint32_t *slot,
+                                                                     const uint32_t *add_first, const uint32_t *add_list,
+                                                                     const uint32_t *flip)
+{
+    const uint32_t i = blockIdx.x;
+    uint32_t *t = snaps + (size_t)slot[i] * MSD_SNAP_WORDS;
+    const uint32_t act = t[16384];
+    if (threadIdx.x == 0) {
+        for (uint32_t k = add_first[i]; k < add_first[i + 1]; ++k) {
+            const uint32_t addr = add_list[k];
+            uint32_t start = group_hash24(addr), h = start;
+            bool full = false;
+            while (t[2 * h + act] != 0xFFFFFFFFu && t[2 * h + act] != addr) {
+                h = (h + 1) & 8191u;
+                if (h == start) {
+                    full = true;
+                    break;
+                }
+            }
+            if (full)
+                continue;
+            if (t[2 * h + act] == 0xFFFFFFFFu)
+                t[2 * h + act] = addr;
+            const uint32_t low = addr & 0xffffu;
+            start = h = group_hash24(low);
+            while (t[2 * h + act] != 0xFFFFFFFFu && (t[2 * h + act] & 0xffffu) != low) {
+                h = (h + 1) & 8191u;
+                if (h == start) {
+                    full = true;
+                    break;
+                }
+            }
+            if (!full && t[2 * h + act] == 0xFFFFFFFFu)
+                t[2 * h + act] = addr;
+        }
+    }
+    __syncthreads();
+    if (flip[i]) {
+        const uint32_t other = act ^ 1u;
+        for (uint32_t h = threadIdx.x; h < 8192u; h += blockDim.x)
+            t[2 * h + other] = 0xFFFFFFFFu;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            t[16384] = other;
+    }
+}
+
+/* Receiver groups: buffer blockIdx.x's last FRONT raw samples -> its receiver's tail slot, for that receiver's next
+ * call (queued behind the scan and the power kernel, which read the old contents). */
+__global__ void __launch_bounds__(256) msd_group_tails_kernel(const uint8_t *iq, const uint32_t *dst_slot, uint8_t *tails,
+                                                              uint32_t bps)
+{
+    const uint32_t b = blockIdx.x, words = FRONT * bps / 16u;
+    const uint4 *src = reinterpret_cast<const uint4 *>(iq + ((size_t)(b + 1) * MSD_CHUNK_SAMPLES - FRONT) * bps);
+    uint4 *dst = reinterpret_cast<uint4 *>(tails + (size_t)dst_slot[b] * FRONT * bps);
+    for (uint32_t w = threadIdx.x; w < words; w += blockDim.x)
+        dst[w] = src[w];
 }
 
 /* The same for the GPU resolve stage, which does not know the number of messages on the host when
@@ -3029,22 +3218,28 @@ extern "C" size_t msd_scan_lds_bytes(int format)
     return format == MSD_FMT_UC8 ? (size_t)LDS_UC8 : (size_t)LDS_COMMON;
 }
 
-template <int FMT, bool FIX2, bool EMIT>
+template <int FMT, bool FIX2, bool EMIT, bool GROUP = false>
 static int launch_scan_fix(const MsdScanParams *p, uint32_t nregions, hipStream_t stream)
 {
     const size_t lds = msd_scan_lds_bytes(FMT);
     const uint32_t nwg = (nregions + WAVES - 1) / WAVES;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&msd_scan_kernel<FMT, FIX2, EMIT>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&msd_scan_kernel<FMT, FIX2, EMIT, GROUP>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess)
         return -5;
-    hipLaunchKernelGGL((msd_scan_kernel<FMT, FIX2, EMIT>), dim3(nwg), dim3(NT), lds, stream, *p);
+    hipLaunchKernelGGL((msd_scan_kernel<FMT, FIX2, EMIT, GROUP>), dim3(nwg), dim3(NT), lds, stream, *p);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
 template <int FMT>
 static int launch_scan_fmt(const MsdScanParams *p, uint32_t nregions, hipStream_t stream)
 {
+    if (p->group_lb) { /* receiver groups: no records of an earlier batch ride along */
+        if (p->emit.nbuffers || p->have_prev)
+            return -22;
+        return p->fix2_112 ? launch_scan_fix<FMT, true, false, true>(p, nregions, stream)
+                           : launch_scan_fix<FMT, false, false, true>(p, nregions, stream);
+    }
     if (p->emit.nbuffers)
         return p->fix2_112 ? launch_scan_fix<FMT, true, true>(p, nregions, stream)
                            : launch_scan_fix<FMT, false, true>(p, nregions, stream);
@@ -3100,6 +3295,74 @@ extern "C" int msd_launch_power(const MsdScanParams *p, int format, const uint64
     default:
         return -22;
     }
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int msd_launch_group_power(const MsdScanParams *p, int format, const uint64_t *d_req, uint32_t nreq,
+                                      unsigned long long *d_out, hipStream_t stream)
+{
+    if (nreq == 0)
+        return 0;
+    if (!p->group_lb)
+        return -22;
+    const dim3 grid((nreq + 3) / 4), block(256);
+    switch (format) {
+    case MSD_FMT_UC8:
+        hipLaunchKernelGGL(msd_group_power_kernel<MSD_FMT_UC8>, grid, block, 0, stream, *p, d_req, nreq, d_out);
+        break;
+    case MSD_FMT_SC16:
+        hipLaunchKernelGGL(msd_group_power_kernel<MSD_FMT_SC16>, grid, block, 0, stream, *p, d_req, nreq, d_out);
+        break;
+    case MSD_FMT_SC16Q11:
+        hipLaunchKernelGGL(msd_group_power_kernel<MSD_FMT_SC16Q11>, grid, block, 0, stream, *p, d_req, nreq, d_out);
+        break;
+    default:
+        return -22;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int msd_launch_group_power_buffers(const MsdScanParams *p, int format, const msd_acc *acc, const uint32_t *nmsgs,
+                                              const uint32_t *todo, uint32_t ntodo, unsigned long long *out, hipStream_t stream)
+{
+    if (ntodo == 0)
+        return 0;
+    if (!p->group_lb)
+        return -22;
+    const dim3 grid(ntodo, 8), block(256);
+    switch (format) {
+    case MSD_FMT_UC8:
+        hipLaunchKernelGGL(msd_group_power_buffers_kernel<MSD_FMT_UC8>, grid, block, 0, stream, *p, acc, nmsgs, todo, out);
+        break;
+    case MSD_FMT_SC16:
+        hipLaunchKernelGGL(msd_group_power_buffers_kernel<MSD_FMT_SC16>, grid, block, 0, stream, *p, acc, nmsgs, todo, out);
+        break;
+    case MSD_FMT_SC16Q11:
+        hipLaunchKernelGGL(msd_group_power_buffers_kernel<MSD_FMT_SC16Q11>, grid, block, 0, stream, *p, acc, nmsgs, todo, out);
+        break;
+    default:
+        return -22;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int msd_launch_group_filter_apply(uint32_t *snaps, uint32_t n, const uint32_t *slot, const uint32_t *add_first,
+                                             const uint32_t *add_list, const uint32_t *flip, hipStream_t stream)
+{
+    if (n == 0)
+        return 0;
+    hipLaunchKernelGGL(msd_group_filter_apply_kernel, dim3(n), dim3(256), 0, stream, snaps, slot, add_first, add_list, flip);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int msd_launch_group_tails(const uint8_t *iq, uint32_t n, const uint32_t *dst_slot, uint8_t *tails, uint32_t bps,
+                                      hipStream_t stream)
+{
+    if (n == 0)
+        return 0;
+    if ((FRONT * bps) % 16u || (reinterpret_cast<uintptr_t>(iq) & 15u) || (reinterpret_cast<uintptr_t>(tails) & 15u))
+        return -22;
+    hipLaunchKernelGGL(msd_group_tails_kernel, dim3(n), dim3(128), 0, stream, iq, dst_slot, tails, bps);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
