@@ -558,10 +558,29 @@ int msd_group_submit_host(msd_group *g, const void *h_iq, const msd_group_entry 
                           msd_group_message_fn sink, void *user);
 int msd_group_reset_receiver(msd_group *g, uint32_t receiver); /* filter, clock, counters, tail */
 int msd_group_get_stats(const msd_group *g, uint32_t receiver, msd_stats *st);
-int msd_group_set_preamble_threshold(msd_group *g, int threshold); /* group-wide */
+int msd_group_set_preamble_threshold(msd_group *g, int threshold); /* group-wide: sets every receiver's threshold */
 /* of the most recent call: hits, tries, resolve_passes (1: the GPU resolve ran; 0: all on the host); since creation:
  * reruns (calls rescanned in pieces) and resolve_fallback (buffers resolved on the host); the kernel times are not kept */
 int msd_group_get_timing(const msd_group *g, msd_timing *t);
+
+/* Per-receiver options: the hot-path options readsb takes per process, so that receivers started differently share a
+ * group.  Every receiver starts with the group's msd_config.preamble_threshold and nfix_crc; a group whose options are
+ * never set decodes as before.  The threshold may change at any time and applies from the receiver's next buffer, as
+ * msd_set_preamble_threshold between two msd_launch_* calls of a context.  The repair level may change only while the
+ * receiver has no history -- after msd_group_create or msd_group_reset_receiver, before its next buffer -- and is
+ * -EBUSY otherwise (readsb cannot change --fix in a running process either); setting the current value is always
+ * allowed.  msd_group_reset_receiver keeps the options; msd_group_set_preamble_threshold sets every receiver's
+ * threshold.  -EINVAL: a receiver out of range, a threshold outside 1..MSD_MAX_PREAMBLE_THRESHOLD, a level outside
+ * 0..2, nonzero reserved words, NULL.  -ENOMEM: the two-bit correction tables (about 92 KiB of device memory, made
+ * with the group when its nfix_crc is 2, else on the first receiver set to 2) could not be made.  Every error leaves
+ * the group's state untouched. */
+typedef struct msd_group_receiver_options {
+    int32_t preamble_threshold; /* 1..MSD_MAX_PREAMBLE_THRESHOLD, as msd_set_preamble_threshold */
+    int32_t nfix_crc;           /* 0 --no-fix, 1 --fix, 2 --aggressive */
+    int32_t reserved[2];        /* 0 */
+} msd_group_receiver_options;
+int msd_group_set_receiver_options(msd_group *g, uint32_t receiver, const msd_group_receiver_options *o);
+int msd_group_get_receiver_options(const msd_group *g, uint32_t receiver, msd_group_receiver_options *o);
 
 #ifdef __cplusplus
 }

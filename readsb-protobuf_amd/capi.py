@@ -218,6 +218,7 @@ EXPORTS = [
     "msd_accept_beast", "msd_accept_frames", "msd_get_remote_stats",
     "msd_group_create", "msd_group_destroy", "msd_group_last_error", "msd_group_submit_device", "msd_group_submit_host",
     "msd_group_reset_receiver", "msd_group_get_stats", "msd_group_set_preamble_threshold", "msd_group_get_timing",
+    "msd_group_set_receiver_options", "msd_group_get_receiver_options",
 ]
 
 _lib = None
@@ -590,6 +591,11 @@ class GroupEntry(C.Structure):
     _fields_ = [("receiver", C.c_uint32), ("flags", C.c_uint32), ("dropped", C.c_uint64)]
 
 
+class GroupReceiverOptions(C.Structure):
+    """msd_group_receiver_options: one receiver's preamble threshold and CRC repair level."""
+    _fields_ = [("preamble_threshold", C.c_int32), ("nfix_crc", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 GROUP_MESSAGE_DTYPE = np.dtype([("receiver", "<u4"), ("m", MESSAGE_DTYPE)])
 _GROUP_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_void_p)
 
@@ -614,6 +620,10 @@ def _group_lib():
         L.msd_group_set_preamble_threshold.argtypes = [C.c_void_p, C.c_int]
         L.msd_group_get_timing.restype = C.c_int
         L.msd_group_get_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
+        L.msd_group_set_receiver_options.restype = C.c_int
+        L.msd_group_set_receiver_options.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(GroupReceiverOptions)]
+        L.msd_group_get_receiver_options.restype = C.c_int
+        L.msd_group_get_receiver_options.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(GroupReceiverOptions)]
         L._group_bound = True
     return L
 
@@ -710,4 +720,19 @@ class ReceiverGroup:
         self._check(_group_lib().msd_group_reset_receiver(self._h, receiver))
 
     def set_preamble_threshold(self, threshold):
+        """Every receiver's threshold."""
         self._check(_group_lib().msd_group_set_preamble_threshold(self._h, threshold))
+
+    def receiver_options(self, receiver):
+        """{"preamble_threshold", "nfix_crc"} of one receiver (the group's configuration until set)."""
+        o = GroupReceiverOptions()
+        self._check(_group_lib().msd_group_get_receiver_options(self._h, receiver, C.byref(o)))
+        return {"preamble_threshold": o.preamble_threshold, "nfix_crc": o.nfix_crc}
+
+    def set_receiver_options(self, receiver, preamble_threshold=None, nfix_crc=None):
+        """One receiver's threshold (from its next buffer) and repair level (only before its first buffer or after
+        reset_receiver, else -EBUSY); None keeps the current value."""
+        cur = self.receiver_options(receiver)
+        o = GroupReceiverOptions(cur["preamble_threshold"] if preamble_threshold is None else int(preamble_threshold),
+                                 cur["nfix_crc"] if nfix_crc is None else int(nfix_crc))
+        self._check(_group_lib().msd_group_set_receiver_options(self._h, receiver, C.byref(o)))

@@ -370,6 +370,8 @@ struct msd_ctx {
      * tail slot (MsdScanParams.group_lb) */
     const uint8_t *group_tails = nullptr;
     const uint32_t *group_lb = nullptr;
+    const uint32_t *group_opt = nullptr; /* every buffer's receiver options (MsdScanParams.group_opt) */
+    bool group_fix2 = false;             /* some buffer of the call is at repair level 2: the FIX2 instantiation */
     char err[256] = {0};
 };
 
@@ -635,8 +637,13 @@ int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pi
         if (c->group_lb) { /* a receiver group: batch_first is a whole number of buffers into the group's call */
             p.group_tails = c->group_tails;
             p.group_lb = c->group_lb + s.batch_first / MSD_CHUNK_SAMPLES;
+            p.group_opt = c->group_opt + s.batch_first / MSD_CHUNK_SAMPLES;
             p.prev_tail = nullptr;
             p.have_prev = 0;
+            if (!c->group_fix2) { /* the two-bit tables may exist, but no buffer of this call is at level 2 */
+                p.fix2_56 = nullptr;
+                p.fix2_112 = nullptr;
+            }
         }
         p.ntiles = ntiles;
         p.tiles_per_wg = tpw;
@@ -3035,6 +3042,8 @@ struct GroupReceiver {
     msd_resolver resolver{}; /* filter, clock (sample_counter) and the counters it sums into `stats` */
     msd_stats stats{};
     bool have_tail = false; /* its tail slot holds the end of its previous buffer */
+    bool history = false;   /* a buffer since creation or the last reset: the repair level is fixed */
+    msd_group_receiver_options opt{}; /* kept across msd_group_reset_receiver */
 };
 
 /* what the host resolver delivers for one entry of a call */
@@ -3086,7 +3095,8 @@ struct msd_group {
     bool gpu = false;     /* resolve on the GPU against the receivers' device snapshots (not MSD_CFG_HOST_RESOLVE) */
     GroupReceiver *rx = nullptr;
     uint8_t *d_tails = nullptr;    /* [max_receivers][MSD_HALO_FRONT] raw samples */
-    uint32_t *d_ctl = nullptr;     /* [2][max_receivers]: look-behind slot per buffer, receiver per buffer */
+    uint32_t *d_ctl = nullptr;     /* [3][max_receivers]: per buffer its look-behind slot, its receiver and its receiver's
+                                      options (threshold | nfix_crc << 16) */
     uint32_t *h_ctl = nullptr;     /* pinned copy */
     uint32_t *d_snaps = nullptr;   /* [max_receivers][MSD_SNAP_WORDS]: every receiver's ICAO filter on the device */
     uint32_t *h_apply = nullptr;   /* pinned, read in place by the filter kernel: slot[n] | add_first[n + 1] | flip[n] */
@@ -3137,6 +3147,46 @@ void group_receiver_reset(GroupReceiver &r)
     msd_resolver_reset(&r.resolver); /* filter, clock and the counters behind r.resolver.stats */
     memset(&r.stats, 0, sizeof r.stats);
     r.have_tail = false;
+    r.history = false;
+}
+
+/* The two-bit correction tables (--aggressive, crc.c:374-379) of the group's context, made when the first receiver is
+ * set to repair level 2 (msd_create makes them when the group's own configuration has nfix_crc 2). */
+int group_make_fix2(msd_group *g)
+{
+    msd_ctx *c = g->ctx;
+    if (c->d_fix2[1])
+        return 0;
+    GHIPCHK(g, hipSetDevice(c->cfg.device));
+    uint64_t *d[2] = {nullptr, nullptr};
+    uint32_t lg[2] = {0, 0};
+    int rc = 0;
+    for (int k = 0; k < 2 && !rc; ++k) {
+        uint64_t *tab = msd_fix2_table(c->tables, k ? 112 : 56, &lg[k]);
+        if (!tab) {
+            rc = gfail(g, -ENOMEM, "two-bit correction table: out of host memory");
+            break;
+        }
+        const size_t bytes = sizeof(uint64_t) << lg[k];
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d[k]), bytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(d[k], tab, bytes, hipMemcpyHostToDevice);
+        free(tab);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rc = gfail(g, e == hipErrorOutOfMemory ? -ENOMEM : -EIO, "two-bit correction table: %s", hipGetErrorString(e));
+        }
+    }
+    if (rc) {
+        (void)hipFree(d[0]);
+        (void)hipFree(d[1]);
+        return rc;
+    }
+    for (int k = 0; k < 2; ++k) {
+        c->d_fix2[k] = d[k];
+        c->fix2_lg[k] = lg[k];
+    }
+    return 0;
 }
 
 int group_check(const msd_group *g, const msd_group_entry *e, uint32_t n)
@@ -3370,13 +3420,17 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     const int format = c->cfg.format;
     const uint64_t nsamples = (uint64_t)n * MSD_CHUNK_SAMPLES;
     /* look-behind: the receiver's tail slot unless it has none yet or lost samples in front of this buffer (fifo.c:178-181) */
-    uint32_t *lb = g->h_ctl, *slot = g->h_ctl + g->max_receivers;
+    uint32_t *lb = g->h_ctl, *slot = g->h_ctl + g->max_receivers, *opt = g->h_ctl + 2 * g->max_receivers;
+    bool fix2 = false;
     for (uint32_t i = 0; i < n; ++i) {
-        const GroupReceiver &r = g->rx[e[i].receiver];
+        GroupReceiver &r = g->rx[e[i].receiver];
         lb[i] = r.have_tail && e[i].dropped == 0 ? e[i].receiver : MSD_GROUP_NO_TAIL;
         slot[i] = e[i].receiver;
+        opt[i] = (uint32_t)r.opt.preamble_threshold | (uint32_t)r.opt.nfix_crc << 16;
+        fix2 |= r.opt.nfix_crc == 2;
+        r.history = true;
     }
-    GHIPCHK(g, hipMemcpyAsync(g->d_ctl, g->h_ctl, sizeof(uint32_t) * 2 * g->max_receivers, hipMemcpyHostToDevice, c->stream));
+    GHIPCHK(g, hipMemcpyAsync(g->d_ctl, g->h_ctl, sizeof(uint32_t) * 3 * g->max_receivers, hipMemcpyHostToDevice, c->stream));
 
     Slot &s = c->slots[0];
     s.busy = true;
@@ -3396,10 +3450,20 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     s.tail_dst = nullptr; /* the group keeps its own tails */
     c->group_tails = g->d_tails;
     c->group_lb = g->d_ctl;
+    c->group_opt = g->d_ctl + 2 * g->max_receivers;
+    c->group_fix2 = fix2;
     struct Unset { /* the context's stream entries never see the group's look-behind */
         msd_ctx *c;
         Slot &s;
-        ~Unset() { c->group_tails = nullptr; c->group_lb = nullptr; s.busy = false; s.download_started = false; }
+        ~Unset()
+        {
+            c->group_tails = nullptr;
+            c->group_lb = nullptr;
+            c->group_opt = nullptr;
+            c->group_fix2 = false;
+            s.busy = false;
+            s.download_started = false;
+        }
     } unset{c, s};
     int rc = enqueue(c, s, format, nullptr);
     s.gpu_resolve = g->gpu; /* start_download: the lists stay on the device unless the arenas overflowed */
@@ -3500,6 +3564,8 @@ int msd_group_create(const msd_config *cfg, uint32_t max_receivers, msd_group **
     msd_config cc = *cfg;
     cc.max_batch_samples = (uint64_t)max_receivers * MSD_CHUNK_SAMPLES;
     cc.flags |= MSD_CFG_NO_HELPER | MSD_CFG_NO_LEAN; /* synchronous calls over the dense candidate lists */
+    if (cc.nfix_crc == 0) /* the single-bit tables always: a receiver may be set to level 1 (the scan gates by level) */
+        cc.nfix_crc = 1;
     int rc = msd_create(&cc, &g->ctx);
     if (rc) {
         delete g;
@@ -3511,8 +3577,8 @@ int msd_group_create(const msd_config *cfg, uint32_t max_receivers, msd_group **
     g->rx = new (std::nothrow) GroupReceiver[max_receivers];
     const size_t tail_bytes = (size_t)max_receivers * MSD_HALO_FRONT * g->ctx->bps;
     if (!g->rx || hipMalloc(reinterpret_cast<void **>(&g->d_tails), tail_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&g->d_ctl), sizeof(uint32_t) * 2 * max_receivers) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&g->h_ctl), sizeof(uint32_t) * 2 * max_receivers, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&g->d_ctl), sizeof(uint32_t) * 3 * max_receivers) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&g->h_ctl), sizeof(uint32_t) * 3 * max_receivers, hipHostMallocDefault) != hipSuccess ||
         (g->gpu && (hipMalloc(reinterpret_cast<void **>(&g->d_snaps), sizeof(uint32_t) * MSD_SNAP_WORDS * max_receivers) != hipSuccess ||
                     hipHostMalloc(reinterpret_cast<void **>(&g->h_apply), sizeof(uint32_t) * (3 * (size_t)max_receivers + 1),
                                   hipHostMallocDefault) != hipSuccess ||
@@ -3526,6 +3592,8 @@ int msd_group_create(const msd_config *cfg, uint32_t max_receivers, msd_group **
     for (uint32_t r = 0; r < max_receivers; ++r) {
         g->rx[r].resolver.stats = &g->rx[r].stats;
         g->rx[r].resolver.threads = 1;
+        g->rx[r].opt.preamble_threshold = cfg->preamble_threshold;
+        g->rx[r].opt.nfix_crc = cfg->nfix_crc;
         group_receiver_reset(g->rx[r]);
         rc = group_upload_snapshot(g, r);
         if (rc) {
@@ -3641,6 +3709,40 @@ int msd_group_set_preamble_threshold(msd_group *g, int threshold)
     const int rc = msd_set_preamble_threshold(g->ctx, threshold);
     if (rc)
         return gfail(g, rc, "%s", g->ctx->err);
+    for (uint32_t r = 0; r < g->max_receivers; ++r)
+        g->rx[r].opt.preamble_threshold = threshold;
+    return 0;
+}
+
+int msd_group_set_receiver_options(msd_group *g, uint32_t receiver, const msd_group_receiver_options *o)
+{
+    if (!g)
+        return -EINVAL;
+    if (!o || receiver >= g->max_receivers)
+        return gfail(g, -EINVAL, "receiver options: a receiver out of range or no options");
+    if (o->preamble_threshold < 1 || o->preamble_threshold > MSD_MAX_PREAMBLE_THRESHOLD || o->nfix_crc < 0 ||
+        o->nfix_crc > 2 || o->reserved[0] || o->reserved[1])
+        return gfail(g, -EINVAL, "receiver options: threshold %d outside 1..%d, repair level %d outside 0..2, or nonzero "
+                     "reserved words", o->preamble_threshold, MSD_MAX_PREAMBLE_THRESHOLD, o->nfix_crc);
+    GroupReceiver &r = g->rx[receiver];
+    if (o->nfix_crc != r.opt.nfix_crc && r.history) /* readsb cannot change --fix in a running process either */
+        return gfail(g, -EBUSY, "receiver %u: the repair level changes only before its first buffer (after a reset)",
+                     receiver);
+    if (o->nfix_crc == 2) {
+        const int rc = group_make_fix2(g);
+        if (rc)
+            return rc;
+    }
+    r.opt.preamble_threshold = o->preamble_threshold;
+    r.opt.nfix_crc = o->nfix_crc;
+    return 0;
+}
+
+int msd_group_get_receiver_options(const msd_group *g, uint32_t receiver, msd_group_receiver_options *o)
+{
+    if (!g || !o || receiver >= g->max_receivers)
+        return -EINVAL;
+    *o = g->rx[receiver].opt;
     return 0;
 }
 

@@ -87,9 +87,12 @@ typedef struct MsdScanParams {
     /* ---- receiver group (msd_group.cpp): the buffers of a batch belong to different receivers ----
      * group_lb != NULL: the look-behind of buffer b is not the end of buffer b - 1 but tail slot group_lb[b] of
      * group_tails (MSD_HALO_FRONT raw samples each), or zeros when group_lb[b] == MSD_GROUP_NO_TAIL.  Selects the
-     * group instantiation of the scan kernel; have_prev must be 0. */
+     * group instantiation of the scan kernel; have_prev must be 0.  group_opt[b]: the options of buffer b's receiver,
+     * preamble threshold | repair level (0..2) << 16, in place of `threshold` and of the context's repair level (the
+     * group's tables hold the single-bit syndromes always; fix2_* are set only if some buffer of the call is at 2). */
     const uint8_t *group_tails;
     const uint32_t *group_lb;
+    const uint32_t *group_opt;
 } MsdScanParams;
 #define MSD_GROUP_NO_TAIL 0xFFFFFFFFu
 

@@ -495,11 +495,14 @@ struct WaveCtx {
  *   step C  syndrome lookup and the filter-independent part of scoreModesMessage, one lane per slot
  *           (crc.c:389-412; mode_s.c:311-409)
  *   step D  records out: per hit, its live tries in phase order at consecutive indices.
- * Returns false if the round has more than SC tries with a known DF (the caller halves it). */
-template <bool FIX2>
+ * Returns false if the round has more than SC tries with a known DF (the caller halves it).
+ * GROUP: nfix is the repair level of the receiver whose buffer holds the round's tile (MsdScanParams.group_opt) --
+ * wave-uniform, since a round never holds hits of two tiles and a tile never straddles a buffer. */
+template <bool FIX2, bool GROUP = false>
 __device__ __forceinline__ bool candidate_round(const MsdScanParams &P, const WaveCtx &X, uint32_t nh, uint64_t tile_pos0,
                                                 msd_hit *hit_out, uint32_t hits_room, msd_try *my_tries,
-                                                uint32_t &tcur, uint32_t try_base /* of my_tries[0] in the hit records */
+                                                uint32_t &tcur, uint32_t try_base /* of my_tries[0] in the hit records */,
+                                                uint32_t nfix /* GROUP only: 0 --no-fix, 1 --fix, 2 --aggressive */
 #ifdef MSD_KERNEL_TIMING
                                                 , uint32_t *tacc, uint32_t *tlast
 #endif
@@ -663,7 +666,7 @@ __device__ __forceinline__ bool candidate_round(const MsdScanParams &P, const Wa
             const uint32_t syndrome = (df == 11) ? (crc & 0xffff80u) : crc;
             if (syndrome != 0) {
                 alive = false;
-                if (FIX2) {
+                if (FIX2 && (!GROUP || nfix == 2)) { /* (a group call runs FIX2 only if some entry is at level 2) */
                     /* --aggressive: modesChecksumDiagnose against the (2, 4) tables, a hash probe in
                      * global memory (10 / 82 KiB, L2-resident) */
                     const uint64_t *tab = (df == 11) ? P.fix2_56 : P.fix2_112;
@@ -685,7 +688,8 @@ __device__ __forceinline__ bool candidate_round(const MsdScanParams &P, const Wa
                 } else {
                     /* modesChecksumDiagnose (crc.c:389-412): exact match in the single-bit table, or give up.  The
                      * table lies in buckets of four (msd_internal.h): one 16-byte read, four compares, no loop. */
-                    if (P.nsyn112) { /* wave-uniform: --no-fix has no table */
+                    if (GROUP ? nfix != 0 : P.nsyn112 != 0) { /* wave-uniform: --no-fix has no table (a group always has
+                                                                   one, and gates by the receiver's level) */
                         const uint32_t bkt = (df == 11) ? (syndrome * P.synh_mul56) >> (32u - MSD_SYNH_LG56)
                                                         : (4u << MSD_SYNH_LG56) / 4u + ((syndrome * P.synh_mul112) >> (32u - MSD_SYNH_LG112));
                         const uint4 e4 = *reinterpret_cast<const uint4 *>(X.syn + 4u * bkt);
@@ -919,6 +923,10 @@ __device__ __forceinline__ void scan_region(const MsdScanParams &P, const WaveCt
     for (uint32_t tile = tile_lo; tile < tile_hi; ++tile) {
         const uint64_t tile_pos0 = (uint64_t)tile * WT; /* first scan position, batch-relative */
         TMARK(8)
+        /* receiver groups: the options of the receiver whose buffer holds this tile (a scalar load, once per tile) */
+        uint32_t gopt = 0;
+        if constexpr (GROUP)
+            gopt = P.group_opt[tile_pos0 / MSD_CHUNK_SAMPLES];
         const uint64_t a0 = P.batch_first + tile_pos0;
 
         /* ---- stage 1: IQ -> magnitudes in LDS; prefetch the next tile's IQ ---- */
@@ -1028,7 +1036,7 @@ __device__ __forceinline__ void scan_region(const MsdScanParams &P, const WaveCt
 #if MSD_TESTS_PRE_PLANE
                 uint32_t ppre = 0; /* the pre-check's own plane: ANDed into the three others once per run, not once per position */
 #endif
-                const int thr = P.threshold, m32 = -32;
+                const int thr = GROUP ? (int)(gopt & 0xffffu) : P.threshold, m32 = -32;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     /* pa[d] = mags[p + 2 + d].  Branch-free, and compare-free: every verdict is the sign bit of a
@@ -1081,7 +1089,7 @@ __device__ __forceinline__ void scan_region(const MsdScanParams &P, const WaveCt
 #define PA(d) (sm[q + 2 + (d)])
                     const uint64_t pre = __ballot(PA(1) > PA(7)) & __ballot(PA(12) > PA(14)) & __ballot(PA(12) > PA(15));
                     const uint32_t base_noise = (uint32_t)(PA(5) + PA(8) + PA(16) + PA(17) + PA(18));
-                    const int ref_level = (int)(__umul24(base_noise, (uint32_t)P.threshold) >> 5); /* < 2^24 each */
+                    const int ref_level = (int)(__umul24(base_noise, GROUP ? gopt & 0xffffu : (uint32_t)P.threshold) >> 5); /* < 2^24 each */
                     const int diff_2_3 = PA(2) - PA(3);
                     const int sum_1_4 = PA(1) + PA(4);
                     const int diff_10_11 = PA(10) - PA(11);
@@ -1150,7 +1158,8 @@ __device__ __forceinline__ void scan_region(const MsdScanParams &P, const WaveCt
                     const uint32_t out0 = hcur + r0;
                     const uint32_t room = out0 < P.hcap ? P.hcap - out0 : 0u;
                     TMARK(3)
-                    if (!candidate_round<FIX2>(P, X, nh, tile_pos0, my_hits + out0, room, my_tries, tcur, try_base
+                    if (!candidate_round<FIX2, GROUP>(P, X, nh, tile_pos0, my_hits + out0, room, my_tries, tcur, try_base,
+                                                      gopt >> 16
 #ifdef MSD_KERNEL_TIMING
                                                , tacc_, &tlast_
 #endif

@@ -7,7 +7,13 @@ A K-entry call takes one 131072-sample UC8 buffer from each of K receivers.  Rea
 131072 / 2.4e6 = 54.6 ms per buffer, so a call of time t sustains K * 54.6 ms / t receivers.  Messages are
 not handed to Python (deliver=False); the counters are.  The kernel trace of the K = 1024 call is a separate run:
 rocprofv3 --kernel-trace --stats -- python scripts/receiver_group_rate.py --only 1024 --reps 1
-(profiles/receiver_group_k1024_kernel_stats.csv)."""
+(profiles/receiver_group_k1024_kernel_stats.csv).
+
+    python scripts/receiver_group_rate.py --mixed [--reps 20]
+
+times the K = 1024 call with per-receiver options (thresholds spread over 40..400, repair levels 0 / 1 / 2 mixed)
+beside the same call with every receiver at the group's defaults, alternating, in one process; writes
+profiles/receiver_group_options_rate.json."""
 import argparse
 import json
 import os
@@ -26,8 +32,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "receiver_group_rate.json"))
+    ap.add_argument("--mixed", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "receiver_group_options_rate.json" if a.mixed else "receiver_group_rate.json")
     import __graft_entry__ as g
     pkg = g.load_package()
     import torch
@@ -39,6 +48,8 @@ def main():
     for r in range(kmax):
         host[r * CHUNK * 2:(r + 1) * CHUNK * 2] = base[(r % 64) * CHUNK * 2:((r % 64) + 1) * CHUNK * 2]
     dev = torch.from_numpy(host).cuda()
+    if a.mixed:
+        return mixed(a, capi, dev, host)
     res = {"buffer_samples": CHUNK, "format": "uc8", "reps": a.reps, "group": {}}
     for k in ks:
         grp = capi.ReceiverGroup(k, fmt=capi.FMT_UC8)
@@ -80,6 +91,44 @@ def main():
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
+
+
+def mixed_options(k):
+    """receiver r: threshold 40 + (97 r) % 361, spread over 40..400; repair level r % 3"""
+    return [(40 + (97 * r) % 361, r % 3) for r in range(k)]
+
+
+def mixed(a, capi, dev, host):
+    k = 1024
+    groups = {"uniform": capi.ReceiverGroup(k, fmt=capi.FMT_UC8), "mixed": capi.ReceiverGroup(k, fmt=capi.FMT_UC8)}
+    opts = mixed_options(k)
+    for r, (t, n) in enumerate(opts):
+        groups["mixed"].set_receiver_options(r, preamble_threshold=t, nfix_crc=n)
+    res = {"buffer_samples": CHUNK, "format": "uc8", "receivers": k, "reps": a.reps,
+           "mixed_options": "threshold 40 + (97 r) % 361, nfix_crc r % 3", "calls": {}}
+    for where, iq in (("device", dev), ("host", host)):
+        ts = {name: [] for name in groups}
+        for grp in groups.values():
+            grp.submit(iq, list(range(k)), deliver=False)  # warm-up
+        for _ in range(a.reps):  # alternating, so that drift of the box falls on both alike
+            for name, grp in groups.items():
+                t0 = time.perf_counter()
+                grp.submit(iq, list(range(k)), deliver=False)
+                ts[name].append(time.perf_counter() - t0)
+        for name, v in ts.items():
+            t = float(np.median(v))
+            res["calls"].setdefault(name, {})[where] = {
+                "call_ms_median": t * 1e3, "call_ms_min": min(v) * 1e3, "call_ms_all": [x * 1e3 for x in v],
+                "gsamples_per_s": k * CHUNK / t / 1e9, "receivers_real_time": k * (CHUNK / 2.4e6) / t}
+        print(where, json.dumps({n: round(res["calls"][n][where]["call_ms_median"], 3) for n in groups}), flush=True)
+    for name, grp in groups.items():
+        t = grp.timing()
+        res["calls"][name]["timing"] = {x: t[x] for x in ("hits", "tries", "reruns", "resolve_passes", "resolve_fallback")}
+        res["calls"][name]["accepted"] = int(sum(sum(grp.stats(r)["demod_accepted"]) for r in range(k)))
+        grp.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
 
 
 if __name__ == "__main__":
