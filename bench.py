@@ -14,6 +14,11 @@ measured with HIP events on the stream it runs on (msd_timing.scan_kernel_ms) fo
 timed region -- a hipEventRecord holds the stream for ~5 us, three per launch are 3 % of the whole-job rate.
 `cpu_baseline` is the oracle (our CPU restatement, kind "port") on one host core over a bounded
 sample of the same capture; it is a reported baseline, never the thing shipped.
+
+A plain run does only what the headline line needs: capture, settle, warm-up, the timed steps, --dump-outputs, the
+line.  --full adds, after the clock has stopped, everything else the benchmark measures and checks: the CPU baselines,
+the diff against the oracle and the second reading, the PCIe-inclusive rate, one lone capture, the replay tool's runs
+and the `also` workloads (N=1); every rank's diff against the oracle and the N-stream CPU baseline (N>1).
 """
 import argparse
 import json
@@ -30,7 +35,7 @@ import __graft_entry__ as graft  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -46,13 +51,19 @@ def parse():
     ap.add_argument("--threshold", type=int, default=58, help="--preamble-threshold (readsb.c:503-505: 40..400, default 58)")
     ap.add_argument("--input", default="siggen", choices=["siggen", "random"],
                     help="random: uniformly random bytes instead of the synthetic capture (candidate-density sweeps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the clock has stopped, also run everything beyond the headline line: CPU baselines, diffs "
+                         "against the oracle and the second reading, PCIe-inclusive rate, lone capture, replay tool, 'also' "
+                         "workloads (over a minute at the default size)")
     ap.add_argument("--cpu-sample", type=int, default=1 << 29, help="samples the CPU baseline replays")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines and the legs behind them (PCIe-inclusive rate, lone capture, "
+                         "replay tool, 'also')")
     ap.add_argument("--check", action="store_true",
-                    help="diff the GPU message list against the oracle even without the CPU baseline leg (it is on by "
-                         "default whenever the baseline replays the whole capture)")
+                    help="diff the GPU message list against the oracle, with or without --full (--full does so by default "
+                         "whenever the CPU baseline replays the whole capture, and at N>1)")
     ap.add_argument("--no-check", action="store_true", help="skip the message-set diff against the oracle")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the replay-tool runs of the literal mag_buf path (about 15 s, 10 of them in real time)")
+    ap.add_argument("--no-dropin", action="store_true", help="with --full: skip the replay-tool runs of the literal mag_buf path (about 15 s, 10 of them in real time)")
     ap.add_argument("--mode-ac", action="store_true", help="BASELINE configs[4]: Mode A/C demodulator on, 500 replies/s")
     ap.add_argument("--fields", action="store_true",
                     help="MSD_CFG_DECODE_FIELDS: also decode header and extended squitter fields of every message")
@@ -61,7 +72,7 @@ def parse():
     ap.add_argument("--dcfilter", action="store_true",
                     help="MSD_CFG_DC_FILTER: the DC-blocking converters (sequential by nature, ~0.1 GS/s); use a small --samples")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the post-clock runs of BASELINE configs[2] and [4] that the default N=1 run appends ('also')")
+                    help="with --full: skip the post-clock runs of BASELINE configs[2] and [4] that the N=1 run appends ('also')")
     ap.add_argument("--no-pin", action="store_true", help="leave the process's CPU affinity alone")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="process group of the N>1 bookkeeping (barrier, MAX time, SUM counts): nccl = RCCL, one GPU per "
@@ -75,7 +86,7 @@ def parse():
                          "and the decoded fields with --fields) as DIR/<name>.npy, one float32/float64 array per record "
                          "field, at most 64 MB in all (a fixed, seeded sample of the rows beyond that, their indices in "
                          "DIR/sample_rows.npy)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
     return args
@@ -576,8 +587,10 @@ def main():
         out["dc_block"] = {"exact_parallel": bool(ex), "passes": passes, "blocks": blocks, "blocks_guessed_all_passes": guessed,
                            "what": "the last batch's DC block (convert.c:137-138): blocks evaluated from 64 candidate start states per pass, "
                                    "an in-order walk that is exact by table hit or by monotonicity; false = the in-order kernel behind the passes took the batch"}
-    # ---- N > 1: the evidence an N = 1 line carries, for every rank, after the clock stopped ----
-    if world > 1 and not args.no_check:
+    # ---- everything below runs after the clock stopped, and only with --full (the oracle diff also with --check) ----
+    baselines = args.full and not args.no_cpu_baseline
+    # ---- N > 1: the evidence an N = 1 line carries, for every rank ----
+    if world > 1 and not args.no_check and (args.full or args.check):
         # every rank: its GPU's ordered message list and counters over the first 256 buffers of ITS capture (seed 10901 + rank)
         # against the oracle on the same samples
         O = graft.load_oracle()
@@ -600,7 +613,7 @@ def main():
         out["messages_checked"] = int(sum(x["messages"] for x in every))
         if out["message_set_diff_vs_oracle"]:
             raise SystemExit("bench: GPU messages differ from the oracle on some rank: " + json.dumps(every))
-    if world > 1 and rank == 0 and not args.no_cpu_baseline and not args.dcfilter:
+    if world > 1 and rank == 0 and baselines and not args.dcfilter:
         # SURVEY.md 8(d) CPU baseline, form (b): N independent streams (captures 10901 .. 10901 + N - 1) on 2 N pinned cores,
         # each stream the reference's reader thread + demodulator thread (readsb.c:271-285, 820-855), thread CPU time
         # (CLOCK_THREAD_CPUTIME_ID, util.c:102-115) and wall time.  The other ranks' GPU work is over: the host's cores are free.
@@ -636,7 +649,7 @@ def main():
 
     # ---- CPU baseline: the oracle on this host, bounded sample (rank 0, N=1 only), after the clock stopped ----
     want = wstats = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and baselines:
         O = graft.load_oracle()
         ns = min(n, args.cpu_sample)
         ofmt = {"uc8": O.FMT_UC8, "sc16": O.FMT_SC16, "sc16q11": O.FMT_SC16Q11}[args.format]
@@ -710,7 +723,7 @@ def main():
                             "oracle's): timestamps, bytes, address, repaired bits, score, phase, CRC, signal level as the same double"}
             except Exception as e:  # noqa: BLE001
                 out["message_set_diff_vs_second_reading"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dcfilter:
+    if rank == 0 and world == 1 and baselines and not args.dcfilter:
         # ---- the drop-in figure: the same capture handed over in host memory (what --ifile sees, sdr_ifile.c:192-216) -- upload
         # over PCIe + kernels + records home, batches in flight, page-locked buffers.  Reported beside `value`, never as it. ----
         try:
@@ -744,7 +757,7 @@ def main():
             del bufs
         except Exception as e:  # noqa: BLE001 -- reported, never fatal for the headline line
             out["pcie_inclusive"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dcfilter:
+    if rank == 0 and world == 1 and baselines and not args.dcfilter:
         # ---- one lone capture, start to finish: the steady-state figure above is K passes chained by msd_restart(); a single
         # file costs the pipeline's fill and drain as well ----
         try:
@@ -760,7 +773,7 @@ def main():
                                         "what": "msd_restart, every batch of the capture launched and collected, device idle before and after"}
         except Exception as e:  # noqa: BLE001
             out["single_capture_ms"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_dropin and args.format == "uc8" and not args.dcfilter:
+    if rank == 0 and world == 1 and baselines and not args.no_dropin and args.format == "uc8" and not args.dcfilter:
         # ---- the path north_star names: "keeping the sdr.h / fifo.h mag_buf interface so it drops in behind --ifile" -- the
         # replay tool (readsb's part: option keys, hooks, the ifile handler) on a 10 s capture file (BASELINE configs[0]: 24 M
         # samples), once through the literal mag_buf path (iq_convert_fn per 131072-sample block, FIFO, demodulate2400(struct
@@ -822,7 +835,7 @@ def main():
             except OSError:
                 pass
         out["dropin_magbuf"] = dropin
-    if rank == 0 and world == 1 and not args.no_also and not args.no_cpu_baseline and args.format == "uc8" and \
+    if rank == 0 and world == 1 and not args.no_also and baselines and args.format == "uc8" and \
             not (args.mode_ac or args.fields or args.dcfilter or args.fix) and n == 1 << 29:
         # BASELINE configs[2] and configs[4] at full size, after the clock stopped, each against the oracle
         for d in dems:

@@ -2,7 +2,7 @@
 # Round-2 evidence set -> gpurun_out/r02/ (copied to profiles/r02_* afterwards)
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r02; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 bash scripts/profile.sh r02 > $O/profile.log 2>&1
 cp gpurun_out/prof_r02/kernel_stats.csv $O/kernel_stats.csv
 cp gpurun_out/prof_r02/kernel_trace_head.csv $O/scan_kernel_trace_head.csv

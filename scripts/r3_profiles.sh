@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/r03; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 
 kstats() { # <name> <bench args...>: rocprofv3 --kernel-trace --stats summary + the scan kernel's first dispatches
   local name=$1; shift

@@ -8,7 +8,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r06; mkdir -p $O
 PARTS=${PARTS:-bench kstats traffic timeline floor configs density}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 
-has bench && timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+has bench && timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 
 kstats() { # <name> <steps> <samples per launch> <bytes per sample> <bench args...>
   local name=$1 steps=$2 spl=$3 bps=$4; shift 4

@@ -65,3 +65,12 @@ def test_diff_against_oracle_counts_fields_and_counters(pkg, oracle):
     st2["demod_preambles"] = wstats["demod_preambles"] + 1
     assert bench.diff_against_oracle(want, st2, want, wstats) == 1
     assert bench.cpu_model()
+
+
+def test_full_is_off_by_default():
+    """a plain run does only what the headline line needs; the baselines, checks and extra workloads wait for --full"""
+    import bench
+    plain = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and not plain.check and not plain.no_cpu_baseline
+    assert bench.parse(["--full"]).full
+    assert (plain.steps, plain.warmup) == (3, 1)

@@ -27,7 +27,7 @@ def test_bench_two_ranks_one_gpu(torch_cuda):
     env = dict(os.environ, MSD_BENCH_DEVICE_OVERRIDE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--settle-seconds", "1", "--samples", str(n), "--dist-backend", "gloo"]
+           "--settle-seconds", "1", "--samples", str(n), "--dist-backend", "gloo", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -47,7 +47,7 @@ def test_bench_two_ranks_one_gpu(torch_cuda):
     if all(cpus):                                                 # sysfs told: the ranks' CPU slices are disjoint
         spans = [tuple(int(x) for x in c.split("-")) for c in cpus]
         assert spans[0][1] < spans[1][0] or spans[1][1] < spans[0][0], cpus
-    # round 6: an N > 1 line carries its own evidence -- every rank's list against the oracle on its own capture ...
+    # round 6: an N > 1 line carries its own evidence (--full) -- every rank's list against the oracle on its own capture ...
     per = d["message_set_diff_vs_oracle_per_rank"]
     assert [x["rank"] for x in per] == [0, 1] and [x["seed"] for x in per] == [10901, 10902]
     assert all(x["diff"] == 0 and x["messages"] > 1000 and x["buffers"] == 256 for x in per), per
