@@ -522,9 +522,10 @@ int msd_get_remote_stats(const msd_ctx *ctx, msd_remote_stats *st);
  *   - every msd_stats counter, the order-sensitive signal and noise power sums summed in its own message order.
  * Delivery: before the call returns, by entry in the order of the call's entries, then in stream order within an entry.
  * -EINVAL, with the group's state untouched: a receiver id out of range, the same receiver twice in one call,
- * n > max_receivers, nonzero entry flags.  msd_group_create refuses (-EINVAL) msd_config.mode_ac -- the Mode A/C pass
- * reads the batch's magnitudes across buffer boundaries (MsdScanParams.mag_out), which in a group belong to other
- * receivers --, MSD_CFG_DC_FILTER -- the DC block's state runs through the batch in order and would have to be kept
+ * n > max_receivers, nonzero entry flags.  msd_group_create refuses (-EINVAL) msd_config.mode_ac -- that flag would
+ * turn on the wrapped context's own Mode A/C pass, which reads across the batch's buffers (and the magnitudes the scan
+ * leaves, MsdScanParams.mag_out), and in a group those buffers belong to other receivers; Mode A/C is switched per
+ * receiver instead (msd_group_set_receiver_mode_ac below) --, MSD_CFG_DC_FILTER -- the DC block's state runs through the batch in order and would have to be kept
  * per receiver --, MSD_FMT_MAG16 -- its buffers arrive as mag_bufs with their own overlap (msd_demodulate_magbufs),
  * not as a stream -- and sc16q11_table_bits -- that converter writes the batch's magnitudes to an array of its own in
  * front of the scan, and the tails and the power kernels would then have to read that array instead of the IQ.
@@ -538,7 +539,9 @@ int msd_get_remote_stats(const msd_ctx *ctx, msd_remote_stats *st);
  * Device memory: the group wraps a context of max_batch_samples = max_receivers x MSD_CHUNK_SAMPLES in the dense
  * layout, about 60 bytes per sample (dense candidate lists and their region arenas, as estimated for max_batch_samples
  * above): about 7.9 MB per receiver, plus its filter snapshot (65.6 KB), the resolve stage's per-buffer records
- * (about 0.1 MB) and its tail slot (656 bytes UC8, 1312 bytes SC16 / SC16Q11); about 8.2 GB for 1024 receivers. ---- */
+ * (about 0.1 MB) and its tail slot (656 bytes UC8, 1312 bytes SC16 / SC16Q11); about 8.2 GB for 1024 receivers.  Once
+ * a receiver has Mode A/C on, 1 byte per sample more (the candidate arena and its ordered copy, 16 bytes per 32
+ * samples each) and 8 KB per receiver (the accepted replies of the GPU resolve): about 136 MB for 1024 receivers. ---- */
 typedef struct msd_group msd_group;
 typedef struct msd_group_entry {
     uint32_t receiver; /* 0 .. max_receivers-1 */
@@ -581,6 +584,17 @@ typedef struct msd_group_receiver_options {
 } msd_group_receiver_options;
 int msd_group_set_receiver_options(msd_group *g, uint32_t receiver, const msd_group_receiver_options *o);
 int msd_group_get_receiver_options(const msd_group *g, uint32_t receiver, msd_group_receiver_options *o);
+
+/* Mode A/C per receiver (readsb --modeac, and mode_ac_auto's switching at run time, net_io.c:1342-1358): on = 1 turns
+ * the receiver's Mode A/C demodulator on, 0 off.  Every receiver starts off.  The switch may change at any time and
+ * applies from the receiver's next buffer (readsb reads Modes.mode_ac once per buffer, readsb.c:829-833); its Mode A/C
+ * replies follow its Mode S messages of the same buffer, and msd_stats.demod_modeac counts them.
+ * msd_group_reset_receiver keeps the switch.  A call in which no receiver has Mode A/C on does exactly what it does
+ * without this switch.  -EINVAL: a receiver out of range, `on` neither 0 nor 1, NULL.  -ENOMEM: the Mode A/C buffers
+ * (made when the first receiver is switched on; see the memory estimate above) could not be made.  Every error leaves
+ * the group's state untouched. */
+int msd_group_set_receiver_mode_ac(msd_group *g, uint32_t receiver, int on);
+int msd_group_get_receiver_mode_ac(const msd_group *g, uint32_t receiver, int *on);
 
 #ifdef __cplusplus
 }

@@ -219,6 +219,7 @@ EXPORTS = [
     "msd_group_create", "msd_group_destroy", "msd_group_last_error", "msd_group_submit_device", "msd_group_submit_host",
     "msd_group_reset_receiver", "msd_group_get_stats", "msd_group_set_preamble_threshold", "msd_group_get_timing",
     "msd_group_set_receiver_options", "msd_group_get_receiver_options",
+    "msd_group_set_receiver_mode_ac", "msd_group_get_receiver_mode_ac",
 ]
 
 _lib = None
@@ -624,6 +625,10 @@ def _group_lib():
         L.msd_group_set_receiver_options.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(GroupReceiverOptions)]
         L.msd_group_get_receiver_options.restype = C.c_int
         L.msd_group_get_receiver_options.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(GroupReceiverOptions)]
+        L.msd_group_set_receiver_mode_ac.restype = C.c_int
+        L.msd_group_set_receiver_mode_ac.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
+        L.msd_group_get_receiver_mode_ac.restype = C.c_int
+        L.msd_group_get_receiver_mode_ac.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
         L._group_bound = True
     return L
 
@@ -736,3 +741,13 @@ class ReceiverGroup:
         o = GroupReceiverOptions(cur["preamble_threshold"] if preamble_threshold is None else int(preamble_threshold),
                                  cur["nfix_crc"] if nfix_crc is None else int(nfix_crc))
         self._check(_group_lib().msd_group_set_receiver_options(self._h, receiver, C.byref(o)))
+
+    def receiver_mode_ac(self, receiver):
+        """1 if the receiver's Mode A/C demodulator is on, else 0 (off until set)."""
+        on = C.c_int()
+        self._check(_group_lib().msd_group_get_receiver_mode_ac(self._h, receiver, C.byref(on)))
+        return on.value
+
+    def set_receiver_mode_ac(self, receiver, on):
+        """Switch one receiver's Mode A/C on (1) or off (0), from its next buffer; reset_receiver keeps it."""
+        self._check(_group_lib().msd_group_set_receiver_mode_ac(self._h, receiver, int(on)))

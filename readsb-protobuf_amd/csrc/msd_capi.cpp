@@ -372,10 +372,21 @@ struct msd_ctx {
     const uint32_t *group_lb = nullptr;
     const uint32_t *group_opt = nullptr; /* every buffer's receiver options (MsdScanParams.group_opt) */
     bool group_fix2 = false;             /* some buffer of the call is at repair level 2: the FIX2 instantiation */
+    /* ... and the call's buffers whose receiver has Mode A/C on: ascending buffer indices, on the device (the group's
+     * control rows) and on the host; group_nac 0: no Mode A/C in this call */
+    const uint32_t *group_ac = nullptr;
+    const uint32_t *group_ac_host = nullptr;
+    uint32_t group_nac = 0;
     char err[256] = {0};
 };
 
 namespace {
+
+/* the batch in hand has a Mode A/C pass: the context's configuration, or a receiver group call with some receiver on */
+inline bool ac_on(const msd_ctx *c)
+{
+    return c->cfg.mode_ac || c->group_nac;
+}
 
 /* why the calling thread's last msd_create failed (there is no context to hold the text yet);
  * msd_last_error(NULL) returns it */
@@ -619,12 +630,12 @@ int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pi
     /* d_sums is zero: whoever published the slot's previous batch left it so.  The offsets kernel
      * overwrites the totals. */
     const bool fm = format == MSD_FMT_SC16 || format == MSD_FMT_SC16Q11 || s.dc;
-    const bool gather_publishes = nwg && !c->cfg.mode_ac && !fm; /* totals and sums are published by the gather kernel */
+    const bool gather_publishes = nwg && !ac_on(c) && !fm; /* totals and sums are published by the gather kernel */
     if (!nwg) {
         HIPCHK(c, hipMemsetAsync(s.d_totals, 0, sizeof(uint64_t) * 4, c->stream));
         s.buf_first_valid = false;
     }
-    if (c->cfg.mode_ac && !(s.nbuffers && s.nsamples)) /* (msd_launch_ac's offsets kernel writes them otherwise) */
+    if (ac_on(c) && !(s.nbuffers && s.nsamples)) /* (msd_launch_ac's offsets kernel writes them otherwise) */
         HIPCHK(c, hipMemsetAsync(s.d_ac_totals, 0, sizeof(uint64_t) * 4, c->stream));
     /* the three timing events cost about 5 us of stream time each (a barrier packet per record): they are
      * recorded for one batch in every c->timing_interval */
@@ -773,7 +784,24 @@ int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pi
         if (rc)
             return fail(c, rc, "float means kernel launch failed");
     }
-    if (c->cfg.mode_ac && s.nbuffers) {
+    if (c->group_lb && c->group_nac && s.nbuffers) {
+        /* a receiver group: the listed buffers of this batch (a whole call, or a piece of a rescanned one) */
+        const uint32_t b0 = (uint32_t)(s.batch_first / MSD_CHUNK_SAMPLES);
+        const uint32_t *lo = std::lower_bound(c->group_ac_host, c->group_ac_host + c->group_nac, b0);
+        const uint32_t *hi = std::lower_bound(lo, c->group_ac_host + c->group_nac, b0 + s.nbuffers);
+        MsdScanParams p{};
+        fill_params(c, s, p);
+        p.group_tails = c->group_tails;
+        p.group_lb = c->group_lb + b0;
+        p.prev_tail = nullptr;
+        p.have_prev = 0;
+        p.debug_flags = c->debug_flags;
+        int rc = msd_launch_group_ac(&p, format, s.d_sums, s.d_fmeans, c->group_ac + (lo - c->group_ac_host), (uint32_t)(hi - lo),
+                                     b0, s.d_ac_regions, c->ac_arena, s.d_ac_counts, s.d_ac_totals, s.d_ac, c->ac_arena,
+                                     c->ac_max_wg, c->stream);
+        if (rc)
+            return fail(c, rc, "Mode A/C kernel launch failed");
+    } else if (c->cfg.mode_ac && s.nbuffers) {
         if (host_noise)
             HIPCHK(c, hipMemcpyAsync(c->d_noise, host_noise, sizeof(uint32_t) * s.nbuffers, hipMemcpyHostToDevice,
                                      c->stream));
@@ -800,7 +828,7 @@ int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pi
 
     /* totals and per-buffer sums go to pinned host memory from this stream, right behind the kernels */
     if (!gather_publishes && !s.lean) {
-        int rc = msd_launch_publish(s.d_totals, c->cfg.mode_ac ? s.d_ac_totals : nullptr, s.d_sums,
+        int rc = msd_launch_publish(s.d_totals, ac_on(c) ? s.d_ac_totals : nullptr, s.d_sums,
                                     fm ? s.d_fmeans : nullptr, s.nbuffers, s.h_totals, s.h_ac_totals, s.h_sums,
                                     s.h_fmeans, c->stream);
         if (rc)
@@ -881,8 +909,8 @@ int rerun_in_pieces(msd_ctx *c, Slot &s, int format)
                 return rc;
             HIPCHK(c, hipEventSynchronize(t.ev_totals));
             const uint64_t H = s.h_totals[0], Tn = s.h_totals[1];
-            const uint64_t nac = c->cfg.mode_ac ? s.h_ac_totals[0] : 0;
-            if (s.h_totals[2] || (c->cfg.mode_ac && s.h_ac_totals[2])) {
+            const uint64_t nac = ac_on(c) ? s.h_ac_totals[0] : 0;
+            if (s.h_totals[2] || (ac_on(c) && s.h_ac_totals[2])) {
                 if (piece == MSD_CHUNK_SAMPLES)
                     return fail(c, -EOVERFLOW, "candidate arena overflow on a single buffer");
                 again = true;
@@ -936,7 +964,7 @@ int rerun_in_pieces(msd_ctx *c, Slot &s, int format)
         s.h_totals[0] = hits.size();
         s.h_totals[1] = tries.size();
         s.h_totals[2] = 0;
-        if (c->cfg.mode_ac) {
+        if (ac_on(c)) {
             s.h_ac_totals[0] = acs.size();
             s.h_ac_totals[2] = 0;
         }
@@ -967,7 +995,7 @@ int start_download(msd_ctx *c, Slot &s, int format)
         fprintf(stderr, "start_download: waited %.3f ms for the totals; scan %.3f ms, all kernels %.3f ms after its start\n",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count(), a, b);
     }
-    const bool overflow = s.h_totals[2] || (c->cfg.mode_ac && s.h_ac_totals[2]);
+    const bool overflow = s.h_totals[2] || (ac_on(c) && s.h_ac_totals[2]);
     if (overflow) {
         int rc = rerun_in_pieces(c, s, format);
         if (rc)
@@ -987,7 +1015,7 @@ int start_download(msd_ctx *c, Slot &s, int format)
             HIPCHK(c, hipMemcpyAsync(s.h_hits, s.d_hits, H * sizeof(msd_hit), hipMemcpyDeviceToHost, c->copy_stream));
         if (Tn)
             HIPCHK(c, hipMemcpyAsync(s.h_tries, s.d_tries, Tn * sizeof(msd_try), hipMemcpyDeviceToHost, c->copy_stream));
-        if (c->cfg.mode_ac) {
+        if (ac_on(c)) {
             const uint64_t nac = s.h_ac_totals[0];
             rc = ensure_ac_host(c, s, nac);
             if (rc)
@@ -1046,7 +1074,7 @@ void gpu_params(const msd_ctx *c, const Slot &s, MsdResolveParams &rp)
     rp.nmsgs = s.d_nmsgs;
     rp.acc = s.d_acc;
     rp.adds = s.d_adds;
-    if (c->cfg.mode_ac) {
+    if (ac_on(c)) {
         rp.ac = s.d_ac;
         rp.ac_totals = s.d_ac_totals;
         rp.acc_ac = s.d_acc_ac;
@@ -3044,6 +3072,7 @@ struct GroupReceiver {
     bool have_tail = false; /* its tail slot holds the end of its previous buffer */
     bool history = false;   /* a buffer since creation or the last reset: the repair level is fixed */
     msd_group_receiver_options opt{}; /* kept across msd_group_reset_receiver */
+    bool mode_ac = false;             /* Mode A/C on (readsb --modeac), likewise kept */
 };
 
 /* what the host resolver delivers for one entry of a call */
@@ -3051,6 +3080,7 @@ struct GroupEntryOut {
     std::vector<msd_message> msgs;
     std::vector<uint64_t> req;
     std::vector<msd_hit> hits; /* the entry's hits, positions made buffer-relative */
+    std::vector<msd_ac_hit> ac; /* its Mode A/C candidates, likewise */
     double means[2] = {0, 0};
     uint32_t valid = MSD_CHUNK_SAMPLES;
 };
@@ -3095,8 +3125,8 @@ struct msd_group {
     bool gpu = false;     /* resolve on the GPU against the receivers' device snapshots (not MSD_CFG_HOST_RESOLVE) */
     GroupReceiver *rx = nullptr;
     uint8_t *d_tails = nullptr;    /* [max_receivers][MSD_HALO_FRONT] raw samples */
-    uint32_t *d_ctl = nullptr;     /* [3][max_receivers]: per buffer its look-behind slot, its receiver and its receiver's
-                                      options (threshold | nfix_crc << 16) */
+    uint32_t *d_ctl = nullptr;     /* [4][max_receivers]: per buffer its look-behind slot, its receiver and its receiver's
+                                      options (threshold | nfix_crc << 16); then the call's buffers with Mode A/C on */
     uint32_t *h_ctl = nullptr;     /* pinned copy */
     uint32_t *d_snaps = nullptr;   /* [max_receivers][MSD_SNAP_WORDS]: every receiver's ICAO filter on the device */
     uint32_t *h_apply = nullptr;   /* pinned, read in place by the filter kernel: slot[n] | add_first[n + 1] | flip[n] */
@@ -3189,6 +3219,57 @@ int group_make_fix2(msd_group *g)
     return 0;
 }
 
+/* The Mode A/C buffers of the group's context (slot 0, the only one a group uses): the candidate kernel's regions and
+ * counts, the ordered list and its totals, and for the GPU resolve the accepted replies per buffer -- made when the first
+ * receiver is switched on.  The arena holds a candidate per 32 samples of a full call, and never less than one per
+ * sample of one buffer, so that a call rescanned in pieces always fits once the pieces are single buffers. */
+int group_make_ac(msd_group *g)
+{
+    msd_ctx *c = g->ctx;
+    Slot &s = c->slots[0];
+    if (s.d_ac)
+        return 0;
+    GHIPCHK(g, hipSetDevice(c->cfg.device));
+    const uint64_t B = c->cfg.max_batch_samples;
+    const uint64_t arena = B / 32 > MIN_HIT_ARENA ? B / 32 : MIN_HIT_ARENA;
+    const uint32_t max_wg = (uint32_t)c->cu_count * 28u; /* as msd_create: one region per resident wavefront */
+    msd_ac_hit *regions = nullptr, *dense = nullptr;
+    msd_wg_counts *counts = nullptr;
+    uint64_t *totals = nullptr, *h_totals = nullptr;
+    uint32_t *acc_ac = nullptr, *nac = nullptr;
+    bool ok = hipMalloc(reinterpret_cast<void **>(&regions), arena * sizeof(msd_ac_hit)) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void **>(&dense), arena * sizeof(msd_ac_hit)) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void **>(&counts), max_wg * sizeof(msd_wg_counts)) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void **>(&totals), 4 * sizeof(uint64_t)) == hipSuccess &&
+              hipHostMalloc(reinterpret_cast<void **>(&h_totals), 4 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
+    if (ok && g->gpu)
+        ok = hipMalloc(reinterpret_cast<void **>(&acc_ac), sizeof(uint32_t) * MSD_RB_AC_CAP * c->max_buffers) == hipSuccess &&
+             hipMalloc(reinterpret_cast<void **>(&nac), sizeof(uint32_t) * c->max_buffers) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        (void)hipFree(regions);
+        (void)hipFree(dense);
+        (void)hipFree(counts);
+        (void)hipFree(totals);
+        if (h_totals)
+            (void)hipHostFree(h_totals);
+        (void)hipFree(acc_ac);
+        (void)hipFree(nac);
+        return gfail(g, -ENOMEM, "Mode A/C buffers: out of memory");
+    }
+    memset(h_totals, 0, 4 * sizeof(uint64_t));
+    s.d_ac_regions = regions;
+    s.d_ac = dense;
+    s.d_ac_counts = counts;
+    s.d_ac_totals = totals;
+    s.h_ac_totals = h_totals;
+    s.d_acc_ac = acc_ac;
+    s.d_nac = nac;
+    c->ac_arena = arena;
+    c->ac_max_wg = max_wg;
+    return 0;
+}
+
 int group_check(const msd_group *g, const msd_group_entry *e, uint32_t n)
 {
     if (n > g->max_receivers)
@@ -3217,14 +3298,18 @@ int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const st
     const uint64_t H = s.h_totals[0];
     const msd_hit *hits = s.h_hits;
     const uint32_t n = s.nbuffers;
-    std::vector<uint64_t> first(n + 1);
+    const uint64_t NA = ac_on(c) ? s.h_ac_totals[0] : 0; /* Mode A/C candidates of the call (s.h_ac), ordered */
+    std::vector<uint64_t> first(n + 1), ac_first(n + 1);
     {
-        uint64_t h = 0;
+        uint64_t h = 0, a = 0;
         for (uint32_t i = 0; i <= n; ++i) {
             const uint64_t pos = (uint64_t)i * MSD_CHUNK_SAMPLES;
             while (h < H && MSD_HIT_POS(hits[h]) < pos)
                 ++h;
+            while (a < NA && s.h_ac[a].pos < pos)
+                ++a;
             first[i] = h;
+            ac_first[i] = a;
         }
     }
     parallel_for((uint32_t)idx.size(), g->threads, [&](uint32_t k) {
@@ -3234,8 +3319,11 @@ int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const st
         o.hits.assign(hits + first[i], hits + first[i + 1]);
         for (msd_hit &h : o.hits)
             h -= (msd_hit)i * MSD_CHUNK_SAMPLES; /* position is the low field */
-        msd_resolve_batch(&r.resolver, 0, 1, &o.valid, o.hits.data(), o.hits.size(), s.h_tries, s.h_totals[1], nullptr, 0,
-                          nullptr, group_emit, &o);
+        o.ac.assign(s.h_ac + ac_first[i], s.h_ac + ac_first[i + 1]); /* (none unless its receiver has Mode A/C on) */
+        for (msd_ac_hit &a : o.ac)
+            a.pos -= (uint64_t)i * MSD_CHUNK_SAMPLES;
+        msd_resolve_batch(&r.resolver, 0, 1, &o.valid, o.hits.data(), o.hits.size(), s.h_tries, s.h_totals[1], o.ac.data(),
+                          o.ac.size(), nullptr, group_emit, &o);
     });
     g->req_all.clear();
     for (uint32_t i : idx)
@@ -3318,6 +3406,8 @@ int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vect
     rp.first_pass = 0;
     rp.ctl_implicit = 0;
     GHIPCHK(g, hipMemsetAsync(s.d_nmsgs, 0, sizeof(uint32_t) * n, c->stream)); /* host-resolved buffers emit nothing */
+    if (rp.ac)
+        GHIPCHK(g, hipMemsetAsync(s.d_nac, 0, sizeof(uint32_t) * n, c->stream));
     int rc = msd_launch_resolve(&rp, ntodo, c->stream);
     if (rc)
         return gfail(g, rc, "resolve kernel launch failed");
@@ -3341,6 +3431,8 @@ int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vect
         if (s.h_rbuf[i].fallback) {
             host.push_back(i);
             GHIPCHK(g, hipMemsetAsync(s.d_nmsgs + i, 0, sizeof(uint32_t), c->stream));
+            if (rp.ac)
+                GHIPCHK(g, hipMemsetAsync(s.d_nac + i, 0, sizeof(uint32_t), c->stream));
             zeroed = true;
         }
     }
@@ -3354,7 +3446,7 @@ int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vect
     for (uint32_t i = 0, k = 0; i < n; ++i) {
         rec_first[i] = total;
         if (k < gpu_idx.size() && gpu_idx[k] == i) {
-            total += s.h_rbuf[i].nmsgs;
+            total += s.h_rbuf[i].nmsgs + s.h_rbuf[i].nac; /* its Mode S messages, then its Mode A/C replies (0: off) */
             ++k;
         }
     }
@@ -3421,6 +3513,7 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     const uint64_t nsamples = (uint64_t)n * MSD_CHUNK_SAMPLES;
     /* look-behind: the receiver's tail slot unless it has none yet or lost samples in front of this buffer (fifo.c:178-181) */
     uint32_t *lb = g->h_ctl, *slot = g->h_ctl + g->max_receivers, *opt = g->h_ctl + 2 * g->max_receivers;
+    uint32_t *ac = g->h_ctl + 3 * g->max_receivers, nac = 0;
     bool fix2 = false;
     for (uint32_t i = 0; i < n; ++i) {
         GroupReceiver &r = g->rx[e[i].receiver];
@@ -3429,8 +3522,12 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
         opt[i] = (uint32_t)r.opt.preamble_threshold | (uint32_t)r.opt.nfix_crc << 16;
         fix2 |= r.opt.nfix_crc == 2;
         r.history = true;
+        if (r.mode_ac) /* readsb.c:829-833: the switch as it stands when the buffer is demodulated */
+            ac[nac++] = i;
+        r.resolver.mode_ac = r.mode_ac; /* (the host resolver, if the buffer goes there) */
     }
-    GHIPCHK(g, hipMemcpyAsync(g->d_ctl, g->h_ctl, sizeof(uint32_t) * 3 * g->max_receivers, hipMemcpyHostToDevice, c->stream));
+    GHIPCHK(g, hipMemcpyAsync(g->d_ctl, g->h_ctl, sizeof(uint32_t) * (3 * (size_t)g->max_receivers + nac), hipMemcpyHostToDevice,
+                              c->stream));
 
     Slot &s = c->slots[0];
     s.busy = true;
@@ -3452,6 +3549,9 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     c->group_lb = g->d_ctl;
     c->group_opt = g->d_ctl + 2 * g->max_receivers;
     c->group_fix2 = fix2;
+    c->group_ac = g->d_ctl + 3 * g->max_receivers;
+    c->group_ac_host = ac;
+    c->group_nac = nac;
     struct Unset { /* the context's stream entries never see the group's look-behind */
         msd_ctx *c;
         Slot &s;
@@ -3461,6 +3561,9 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
             c->group_lb = nullptr;
             c->group_opt = nullptr;
             c->group_fix2 = false;
+            c->group_ac = nullptr;
+            c->group_ac_host = nullptr;
+            c->group_nac = 0;
             s.busy = false;
             s.download_started = false;
         }
@@ -3506,6 +3609,14 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
                 GHIPCHK(g, hipMemcpyAsync(s.h_hits, s.d_hits, s.h_totals[0] * sizeof(msd_hit), hipMemcpyDeviceToHost, c->stream));
             if (s.h_totals[1])
                 GHIPCHK(g, hipMemcpyAsync(s.h_tries, s.d_tries, s.h_totals[1] * sizeof(msd_try), hipMemcpyDeviceToHost, c->stream));
+            if (nac) {
+                rc = ensure_ac_host(c, s, s.h_ac_totals[0]);
+                if (rc)
+                    return gfail(g, rc, "lists: %s", c->err);
+                if (s.h_ac_totals[0])
+                    GHIPCHK(g, hipMemcpyAsync(s.h_ac, s.d_ac, s.h_ac_totals[0] * sizeof(msd_ac_hit), hipMemcpyDeviceToHost,
+                                              c->stream));
+            }
             GHIPCHK(g, hipStreamSynchronize(c->stream));
         }
     } else {
@@ -3577,8 +3688,8 @@ int msd_group_create(const msd_config *cfg, uint32_t max_receivers, msd_group **
     g->rx = new (std::nothrow) GroupReceiver[max_receivers];
     const size_t tail_bytes = (size_t)max_receivers * MSD_HALO_FRONT * g->ctx->bps;
     if (!g->rx || hipMalloc(reinterpret_cast<void **>(&g->d_tails), tail_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&g->d_ctl), sizeof(uint32_t) * 3 * max_receivers) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&g->h_ctl), sizeof(uint32_t) * 3 * max_receivers, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&g->d_ctl), sizeof(uint32_t) * 4 * max_receivers) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&g->h_ctl), sizeof(uint32_t) * 4 * max_receivers, hipHostMallocDefault) != hipSuccess ||
         (g->gpu && (hipMalloc(reinterpret_cast<void **>(&g->d_snaps), sizeof(uint32_t) * MSD_SNAP_WORDS * max_receivers) != hipSuccess ||
                     hipHostMalloc(reinterpret_cast<void **>(&g->h_apply), sizeof(uint32_t) * (3 * (size_t)max_receivers + 1),
                                   hipHostMallocDefault) != hipSuccess ||
@@ -3743,6 +3854,29 @@ int msd_group_get_receiver_options(const msd_group *g, uint32_t receiver, msd_gr
     if (!g || !o || receiver >= g->max_receivers)
         return -EINVAL;
     *o = g->rx[receiver].opt;
+    return 0;
+}
+
+int msd_group_set_receiver_mode_ac(msd_group *g, uint32_t receiver, int on)
+{
+    if (!g)
+        return -EINVAL;
+    if (receiver >= g->max_receivers || (on != 0 && on != 1))
+        return gfail(g, -EINVAL, "Mode A/C: receiver %u out of range or switch %d not 0 or 1", receiver, on);
+    if (on) {
+        const int rc = group_make_ac(g);
+        if (rc)
+            return rc;
+    }
+    g->rx[receiver].mode_ac = on != 0;
+    return 0;
+}
+
+int msd_group_get_receiver_mode_ac(const msd_group *g, uint32_t receiver, int *on)
+{
+    if (!g || !on || receiver >= g->max_receivers)
+        return -EINVAL;
+    *on = g->rx[receiver].mode_ac ? 1 : 0;
     return 0;
 }
 

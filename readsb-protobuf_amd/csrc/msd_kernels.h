@@ -211,6 +211,14 @@ int msd_launch_ac(const MsdScanParams *p, int format, const uint64_t *d_sums, co
                   uint32_t nbuffers, uint32_t *d_noise, int noise_ready, msd_ac_hit *d_regions,
                   uint64_t region_total, msd_wg_counts *d_counts, uint64_t *d_offsets, uint64_t *d_totals,
                   msd_ac_hit *d_dense, uint64_t dense_cap, uint32_t max_wg, int phase, hipStream_t stream);
+/* receiver groups (p->group_lb set): the Mode A/C candidate stage of the buffers d_list[0 .. nlist) - list_first only
+ * (ascending; the entries whose receiver has Mode A/C on), each buffer's look-behind from its tail slot; noise levels
+ * from the buffers' own sums (d_fmeans for SC16 / SC16Q11).  d_totals and d_dense as msd_launch_ac; nlist 0 launches no
+ * kernel and zeroes d_totals. */
+int msd_launch_group_ac(const MsdScanParams *p, int format, const uint64_t *d_sums, const float *d_fmeans,
+                        const uint32_t *d_list, uint32_t nlist, uint32_t list_first, msd_ac_hit *d_regions,
+                        uint64_t region_total, msd_wg_counts *d_counts, uint64_t *d_totals, msd_ac_hit *d_dense,
+                        uint64_t dense_cap, uint32_t max_wg, hipStream_t stream);
 /* SC16Q11 through the table of a -DSC16Q11_TABLE_BITS reference (convert.c:264-328): IQ -> u16 magnitudes; d_sums (or NULL)
  * receives the level / power sums the converter entry reports */
 int msd_launch_q11_table(const void *d_iq, uint64_t nsamples, const uint16_t *d_table, int bits, uint16_t *d_mag,

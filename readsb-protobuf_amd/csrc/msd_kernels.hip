@@ -2915,11 +2915,17 @@ constexpr int ACW_BITS_BYTES = 4 * 64 * 4;     /* clock, two thresholds, bits of
 constexpr int ACW_BYTES = ACW_MAGS_BYTES + ACW_SURV_BYTES + ACW_BITS_BYTES;
 static_assert(ACW_LOAD % 8 == 0 && MSD_CHUNK_SAMPLES % ACW == 0 && ACW_BYTES % 16 == 0, "whole groups, tiles inside one buffer");
 
-template <int FMT>
+/* GROUP (receiver groups, MsdScanParams.group_lb): only the buffers listed in ac_list -- ascending batch buffer indices
+ * plus list_first, the entries whose receiver has Mode A/C on -- are scanned, MSD_CHUNK_SAMPLES / ACW tiles each, tile t
+ * in buffer ac_list[t / (MSD_CHUNK_SAMPLES / ACW)] - list_first.  A buffer's first tile takes its look-behind from its
+ * receiver's tail slot, or zeros, never from the batch's previous buffer (fetch_lookbehind). */
+constexpr uint32_t AC_TILES_PER_BUFFER = MSD_CHUNK_SAMPLES / ACW;
+template <int FMT, bool GROUP = false>
 __global__ void __launch_bounds__(ACNT, 5) msd_ac_wave_kernel(const MsdScanParams P, uint32_t ntiles, uint32_t tiles_per_wave,
                                                             const uint32_t *noise_levels /* or NULL: from the sums */,
                                                             const uint64_t *sums, const float *fmeans, int use_float, msd_ac_hit *out,
-                                                            uint32_t cap, msd_wg_counts *counts)
+                                                            uint32_t cap, msd_wg_counts *counts,
+                                                            const uint32_t *ac_list /* GROUP only */, uint32_t list_first)
 {
     __shared__ __attribute__((aligned(16))) unsigned char lds[(ACNT / 64) * ACW_BYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2945,8 +2951,29 @@ __global__ void __launch_bounds__(ACNT, 5) msd_ac_wave_kernel(const MsdScanParam
      * addresses (fetch_group selects one of four sources per lane and group: a dozen 64-bit compares and selects), and in
      * the 16-bit-magnitude instantiation, the one the pipeline uses, its words go to the LDS as they came. */
     bool inside_next = false;
+    /* GROUP: the first F1 position of a tile, batch-relative (a scalar load of the list, once per tile) */
+    auto group_tile_pos = [&](uint32_t tile) -> uint64_t {
+        return (uint64_t)(ac_list[tile / AC_TILES_PER_BUFFER] - list_first) * MSD_CHUNK_SAMPLES +
+               (uint64_t)(tile % AC_TILES_PER_BUFFER) * ACW;
+    };
     auto fetch = [&](uint32_t tile) {
-        const int64_t rel0 = (int64_t)((uint64_t)tile * ACW) - FRONT;
+        int64_t rel0 = (int64_t)((uint64_t)tile * ACW) - FRONT;
+        if constexpr (GROUP) {
+            const uint64_t tp = group_tile_pos(tile);
+            rel0 = (int64_t)tp - FRONT;
+            if (tp % MSD_CHUNK_SAMPLES == 0) { /* wave-uniform: a buffer's first tile -- its receiver's look-behind */
+                inside_next = false;
+#pragma unroll
+                for (int i = 0; i < GPT_W; ++i) {
+                    const int g = lane + 64 * i;
+                    if (g < FRONT / 8) /* the FRONT samples in front of the buffer: the tail slot, or zeros */
+                        vg[i] = fetch_lookbehind<FMT>(P, tp, g, rg[i]);
+                    else
+                        vg[i] = fetch_group<FMT>(P, (int64_t)P.batch_first + rel0 + 8 * (g < ACW_GROUPS ? g : 0), rg[i]);
+                }
+                return;
+            }
+        }
         inside_next = rel0 >= 0 && (uint64_t)rel0 + ACW_LOAD <= (P.nsamples & ~7ull); /* wave-uniform */
         if (inside_next) {
             constexpr int BPS = RawGroup<FMT>::WORDS / 2;
@@ -2975,7 +3002,7 @@ __global__ void __launch_bounds__(ACNT, 5) msd_ac_wave_kernel(const MsdScanParam
     if (tile_lo < tile_hi)
         fetch(tile_lo);
     for (uint32_t tile = tile_lo; tile < tile_hi; ++tile) {
-        const uint64_t pos0 = (uint64_t)tile * ACW; /* batch-relative */
+        const uint64_t pos0 = GROUP ? group_tile_pos(tile) : (uint64_t)tile * ACW; /* batch-relative */
         const bool inside = inside_next;
         if (FMT == MSD_FMT_MAG16 && inside) { /* wave-uniform */
 #pragma unroll
@@ -3434,7 +3461,7 @@ extern "C" int msd_launch_ac(const MsdScanParams *p, int format, const uint64_t 
         cap = (uint64_t)tpw * ACW;
 #define MSD_AC_LAUNCH(F)                                                                                                     \
     hipLaunchKernelGGL(msd_ac_wave_kernel<F>, dim3(nblocks), dim3(ACNT), 0, stream, *p, ntiles, tpw, levels, d_sums, d_fmeans, \
-                       use_float, d_regions, (uint32_t)cap, d_counts)
+                       use_float, d_regions, (uint32_t)cap, d_counts, nullptr, 0u)
     if (phase != 2)
         switch (format) {
         case MSD_FMT_UC8: MSD_AC_LAUNCH(MSD_FMT_UC8); break;
@@ -3448,6 +3475,43 @@ extern "C" int msd_launch_ac(const MsdScanParams *p, int format, const uint64_t 
     if (phase != 1)
         hipLaunchKernelGGL(msd_ac_gather_kernel, dim3(nblocks), dim3(256), 0, stream, d_counts, nblocks, d_regions, (uint32_t)cap, d_dense,
                        dense_cap, d_totals);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int msd_launch_group_ac(const MsdScanParams *p, int format, const uint64_t *d_sums, const float *d_fmeans,
+                                   const uint32_t *d_list, uint32_t nlist, uint32_t list_first, msd_ac_hit *d_regions,
+                                   uint64_t region_total, msd_wg_counts *d_counts, uint64_t *d_totals, msd_ac_hit *d_dense,
+                                   uint64_t dense_cap, uint32_t max_wg, hipStream_t stream)
+{
+    if (!p->group_lb)
+        return -22;
+    if (nlist == 0) { /* no buffer of the call has Mode A/C on: no kernel */
+        (void)hipMemsetAsync(d_totals, 0, 4 * sizeof(uint64_t), stream);
+        return hipGetLastError() == hipSuccess ? 0 : -5;
+    }
+    const int use_float = (format == MSD_FMT_SC16 || format == MSD_FMT_SC16Q11);
+    /* the same split as msd_launch_ac, over the listed buffers' tiles only */
+    const uint32_t ntiles = nlist * AC_TILES_PER_BUFFER;
+    uint32_t tpw = (ntiles + max_wg - 1) / max_wg;
+    if (tpw == 0)
+        tpw = 1;
+    const uint32_t nwg = (ntiles + tpw - 1) / tpw;
+    const uint32_t nblocks = (nwg + ACNT / 64 - 1) / (ACNT / 64);
+    uint64_t cap = region_total / ((uint64_t)nblocks * (ACNT / 64));
+    if (cap > (uint64_t)tpw * ACW)
+        cap = (uint64_t)tpw * ACW;
+#define MSD_GROUP_AC_LAUNCH(F)                                                                                              \
+    hipLaunchKernelGGL((msd_ac_wave_kernel<F, true>), dim3(nblocks), dim3(ACNT), 0, stream, *p, ntiles, tpw, nullptr, d_sums, \
+                       d_fmeans, use_float, d_regions, (uint32_t)cap, d_counts, d_list, list_first)
+    switch (format) {
+    case MSD_FMT_UC8: MSD_GROUP_AC_LAUNCH(MSD_FMT_UC8); break;
+    case MSD_FMT_SC16: MSD_GROUP_AC_LAUNCH(MSD_FMT_SC16); break;
+    case MSD_FMT_SC16Q11: MSD_GROUP_AC_LAUNCH(MSD_FMT_SC16Q11); break;
+    default: return -22;
+    }
+#undef MSD_GROUP_AC_LAUNCH
+    hipLaunchKernelGGL(msd_ac_gather_kernel, dim3(nblocks), dim3(256), 0, stream, d_counts, nblocks, d_regions, (uint32_t)cap,
+                       d_dense, dense_cap, d_totals);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -13,7 +13,14 @@ rocprofv3 --kernel-trace --stats -- python scripts/receiver_group_rate.py --only
 
 times the K = 1024 call with per-receiver options (thresholds spread over 40..400, repair levels 0 / 1 / 2 mixed)
 beside the same call with every receiver at the group's defaults, alternating, in one process; writes
-profiles/receiver_group_options_rate.json."""
+profiles/receiver_group_options_rate.json.
+
+    python scripts/receiver_group_rate.py --modeac [--reps 20]
+
+times the K = 1024 call with Mode A/C off for every receiver, on for every other one, and on for all, alternating, in
+one process, over a capture with 2000 Mode A/C replies a second; writes profiles/receiver_group_modeac_rate.json.  Its
+kernel trace: rocprofv3 --kernel-trace --stats -- python scripts/receiver_group_rate.py --modeac --reps 3 --out
+/tmp/x.json (profiles/receiver_group_modeac_k1024_kernel_stats.csv)."""
 import argparse
 import json
 import os
@@ -33,15 +40,18 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", type=int, default=0)
     ap.add_argument("--mixed", action="store_true")
+    ap.add_argument("--modeac", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "receiver_group_options_rate.json" if a.mixed else "receiver_group_rate.json")
+        a.out = os.path.join(ROOT, "profiles", "receiver_group_options_rate.json" if a.mixed else
+                             "receiver_group_modeac_rate.json" if a.modeac else "receiver_group_rate.json")
     import __graft_entry__ as g
     pkg = g.load_package()
     import torch
     capi, siggen = pkg.capi, pkg.siggen
-    base = siggen.generate(siggen.make_cfg(seed=17, msgs_per_sec=3000, n_aircraft=60), 64 * CHUNK)
+    base = siggen.generate(siggen.make_cfg(seed=17, msgs_per_sec=3000, n_aircraft=60, ac_per_sec=2000 if a.modeac else 0),
+                           64 * CHUNK)
     ks = [a.only] if a.only else [1, 16, 256, 1024]
     kmax = max(ks)
     host = np.empty(kmax * CHUNK * 2, dtype=np.uint8)
@@ -50,6 +60,8 @@ def main():
     dev = torch.from_numpy(host).cuda()
     if a.mixed:
         return mixed(a, capi, dev, host)
+    if a.modeac:
+        return modeac(a, capi, dev, host)
     res = {"buffer_samples": CHUNK, "format": "uc8", "reps": a.reps, "group": {}}
     for k in ks:
         grp = capi.ReceiverGroup(k, fmt=capi.FMT_UC8)
@@ -106,6 +118,23 @@ def mixed(a, capi, dev, host):
         groups["mixed"].set_receiver_options(r, preamble_threshold=t, nfix_crc=n)
     res = {"buffer_samples": CHUNK, "format": "uc8", "receivers": k, "reps": a.reps,
            "mixed_options": "threshold 40 + (97 r) % 361, nfix_crc r % 3", "calls": {}}
+    alternate(a, k, groups, dev, host, res)
+
+
+def modeac(a, capi, dev, host):
+    k = 1024
+    groups = {name: capi.ReceiverGroup(k, fmt=capi.FMT_UC8) for name in ("off", "half", "all")}
+    for r in range(k):
+        if r % 2 == 0:
+            groups["half"].set_receiver_mode_ac(r, 1)
+        groups["all"].set_receiver_mode_ac(r, 1)
+    res = {"buffer_samples": CHUNK, "format": "uc8", "receivers": k, "reps": a.reps,
+           "capture": "siggen seed 17, 3000 Mode S and 2000 Mode A/C replies a second",
+           "mode_ac": "off: none, half: even receivers, all: every receiver", "calls": {}}
+    alternate(a, k, groups, dev, host, res, modeac=True)
+
+
+def alternate(a, k, groups, dev, host, res, modeac=False):
     for where, iq in (("device", dev), ("host", host)):
         ts = {name: [] for name in groups}
         for grp in groups.values():
@@ -125,6 +154,8 @@ def mixed(a, capi, dev, host):
         t = grp.timing()
         res["calls"][name]["timing"] = {x: t[x] for x in ("hits", "tries", "reruns", "resolve_passes", "resolve_fallback")}
         res["calls"][name]["accepted"] = int(sum(sum(grp.stats(r)["demod_accepted"]) for r in range(k)))
+        if modeac:
+            res["calls"][name]["demod_modeac"] = int(sum(grp.stats(r)["demod_modeac"] for r in range(k)))
         grp.close()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
