@@ -10,6 +10,8 @@
  * With three batches in flight (msd_launch_device / msd_collect), while the host resolves batch k
  * the lists of batch k+1 come down and the GPU scans batch k+2; msd_submit_* is the depth-1
  * synchronous form.
+ *
+ * Receiver groups (msd_group_*) are driven from msd_group.cpp; msd_ctx.h is what it shares with this file.
  */
 #include <hip/hip_runtime.h>
 
@@ -31,118 +33,17 @@
 #include <vector>
 
 #include "modes_hip.h"
+#include "msd_ctx.h"
 #include "msd_internal.h"
 #include "msd_frames.h"
 #include "msd_kernels.h"
 
 extern "C" int msd_tables_selftest(const msd_tables *t);
 
-namespace {
+#pragma GCC visibility push(hidden) /* internal, some of it shared with msd_group.cpp (msd_ctx.h) */
+namespace msd_impl {
 
-constexpr uint64_t MIN_HIT_ARENA = 131072;      /* every position of one buffer */
-constexpr uint64_t MIN_TRY_ARENA = 131072 * 5;  /* every phase of every position of one buffer */
 constexpr int TAIL_SAMPLES = MSD_HALO_FRONT;
-
-/* One helper thread per context for the per-message part of finishing a batch (signal level, power
- * statistics, the copy into the caller's arrays), so that it overlaps with the calling thread queueing
- * the next batch's resolve.  At most one job at a time; run() returns at once, wait() joins it. */
-struct Helper {
-    /* one worker thread, jobs in order.  A job may call mark_delivered() when the part its poster waits for is
-     * done; what it does after that is background work that the next job queues up behind.  Both sides spin for
-     * a few hundred microseconds before they sleep: in a running stream the next event is never further away,
-     * and a sleeping thread on a busy host comes back late. */
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::function<void()>> jobs;
-    std::atomic<uint64_t> posted{0}, delivered{0}, finished{0}; /* jobs posted / past their delivery point / complete */
-    bool stop = false;
-    int device = 0;
-    static void relax()
-    {
-#if defined(__x86_64__) || defined(__i386__)
-        __builtin_ia32_pause();
-#endif
-    }
-    template <typename Pred>
-    static bool spin_for(Pred pred, int microseconds)
-    {
-        const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(microseconds);
-        for (;;) {
-            for (int i = 0; i < 64; ++i) {
-                if (pred())
-                    return true;
-                relax();
-            }
-            if (std::chrono::steady_clock::now() >= until)
-                return false;
-        }
-    }
-    void loop()
-    {
-        (void)hipSetDevice(device);
-        uint64_t taken = 0;
-        for (;;) {
-            (void)spin_for([&] { return posted.load(std::memory_order_acquire) > taken; }, 2000);
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !jobs.empty() || stop; });
-            if (jobs.empty())
-                return; /* stop, and nothing left to do */
-            std::function<void()> job = std::move(jobs.front());
-            jobs.pop_front();
-            ++taken;
-            lk.unlock();
-            job();
-            lk.lock();
-            finished.store(taken, std::memory_order_release);
-            if (delivered.load(std::memory_order_relaxed) < taken)
-                delivered.store(taken, std::memory_order_release);
-            cv.notify_all();
-        }
-    }
-    void run(std::function<void()> f) /* does not wait: the job starts when the ones before it are complete */
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        if (!th.joinable())
-            th = std::thread([this] { loop(); });
-        jobs.push_back(std::move(f));
-        posted.fetch_add(1, std::memory_order_release);
-        cv.notify_all();
-    }
-    void mark_delivered() /* from the running job */
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        delivered.store(finished.load(std::memory_order_relaxed) + 1, std::memory_order_release);
-        cv.notify_all();
-    }
-    void wait_delivered() /* the last job posted has passed its delivery point */
-    {
-        const uint64_t want = posted.load(std::memory_order_acquire);
-        if (spin_for([&] { return delivered.load(std::memory_order_acquire) >= want; }, 2000))
-            return;
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return delivered.load(std::memory_order_acquire) >= want; });
-    }
-    void wait() /* everything posted is complete */
-    {
-        const uint64_t want = posted.load(std::memory_order_acquire);
-        if (spin_for([&] { return finished.load(std::memory_order_acquire) >= want; }, 200))
-            return;
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return finished.load(std::memory_order_acquire) >= want; });
-    }
-    void shutdown()
-    {
-        wait();
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            stop = true;
-            cv.notify_all();
-        }
-        if (th.joinable())
-            th.join();
-    }
-};
 
 /* hipEventSynchronize for events that are about to fire: poll for two milliseconds first -- eight batch periods; the
  * runtime's wait may put the thread to sleep, and on a busy host it then comes back late, which the in-order chain
@@ -160,234 +61,6 @@ static hipError_t event_wait(hipEvent_t ev)
     }
 }
 
-struct Slot {
-    bool busy = false;
-    bool download_started = false;
-    bool gpu_resolve = false; /* the candidate lists stay in HBM: resolved there (msd_resolve_kernels.hip) */
-    bool resolve_inflight = false; /* its first resolve pass (and the speculative message records) are queued */
-    int threshold = 0;             /* Modes.preambleThreshold when the batch was launched */
-    bool timed = false;            /* ev_start / ev_scan / ev_kernels were recorded for this batch */
-    bool state_reset_done = false; /* ... and filter and clocks have been reset already (its chain was queued early) */
-    bool reset_before = false;     /* msd_restart(): first batch of a new capture -- filter, clock and counters start
-                                      over when its turn comes */
-    bool dc = false;               /* --dcfilter: d_iq points at d_dcmag, the float sums come from d_magsq */
-    uint16_t *d_dcmag = nullptr;   /* DC-blocked magnitudes of the batch (what the scan kernel reads) */
-    float *d_magsq = nullptr;      /* their clamped squares, for the per-buffer float sums */
-    uint64_t dropped_before = 0;   /* msd_note_dropped(): samples missing in front of this batch, not yet on the clock */
-    uint32_t resolve_ntodo = 0;
-    msd_rbuf *h_rbuf = nullptr;    /* pinned; the resolve kernel reports straight into it */
-    msd_acc *d_acc = nullptr;
-    uint32_t *d_adds = nullptr, *d_nmsgs = nullptr, *d_acc_ac = nullptr, *d_nac = nullptr;
-    uint32_t *d_pred = nullptr; /* the batch's prediction table (msd_internal.h: MSD_PRED_WORDS), filled by its scan */
-    uint32_t pred_gen = 0, pred_uses = 0; /* its generation for the batch in the slot; batches it has served */
-    /* lean layout (UC8 / magnitudes, Mode S only, chain in order, resolve on the GPU): no gather kernel -- the
-     * candidate lists stay in this slot's own region arenas until the batch's records are out, the resolve
-     * workgroups read their buffer's region slices, the first resolve pass publishes sums and totals */
-    bool lean = false;
-    bool power_done = false; /* the batch's signal power kernel has been queued (d_powr, d_rec_off) */
-    bool ahead_done = false; /* its resolve passes are through and its filter changes committed (by the msd_collect of
-                                the batch before it); counters and delivery wait for its own msd_collect */
-    int ahead_verdict = 0;   /* 1 / 2: the msd_collect before this batch's already found that the host resolver has to take
-                                it / that its arenas overflowed (resolve_passes); nothing was committed */
-    bool records_current = true; /* no further resolve pass ran after the one whose records were written */
-    uint32_t npass = 0;
-    uint64_t sample_counter0 = 0; /* the sample clock at the batch's first sample (gpu_begin) */
-    msd_hit *d_rhits = nullptr;
-    msd_try *d_rtries = nullptr;
-    msd_region_counts *d_rcounts = nullptr;
-    msd_wg_totals *d_rwgt = nullptr;
-    uint32_t lean_k = 0, lean_hcap = 0, lean_tcap = 0, lean_nreg = 0; /* regions per buffer, slice capacities, regions */
-    /* the slot's own arena sizes: the context's (msd_config) to begin with; grow_and_rescan() enlarges the region slices of
-     * a slot whose batch overflowed them, lean_gather_now() the dense lists if somebody on the host wants such a batch */
-    uint64_t rhit_arena = 0, rtry_arena = 0, dense_hits = 0, dense_tries = 0;
-    uint64_t *d_powr = nullptr; /* [buffer][MSD_RB_MSG_CAP] signal power of the accepted messages */
-    uint8_t *h_ctl = nullptr; /* pinned, read by the kernels in place: ts[2n] u64 | valid[n] | snap_idx[n] | todo[n] */
-    msd_wire *d_wire = nullptr, *h_wire = nullptr; /* message records of the emit kernel and their pinned copy */
-    unsigned long long *h_side = nullptr;          /* per record: power sum | signal_len << 48, for the statistics */
-    msd_fields *h_fields = nullptr; /* pinned: header fields next to the records (MSD_CFG_DECODE_FIELDS) */
-    msd_fields *d_fields = nullptr; /* their device copy when the records travel by DMA (records_dma) */
-    hipEvent_t ev_resolve = nullptr, ev_records = nullptr, ev_power = nullptr;
-    hipEvent_t ev_scanned = nullptr; /* side-stream layout: this batch's scan + gather are done (its float sums / Mode A/C kernels follow) */
-    uint64_t launch_seq = 0;         /* running number of the launch that filled the slot */
-    /* batch description */
-    const uint8_t *d_iq = nullptr;
-    const uint8_t *d_prev = nullptr;
-    int have_prev = 0;
-    uint64_t batch_first = 0; /* absolute sample index */
-    uint64_t nsamples = 0;
-    uint32_t nbuffers = 0;
-    int last = 0;
-    /* device */
-    msd_hit *d_hits = nullptr;
-    msd_try *d_tries = nullptr;
-    uint64_t *d_totals = nullptr;
-    float *d_tile_sums = nullptr;    /* SC16 / SC16Q11: the scan's per-tile float sums, for the float-sum kernel's predictions */
-    void *d_fm_work = nullptr;       /* 16-bit IQ, --dcfilter: the float-sum kernels' hand-over (msd_fm_work_bytes) */
-    msd_ac_hit *d_ac_regions = nullptr; /* Mode A/C: the candidate kernel's region slices and counts, gathered into d_ac */
-    msd_wg_counts *d_ac_counts = nullptr;
-    uint32_t *d_rec_off = nullptr;   /* [max_buffers + 2] records in front of each buffer's (power kernel) */
-    uint32_t *d_buf_first = nullptr; /* [max_buffers + 2] start of each buffer's hits in d_hits (gather kernel) */
-    bool buf_first_valid = false;
-    uint64_t *d_sums = nullptr;
-    uint16_t *d_mag = nullptr;        /* Mode A/C: the batch's magnitudes as the scan computed them (MsdScanParams.mag_out) */
-    const uint16_t *d_mag_prev = nullptr; /* ... and the last MSD_HALO_FRONT of the batch before, in that batch's own array */
-    bool mag_pass = false;            /* this batch's Mode A/C candidate kernel reads d_mag */
-    float *d_fmeans = nullptr;
-    /* pinned host */
-    uint64_t *h_totals = nullptr;
-    uint64_t *h_sums = nullptr;
-    float *h_fmeans = nullptr;
-    msd_hit *h_hits = nullptr;
-    size_t h_hits_cap = 0;
-    msd_try *h_tries = nullptr;
-    size_t h_tries_cap = 0;
-    uint8_t *d_ragged = nullptr; /* zero-padded copy of a partially filled last 8-sample group */
-    uint8_t *tail_dst = nullptr; /* where the gather kernel leaves the batch's last samples for its successor */
-    uint8_t *d_upload = nullptr; /* msd_launch_host: this slot's copy of the batch in HBM */
-    hipEvent_t ev_upload = nullptr;
-    /* Mode A/C candidates */
-    msd_ac_hit *d_ac = nullptr;
-    uint64_t *d_ac_totals = nullptr, *h_ac_totals = nullptr;
-    msd_ac_hit *h_ac = nullptr;
-    size_t h_ac_cap = 0;
-    /* deferred signal power of the accepted messages */
-    uint64_t *d_req = nullptr, *d_pow = nullptr, *h_req = nullptr, *h_pow = nullptr;
-    size_t req_cap = 0;
-    hipEvent_t ev_start = nullptr, ev_scan = nullptr, ev_kernels = nullptr, ev_totals = nullptr,
-               ev_copy0 = nullptr, ev_copy1 = nullptr;
-};
-
-} /* namespace */
-
-struct msd_ctx {
-    msd_config cfg{};
-    hipStream_t stream = nullptr, copy_stream = nullptr, aux_stream = nullptr, emit_stream = nullptr;
-    bool own_stream = false;
-    int bps = 2;
-    msd_tables *tables = nullptr;
-    uint16_t *d_lut = nullptr;
-    uint32_t *d_crc = nullptr, *d_syn56 = nullptr, *d_syn112 = nullptr, *d_slicer = nullptr, *d_synhash = nullptr;
-    uint64_t *d_fix2[2] = {nullptr, nullptr}; /* two-bit correction tables for 56 / 112 bits (nfix_crc == 2) */
-    uint32_t fix2_lg[2] = {0, 0};
-    /* per-workgroup candidate regions (shared by all batches: stream order serialises them) */
-    msd_hit *d_region_hits = nullptr;
-    msd_try *d_region_tries = nullptr;
-    uint64_t hit_arena = 0, try_arena = 0;
-    uint64_t *h_conv = nullptr; /* msd_convert_begin / _end: the sums of the conversion in flight (page-locked) */
-    bool conv_pending = false;
-    unsigned conv_n = 0;
-    const msd_magbuf_view *magbuf_views = nullptr; /* msd_demodulate_magbufs: the caller's buffers while its finish() runs */
-    const uint32_t *magbuf_noise = nullptr;        /* ... and their Mode A/C noise levels (demod_2400.c:530-531 from the caller's
-                                                      means), for a batch that has to be scanned again in pieces */
-    unsigned magbuf_nviews = 0;
-    double want_hits_per_sample = 0, want_tries_per_sample = 0; /* region slices a slot should have at its next launch (grow_and_rescan) */
-    msd_region_counts *d_counts = nullptr; /* per region (wavefront) of the scan kernel */
-    msd_wg_totals *d_wg_totals = nullptr;  /* per workgroup of the scan kernel */
-    uint32_t max_wg = 0, max_buffers = 0;  /* max_wg: most regions a scan is split into */
-    /* Mode A/C candidate regions */
-    uint64_t ac_arena = 0;
-    uint64_t *d_ac_offsets = nullptr;
-    uint32_t *d_noise = nullptr;
-    void *d_fm_work = nullptr;       /* 16-bit IQ, --dcfilter: the float-sum kernels' hand-over (msd_fm_work_bytes) */
-    uint32_t ac_max_wg = 0;
-    unsigned long long *d_timers = nullptr; /* MSD_KERNEL_TIMING experiments */
-    /* GPU resolve stage: per-buffer reports, accepted-message records, filter snapshots, control arrays */
-    bool gpu_resolve = false;
-    uint32_t *d_snaps = nullptr, *h_snaps = nullptr;
-    uint32_t snaps_uploaded = 0;
-    uint32_t inline_adds = MSD_RB_ADD_INLINE; /* msd_config.test_inline_adds lowers it */
-    bool want_fields = false;       /* MSD_CFG_DECODE_FIELDS */
-    msd_fields_fn fsink = nullptr;  /* set while msd_collect_fields runs: messages go here with their fields */
-    void *fuser = nullptr;
-    std::vector<msd_fields> out_fields; /* host-resolve path */
-    bool records_dma = false; /* MSD_RECORDS_DMA=1: fetch the message records with a DMA instead of kernel stores */
-    hipEvent_t ev_aux = nullptr, ev_inputs = nullptr;
-    msd_pred_entry *h_pred = nullptr;
-    uint32_t *h_pred_count = nullptr;
-    msd_pred_patch *h_patches = nullptr;
-    uint32_t npatches = 0;
-    /* the last MSD_HALO_FRONT samples of the previous batch, one buffer per pipeline stage + 1 */
-    uint8_t *d_tail[MSD_PIPELINE_DEPTH + 1] = {};
-    int tail_cur = 0;
-    bool have_prev = false;
-    uint8_t *d_stage = nullptr; /* msd_submit_host / msd_convert / msd_demodulate_magbuf staging */
-    uint16_t *d_mag = nullptr;
-    Slot slots[MSD_PIPELINE_DEPTH];
-    int head = 0, outstanding = 0;
-    uint64_t next_sample = 0;
-    bool finished = false;
-    uint64_t pending_dropped = 0; /* msd_note_dropped() since the last launch */
-    bool restart_pending = false; /* msd_restart() since the last launch */
-    const uint16_t *mag_prev = nullptr; /* Mode A/C: where the previous batch's last magnitudes are (its slot's d_mag) */
-    uint32_t timing_interval = 1; /* msd_set_timing_interval() */
-    /* experiment knobs, read from the environment once in msd_create */
-    bool trace = false;      /* MSD_RESOLVE_TRACE */
-    bool repass_aux = false; /* MSD_REPASS_AUX */
-    /* In-order layout without field decoding: the record kernel of a batch is not launched; the wavefronts of the
-     * next scan write the records on their way in (MsdScanParams.emit).  pending_emit: resolve chain and signal
-     * power queued, records not yet.  MSD_EMIT_FUSED=0 turns it off. */
-    std::vector<uint32_t> bg_valid, bg_buf; /* the statistics half of finishing a batch, on the helper thread */
-    std::vector<double> bg_means;
-    std::vector<uint64_t> bg_scaled; /* per message: power sum | signal_len << 48 (msd_emit_impl.h) */
-    bool emit_fused = false;
-    bool power_fused = true; /* no signal power kernel: the resolve workgroups sum it (MSD_POWER_FUSED=0 keeps the kernel) */
-    struct Slot *pending_emit = nullptr;
-    bool chain_inline = true; /* MSD_CHAIN_INLINE=0: resolve chain on side streams instead of in order on the scan stream */
-    bool lean_ok = false;     /* the configuration allows the lean layout (Slot::lean; MSD_LEAN=0 turns it off) */
-    bool wait_inputs_on_stream = false; /* MSD_WAIT_INPUTS_ON_STREAM=1: the resolve kernel's stream waits for the snapshot upload */
-    bool resolve_ahead = true; /* msd_collect also takes the next batch through its resolve passes (MSD_RESOLVE_AHEAD=0: no) */
-    int debug_flags = 0;     /* MSD_DEBUG_FLAGS */
-    uint64_t enqueue_seq = 0;
-    uint64_t launch_count = 0;
-    bool dc = false;              /* MSD_CFG_DC_FILTER */
-    int q11_bits = 0;             /* msd_config.sc16q11_table_bits in effect: the batches' IQ goes through d_q11_table first */
-    uint16_t *d_q11_table = nullptr;
-    float *d_conv_magsq = nullptr; /* msd_convert of a MSD_CFG_DC_FILTER context: the clamped squares of the call's samples */
-    float dc_a = 0, dc_b = 1;     /* struct converter_state, convert.c:28-33,479-482 */
-    float *d_dcstate = nullptr;   /* z1_I, z1_Q on the device, carried from batch to batch */
-    void *d_dc_work = nullptr;    /* the parallel-in-time DC filter's blocks, tables and control word (msd_dcp_work_bytes) */
-    bool dc_last_parallel = false; /* the most recent DC block went through the parallel kernels (msd_dc_filter_status) */
-    uint32_t dc_last_blocks = 0;
-    bool dc_fused = false;        /* MSD_CFG_DC_FUSED_LAUNCH: the passes in one cooperative launch (measured slower) */
-    int dc_passes = 24;           /* passes queued per batch (MSD_CFG_DC_ONE_PASS: 1, so that the in-order kernel behind them runs) */
-    int scan_format = 0;          /* what the scan and its follow-up kernels read: cfg.format, or MAG16 behind the DC filter */
-    size_t scan_bps = 2;
-    msd_resolver resolver{};
-    msd_stats stats{};
-    msd_timing timing{};
-    std::vector<double> means;
-    std::vector<uint32_t> valid;
-    std::vector<msd_message> out_msgs;
-    std::vector<uint64_t> out_req;
-    std::vector<uint32_t> out_buf;
-    int cu_count = 256;
-    Helper helper;
-    bool failed = false;    /* a batch could not be finished: only msd_reset() / msd_destroy() are accepted */
-    bool scan_queued = false; /* enqueue(): its scan kernel is on the stream (a later failure cannot be undone) */
-    bool no_helper = false; /* MSD_NO_HELPER: everything on the calling thread */
-    void *frames = nullptr; /* Beast / AVR input (msd_frames.cpp) */
-    /* receiver group (msd_group_*): set while a group call runs -- every buffer's look-behind comes from its receiver's
-     * tail slot (MsdScanParams.group_lb) */
-    const uint8_t *group_tails = nullptr;
-    const uint32_t *group_lb = nullptr;
-    const uint32_t *group_opt = nullptr; /* every buffer's receiver options (MsdScanParams.group_opt) */
-    bool group_fix2 = false;             /* some buffer of the call is at repair level 2: the FIX2 instantiation */
-    /* ... and the call's buffers whose receiver has Mode A/C on: ascending buffer indices, on the device (the group's
-     * control rows) and on the host; group_nac 0: no Mode A/C in this call */
-    const uint32_t *group_ac = nullptr;
-    const uint32_t *group_ac_host = nullptr;
-    uint32_t group_nac = 0;
-    char err[256] = {0};
-};
-
-namespace {
-
-/* the batch in hand has a Mode A/C pass: the context's configuration, or a receiver group call with some receiver on */
-inline bool ac_on(const msd_ctx *c)
-{
-    return c->cfg.mode_ac || c->group_nac;
-}
-
 /* why the calling thread's last msd_create failed (there is no context to hold the text yet);
  * msd_last_error(NULL) returns it */
 thread_local char g_create_err[256] = {0};
@@ -402,13 +75,6 @@ int fail(msd_ctx *c, int code, const char *fmt, ...)
     }
     return code;
 }
-
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail((c), -EIO, "%s failed: %s", #call, hipGetErrorString(e_));              \
-    } while (0)
 
 void emit_thunk(const msd_message *mm, const uint64_t *power_req, uint32_t count, uint32_t buffer, void *user)
 {
@@ -479,6 +145,18 @@ void fill_params(const msd_ctx *c, const Slot &s, MsdScanParams &p)
     p.fix2_112 = c->d_fix2[1];
     p.fix2_lg56 = c->fix2_lg[0];
     p.fix2_lg112 = c->fix2_lg[1];
+    if (const GroupCall *g = s.group) { /* a receiver group: batch_first is a whole number of buffers into the call */
+        const uint64_t b0 = s.batch_first / MSD_CHUNK_SAMPLES;
+        p.group_tails = g->tails;
+        p.group_lb = g->lb + b0;
+        p.group_opt = g->opt + b0;
+        p.prev_tail = nullptr;
+        p.have_prev = 0;
+        if (!g->fix2) { /* the two-bit tables may exist, but no buffer of this call is at level 2 */
+            p.fix2_56 = nullptr;
+            p.fix2_112 = nullptr;
+        }
+    }
 }
 
 int ensure_host(msd_ctx *c, Slot &s, size_t nh, size_t nt)
@@ -508,6 +186,37 @@ int ensure_host(msd_ctx *c, Slot &s, size_t nh, size_t nt)
     return 0;
 }
 
+hipError_t upload_fix2(msd_ctx *c, bool *host_oom)
+{
+    uint64_t *d[2] = {nullptr, nullptr};
+    uint32_t lg[2] = {0, 0};
+    hipError_t e = hipSuccess;
+    *host_oom = false;
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        uint64_t *tab = msd_fix2_table(c->tables, k ? 112 : 56, &lg[k]);
+        if (!tab) {
+            *host_oom = true;
+            e = hipErrorOutOfMemory;
+            break;
+        }
+        const size_t bytes = sizeof(uint64_t) << lg[k];
+        e = hipMalloc(reinterpret_cast<void **>(&d[k]), bytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(d[k], tab, bytes, hipMemcpyHostToDevice);
+        free(tab);
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(d[0]);
+        (void)hipFree(d[1]);
+        return e;
+    }
+    for (int k = 0; k < 2; ++k) {
+        c->d_fix2[k] = d[k];
+        c->fix2_lg[k] = lg[k];
+    }
+    return hipSuccess;
+}
+
 size_t bps_of(int format)
 {
     return (format == MSD_FMT_UC8 || format == MSD_FMT_MAG16) ? 2 : 4;
@@ -515,8 +224,6 @@ size_t bps_of(int format)
 
 /* Enqueue the GPU stage for `nsamples` samples at d_iq (absolute index batch_first). */
 int flush_pending_emit(msd_ctx *c);
-struct GpuCtl;
-void gpu_params(const msd_ctx *c, const Slot &s, MsdResolveParams &rp);
 
 bool gpu_eligible(const msd_ctx *c, const Slot &s);
 
@@ -552,7 +259,7 @@ int ensure_dense(msd_ctx *c, Slot &s)
     return 0;
 }
 
-int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pipelined = false)
+int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pipelined)
 {
     const uint64_t tile = msd_scan_tile(format);
     const uint64_t ntiles64 = (s.nsamples + tile - 1) / tile;
@@ -630,12 +337,12 @@ int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pi
     /* d_sums is zero: whoever published the slot's previous batch left it so.  The offsets kernel
      * overwrites the totals. */
     const bool fm = format == MSD_FMT_SC16 || format == MSD_FMT_SC16Q11 || s.dc;
-    const bool gather_publishes = nwg && !ac_on(c) && !fm; /* totals and sums are published by the gather kernel */
+    const bool gather_publishes = nwg && !ac_on(c, s) && !fm; /* totals and sums are published by the gather kernel */
     if (!nwg) {
         HIPCHK(c, hipMemsetAsync(s.d_totals, 0, sizeof(uint64_t) * 4, c->stream));
         s.buf_first_valid = false;
     }
-    if (ac_on(c) && !(s.nbuffers && s.nsamples)) /* (msd_launch_ac's offsets kernel writes them otherwise) */
+    if (ac_on(c, s) && !(s.nbuffers && s.nsamples)) /* (msd_launch_ac's offsets kernel writes them otherwise) */
         HIPCHK(c, hipMemsetAsync(s.d_ac_totals, 0, sizeof(uint64_t) * 4, c->stream));
     /* the three timing events cost about 5 us of stream time each (a barrier packet per record): they are
      * recorded for one batch in every c->timing_interval */
@@ -645,17 +352,6 @@ int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pi
     if (nwg) {
         MsdScanParams p{};
         fill_params(c, s, p);
-        if (c->group_lb) { /* a receiver group: batch_first is a whole number of buffers into the group's call */
-            p.group_tails = c->group_tails;
-            p.group_lb = c->group_lb + s.batch_first / MSD_CHUNK_SAMPLES;
-            p.group_opt = c->group_opt + s.batch_first / MSD_CHUNK_SAMPLES;
-            p.prev_tail = nullptr;
-            p.have_prev = 0;
-            if (!c->group_fix2) { /* the two-bit tables may exist, but no buffer of this call is at level 2 */
-                p.fix2_56 = nullptr;
-                p.fix2_112 = nullptr;
-            }
-        }
         p.ntiles = ntiles;
         p.tiles_per_wg = tpw;
         p.hits = s.lean ? s.d_rhits : c->d_region_hits;
@@ -784,19 +480,16 @@ int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pi
         if (rc)
             return fail(c, rc, "float means kernel launch failed");
     }
-    if (c->group_lb && c->group_nac && s.nbuffers) {
+    if (s.group && s.group->nac && s.nbuffers) {
         /* a receiver group: the listed buffers of this batch (a whole call, or a piece of a rescanned one) */
+        const GroupCall &g = *s.group;
         const uint32_t b0 = (uint32_t)(s.batch_first / MSD_CHUNK_SAMPLES);
-        const uint32_t *lo = std::lower_bound(c->group_ac_host, c->group_ac_host + c->group_nac, b0);
-        const uint32_t *hi = std::lower_bound(lo, c->group_ac_host + c->group_nac, b0 + s.nbuffers);
+        const uint32_t *lo = std::lower_bound(g.ac_host, g.ac_host + g.nac, b0);
+        const uint32_t *hi = std::lower_bound(lo, g.ac_host + g.nac, b0 + s.nbuffers);
         MsdScanParams p{};
         fill_params(c, s, p);
-        p.group_tails = c->group_tails;
-        p.group_lb = c->group_lb + b0;
-        p.prev_tail = nullptr;
-        p.have_prev = 0;
         p.debug_flags = c->debug_flags;
-        int rc = msd_launch_group_ac(&p, format, s.d_sums, s.d_fmeans, c->group_ac + (lo - c->group_ac_host), (uint32_t)(hi - lo),
+        int rc = msd_launch_group_ac(&p, format, s.d_sums, s.d_fmeans, g.ac + (lo - g.ac_host), (uint32_t)(hi - lo),
                                      b0, s.d_ac_regions, c->ac_arena, s.d_ac_counts, s.d_ac_totals, s.d_ac, c->ac_arena,
                                      c->ac_max_wg, c->stream);
         if (rc)
@@ -828,7 +521,7 @@ int enqueue(msd_ctx *c, Slot &s, int format, const uint32_t *host_noise, bool pi
 
     /* totals and per-buffer sums go to pinned host memory from this stream, right behind the kernels */
     if (!gather_publishes && !s.lean) {
-        int rc = msd_launch_publish(s.d_totals, ac_on(c) ? s.d_ac_totals : nullptr, s.d_sums,
+        int rc = msd_launch_publish(s.d_totals, ac_on(c, s) ? s.d_ac_totals : nullptr, s.d_sums,
                                     fm ? s.d_fmeans : nullptr, s.nbuffers, s.h_totals, s.h_ac_totals, s.h_sums,
                                     s.h_fmeans, c->stream);
         if (rc)
@@ -909,8 +602,8 @@ int rerun_in_pieces(msd_ctx *c, Slot &s, int format)
                 return rc;
             HIPCHK(c, hipEventSynchronize(t.ev_totals));
             const uint64_t H = s.h_totals[0], Tn = s.h_totals[1];
-            const uint64_t nac = ac_on(c) ? s.h_ac_totals[0] : 0;
-            if (s.h_totals[2] || (ac_on(c) && s.h_ac_totals[2])) {
+            const uint64_t nac = ac_on(c, s) ? s.h_ac_totals[0] : 0;
+            if (s.h_totals[2] || (ac_on(c, s) && s.h_ac_totals[2])) {
                 if (piece == MSD_CHUNK_SAMPLES)
                     return fail(c, -EOVERFLOW, "candidate arena overflow on a single buffer");
                 again = true;
@@ -964,7 +657,7 @@ int rerun_in_pieces(msd_ctx *c, Slot &s, int format)
         s.h_totals[0] = hits.size();
         s.h_totals[1] = tries.size();
         s.h_totals[2] = 0;
-        if (ac_on(c)) {
+        if (ac_on(c, s)) {
             s.h_ac_totals[0] = acs.size();
             s.h_ac_totals[2] = 0;
         }
@@ -995,7 +688,7 @@ int start_download(msd_ctx *c, Slot &s, int format)
         fprintf(stderr, "start_download: waited %.3f ms for the totals; scan %.3f ms, all kernels %.3f ms after its start\n",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count(), a, b);
     }
-    const bool overflow = s.h_totals[2] || (ac_on(c) && s.h_ac_totals[2]);
+    const bool overflow = s.h_totals[2] || (ac_on(c, s) && s.h_ac_totals[2]);
     if (overflow) {
         int rc = rerun_in_pieces(c, s, format);
         if (rc)
@@ -1015,7 +708,7 @@ int start_download(msd_ctx *c, Slot &s, int format)
             HIPCHK(c, hipMemcpyAsync(s.h_hits, s.d_hits, H * sizeof(msd_hit), hipMemcpyDeviceToHost, c->copy_stream));
         if (Tn)
             HIPCHK(c, hipMemcpyAsync(s.h_tries, s.d_tries, Tn * sizeof(msd_try), hipMemcpyDeviceToHost, c->copy_stream));
-        if (ac_on(c)) {
+        if (ac_on(c, s)) {
             const uint64_t nac = s.h_ac_totals[0];
             rc = ensure_ac_host(c, s, nac);
             if (rc)
@@ -1040,11 +733,6 @@ constexpr uint32_t SNAP_CAP = 64; /* filter membership versions of one batch kep
  * them), so they never share compute units with a scan kernel; everything they report lands in
  * pinned host memory, the host waits for one event.  Only the rare further passes use the
  * high-priority aux stream. */
-struct GpuCtl {
-    uint64_t *h_ts;
-    uint32_t *h_valid, *h_snap, *h_todo;
-};
-
 GpuCtl gpu_ctl(const msd_ctx *c, const Slot &s)
 {
     const size_t N = c->max_buffers;
@@ -1074,7 +762,7 @@ void gpu_params(const msd_ctx *c, const Slot &s, MsdResolveParams &rp)
     rp.nmsgs = s.d_nmsgs;
     rp.acc = s.d_acc;
     rp.adds = s.d_adds;
-    if (ac_on(c)) {
+    if (ac_on(c, s)) {
         rp.ac = s.d_ac;
         rp.ac_totals = s.d_ac_totals;
         rp.acc_ac = s.d_acc_ac;
@@ -2201,7 +1889,10 @@ void destroy(msd_ctx *c)
     delete c;
 }
 
-} /* namespace */
+} /* namespace msd_impl */
+#pragma GCC visibility pop
+
+using namespace msd_impl;
 
 extern "C" {
 
@@ -2308,19 +1999,13 @@ static int create_context(const msd_config *cfg, msd_ctx **out, bool *out_of_mem
     CK(hipMalloc(reinterpret_cast<void **>(&c->d_synhash), sizeof c->tables->synhash));
     CK(hipMemcpy(c->d_synhash, c->tables->synhash, sizeof c->tables->synhash, hipMemcpyHostToDevice));
     if (cfg->nfix_crc == 2) { /* --aggressive, crc.c:374-379 */
-        for (int k = 0; k < 2; ++k) {
-            uint64_t *tab = msd_fix2_table(c->tables, k ? 112 : 56, &c->fix2_lg[k]);
-            if (!tab) {
-                destroy(c);
-                return -ENOMEM;
-            }
-            const size_t bytes = sizeof(uint64_t) << c->fix2_lg[k];
-            hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_fix2[k]), bytes);
-            if (e == hipSuccess)
-                e = hipMemcpy(c->d_fix2[k], tab, bytes, hipMemcpyHostToDevice);
-            free(tab);
-            CK(e);
+        bool host_oom = false;
+        const hipError_t e = upload_fix2(c, &host_oom);
+        if (host_oom) {
+            destroy(c);
+            return -ENOMEM;
         }
+        CK(e);
     }
 
     const uint64_t B = c->cfg.max_batch_samples;
@@ -3056,835 +2741,6 @@ int msd_demodulate_magbuf(msd_ctx *c, const uint16_t *data, unsigned validLength
 {
     const msd_magbuf_view one = {data, validLength, overlap, sampleTimestamp, sysTimestamp, mean_level, mean_power};
     return msd_demodulate_magbufs(c, &one, 1, sink, user);
-}
-
-} /* extern "C" */
-
-/* ---------------------------------------------------------------------------------------------------------------- */
-/* receiver groups (modes_hip.h msd_group_*)                                                          */
-/* ---------------------------------------------------------------------------------------------------------------- */
-
-namespace {
-
-struct GroupReceiver {
-    msd_resolver resolver{}; /* filter, clock (sample_counter) and the counters it sums into `stats` */
-    msd_stats stats{};
-    bool have_tail = false; /* its tail slot holds the end of its previous buffer */
-    bool history = false;   /* a buffer since creation or the last reset: the repair level is fixed */
-    msd_group_receiver_options opt{}; /* kept across msd_group_reset_receiver */
-    bool mode_ac = false;             /* Mode A/C on (readsb --modeac), likewise kept */
-};
-
-/* what the host resolver delivers for one entry of a call */
-struct GroupEntryOut {
-    std::vector<msd_message> msgs;
-    std::vector<uint64_t> req;
-    std::vector<msd_hit> hits; /* the entry's hits, positions made buffer-relative */
-    std::vector<msd_ac_hit> ac; /* its Mode A/C candidates, likewise */
-    double means[2] = {0, 0};
-    uint32_t valid = MSD_CHUNK_SAMPLES;
-};
-
-void group_emit(const msd_message *mm, const uint64_t *power_req, uint32_t count, uint32_t, void *user)
-{
-    GroupEntryOut *o = static_cast<GroupEntryOut *>(user);
-    o->msgs.insert(o->msgs.end(), mm, mm + count);
-    o->req.insert(o->req.end(), power_req, power_req + count);
-}
-
-/* body(i) for i in [0, n) on up to `threads` host threads (the calling one included); the work of a thread that could
- * not be started is done by the others */
-void parallel_for(uint32_t n, uint32_t threads, const std::function<void(uint32_t)> &body)
-{
-    if (threads > n)
-        threads = n;
-    std::atomic<uint32_t> next{0};
-    auto work = [&]() {
-        for (uint32_t i; (i = next.fetch_add(1)) < n;)
-            body(i);
-    };
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < threads; ++t) {
-        try {
-            pool.emplace_back(work);
-        } catch (...) {
-            break;
-        }
-    }
-    work();
-    for (std::thread &t : pool)
-        t.join();
-}
-
-} /* namespace */
-
-struct msd_group {
-    msd_ctx *ctx = nullptr;
-    uint32_t max_receivers = 0;
-    uint32_t threads = 1; /* host threads of the per-receiver work */
-    bool gpu = false;     /* resolve on the GPU against the receivers' device snapshots (not MSD_CFG_HOST_RESOLVE) */
-    GroupReceiver *rx = nullptr;
-    uint8_t *d_tails = nullptr;    /* [max_receivers][MSD_HALO_FRONT] raw samples */
-    uint32_t *d_ctl = nullptr;     /* [4][max_receivers]: per buffer its look-behind slot, its receiver and its receiver's
-                                      options (threshold | nfix_crc << 16); then the call's buffers with Mode A/C on */
-    uint32_t *h_ctl = nullptr;     /* pinned copy */
-    uint32_t *d_snaps = nullptr;   /* [max_receivers][MSD_SNAP_WORDS]: every receiver's ICAO filter on the device */
-    uint32_t *h_apply = nullptr;   /* pinned, read in place by the filter kernel: slot[n] | add_first[n + 1] | flip[n] */
-    uint32_t *h_adds = nullptr;    /* pinned: the entries' adds, max_receivers * MSD_RB_MSG_CAP */
-    uint32_t *h_snap = nullptr;    /* pinned staging of one snapshot */
-    uint64_t host_buffers = 0;     /* buffers resolved on the host (msd_timing.resolve_fallback) */
-    std::vector<GroupEntryOut> out;
-    std::vector<uint64_t> req_all;
-    char err[256] = {0};
-};
-
-namespace {
-
-int gfail(msd_group *g, int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g->err, sizeof g->err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define GHIPCHK(g, call)                                                                        \
-    do {                                                                                        \
-        hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return gfail((g), -EIO, "%s failed: %s", #call, hipGetErrorString(e_));             \
-    } while (0)
-
-/* the receiver's host filter -> its device snapshot (at creation, reset and after a buffer resolved on the host) */
-int group_upload_snapshot(msd_group *g, uint32_t receiver)
-{
-    if (!g->gpu)
-        return 0;
-    const msd_filter &f = g->rx[receiver].resolver.filter;
-    for (uint32_t h = 0; h < 8192; ++h) {
-        g->h_snap[2 * h] = f.slot[0][h];
-        g->h_snap[2 * h + 1] = f.slot[1][h];
-    }
-    g->h_snap[16384] = (uint32_t)f.active;
-    GHIPCHK(g, hipMemcpy(g->d_snaps + (size_t)receiver * MSD_SNAP_WORDS, g->h_snap, sizeof(uint32_t) * MSD_SNAP_WORDS,
-                         hipMemcpyHostToDevice));
-    return 0;
-}
-
-void group_receiver_reset(GroupReceiver &r)
-{
-    msd_resolver_reset(&r.resolver); /* filter, clock and the counters behind r.resolver.stats */
-    memset(&r.stats, 0, sizeof r.stats);
-    r.have_tail = false;
-    r.history = false;
-}
-
-/* The two-bit correction tables (--aggressive, crc.c:374-379) of the group's context, made when the first receiver is
- * set to repair level 2 (msd_create makes them when the group's own configuration has nfix_crc 2). */
-int group_make_fix2(msd_group *g)
-{
-    msd_ctx *c = g->ctx;
-    if (c->d_fix2[1])
-        return 0;
-    GHIPCHK(g, hipSetDevice(c->cfg.device));
-    uint64_t *d[2] = {nullptr, nullptr};
-    uint32_t lg[2] = {0, 0};
-    int rc = 0;
-    for (int k = 0; k < 2 && !rc; ++k) {
-        uint64_t *tab = msd_fix2_table(c->tables, k ? 112 : 56, &lg[k]);
-        if (!tab) {
-            rc = gfail(g, -ENOMEM, "two-bit correction table: out of host memory");
-            break;
-        }
-        const size_t bytes = sizeof(uint64_t) << lg[k];
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d[k]), bytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(d[k], tab, bytes, hipMemcpyHostToDevice);
-        free(tab);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            rc = gfail(g, e == hipErrorOutOfMemory ? -ENOMEM : -EIO, "two-bit correction table: %s", hipGetErrorString(e));
-        }
-    }
-    if (rc) {
-        (void)hipFree(d[0]);
-        (void)hipFree(d[1]);
-        return rc;
-    }
-    for (int k = 0; k < 2; ++k) {
-        c->d_fix2[k] = d[k];
-        c->fix2_lg[k] = lg[k];
-    }
-    return 0;
-}
-
-/* The Mode A/C buffers of the group's context (slot 0, the only one a group uses): the candidate kernel's regions and
- * counts, the ordered list and its totals, and for the GPU resolve the accepted replies per buffer -- made when the first
- * receiver is switched on.  The arena holds a candidate per 32 samples of a full call, and never less than one per
- * sample of one buffer, so that a call rescanned in pieces always fits once the pieces are single buffers. */
-int group_make_ac(msd_group *g)
-{
-    msd_ctx *c = g->ctx;
-    Slot &s = c->slots[0];
-    if (s.d_ac)
-        return 0;
-    GHIPCHK(g, hipSetDevice(c->cfg.device));
-    const uint64_t B = c->cfg.max_batch_samples;
-    const uint64_t arena = B / 32 > MIN_HIT_ARENA ? B / 32 : MIN_HIT_ARENA;
-    const uint32_t max_wg = (uint32_t)c->cu_count * 28u; /* as msd_create: one region per resident wavefront */
-    msd_ac_hit *regions = nullptr, *dense = nullptr;
-    msd_wg_counts *counts = nullptr;
-    uint64_t *totals = nullptr, *h_totals = nullptr;
-    uint32_t *acc_ac = nullptr, *nac = nullptr;
-    bool ok = hipMalloc(reinterpret_cast<void **>(&regions), arena * sizeof(msd_ac_hit)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&dense), arena * sizeof(msd_ac_hit)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&counts), max_wg * sizeof(msd_wg_counts)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&totals), 4 * sizeof(uint64_t)) == hipSuccess &&
-              hipHostMalloc(reinterpret_cast<void **>(&h_totals), 4 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-    if (ok && g->gpu)
-        ok = hipMalloc(reinterpret_cast<void **>(&acc_ac), sizeof(uint32_t) * MSD_RB_AC_CAP * c->max_buffers) == hipSuccess &&
-             hipMalloc(reinterpret_cast<void **>(&nac), sizeof(uint32_t) * c->max_buffers) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        (void)hipFree(regions);
-        (void)hipFree(dense);
-        (void)hipFree(counts);
-        (void)hipFree(totals);
-        if (h_totals)
-            (void)hipHostFree(h_totals);
-        (void)hipFree(acc_ac);
-        (void)hipFree(nac);
-        return gfail(g, -ENOMEM, "Mode A/C buffers: out of memory");
-    }
-    memset(h_totals, 0, 4 * sizeof(uint64_t));
-    s.d_ac_regions = regions;
-    s.d_ac = dense;
-    s.d_ac_counts = counts;
-    s.d_ac_totals = totals;
-    s.h_ac_totals = h_totals;
-    s.d_acc_ac = acc_ac;
-    s.d_nac = nac;
-    c->ac_arena = arena;
-    c->ac_max_wg = max_wg;
-    return 0;
-}
-
-int group_check(const msd_group *g, const msd_group_entry *e, uint32_t n)
-{
-    if (n > g->max_receivers)
-        return -EINVAL;
-    if (n && !e)
-        return -EINVAL;
-    std::vector<bool> seen(g->max_receivers, false);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (e[i].receiver >= g->max_receivers || e[i].flags != 0 || seen[e[i].receiver])
-            return -EINVAL;
-        seen[e[i].receiver] = true;
-    }
-    return 0;
-}
-
-constexpr uint32_t GROUP_FULL_GUARD = 6000u; /* occupied active slots above which a buffer is resolved on the host (as the
-                                                context's replay does: a buffer adds at most 970 addresses, two slots each) */
-
-/* The entries idx[] on the host: each buffer through the host resolver's sequential path against its receiver's filter,
- * hit positions made buffer-relative; then the signal power of their messages with the group look-behind.  The
- * candidate lists must be in s.h_hits / s.h_tries. */
-int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const std::vector<uint32_t> &idx)
-{
-    msd_ctx *c = g->ctx;
-    const int format = c->cfg.format;
-    const uint64_t H = s.h_totals[0];
-    const msd_hit *hits = s.h_hits;
-    const uint32_t n = s.nbuffers;
-    const uint64_t NA = ac_on(c) ? s.h_ac_totals[0] : 0; /* Mode A/C candidates of the call (s.h_ac), ordered */
-    std::vector<uint64_t> first(n + 1), ac_first(n + 1);
-    {
-        uint64_t h = 0, a = 0;
-        for (uint32_t i = 0; i <= n; ++i) {
-            const uint64_t pos = (uint64_t)i * MSD_CHUNK_SAMPLES;
-            while (h < H && MSD_HIT_POS(hits[h]) < pos)
-                ++h;
-            while (a < NA && s.h_ac[a].pos < pos)
-                ++a;
-            first[i] = h;
-            ac_first[i] = a;
-        }
-    }
-    parallel_for((uint32_t)idx.size(), g->threads, [&](uint32_t k) {
-        const uint32_t i = idx[k];
-        GroupEntryOut &o = g->out[i];
-        GroupReceiver &r = g->rx[e[i].receiver];
-        o.hits.assign(hits + first[i], hits + first[i + 1]);
-        for (msd_hit &h : o.hits)
-            h -= (msd_hit)i * MSD_CHUNK_SAMPLES; /* position is the low field */
-        o.ac.assign(s.h_ac + ac_first[i], s.h_ac + ac_first[i + 1]); /* (none unless its receiver has Mode A/C on) */
-        for (msd_ac_hit &a : o.ac)
-            a.pos -= (uint64_t)i * MSD_CHUNK_SAMPLES;
-        msd_resolve_batch(&r.resolver, 0, 1, &o.valid, o.hits.data(), o.hits.size(), s.h_tries, s.h_totals[1], o.ac.data(),
-                          o.ac.size(), nullptr, group_emit, &o);
-    });
-    g->req_all.clear();
-    for (uint32_t i : idx)
-        for (uint64_t q : g->out[i].req)
-            g->req_all.push_back(q + ((uint64_t)i * MSD_CHUNK_SAMPLES << 16));
-    const size_t nm = g->req_all.size();
-    if (nm) {
-        MsdScanParams p{};
-        fill_params(c, s, p);
-        p.have_prev = 0;
-        p.prev_tail = nullptr;
-        p.group_tails = g->d_tails;
-        p.group_lb = g->d_ctl;
-        int rc = ensure_req(c, s, nm);
-        if (rc)
-            return gfail(g, rc, "power: %s", c->err);
-        memcpy(s.h_req, g->req_all.data(), nm * sizeof(uint64_t));
-        GHIPCHK(g, hipMemcpyAsync(s.d_req, s.h_req, nm * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        rc = msd_launch_group_power(&p, format, s.d_req, (uint32_t)nm, reinterpret_cast<unsigned long long *>(s.d_pow),
-                                    c->stream);
-        if (rc)
-            return gfail(g, rc, "group power kernel launch failed");
-        GHIPCHK(g, hipMemcpyAsync(s.h_pow, s.d_pow, nm * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        GHIPCHK(g, hipStreamSynchronize(c->stream));
-    }
-    std::vector<uint64_t> pow_first(idx.size() + 1, 0);
-    for (size_t k = 0; k < idx.size(); ++k)
-        pow_first[k + 1] = pow_first[k] + g->out[idx[k]].req.size();
-    parallel_for((uint32_t)idx.size(), g->threads, [&](uint32_t k) {
-        GroupEntryOut &o = g->out[idx[k]];
-        GroupReceiver &r = g->rx[e[idx[k]].receiver];
-        const std::vector<uint32_t> buf(o.msgs.size(), 0u);
-        msd_resolve_power(&r.resolver, 1, &o.valid, o.means, o.msgs.data(), sizeof(msd_message), o.req.data(), buf.data(),
-                          s.h_pow + pow_first[k], sizeof(uint64_t), o.msgs.size());
-    });
-    g->host_buffers += idx.size();
-    for (uint32_t i : idx) { /* the device copies follow the host filters */
-        const int rc = group_upload_snapshot(g, e[i].receiver);
-        if (rc)
-            return rc;
-    }
-    return 0;
-}
-
-/* The GPU resolve of one call: every buffer in one pass of msd_resolve_kernel against its own receiver's snapshot
- * (snap_idx = receiver), signal power and records on the device, then the receivers' filter changes applied to the host
- * filters and, by msd_group_filter_apply_kernel, to the device snapshots.  Buffers the kernel hands back (fallback) and
- * receivers whose active table is nearly full are returned in `host` for group_host_entries. */
-int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vector<uint32_t> &gpu_idx,
-                      std::vector<uint32_t> &host, std::vector<uint32_t> &rec_first)
-{
-    msd_ctx *c = g->ctx;
-    const uint32_t n = s.nbuffers;
-    const GpuCtl ctl = gpu_ctl(c, s);
-    gpu_idx.clear();
-    for (uint32_t i = 0; i < n; ++i) {
-        GroupReceiver &r = g->rx[e[i].receiver];
-        /* sdr_ifile.c:187-190 on the receiver's own clock (the drops are on it already) */
-        const uint64_t sample_ts = (uint64_t)(r.resolver.sample_counter * 12e6 / 2400000.0);
-        ctl.h_ts[2 * i] = sample_ts;
-        ctl.h_ts[2 * i + 1] = sample_ts / 12000u;
-        ctl.h_valid[i] = MSD_CHUNK_SAMPLES;
-        ctl.h_snap[i] = e[i].receiver;
-        if (r.resolver.filter.active_used > GROUP_FULL_GUARD) {
-            host.push_back(i);
-        } else {
-            ctl.h_todo[gpu_idx.size()] = i;
-            gpu_idx.push_back(i);
-        }
-    }
-    const uint32_t ntodo = (uint32_t)gpu_idx.size();
-    if (!ntodo)
-        return 0;
-    MsdResolveParams rp{};
-    gpu_params(c, s, rp);
-    rp.snaps = g->d_snaps;
-    rp.pred = reinterpret_cast<const unsigned long long *>(s.d_pred); /* never written by a group scan: no predictions */
-    rp.pred_gen = 0;
-    rp.power = nullptr;   /* the fused power would read the batch's previous buffer as look-behind */
-    rp.first_pass = 0;
-    rp.ctl_implicit = 0;
-    GHIPCHK(g, hipMemsetAsync(s.d_nmsgs, 0, sizeof(uint32_t) * n, c->stream)); /* host-resolved buffers emit nothing */
-    if (rp.ac)
-        GHIPCHK(g, hipMemsetAsync(s.d_nac, 0, sizeof(uint32_t) * n, c->stream));
-    int rc = msd_launch_resolve(&rp, ntodo, c->stream);
-    if (rc)
-        return gfail(g, rc, "resolve kernel launch failed");
-    MsdScanParams p{};
-    fill_params(c, s, p);
-    p.have_prev = 0;
-    p.prev_tail = nullptr;
-    p.group_tails = g->d_tails;
-    p.group_lb = g->d_ctl;
-    rc = msd_launch_group_power_buffers(&p, c->cfg.format, s.d_acc, s.d_nmsgs, rp.todo, ntodo,
-                                        reinterpret_cast<unsigned long long *>(s.d_powr), c->stream);
-    if (rc)
-        return gfail(g, rc, "group power kernel launch failed");
-    GHIPCHK(g, hipStreamSynchronize(c->stream));
-    /* the kernel's verdicts: a buffer it could not finish goes to the host, its records must not be emitted */
-    uint32_t total = 0;
-    bool zeroed = false;
-    rec_first.assign(n + 1, 0);
-    for (uint32_t k = 0; k < ntodo; ++k) {
-        const uint32_t i = gpu_idx[k];
-        if (s.h_rbuf[i].fallback) {
-            host.push_back(i);
-            GHIPCHK(g, hipMemsetAsync(s.d_nmsgs + i, 0, sizeof(uint32_t), c->stream));
-            if (rp.ac)
-                GHIPCHK(g, hipMemsetAsync(s.d_nac + i, 0, sizeof(uint32_t), c->stream));
-            zeroed = true;
-        }
-    }
-    if (zeroed) {
-        std::vector<uint32_t> keep;
-        for (uint32_t i : gpu_idx)
-            if (!s.h_rbuf[i].fallback)
-                keep.push_back(i);
-        gpu_idx.swap(keep);
-    }
-    for (uint32_t i = 0, k = 0; i < n; ++i) {
-        rec_first[i] = total;
-        if (k < gpu_idx.size() && gpu_idx[k] == i) {
-            total += s.h_rbuf[i].nmsgs + s.h_rbuf[i].nac; /* its Mode S messages, then its Mode A/C replies (0: off) */
-            ++k;
-        }
-    }
-    rec_first[n] = total;
-    if (total) {
-        rc = ensure_req(c, s, total);
-        if (rc)
-            return gfail(g, rc, "records: %s", c->err);
-        rc = msd_launch_emit(&rp, n, reinterpret_cast<const unsigned long long *>(s.d_powr), s.h_side, s.h_wire, nullptr,
-                             (uint32_t)s.req_cap, c->stream);
-        if (rc)
-            return gfail(g, rc, "emit kernel launch failed");
-    }
-    /* the filter changes, in each receiver's order: adds, then the flip (readsb.c:331) -- on the host filters here, on
-     * the device snapshots by the filter kernel below */
-    const uint32_t m = (uint32_t)gpu_idx.size();
-    uint32_t *a_slot = g->h_apply, *a_first = g->h_apply + g->max_receivers, *a_flip = a_first + g->max_receivers + 1;
-    a_first[0] = 0;
-    for (uint32_t k = 0; k < m; ++k) { /* the add lists, concatenated */
-        const uint32_t i = gpu_idx[k];
-        const msd_rbuf &rb = s.h_rbuf[i];
-        const uint32_t *adds = rb.nshort <= MSD_RB_ADD_INLINE ? rb.adds : s.d_adds + (size_t)i * MSD_RB_MSG_CAP;
-        const uint32_t na = rb.nshort <= MSD_RB_ADD_INLINE ? rb.nshort : rb.nadds;
-        memcpy(g->h_adds + a_first[k], adds, sizeof(uint32_t) * na);
-        a_first[k + 1] = a_first[k] + na;
-        a_slot[k] = e[i].receiver;
-    }
-    parallel_for(m, g->threads, [&](uint32_t k) {
-        const uint32_t i = gpu_idx[k];
-        const msd_rbuf &rb = s.h_rbuf[i];
-        GroupReceiver &r = g->rx[e[i].receiver];
-        for (uint32_t j = a_first[k]; j < a_first[k + 1]; ++j)
-            msd_filter_add(&r.resolver.filter, g->h_adds[j]);
-        const int active = r.resolver.filter.active;
-        const uint64_t next_flip = r.resolver.filter.next_flip;
-        msd_filter_expire(&r.resolver.filter, rb.end_now);
-        a_flip[k] = (r.resolver.filter.active != active || r.resolver.filter.next_flip != next_flip) ? 1u : 0u;
-        r.resolver.sample_counter += MSD_CHUNK_SAMPLES;
-        r.resolver.ifile_now = rb.end_now;
-        msd_gpu_resolve_commit_stats(&r.resolver, 1, &ctl.h_valid[i], &rb);
-    });
-    rc = msd_launch_group_filter_apply(g->d_snaps, m, a_slot, a_first, g->h_adds, a_flip, c->stream);
-    if (rc)
-        return gfail(g, rc, "group filter kernel launch failed");
-    GHIPCHK(g, hipStreamSynchronize(c->stream));
-    /* signal level is in the records; the order-sensitive power statistics per receiver, in its own message order */
-    parallel_for(m, g->threads, [&](uint32_t k) {
-        const uint32_t i = gpu_idx[k];
-        GroupReceiver &r = g->rx[e[i].receiver];
-        const uint32_t nm = rec_first[i + 1] - rec_first[i];
-        const std::vector<uint32_t> buf(nm ? nm : 1, 0u);
-        msd_resolve_power_stats(&r.resolver, 1, &ctl.h_valid[i], g->out[i].means, buf.data(),
-                                reinterpret_cast<const uint64_t *>(s.h_side) + rec_first[i], nm);
-    });
-    return 0;
-}
-
-/* one call: scan (group instantiation); then every entry resolved against its own receiver's state -- on the GPU, or
- * on host threads (MSD_CFG_HOST_RESOLVE, a rescanned overflow, the kernel's fallback); tails; delivery in entry order */
-int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint32_t n, msd_group_message_fn sink, void *user)
-{
-    msd_ctx *c = g->ctx;
-    const int format = c->cfg.format;
-    const uint64_t nsamples = (uint64_t)n * MSD_CHUNK_SAMPLES;
-    /* look-behind: the receiver's tail slot unless it has none yet or lost samples in front of this buffer (fifo.c:178-181) */
-    uint32_t *lb = g->h_ctl, *slot = g->h_ctl + g->max_receivers, *opt = g->h_ctl + 2 * g->max_receivers;
-    uint32_t *ac = g->h_ctl + 3 * g->max_receivers, nac = 0;
-    bool fix2 = false;
-    for (uint32_t i = 0; i < n; ++i) {
-        GroupReceiver &r = g->rx[e[i].receiver];
-        lb[i] = r.have_tail && e[i].dropped == 0 ? e[i].receiver : MSD_GROUP_NO_TAIL;
-        slot[i] = e[i].receiver;
-        opt[i] = (uint32_t)r.opt.preamble_threshold | (uint32_t)r.opt.nfix_crc << 16;
-        fix2 |= r.opt.nfix_crc == 2;
-        r.history = true;
-        if (r.mode_ac) /* readsb.c:829-833: the switch as it stands when the buffer is demodulated */
-            ac[nac++] = i;
-        r.resolver.mode_ac = r.mode_ac; /* (the host resolver, if the buffer goes there) */
-    }
-    GHIPCHK(g, hipMemcpyAsync(g->d_ctl, g->h_ctl, sizeof(uint32_t) * (3 * (size_t)g->max_receivers + nac), hipMemcpyHostToDevice,
-                              c->stream));
-
-    Slot &s = c->slots[0];
-    s.busy = true;
-    s.d_iq = d_iq;
-    s.d_prev = nullptr;
-    s.have_prev = 0;
-    s.threshold = c->cfg.preamble_threshold;
-    s.dropped_before = 0;
-    s.gpu_resolve = false; /* no prediction table from the scan */
-    s.resolve_inflight = false;
-    s.reset_before = false;
-    s.dc = false;
-    s.batch_first = 0;
-    s.nsamples = nsamples;
-    s.nbuffers = n;
-    s.last = 0;
-    s.tail_dst = nullptr; /* the group keeps its own tails */
-    c->group_tails = g->d_tails;
-    c->group_lb = g->d_ctl;
-    c->group_opt = g->d_ctl + 2 * g->max_receivers;
-    c->group_fix2 = fix2;
-    c->group_ac = g->d_ctl + 3 * g->max_receivers;
-    c->group_ac_host = ac;
-    c->group_nac = nac;
-    struct Unset { /* the context's stream entries never see the group's look-behind */
-        msd_ctx *c;
-        Slot &s;
-        ~Unset()
-        {
-            c->group_tails = nullptr;
-            c->group_lb = nullptr;
-            c->group_opt = nullptr;
-            c->group_fix2 = false;
-            c->group_ac = nullptr;
-            c->group_ac_host = nullptr;
-            c->group_nac = 0;
-            s.busy = false;
-            s.download_started = false;
-        }
-    } unset{c, s};
-    int rc = enqueue(c, s, format, nullptr);
-    s.gpu_resolve = g->gpu; /* start_download: the lists stay on the device unless the arenas overflowed */
-    if (!rc)
-        rc = start_download(c, s, format); /* an arena overflow is scanned again in pieces here (rerun_in_pieces) */
-    if (rc)
-        return gfail(g, rc, "scan: %s", c->err);
-    GHIPCHK(g, hipEventSynchronize(s.ev_copy1));
-    const bool fm = format == MSD_FMT_SC16 || format == MSD_FMT_SC16Q11;
-
-    if (g->out.size() < n)
-        g->out.resize(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        GroupEntryOut &o = g->out[i];
-        GroupReceiver &r = g->rx[e[i].receiver];
-        o.msgs.clear();
-        o.req.clear();
-        if (fm) { /* convert.c:245-251 */
-            o.means[0] = (double)(s.h_fmeans[2 * i] / (float)MSD_CHUNK_SAMPLES);
-            o.means[1] = (double)(s.h_fmeans[2 * i + 1] / (float)MSD_CHUNK_SAMPLES);
-        } else { /* convert.c:104-110 */
-            o.means[0] = (double)s.h_sums[2 * i] / 65536.0 / (double)MSD_CHUNK_SAMPLES;
-            o.means[1] = (double)s.h_sums[2 * i + 1] / 65535.0 / 65535.0 / (double)MSD_CHUNK_SAMPLES;
-        }
-        /* samples lost in front of the buffer go onto its receiver's clock first (sdr_rtlsdr.c:284,299; readsb.c:836) */
-        r.resolver.sample_counter += e[i].dropped;
-        r.stats.samples_dropped += e[i].dropped;
-    }
-    std::vector<uint32_t> gpu_idx, host, rec_first;
-    if (s.gpu_resolve) {
-        rc = group_gpu_entries(g, s, e, gpu_idx, host, rec_first);
-        if (rc)
-            return rc;
-        if (!host.empty()) { /* their candidate lists after all */
-            std::sort(host.begin(), host.end());
-            rc = ensure_host(c, s, s.h_totals[0], s.h_totals[1]);
-            if (rc)
-                return gfail(g, rc, "lists: %s", c->err);
-            if (s.h_totals[0])
-                GHIPCHK(g, hipMemcpyAsync(s.h_hits, s.d_hits, s.h_totals[0] * sizeof(msd_hit), hipMemcpyDeviceToHost, c->stream));
-            if (s.h_totals[1])
-                GHIPCHK(g, hipMemcpyAsync(s.h_tries, s.d_tries, s.h_totals[1] * sizeof(msd_try), hipMemcpyDeviceToHost, c->stream));
-            if (nac) {
-                rc = ensure_ac_host(c, s, s.h_ac_totals[0]);
-                if (rc)
-                    return gfail(g, rc, "lists: %s", c->err);
-                if (s.h_ac_totals[0])
-                    GHIPCHK(g, hipMemcpyAsync(s.h_ac, s.d_ac, s.h_ac_totals[0] * sizeof(msd_ac_hit), hipMemcpyDeviceToHost,
-                                              c->stream));
-            }
-            GHIPCHK(g, hipStreamSynchronize(c->stream));
-        }
-    } else {
-        for (uint32_t i = 0; i < n; ++i)
-            host.push_back(i);
-    }
-    c->timing.hits = s.h_totals[0];
-    c->timing.tries = s.h_totals[1];
-    c->timing.resolve_passes = gpu_idx.empty() ? 0 : 1;
-    if (!host.empty()) {
-        rc = group_host_entries(g, s, e, host);
-        if (rc)
-            return rc;
-    }
-    c->timing.resolve_fallback = g->host_buffers;
-    /* every buffer's end becomes its receiver's look-behind (behind the scan, its reruns and the power kernels) */
-    rc = msd_launch_group_tails(d_iq, n, g->d_ctl + g->max_receivers, g->d_tails, (uint32_t)c->bps, c->stream);
-    if (rc)
-        return gfail(g, rc, "group tail kernel launch failed");
-    GHIPCHK(g, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; ++i)
-        g->rx[e[i].receiver].have_tail = true;
-    if (sink) {
-        std::vector<bool> on_gpu(n, false);
-        for (uint32_t i : gpu_idx)
-            on_gpu[i] = true;
-        for (uint32_t i = 0; i < n; ++i) {
-            if (on_gpu[i]) {
-                for (uint32_t k = rec_first[i]; k < rec_first[i + 1]; ++k)
-                    sink(e[i].receiver, &s.h_wire[k].mm, user);
-            } else {
-                for (const msd_message &m : g->out[i].msgs)
-                    sink(e[i].receiver, &m, user);
-            }
-        }
-    }
-    return 0;
-}
-
-} /* namespace */
-
-extern "C" {
-
-int msd_group_create(const msd_config *cfg, uint32_t max_receivers, msd_group **out)
-{
-    if (!cfg || !out)
-        return -EINVAL;
-    *out = nullptr;
-    if (max_receivers == 0 || (uint64_t)max_receivers * MSD_CHUNK_SAMPLES > MSD_MAX_BATCH_SAMPLES / 2 ||
-        cfg->mode_ac || (cfg->flags & MSD_CFG_DC_FILTER) || cfg->format == MSD_FMT_MAG16 || cfg->sc16q11_table_bits)
-        return -EINVAL;
-    msd_group *g = new (std::nothrow) msd_group;
-    if (!g)
-        return -ENOMEM;
-    g->gpu = !(cfg->flags & MSD_CFG_HOST_RESOLVE);
-    msd_config cc = *cfg;
-    cc.max_batch_samples = (uint64_t)max_receivers * MSD_CHUNK_SAMPLES;
-    cc.flags |= MSD_CFG_NO_HELPER | MSD_CFG_NO_LEAN; /* synchronous calls over the dense candidate lists */
-    if (cc.nfix_crc == 0) /* the single-bit tables always: a receiver may be set to level 1 (the scan gates by level) */
-        cc.nfix_crc = 1;
-    int rc = msd_create(&cc, &g->ctx);
-    if (rc) {
-        delete g;
-        return rc;
-    }
-    g->max_receivers = max_receivers;
-    const unsigned hw = std::thread::hardware_concurrency();
-    g->threads = cfg->resolve_threads > 0 ? (uint32_t)cfg->resolve_threads : std::max(1u, std::min(16u, hw / 8u));
-    g->rx = new (std::nothrow) GroupReceiver[max_receivers];
-    const size_t tail_bytes = (size_t)max_receivers * MSD_HALO_FRONT * g->ctx->bps;
-    if (!g->rx || hipMalloc(reinterpret_cast<void **>(&g->d_tails), tail_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&g->d_ctl), sizeof(uint32_t) * 4 * max_receivers) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&g->h_ctl), sizeof(uint32_t) * 4 * max_receivers, hipHostMallocDefault) != hipSuccess ||
-        (g->gpu && (hipMalloc(reinterpret_cast<void **>(&g->d_snaps), sizeof(uint32_t) * MSD_SNAP_WORDS * max_receivers) != hipSuccess ||
-                    hipHostMalloc(reinterpret_cast<void **>(&g->h_apply), sizeof(uint32_t) * (3 * (size_t)max_receivers + 1),
-                                  hipHostMallocDefault) != hipSuccess ||
-                    hipHostMalloc(reinterpret_cast<void **>(&g->h_adds), sizeof(uint32_t) * MSD_RB_MSG_CAP * (size_t)max_receivers,
-                                  hipHostMallocDefault) != hipSuccess ||
-                    hipHostMalloc(reinterpret_cast<void **>(&g->h_snap), sizeof(uint32_t) * MSD_SNAP_WORDS, hipHostMallocDefault) != hipSuccess))) {
-        (void)hipGetLastError();
-        msd_group_destroy(g);
-        return -ENOMEM;
-    }
-    for (uint32_t r = 0; r < max_receivers; ++r) {
-        g->rx[r].resolver.stats = &g->rx[r].stats;
-        g->rx[r].resolver.threads = 1;
-        g->rx[r].opt.preamble_threshold = cfg->preamble_threshold;
-        g->rx[r].opt.nfix_crc = cfg->nfix_crc;
-        group_receiver_reset(g->rx[r]);
-        rc = group_upload_snapshot(g, r);
-        if (rc) {
-            msd_group_destroy(g);
-            return rc;
-        }
-    }
-    *out = g;
-    return 0;
-}
-
-void msd_group_destroy(msd_group *g)
-{
-    if (!g)
-        return;
-    if (g->ctx)
-        (void)hipSetDevice(g->ctx->cfg.device);
-    if (g->rx) {
-        for (uint32_t r = 0; r < g->max_receivers; ++r)
-            msd_resolver_free(&g->rx[r].resolver);
-        delete[] g->rx;
-    }
-    (void)hipFree(g->d_tails);
-    (void)hipFree(g->d_ctl);
-    (void)hipHostFree(g->h_ctl);
-    (void)hipFree(g->d_snaps);
-    (void)hipHostFree(g->h_apply);
-    (void)hipHostFree(g->h_adds);
-    (void)hipHostFree(g->h_snap);
-    msd_destroy(g->ctx);
-    delete g;
-}
-
-const char *msd_group_last_error(const msd_group *g)
-{
-    return g ? g->err : "no group";
-}
-
-int msd_group_submit_device(msd_group *g, const void *d_iq, const msd_group_entry *e, uint32_t n,
-                            msd_group_message_fn sink, void *user)
-{
-    if (!g)
-        return -EINVAL;
-    if (group_check(g, e, n))
-        return gfail(g, -EINVAL, "entries: a receiver out of range or given twice, nonzero flags, or more than max_receivers");
-    if (n && (!d_iq || (reinterpret_cast<uintptr_t>(d_iq) & 15u)))
-        return gfail(g, -EINVAL, "IQ pointer must be non-null and 16-byte aligned");
-    if (g->ctx->failed)
-        return gfail(g, -EIO, "an earlier call failed");
-    if (n == 0)
-        return 0;
-    GHIPCHK(g, hipSetDevice(g->ctx->cfg.device));
-    const int rc = group_run(g, static_cast<const uint8_t *>(d_iq), e, n, sink, user);
-    if (rc)
-        g->ctx->failed = true;
-    return rc;
-}
-
-int msd_group_submit_host(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n,
-                          msd_group_message_fn sink, void *user)
-{
-    if (!g)
-        return -EINVAL;
-    if (group_check(g, e, n))
-        return gfail(g, -EINVAL, "entries: a receiver out of range or given twice, nonzero flags, or more than max_receivers");
-    if (n && !h_iq)
-        return gfail(g, -EINVAL, "IQ pointer must be non-null");
-    msd_ctx *c = g->ctx;
-    if (c->failed)
-        return gfail(g, -EIO, "an earlier call failed");
-    if (n == 0)
-        return 0;
-    auto stage = [&]() -> int {
-        GHIPCHK(g, hipSetDevice(c->cfg.device));
-        if (!c->d_stage)
-            GHIPCHK(g, hipMalloc(reinterpret_cast<void **>(&c->d_stage), c->cfg.max_batch_samples * 4 + 64));
-        GHIPCHK(g, hipMemcpyAsync(c->d_stage, h_iq, (size_t)n * MSD_CHUNK_SAMPLES * c->bps, hipMemcpyHostToDevice, c->stream));
-        return 0;
-    };
-    const int rc = stage();
-    if (rc) {
-        c->failed = true;
-        return rc;
-    }
-    return msd_group_submit_device(g, c->d_stage, e, n, sink, user);
-}
-
-int msd_group_reset_receiver(msd_group *g, uint32_t receiver)
-{
-    if (!g || receiver >= g->max_receivers)
-        return -EINVAL;
-    if (g->ctx->failed)
-        return gfail(g, -EIO, "an earlier call failed");
-    group_receiver_reset(g->rx[receiver]);
-    const int rc = group_upload_snapshot(g, receiver);
-    if (rc)
-        g->ctx->failed = true;
-    return rc;
-}
-
-int msd_group_get_stats(const msd_group *g, uint32_t receiver, msd_stats *st)
-{
-    if (!g || !st || receiver >= g->max_receivers)
-        return -EINVAL;
-    *st = g->rx[receiver].stats;
-    return 0;
-}
-
-int msd_group_set_preamble_threshold(msd_group *g, int threshold)
-{
-    if (!g)
-        return -EINVAL;
-    const int rc = msd_set_preamble_threshold(g->ctx, threshold);
-    if (rc)
-        return gfail(g, rc, "%s", g->ctx->err);
-    for (uint32_t r = 0; r < g->max_receivers; ++r)
-        g->rx[r].opt.preamble_threshold = threshold;
-    return 0;
-}
-
-int msd_group_set_receiver_options(msd_group *g, uint32_t receiver, const msd_group_receiver_options *o)
-{
-    if (!g)
-        return -EINVAL;
-    if (!o || receiver >= g->max_receivers)
-        return gfail(g, -EINVAL, "receiver options: a receiver out of range or no options");
-    if (o->preamble_threshold < 1 || o->preamble_threshold > MSD_MAX_PREAMBLE_THRESHOLD || o->nfix_crc < 0 ||
-        o->nfix_crc > 2 || o->reserved[0] || o->reserved[1])
-        return gfail(g, -EINVAL, "receiver options: threshold %d outside 1..%d, repair level %d outside 0..2, or nonzero "
-                     "reserved words", o->preamble_threshold, MSD_MAX_PREAMBLE_THRESHOLD, o->nfix_crc);
-    GroupReceiver &r = g->rx[receiver];
-    if (o->nfix_crc != r.opt.nfix_crc && r.history) /* readsb cannot change --fix in a running process either */
-        return gfail(g, -EBUSY, "receiver %u: the repair level changes only before its first buffer (after a reset)",
-                     receiver);
-    if (o->nfix_crc == 2) {
-        const int rc = group_make_fix2(g);
-        if (rc)
-            return rc;
-    }
-    r.opt.preamble_threshold = o->preamble_threshold;
-    r.opt.nfix_crc = o->nfix_crc;
-    return 0;
-}
-
-int msd_group_get_receiver_options(const msd_group *g, uint32_t receiver, msd_group_receiver_options *o)
-{
-    if (!g || !o || receiver >= g->max_receivers)
-        return -EINVAL;
-    *o = g->rx[receiver].opt;
-    return 0;
-}
-
-int msd_group_set_receiver_mode_ac(msd_group *g, uint32_t receiver, int on)
-{
-    if (!g)
-        return -EINVAL;
-    if (receiver >= g->max_receivers || (on != 0 && on != 1))
-        return gfail(g, -EINVAL, "Mode A/C: receiver %u out of range or switch %d not 0 or 1", receiver, on);
-    if (on) {
-        const int rc = group_make_ac(g);
-        if (rc)
-            return rc;
-    }
-    g->rx[receiver].mode_ac = on != 0;
-    return 0;
-}
-
-int msd_group_get_receiver_mode_ac(const msd_group *g, uint32_t receiver, int *on)
-{
-    if (!g || !on || receiver >= g->max_receivers)
-        return -EINVAL;
-    *on = g->rx[receiver].mode_ac ? 1 : 0;
-    return 0;
-}
-
-int msd_group_get_timing(const msd_group *g, msd_timing *t)
-{
-    if (!g)
-        return -EINVAL;
-    return msd_get_timing(g->ctx, t);
 }
 
 } /* extern "C" */

@@ -1,0 +1,810 @@
+/*
+ * msd_group.cpp -- receiver groups (modes_hip.h msd_group_*): one buffer from each of many live
+ * receivers in one call of a wrapped context.  The call runs through the context's stream pipeline as a batch whose
+ * slot carries a GroupCall (msd_ctx.h); every buffer is then resolved against its own receiver's state.
+ */
+#include <algorithm>
+#include <atomic>
+#include <cerrno>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <new>
+#include <thread>
+#include <vector>
+
+#include "msd_ctx.h" /* the context, and with it modes_hip.h, msd_internal.h and msd_kernels.h */
+
+using namespace msd_impl;
+
+namespace {
+
+struct GroupReceiver {
+    msd_resolver resolver{}; /* filter, clock (sample_counter) and the counters it sums into `stats` */
+    msd_stats stats{};
+    bool have_tail = false; /* its tail slot holds the end of its previous buffer */
+    bool history = false;   /* a buffer since creation or the last reset: the repair level is fixed */
+    msd_group_receiver_options opt{}; /* kept across msd_group_reset_receiver */
+    bool mode_ac = false;             /* Mode A/C on (readsb --modeac), likewise kept */
+};
+
+/* what the host resolver delivers for one entry of a call */
+struct GroupEntryOut {
+    std::vector<msd_message> msgs;
+    std::vector<uint64_t> req;
+    std::vector<msd_hit> hits; /* the entry's hits, positions made buffer-relative */
+    std::vector<msd_ac_hit> ac; /* its Mode A/C candidates, likewise */
+    double means[2] = {0, 0};
+    uint32_t valid = MSD_CHUNK_SAMPLES;
+};
+
+void group_emit(const msd_message *mm, const uint64_t *power_req, uint32_t count, uint32_t, void *user)
+{
+    GroupEntryOut *o = static_cast<GroupEntryOut *>(user);
+    o->msgs.insert(o->msgs.end(), mm, mm + count);
+    o->req.insert(o->req.end(), power_req, power_req + count);
+}
+
+/* body(i) for i in [0, n) on up to `threads` host threads (the calling one included); the work of a thread that could
+ * not be started is done by the others */
+void parallel_for(uint32_t n, uint32_t threads, const std::function<void(uint32_t)> &body)
+{
+    if (threads > n)
+        threads = n;
+    std::atomic<uint32_t> next{0};
+    auto work = [&]() {
+        for (uint32_t i; (i = next.fetch_add(1)) < n;)
+            body(i);
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < threads; ++t) {
+        try {
+            pool.emplace_back(work);
+        } catch (...) {
+            break;
+        }
+    }
+    work();
+    for (std::thread &t : pool)
+        t.join();
+}
+
+} /* namespace */
+
+struct msd_group {
+    msd_ctx *ctx = nullptr;
+    uint32_t max_receivers = 0;
+    uint32_t threads = 1; /* host threads of the per-receiver work */
+    bool gpu = false;     /* resolve on the GPU against the receivers' device snapshots (not MSD_CFG_HOST_RESOLVE) */
+    GroupReceiver *rx = nullptr;
+    uint8_t *d_tails = nullptr;    /* [max_receivers][MSD_HALO_FRONT] raw samples */
+    uint32_t *d_ctl = nullptr;     /* [4][max_receivers]: per buffer its look-behind slot, its receiver and its receiver's
+                                      options (threshold | nfix_crc << 16); then the call's buffers with Mode A/C on */
+    uint32_t *h_ctl = nullptr;     /* pinned copy */
+    uint32_t *d_snaps = nullptr;   /* [max_receivers][MSD_SNAP_WORDS]: every receiver's ICAO filter on the device */
+    uint32_t *h_apply = nullptr;   /* pinned, read in place by the filter kernel: slot[n] | add_first[n + 1] | flip[n] */
+    uint32_t *h_adds = nullptr;    /* pinned: the entries' adds, max_receivers * MSD_RB_MSG_CAP */
+    uint32_t *h_snap = nullptr;    /* pinned staging of one snapshot */
+    uint64_t host_buffers = 0;     /* buffers resolved on the host (msd_timing.resolve_fallback) */
+    std::vector<GroupEntryOut> out;
+    std::vector<uint64_t> req_all;
+    char err[256] = {0};
+};
+
+namespace {
+
+int gfail(msd_group *g, int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g->err, sizeof g->err, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define GHIPCHK(g, call)                                                                        \
+    do {                                                                                        \
+        hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return gfail((g), -EIO, "%s failed: %s", #call, hipGetErrorString(e_));             \
+    } while (0)
+
+/* the receiver's host filter -> its device snapshot (at creation, reset and after a buffer resolved on the host) */
+int group_upload_snapshot(msd_group *g, uint32_t receiver)
+{
+    if (!g->gpu)
+        return 0;
+    const msd_filter &f = g->rx[receiver].resolver.filter;
+    for (uint32_t h = 0; h < 8192; ++h) {
+        g->h_snap[2 * h] = f.slot[0][h];
+        g->h_snap[2 * h + 1] = f.slot[1][h];
+    }
+    g->h_snap[16384] = (uint32_t)f.active;
+    GHIPCHK(g, hipMemcpy(g->d_snaps + (size_t)receiver * MSD_SNAP_WORDS, g->h_snap, sizeof(uint32_t) * MSD_SNAP_WORDS,
+                         hipMemcpyHostToDevice));
+    return 0;
+}
+
+void group_receiver_reset(GroupReceiver &r)
+{
+    msd_resolver_reset(&r.resolver); /* filter, clock and the counters behind r.resolver.stats */
+    memset(&r.stats, 0, sizeof r.stats);
+    r.have_tail = false;
+    r.history = false;
+}
+
+/* The two-bit correction tables (--aggressive, crc.c:374-379) of the group's context, made when the first receiver is
+ * set to repair level 2 (msd_create makes them when the group's own configuration has nfix_crc 2). */
+int group_make_fix2(msd_group *g)
+{
+    msd_ctx *c = g->ctx;
+    if (c->d_fix2[1])
+        return 0;
+    GHIPCHK(g, hipSetDevice(c->cfg.device));
+    bool host_oom = false;
+    const hipError_t e = upload_fix2(c, &host_oom);
+    if (host_oom)
+        return gfail(g, -ENOMEM, "two-bit correction table: out of host memory");
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return gfail(g, e == hipErrorOutOfMemory ? -ENOMEM : -EIO, "two-bit correction table: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+/* The Mode A/C buffers of the group's context (slot 0, the only one a group uses): the candidate kernel's regions and
+ * counts, the ordered list and its totals, and for the GPU resolve the accepted replies per buffer -- made when the first
+ * receiver is switched on.  The arena holds a candidate per 32 samples of a full call, and never less than one per
+ * sample of one buffer, so that a call rescanned in pieces always fits once the pieces are single buffers. */
+int group_make_ac(msd_group *g)
+{
+    msd_ctx *c = g->ctx;
+    Slot &s = c->slots[0];
+    if (s.d_ac)
+        return 0;
+    GHIPCHK(g, hipSetDevice(c->cfg.device));
+    const uint64_t B = c->cfg.max_batch_samples;
+    const uint64_t arena = B / 32 > MIN_HIT_ARENA ? B / 32 : MIN_HIT_ARENA;
+    const uint32_t max_wg = (uint32_t)c->cu_count * 28u; /* as msd_create: one region per resident wavefront */
+    msd_ac_hit *regions = nullptr, *dense = nullptr;
+    msd_wg_counts *counts = nullptr;
+    uint64_t *totals = nullptr, *h_totals = nullptr;
+    uint32_t *acc_ac = nullptr, *nac = nullptr;
+    bool ok = hipMalloc(reinterpret_cast<void **>(&regions), arena * sizeof(msd_ac_hit)) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void **>(&dense), arena * sizeof(msd_ac_hit)) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void **>(&counts), max_wg * sizeof(msd_wg_counts)) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void **>(&totals), 4 * sizeof(uint64_t)) == hipSuccess &&
+              hipHostMalloc(reinterpret_cast<void **>(&h_totals), 4 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
+    if (ok && g->gpu)
+        ok = hipMalloc(reinterpret_cast<void **>(&acc_ac), sizeof(uint32_t) * MSD_RB_AC_CAP * c->max_buffers) == hipSuccess &&
+             hipMalloc(reinterpret_cast<void **>(&nac), sizeof(uint32_t) * c->max_buffers) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        (void)hipFree(regions);
+        (void)hipFree(dense);
+        (void)hipFree(counts);
+        (void)hipFree(totals);
+        if (h_totals)
+            (void)hipHostFree(h_totals);
+        (void)hipFree(acc_ac);
+        (void)hipFree(nac);
+        return gfail(g, -ENOMEM, "Mode A/C buffers: out of memory");
+    }
+    memset(h_totals, 0, 4 * sizeof(uint64_t));
+    s.d_ac_regions = regions;
+    s.d_ac = dense;
+    s.d_ac_counts = counts;
+    s.d_ac_totals = totals;
+    s.h_ac_totals = h_totals;
+    s.d_acc_ac = acc_ac;
+    s.d_nac = nac;
+    c->ac_arena = arena;
+    c->ac_max_wg = max_wg;
+    return 0;
+}
+
+int group_check(const msd_group *g, const msd_group_entry *e, uint32_t n)
+{
+    if (n > g->max_receivers)
+        return -EINVAL;
+    if (n && !e)
+        return -EINVAL;
+    std::vector<bool> seen(g->max_receivers, false);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (e[i].receiver >= g->max_receivers || e[i].flags != 0 || seen[e[i].receiver])
+            return -EINVAL;
+        seen[e[i].receiver] = true;
+    }
+    return 0;
+}
+
+constexpr uint32_t GROUP_FULL_GUARD = 6000u; /* occupied active slots above which a buffer is resolved on the host (as the
+                                                context's replay does: a buffer adds at most 970 addresses, two slots each) */
+
+/* The entries idx[] on the host: each buffer through the host resolver's sequential path against its receiver's filter,
+ * hit positions made buffer-relative; then the signal power of their messages with the group look-behind.  The
+ * candidate lists must be in s.h_hits / s.h_tries. */
+int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const std::vector<uint32_t> &idx)
+{
+    msd_ctx *c = g->ctx;
+    const int format = c->cfg.format;
+    const uint64_t H = s.h_totals[0];
+    const msd_hit *hits = s.h_hits;
+    const uint32_t n = s.nbuffers;
+    const uint64_t NA = ac_on(c, s) ? s.h_ac_totals[0] : 0; /* Mode A/C candidates of the call (s.h_ac), ordered */
+    std::vector<uint64_t> first(n + 1), ac_first(n + 1);
+    {
+        uint64_t h = 0, a = 0;
+        for (uint32_t i = 0; i <= n; ++i) {
+            const uint64_t pos = (uint64_t)i * MSD_CHUNK_SAMPLES;
+            while (h < H && MSD_HIT_POS(hits[h]) < pos)
+                ++h;
+            while (a < NA && s.h_ac[a].pos < pos)
+                ++a;
+            first[i] = h;
+            ac_first[i] = a;
+        }
+    }
+    parallel_for((uint32_t)idx.size(), g->threads, [&](uint32_t k) {
+        const uint32_t i = idx[k];
+        GroupEntryOut &o = g->out[i];
+        GroupReceiver &r = g->rx[e[i].receiver];
+        o.hits.assign(hits + first[i], hits + first[i + 1]);
+        for (msd_hit &h : o.hits)
+            h -= (msd_hit)i * MSD_CHUNK_SAMPLES; /* position is the low field */
+        o.ac.assign(s.h_ac + ac_first[i], s.h_ac + ac_first[i + 1]); /* (none unless its receiver has Mode A/C on) */
+        for (msd_ac_hit &a : o.ac)
+            a.pos -= (uint64_t)i * MSD_CHUNK_SAMPLES;
+        msd_resolve_batch(&r.resolver, 0, 1, &o.valid, o.hits.data(), o.hits.size(), s.h_tries, s.h_totals[1], o.ac.data(),
+                          o.ac.size(), nullptr, group_emit, &o);
+    });
+    g->req_all.clear();
+    for (uint32_t i : idx)
+        for (uint64_t q : g->out[i].req)
+            g->req_all.push_back(q + ((uint64_t)i * MSD_CHUNK_SAMPLES << 16));
+    const size_t nm = g->req_all.size();
+    if (nm) {
+        MsdScanParams p{};
+        fill_params(c, s, p);
+        int rc = ensure_req(c, s, nm);
+        if (rc)
+            return gfail(g, rc, "power: %s", c->err);
+        memcpy(s.h_req, g->req_all.data(), nm * sizeof(uint64_t));
+        GHIPCHK(g, hipMemcpyAsync(s.d_req, s.h_req, nm * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        rc = msd_launch_power(&p, format, s.d_req, (uint32_t)nm, reinterpret_cast<unsigned long long *>(s.d_pow), c->stream);
+        if (rc)
+            return gfail(g, rc, "group power kernel launch failed");
+        GHIPCHK(g, hipMemcpyAsync(s.h_pow, s.d_pow, nm * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        GHIPCHK(g, hipStreamSynchronize(c->stream));
+    }
+    std::vector<uint64_t> pow_first(idx.size() + 1, 0);
+    for (size_t k = 0; k < idx.size(); ++k)
+        pow_first[k + 1] = pow_first[k] + g->out[idx[k]].req.size();
+    parallel_for((uint32_t)idx.size(), g->threads, [&](uint32_t k) {
+        GroupEntryOut &o = g->out[idx[k]];
+        GroupReceiver &r = g->rx[e[idx[k]].receiver];
+        const std::vector<uint32_t> buf(o.msgs.size(), 0u);
+        msd_resolve_power(&r.resolver, 1, &o.valid, o.means, o.msgs.data(), sizeof(msd_message), o.req.data(), buf.data(),
+                          s.h_pow + pow_first[k], sizeof(uint64_t), o.msgs.size());
+    });
+    g->host_buffers += idx.size();
+    for (uint32_t i : idx) { /* the device copies follow the host filters */
+        const int rc = group_upload_snapshot(g, e[i].receiver);
+        if (rc)
+            return rc;
+    }
+    return 0;
+}
+
+/* The GPU resolve of one call: every buffer in one pass of msd_resolve_kernel against its own receiver's snapshot
+ * (snap_idx = receiver), signal power and records on the device, then the receivers' filter changes applied to the host
+ * filters and, by msd_group_filter_apply_kernel, to the device snapshots.  Buffers the kernel hands back (fallback) and
+ * receivers whose active table is nearly full are returned in `host` for group_host_entries. */
+int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vector<uint32_t> &gpu_idx,
+                      std::vector<uint32_t> &host, std::vector<uint32_t> &rec_first)
+{
+    msd_ctx *c = g->ctx;
+    const uint32_t n = s.nbuffers;
+    const GpuCtl ctl = gpu_ctl(c, s);
+    gpu_idx.clear();
+    for (uint32_t i = 0; i < n; ++i) {
+        GroupReceiver &r = g->rx[e[i].receiver];
+        /* sdr_ifile.c:187-190 on the receiver's own clock (the drops are on it already) */
+        const uint64_t sample_ts = (uint64_t)(r.resolver.sample_counter * 12e6 / 2400000.0);
+        ctl.h_ts[2 * i] = sample_ts;
+        ctl.h_ts[2 * i + 1] = sample_ts / 12000u;
+        ctl.h_valid[i] = MSD_CHUNK_SAMPLES;
+        ctl.h_snap[i] = e[i].receiver;
+        if (r.resolver.filter.active_used > GROUP_FULL_GUARD) {
+            host.push_back(i);
+        } else {
+            ctl.h_todo[gpu_idx.size()] = i;
+            gpu_idx.push_back(i);
+        }
+    }
+    const uint32_t ntodo = (uint32_t)gpu_idx.size();
+    if (!ntodo)
+        return 0;
+    MsdResolveParams rp{};
+    gpu_params(c, s, rp);
+    rp.snaps = g->d_snaps;
+    rp.pred = reinterpret_cast<const unsigned long long *>(s.d_pred); /* never written by a group scan: no predictions */
+    rp.pred_gen = 0;
+    rp.power = nullptr;   /* the fused power would read the batch's previous buffer as look-behind */
+    rp.first_pass = 0;
+    rp.ctl_implicit = 0;
+    GHIPCHK(g, hipMemsetAsync(s.d_nmsgs, 0, sizeof(uint32_t) * n, c->stream)); /* host-resolved buffers emit nothing */
+    if (rp.ac)
+        GHIPCHK(g, hipMemsetAsync(s.d_nac, 0, sizeof(uint32_t) * n, c->stream));
+    int rc = msd_launch_resolve(&rp, ntodo, c->stream);
+    if (rc)
+        return gfail(g, rc, "resolve kernel launch failed");
+    MsdScanParams p{};
+    fill_params(c, s, p);
+    rc = msd_launch_group_power_buffers(&p, c->cfg.format, s.d_acc, s.d_nmsgs, rp.todo, ntodo,
+                                        reinterpret_cast<unsigned long long *>(s.d_powr), c->stream);
+    if (rc)
+        return gfail(g, rc, "group power kernel launch failed");
+    GHIPCHK(g, hipStreamSynchronize(c->stream));
+    /* the kernel's verdicts: a buffer it could not finish goes to the host, its records must not be emitted */
+    uint32_t total = 0;
+    bool zeroed = false;
+    rec_first.assign(n + 1, 0);
+    for (uint32_t k = 0; k < ntodo; ++k) {
+        const uint32_t i = gpu_idx[k];
+        if (s.h_rbuf[i].fallback) {
+            host.push_back(i);
+            GHIPCHK(g, hipMemsetAsync(s.d_nmsgs + i, 0, sizeof(uint32_t), c->stream));
+            if (rp.ac)
+                GHIPCHK(g, hipMemsetAsync(s.d_nac + i, 0, sizeof(uint32_t), c->stream));
+            zeroed = true;
+        }
+    }
+    if (zeroed) {
+        std::vector<uint32_t> keep;
+        for (uint32_t i : gpu_idx)
+            if (!s.h_rbuf[i].fallback)
+                keep.push_back(i);
+        gpu_idx.swap(keep);
+    }
+    for (uint32_t i = 0, k = 0; i < n; ++i) {
+        rec_first[i] = total;
+        if (k < gpu_idx.size() && gpu_idx[k] == i) {
+            total += s.h_rbuf[i].nmsgs + s.h_rbuf[i].nac; /* its Mode S messages, then its Mode A/C replies (0: off) */
+            ++k;
+        }
+    }
+    rec_first[n] = total;
+    if (total) {
+        rc = ensure_req(c, s, total);
+        if (rc)
+            return gfail(g, rc, "records: %s", c->err);
+        rc = msd_launch_emit(&rp, n, reinterpret_cast<const unsigned long long *>(s.d_powr), s.h_side, s.h_wire, nullptr,
+                             (uint32_t)s.req_cap, c->stream);
+        if (rc)
+            return gfail(g, rc, "emit kernel launch failed");
+    }
+    /* the filter changes, in each receiver's order: adds, then the flip (readsb.c:331) -- on the host filters here, on
+     * the device snapshots by the filter kernel below */
+    const uint32_t m = (uint32_t)gpu_idx.size();
+    uint32_t *a_slot = g->h_apply, *a_first = g->h_apply + g->max_receivers, *a_flip = a_first + g->max_receivers + 1;
+    a_first[0] = 0;
+    for (uint32_t k = 0; k < m; ++k) { /* the add lists, concatenated */
+        const uint32_t i = gpu_idx[k];
+        const msd_rbuf &rb = s.h_rbuf[i];
+        const uint32_t *adds = rb.nshort <= MSD_RB_ADD_INLINE ? rb.adds : s.d_adds + (size_t)i * MSD_RB_MSG_CAP;
+        const uint32_t na = rb.nshort <= MSD_RB_ADD_INLINE ? rb.nshort : rb.nadds;
+        memcpy(g->h_adds + a_first[k], adds, sizeof(uint32_t) * na);
+        a_first[k + 1] = a_first[k] + na;
+        a_slot[k] = e[i].receiver;
+    }
+    parallel_for(m, g->threads, [&](uint32_t k) {
+        const uint32_t i = gpu_idx[k];
+        const msd_rbuf &rb = s.h_rbuf[i];
+        GroupReceiver &r = g->rx[e[i].receiver];
+        for (uint32_t j = a_first[k]; j < a_first[k + 1]; ++j)
+            msd_filter_add(&r.resolver.filter, g->h_adds[j]);
+        const int active = r.resolver.filter.active;
+        const uint64_t next_flip = r.resolver.filter.next_flip;
+        msd_filter_expire(&r.resolver.filter, rb.end_now);
+        a_flip[k] = (r.resolver.filter.active != active || r.resolver.filter.next_flip != next_flip) ? 1u : 0u;
+        r.resolver.sample_counter += MSD_CHUNK_SAMPLES;
+        r.resolver.ifile_now = rb.end_now;
+        msd_gpu_resolve_commit_stats(&r.resolver, 1, &ctl.h_valid[i], &rb);
+    });
+    rc = msd_launch_group_filter_apply(g->d_snaps, m, a_slot, a_first, g->h_adds, a_flip, c->stream);
+    if (rc)
+        return gfail(g, rc, "group filter kernel launch failed");
+    GHIPCHK(g, hipStreamSynchronize(c->stream));
+    /* signal level is in the records; the order-sensitive power statistics per receiver, in its own message order */
+    parallel_for(m, g->threads, [&](uint32_t k) {
+        const uint32_t i = gpu_idx[k];
+        GroupReceiver &r = g->rx[e[i].receiver];
+        const uint32_t nm = rec_first[i + 1] - rec_first[i];
+        const std::vector<uint32_t> buf(nm ? nm : 1, 0u);
+        msd_resolve_power_stats(&r.resolver, 1, &ctl.h_valid[i], g->out[i].means, buf.data(),
+                                reinterpret_cast<const uint64_t *>(s.h_side) + rec_first[i], nm);
+    });
+    return 0;
+}
+
+/* one call: scan (group instantiation); then every entry resolved against its own receiver's state -- on the GPU, or
+ * on host threads (MSD_CFG_HOST_RESOLVE, a rescanned overflow, the kernel's fallback); tails; delivery in entry order */
+int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint32_t n, msd_group_message_fn sink, void *user)
+{
+    msd_ctx *c = g->ctx;
+    const int format = c->cfg.format;
+    const uint64_t nsamples = (uint64_t)n * MSD_CHUNK_SAMPLES;
+    /* look-behind: the receiver's tail slot unless it has none yet or lost samples in front of this buffer (fifo.c:178-181) */
+    uint32_t *lb = g->h_ctl, *slot = g->h_ctl + g->max_receivers, *opt = g->h_ctl + 2 * g->max_receivers;
+    uint32_t *ac = g->h_ctl + 3 * g->max_receivers, nac = 0;
+    bool fix2 = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        GroupReceiver &r = g->rx[e[i].receiver];
+        lb[i] = r.have_tail && e[i].dropped == 0 ? e[i].receiver : MSD_GROUP_NO_TAIL;
+        slot[i] = e[i].receiver;
+        opt[i] = (uint32_t)r.opt.preamble_threshold | (uint32_t)r.opt.nfix_crc << 16;
+        fix2 |= r.opt.nfix_crc == 2;
+        r.history = true;
+        if (r.mode_ac) /* readsb.c:829-833: the switch as it stands when the buffer is demodulated */
+            ac[nac++] = i;
+        r.resolver.mode_ac = r.mode_ac; /* (the host resolver, if the buffer goes there) */
+    }
+    GHIPCHK(g, hipMemcpyAsync(g->d_ctl, g->h_ctl, sizeof(uint32_t) * (3 * (size_t)g->max_receivers + nac), hipMemcpyHostToDevice,
+                              c->stream));
+
+    GroupCall call;
+    call.tails = g->d_tails;
+    call.lb = g->d_ctl;
+    call.opt = g->d_ctl + 2 * g->max_receivers;
+    call.ac = g->d_ctl + 3 * g->max_receivers;
+    call.ac_host = ac;
+    call.nac = nac;
+    call.fix2 = fix2;
+    Slot &s = c->slots[0];
+    s.group = &call;
+    s.busy = true;
+    s.d_iq = d_iq;
+    s.d_prev = nullptr;
+    s.have_prev = 0;
+    s.threshold = c->cfg.preamble_threshold;
+    s.dropped_before = 0;
+    s.gpu_resolve = false; /* no prediction table from the scan */
+    s.resolve_inflight = false;
+    s.reset_before = false;
+    s.dc = false;
+    s.batch_first = 0;
+    s.nsamples = nsamples;
+    s.nbuffers = n;
+    s.last = 0;
+    s.tail_dst = nullptr; /* the group keeps its own tails */
+    struct Release { /* on every way out: the slot is free again, and no later batch in it sees the call */
+        Slot &s;
+        ~Release()
+        {
+            s.group = nullptr;
+            s.busy = false;
+            s.download_started = false;
+        }
+    } release{s};
+    int rc = enqueue(c, s, format, nullptr);
+    s.gpu_resolve = g->gpu; /* start_download: the lists stay on the device unless the arenas overflowed */
+    if (!rc)
+        rc = start_download(c, s, format); /* an arena overflow is scanned again in pieces here (rerun_in_pieces) */
+    if (rc)
+        return gfail(g, rc, "scan: %s", c->err);
+    GHIPCHK(g, hipEventSynchronize(s.ev_copy1));
+    const bool fm = format == MSD_FMT_SC16 || format == MSD_FMT_SC16Q11;
+
+    if (g->out.size() < n)
+        g->out.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        GroupEntryOut &o = g->out[i];
+        GroupReceiver &r = g->rx[e[i].receiver];
+        o.msgs.clear();
+        o.req.clear();
+        if (fm) { /* convert.c:245-251 */
+            o.means[0] = (double)(s.h_fmeans[2 * i] / (float)MSD_CHUNK_SAMPLES);
+            o.means[1] = (double)(s.h_fmeans[2 * i + 1] / (float)MSD_CHUNK_SAMPLES);
+        } else { /* convert.c:104-110 */
+            o.means[0] = (double)s.h_sums[2 * i] / 65536.0 / (double)MSD_CHUNK_SAMPLES;
+            o.means[1] = (double)s.h_sums[2 * i + 1] / 65535.0 / 65535.0 / (double)MSD_CHUNK_SAMPLES;
+        }
+        /* samples lost in front of the buffer go onto its receiver's clock first (sdr_rtlsdr.c:284,299; readsb.c:836) */
+        r.resolver.sample_counter += e[i].dropped;
+        r.stats.samples_dropped += e[i].dropped;
+    }
+    std::vector<uint32_t> gpu_idx, host, rec_first;
+    if (s.gpu_resolve) {
+        rc = group_gpu_entries(g, s, e, gpu_idx, host, rec_first);
+        if (rc)
+            return rc;
+        if (!host.empty()) { /* their candidate lists after all */
+            std::sort(host.begin(), host.end());
+            rc = ensure_host(c, s, s.h_totals[0], s.h_totals[1]);
+            if (rc)
+                return gfail(g, rc, "lists: %s", c->err);
+            if (s.h_totals[0])
+                GHIPCHK(g, hipMemcpyAsync(s.h_hits, s.d_hits, s.h_totals[0] * sizeof(msd_hit), hipMemcpyDeviceToHost, c->stream));
+            if (s.h_totals[1])
+                GHIPCHK(g, hipMemcpyAsync(s.h_tries, s.d_tries, s.h_totals[1] * sizeof(msd_try), hipMemcpyDeviceToHost, c->stream));
+            if (nac) {
+                rc = ensure_ac_host(c, s, s.h_ac_totals[0]);
+                if (rc)
+                    return gfail(g, rc, "lists: %s", c->err);
+                if (s.h_ac_totals[0])
+                    GHIPCHK(g, hipMemcpyAsync(s.h_ac, s.d_ac, s.h_ac_totals[0] * sizeof(msd_ac_hit), hipMemcpyDeviceToHost,
+                                              c->stream));
+            }
+            GHIPCHK(g, hipStreamSynchronize(c->stream));
+        }
+    } else {
+        for (uint32_t i = 0; i < n; ++i)
+            host.push_back(i);
+    }
+    c->timing.hits = s.h_totals[0];
+    c->timing.tries = s.h_totals[1];
+    c->timing.resolve_passes = gpu_idx.empty() ? 0 : 1;
+    if (!host.empty()) {
+        rc = group_host_entries(g, s, e, host);
+        if (rc)
+            return rc;
+    }
+    c->timing.resolve_fallback = g->host_buffers;
+    /* every buffer's end becomes its receiver's look-behind (behind the scan, its reruns and the power kernels) */
+    rc = msd_launch_group_tails(d_iq, n, g->d_ctl + g->max_receivers, g->d_tails, (uint32_t)c->bps, c->stream);
+    if (rc)
+        return gfail(g, rc, "group tail kernel launch failed");
+    GHIPCHK(g, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n; ++i)
+        g->rx[e[i].receiver].have_tail = true;
+    if (sink) {
+        std::vector<bool> on_gpu(n, false);
+        for (uint32_t i : gpu_idx)
+            on_gpu[i] = true;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (on_gpu[i]) {
+                for (uint32_t k = rec_first[i]; k < rec_first[i + 1]; ++k)
+                    sink(e[i].receiver, &s.h_wire[k].mm, user);
+            } else {
+                for (const msd_message &m : g->out[i].msgs)
+                    sink(e[i].receiver, &m, user);
+            }
+        }
+    }
+    return 0;
+}
+
+} /* namespace */
+
+extern "C" {
+
+int msd_group_create(const msd_config *cfg, uint32_t max_receivers, msd_group **out)
+{
+    if (!cfg || !out)
+        return -EINVAL;
+    *out = nullptr;
+    if (max_receivers == 0 || (uint64_t)max_receivers * MSD_CHUNK_SAMPLES > MSD_MAX_BATCH_SAMPLES / 2 ||
+        cfg->mode_ac || (cfg->flags & MSD_CFG_DC_FILTER) || cfg->format == MSD_FMT_MAG16 || cfg->sc16q11_table_bits)
+        return -EINVAL;
+    msd_group *g = new (std::nothrow) msd_group;
+    if (!g)
+        return -ENOMEM;
+    g->gpu = !(cfg->flags & MSD_CFG_HOST_RESOLVE);
+    msd_config cc = *cfg;
+    cc.max_batch_samples = (uint64_t)max_receivers * MSD_CHUNK_SAMPLES;
+    cc.flags |= MSD_CFG_NO_HELPER | MSD_CFG_NO_LEAN; /* synchronous calls over the dense candidate lists */
+    if (cc.nfix_crc == 0) /* the single-bit tables always: a receiver may be set to level 1 (the scan gates by level) */
+        cc.nfix_crc = 1;
+    int rc = msd_create(&cc, &g->ctx);
+    if (rc) {
+        delete g;
+        return rc;
+    }
+    g->max_receivers = max_receivers;
+    const unsigned hw = std::thread::hardware_concurrency();
+    g->threads = cfg->resolve_threads > 0 ? (uint32_t)cfg->resolve_threads : std::max(1u, std::min(16u, hw / 8u));
+    g->rx = new (std::nothrow) GroupReceiver[max_receivers];
+    const size_t tail_bytes = (size_t)max_receivers * MSD_HALO_FRONT * g->ctx->bps;
+    if (!g->rx || hipMalloc(reinterpret_cast<void **>(&g->d_tails), tail_bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&g->d_ctl), sizeof(uint32_t) * 4 * max_receivers) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&g->h_ctl), sizeof(uint32_t) * 4 * max_receivers, hipHostMallocDefault) != hipSuccess ||
+        (g->gpu && (hipMalloc(reinterpret_cast<void **>(&g->d_snaps), sizeof(uint32_t) * MSD_SNAP_WORDS * max_receivers) != hipSuccess ||
+                    hipHostMalloc(reinterpret_cast<void **>(&g->h_apply), sizeof(uint32_t) * (3 * (size_t)max_receivers + 1),
+                                  hipHostMallocDefault) != hipSuccess ||
+                    hipHostMalloc(reinterpret_cast<void **>(&g->h_adds), sizeof(uint32_t) * MSD_RB_MSG_CAP * (size_t)max_receivers,
+                                  hipHostMallocDefault) != hipSuccess ||
+                    hipHostMalloc(reinterpret_cast<void **>(&g->h_snap), sizeof(uint32_t) * MSD_SNAP_WORDS, hipHostMallocDefault) != hipSuccess))) {
+        (void)hipGetLastError();
+        msd_group_destroy(g);
+        return -ENOMEM;
+    }
+    for (uint32_t r = 0; r < max_receivers; ++r) {
+        g->rx[r].resolver.stats = &g->rx[r].stats;
+        g->rx[r].resolver.threads = 1;
+        g->rx[r].opt.preamble_threshold = cfg->preamble_threshold;
+        g->rx[r].opt.nfix_crc = cfg->nfix_crc;
+        group_receiver_reset(g->rx[r]);
+        rc = group_upload_snapshot(g, r);
+        if (rc) {
+            msd_group_destroy(g);
+            return rc;
+        }
+    }
+    *out = g;
+    return 0;
+}
+
+void msd_group_destroy(msd_group *g)
+{
+    if (!g)
+        return;
+    if (g->ctx)
+        (void)hipSetDevice(g->ctx->cfg.device);
+    if (g->rx) {
+        for (uint32_t r = 0; r < g->max_receivers; ++r)
+            msd_resolver_free(&g->rx[r].resolver);
+        delete[] g->rx;
+    }
+    (void)hipFree(g->d_tails);
+    (void)hipFree(g->d_ctl);
+    (void)hipHostFree(g->h_ctl);
+    (void)hipFree(g->d_snaps);
+    (void)hipHostFree(g->h_apply);
+    (void)hipHostFree(g->h_adds);
+    (void)hipHostFree(g->h_snap);
+    msd_destroy(g->ctx);
+    delete g;
+}
+
+const char *msd_group_last_error(const msd_group *g)
+{
+    return g ? g->err : "no group";
+}
+
+int msd_group_submit_device(msd_group *g, const void *d_iq, const msd_group_entry *e, uint32_t n,
+                            msd_group_message_fn sink, void *user)
+{
+    if (!g)
+        return -EINVAL;
+    if (group_check(g, e, n))
+        return gfail(g, -EINVAL, "entries: a receiver out of range or given twice, nonzero flags, or more than max_receivers");
+    if (n && (!d_iq || (reinterpret_cast<uintptr_t>(d_iq) & 15u)))
+        return gfail(g, -EINVAL, "IQ pointer must be non-null and 16-byte aligned");
+    if (g->ctx->failed)
+        return gfail(g, -EIO, "an earlier call failed");
+    if (n == 0)
+        return 0;
+    GHIPCHK(g, hipSetDevice(g->ctx->cfg.device));
+    const int rc = group_run(g, static_cast<const uint8_t *>(d_iq), e, n, sink, user);
+    if (rc)
+        g->ctx->failed = true;
+    return rc;
+}
+
+int msd_group_submit_host(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n,
+                          msd_group_message_fn sink, void *user)
+{
+    if (!g)
+        return -EINVAL;
+    if (group_check(g, e, n))
+        return gfail(g, -EINVAL, "entries: a receiver out of range or given twice, nonzero flags, or more than max_receivers");
+    if (n && !h_iq)
+        return gfail(g, -EINVAL, "IQ pointer must be non-null");
+    msd_ctx *c = g->ctx;
+    if (c->failed)
+        return gfail(g, -EIO, "an earlier call failed");
+    if (n == 0)
+        return 0;
+    auto stage = [&]() -> int {
+        GHIPCHK(g, hipSetDevice(c->cfg.device));
+        if (!c->d_stage)
+            GHIPCHK(g, hipMalloc(reinterpret_cast<void **>(&c->d_stage), c->cfg.max_batch_samples * 4 + 64));
+        GHIPCHK(g, hipMemcpyAsync(c->d_stage, h_iq, (size_t)n * MSD_CHUNK_SAMPLES * c->bps, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    };
+    const int rc = stage();
+    if (rc) {
+        c->failed = true;
+        return rc;
+    }
+    return msd_group_submit_device(g, c->d_stage, e, n, sink, user);
+}
+
+int msd_group_reset_receiver(msd_group *g, uint32_t receiver)
+{
+    if (!g || receiver >= g->max_receivers)
+        return -EINVAL;
+    if (g->ctx->failed)
+        return gfail(g, -EIO, "an earlier call failed");
+    group_receiver_reset(g->rx[receiver]);
+    const int rc = group_upload_snapshot(g, receiver);
+    if (rc)
+        g->ctx->failed = true;
+    return rc;
+}
+
+int msd_group_get_stats(const msd_group *g, uint32_t receiver, msd_stats *st)
+{
+    if (!g || !st || receiver >= g->max_receivers)
+        return -EINVAL;
+    *st = g->rx[receiver].stats;
+    return 0;
+}
+
+int msd_group_set_preamble_threshold(msd_group *g, int threshold)
+{
+    if (!g)
+        return -EINVAL;
+    const int rc = msd_set_preamble_threshold(g->ctx, threshold);
+    if (rc)
+        return gfail(g, rc, "%s", g->ctx->err);
+    for (uint32_t r = 0; r < g->max_receivers; ++r)
+        g->rx[r].opt.preamble_threshold = threshold;
+    return 0;
+}
+
+int msd_group_set_receiver_options(msd_group *g, uint32_t receiver, const msd_group_receiver_options *o)
+{
+    if (!g)
+        return -EINVAL;
+    if (!o || receiver >= g->max_receivers)
+        return gfail(g, -EINVAL, "receiver options: a receiver out of range or no options");
+    if (o->preamble_threshold < 1 || o->preamble_threshold > MSD_MAX_PREAMBLE_THRESHOLD || o->nfix_crc < 0 ||
+        o->nfix_crc > 2 || o->reserved[0] || o->reserved[1])
+        return gfail(g, -EINVAL, "receiver options: threshold %d outside 1..%d, repair level %d outside 0..2, or nonzero "
+                     "reserved words", o->preamble_threshold, MSD_MAX_PREAMBLE_THRESHOLD, o->nfix_crc);
+    GroupReceiver &r = g->rx[receiver];
+    if (o->nfix_crc != r.opt.nfix_crc && r.history) /* readsb cannot change --fix in a running process either */
+        return gfail(g, -EBUSY, "receiver %u: the repair level changes only before its first buffer (after a reset)",
+                     receiver);
+    if (o->nfix_crc == 2) {
+        const int rc = group_make_fix2(g);
+        if (rc)
+            return rc;
+    }
+    r.opt.preamble_threshold = o->preamble_threshold;
+    r.opt.nfix_crc = o->nfix_crc;
+    return 0;
+}
+
+int msd_group_get_receiver_options(const msd_group *g, uint32_t receiver, msd_group_receiver_options *o)
+{
+    if (!g || !o || receiver >= g->max_receivers)
+        return -EINVAL;
+    *o = g->rx[receiver].opt;
+    return 0;
+}
+
+int msd_group_set_receiver_mode_ac(msd_group *g, uint32_t receiver, int on)
+{
+    if (!g)
+        return -EINVAL;
+    if (receiver >= g->max_receivers || (on != 0 && on != 1))
+        return gfail(g, -EINVAL, "Mode A/C: receiver %u out of range or switch %d not 0 or 1", receiver, on);
+    if (on) {
+        const int rc = group_make_ac(g);
+        if (rc)
+            return rc;
+    }
+    g->rx[receiver].mode_ac = on != 0;
+    return 0;
+}
+
+int msd_group_get_receiver_mode_ac(const msd_group *g, uint32_t receiver, int *on)
+{
+    if (!g || !on || receiver >= g->max_receivers)
+        return -EINVAL;
+    *on = g->rx[receiver].mode_ac ? 1 : 0;
+    return 0;
+}
+
+int msd_group_get_timing(const msd_group *g, msd_timing *t)
+{
+    if (!g)
+        return -EINVAL;
+    return msd_get_timing(g->ctx, t);
+}
+
+} /* extern "C" */

@@ -184,12 +184,10 @@ int msd_launch_gather(const msd_region_counts *counts, const msd_wg_totals *wg_t
                       msd_try *dense_tries, uint64_t dense_tcap, uint64_t *sums, uint32_t nbuffers, uint64_t *h_totals,
                       uint64_t *h_sums, void *wipe, uint32_t wipe_bytes, const void *tail_src, void *tail_dst,
                       uint32_t tail_bytes, uint32_t region_len, uint32_t *buf_first, uint32_t try_abs, hipStream_t stream);
+/* signal power of the accepted messages: d_out[i] from d_req[i] = batch-relative scan position << 16 | samples; with
+ * p->group_lb every buffer's look-behind from its tail slot (receiver groups) */
 int msd_launch_power(const MsdScanParams *p, int format, const uint64_t *d_req, uint32_t nreq,
                      unsigned long long *d_out, hipStream_t stream);
-/* receiver groups: the same signal power with every buffer's look-behind from its tail slot (p->group_lb);
- * req = batch-relative scan position << 16 | samples */
-int msd_launch_group_power(const MsdScanParams *p, int format, const uint64_t *d_req, uint32_t nreq,
-                           unsigned long long *d_out, hipStream_t stream);
 /* receiver groups: tails[dst_slot[i]] = the last MSD_HALO_FRONT raw samples of buffer i of iq (n buffers of
  * MSD_CHUNK_SAMPLES), bps bytes per sample */
 /* receiver groups, GPU resolve: out[b][m] = signal power of accepted message m < nmsgs[b] of buffer b = todo[w], from

@@ -1572,6 +1572,32 @@ __device__ inline void msd_emit_slice(const MsdEmitJob &J, const uint16_t *lut_g
     }
 }
 
+/* The samples the messages of buffer b read, their scan positions counted from P.batch_first.  A receiver group
+ * (P.group_lb, wave-uniform): the buffer alone, with the samples in front of it from its receiver's tail slot (or
+ * silence) instead of the batch's previous buffer -- a message never reaches into the next buffer (j + 19 + 268 <
+ * 131072 + 326), so a buffer and its look-behind are all it reads.  Otherwise the whole batch. */
+template <int FMT>
+__device__ __forceinline__ MsdSampleSource buffer_source(const MsdScanParams &P, uint64_t b)
+{
+    constexpr int BPS = (FMT == MSD_FMT_SC16 || FMT == MSD_FMT_SC16Q11) ? 4 : 2;
+    MsdSampleSource S;
+    if (P.group_lb) {
+        const uint32_t slot = P.group_lb[b];
+        S.iq = P.iq + b * MSD_CHUNK_SAMPLES * BPS;
+        S.have_prev = slot != MSD_GROUP_NO_TAIL;
+        S.prev_tail = S.have_prev ? P.group_tails + (size_t)slot * FRONT * BPS : nullptr;
+        S.batch_first = P.batch_first + b * MSD_CHUNK_SAMPLES;
+        S.nsamples = min((uint64_t)MSD_CHUNK_SAMPLES, P.nsamples - b * MSD_CHUNK_SAMPLES);
+    } else {
+        S.iq = P.iq;
+        S.prev_tail = P.prev_tail;
+        S.have_prev = P.have_prev;
+        S.batch_first = P.batch_first;
+        S.nsamples = P.nsamples;
+    }
+    return S;
+}
+
 /* Signal power of the accepted messages (demod_2400.c:386-399): sum of m[j+19+k]^2 over
  * msglen*12/5 samples.  Only accepted messages need it, so it runs after the resolve stage on
  * their positions: one wavefront per message. */
@@ -1585,42 +1611,9 @@ __global__ void __launch_bounds__(256) msd_power_kernel(const MsdScanParams P, c
         return;
     const uint64_t rq = req[i];
     const int len = (int)(rq & 0xffffu);
-    const int64_t n0 = (int64_t)P.batch_first + (int64_t)(rq >> 16) - (int64_t)MSD_OVERLAP + 19;
-    unsigned long long acc = 0;
-    for (int k = lane; k < len; k += 64) {
-        const uint32_t x = stream_mag<FMT>(P, n0 + k, P.lut);
-        acc += (unsigned long long)(x * x);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        acc += __shfl_down(acc, o);
-    if (lane == 0)
-        out[i] = acc;
-}
-
-/* Receiver groups: the same sums, with the samples in front of a buffer from its receiver's tail slot
- * (P.group_lb) instead of the batch's previous buffer.  A message never reaches into the next buffer
- * (j + 19 + 268 < 131072 + 326), so a buffer and its look-behind are all it reads. */
-template <int FMT>
-__global__ void __launch_bounds__(256) msd_group_power_kernel(const MsdScanParams P, const uint64_t *req, uint32_t nreq,
-                                                              unsigned long long *out)
-{
-    constexpr int BPS = (FMT == MSD_FMT_SC16 || FMT == MSD_FMT_SC16Q11) ? 4 : 2;
-    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (i >= nreq)
-        return;
-    const uint64_t rq = req[i];
-    const int len = (int)(rq & 0xffffu);
-    const uint64_t pos = rq >> 16, b = pos / MSD_CHUNK_SAMPLES;
-    const uint32_t slot = P.group_lb[b];
-    MsdSampleSource S;
-    S.iq = P.iq + b * MSD_CHUNK_SAMPLES * BPS;
-    S.have_prev = slot != MSD_GROUP_NO_TAIL;
-    S.prev_tail = S.have_prev ? P.group_tails + (size_t)slot * FRONT * BPS : nullptr;
-    S.batch_first = 0;
-    S.nsamples = min((uint64_t)MSD_CHUNK_SAMPLES, P.nsamples - b * MSD_CHUNK_SAMPLES);
-    const int64_t n0 = (int64_t)(pos - b * MSD_CHUNK_SAMPLES) - (int64_t)MSD_OVERLAP + 19;
+    const uint64_t pos = rq >> 16;
+    const MsdSampleSource S = buffer_source<FMT>(P, pos / MSD_CHUNK_SAMPLES);
+    const int64_t n0 = (int64_t)P.batch_first + (int64_t)pos - (int64_t)MSD_OVERLAP + 19;
     unsigned long long acc = 0;
     for (int k = lane; k < len; k += 64) {
         const uint32_t x = msd_stream_mag<FMT>(S, n0 + k, P.lut);
@@ -1640,20 +1633,13 @@ __global__ void __launch_bounds__(256) msd_group_power_buffers_kernel(const MsdS
                                                                       const uint32_t *nmsgs, const uint32_t *todo,
                                                                       unsigned long long *out)
 {
-    constexpr int BPS = (FMT == MSD_FMT_SC16 || FMT == MSD_FMT_SC16Q11) ? 4 : 2;
     const uint32_t b = todo[blockIdx.x];
     const int lane = threadIdx.x & 63;
     const uint32_t n = min(nmsgs[b], MSD_RB_MSG_CAP);
-    const uint32_t slot = P.group_lb[b];
-    MsdSampleSource S;
-    S.iq = P.iq + (size_t)b * MSD_CHUNK_SAMPLES * BPS;
-    S.have_prev = slot != MSD_GROUP_NO_TAIL;
-    S.prev_tail = S.have_prev ? P.group_tails + (size_t)slot * FRONT * BPS : nullptr;
-    S.batch_first = 0;
-    S.nsamples = MSD_CHUNK_SAMPLES;
+    const MsdSampleSource S = buffer_source<FMT>(P, b);
     for (uint32_t m = blockIdx.y * 4 + (threadIdx.x >> 6); m < n; m += 4 * gridDim.y) {
         const msd_acc a = acc[(size_t)b * MSD_RB_MSG_CAP + m];
-        const int64_t n0 = (int64_t)a.pos - (int64_t)b * MSD_CHUNK_SAMPLES - (int64_t)MSD_OVERLAP + 19;
+        const int64_t n0 = (int64_t)P.batch_first + (int64_t)a.pos - (int64_t)MSD_OVERLAP + 19;
         unsigned long long sum = 0;
         for (int k = lane; k < (int)a.len; k += 64) {
             const uint32_t x = msd_stream_mag<FMT>(S, n0 + k, P.lut);
@@ -3334,30 +3320,6 @@ extern "C" int msd_launch_power(const MsdScanParams *p, int format, const uint64
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-extern "C" int msd_launch_group_power(const MsdScanParams *p, int format, const uint64_t *d_req, uint32_t nreq,
-                                      unsigned long long *d_out, hipStream_t stream)
-{
-    if (nreq == 0)
-        return 0;
-    if (!p->group_lb)
-        return -22;
-    const dim3 grid((nreq + 3) / 4), block(256);
-    switch (format) {
-    case MSD_FMT_UC8:
-        hipLaunchKernelGGL(msd_group_power_kernel<MSD_FMT_UC8>, grid, block, 0, stream, *p, d_req, nreq, d_out);
-        break;
-    case MSD_FMT_SC16:
-        hipLaunchKernelGGL(msd_group_power_kernel<MSD_FMT_SC16>, grid, block, 0, stream, *p, d_req, nreq, d_out);
-        break;
-    case MSD_FMT_SC16Q11:
-        hipLaunchKernelGGL(msd_group_power_kernel<MSD_FMT_SC16Q11>, grid, block, 0, stream, *p, d_req, nreq, d_out);
-        break;
-    default:
-        return -22;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
 extern "C" int msd_launch_group_power_buffers(const MsdScanParams *p, int format, const msd_acc *acc, const uint32_t *nmsgs,
                                               const uint32_t *todo, uint32_t ntodo, unsigned long long *out, hipStream_t stream)
 {
@@ -3429,6 +3391,27 @@ extern "C" int msd_launch_power_buffers(const MsdScanParams *p, int format, cons
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
+/* The region split of the Mode A/C candidate kernel: ntiles tiles over at most max_wg regions, one per wavefront
+ * (ACNT / 64 a workgroup); tpw tiles a region, nblocks workgroups, cap candidates a region's slice of region_total. */
+struct AcSplit {
+    uint32_t tpw, nblocks;
+    uint64_t cap;
+};
+
+static AcSplit ac_split(uint32_t ntiles, uint32_t max_wg, uint64_t region_total)
+{
+    AcSplit a;
+    a.tpw = (ntiles + max_wg - 1) / max_wg;
+    if (a.tpw == 0)
+        a.tpw = 1;
+    const uint32_t nwg = (ntiles + a.tpw - 1) / a.tpw; /* regions = wavefronts */
+    a.nblocks = (nwg + ACNT / 64 - 1) / (ACNT / 64);
+    a.cap = region_total / ((uint64_t)a.nblocks * (ACNT / 64));
+    if (a.cap > (uint64_t)a.tpw * ACW)
+        a.cap = (uint64_t)a.tpw * ACW;
+    return a;
+}
+
 extern "C" int msd_launch_ac(const MsdScanParams *p, int format, const uint64_t *d_sums, const float *d_fmeans,
                              uint32_t nbuffers, uint32_t *d_noise, int noise_ready, msd_ac_hit *d_regions,
                              uint64_t region_total, msd_wg_counts *d_counts, uint64_t *d_offsets,
@@ -3451,17 +3434,10 @@ extern "C" int msd_launch_ac(const MsdScanParams *p, int format, const uint64_t 
             (void)hipMemsetAsync(d_totals, 0, 4 * sizeof(uint64_t), stream);
         return 0;
     }
-    uint32_t tpw = (ntiles + max_wg - 1) / max_wg;
-    if (tpw == 0)
-        tpw = 1;
-    const uint32_t nwg = (ntiles + tpw - 1) / tpw; /* regions = wavefronts */
-    const uint32_t nblocks = (nwg + ACNT / 64 - 1) / (ACNT / 64);
-    uint64_t cap = region_total / ((uint64_t)nblocks * (ACNT / 64));
-    if (cap > (uint64_t)tpw * ACW)
-        cap = (uint64_t)tpw * ACW;
-#define MSD_AC_LAUNCH(F)                                                                                                     \
-    hipLaunchKernelGGL(msd_ac_wave_kernel<F>, dim3(nblocks), dim3(ACNT), 0, stream, *p, ntiles, tpw, levels, d_sums, d_fmeans, \
-                       use_float, d_regions, (uint32_t)cap, d_counts, nullptr, 0u)
+    const AcSplit a = ac_split(ntiles, max_wg, region_total);
+#define MSD_AC_LAUNCH(F)                                                                                                        \
+    hipLaunchKernelGGL(msd_ac_wave_kernel<F>, dim3(a.nblocks), dim3(ACNT), 0, stream, *p, ntiles, a.tpw, levels, d_sums, d_fmeans, \
+                       use_float, d_regions, (uint32_t)a.cap, d_counts, nullptr, 0u)
     if (phase != 2)
         switch (format) {
         case MSD_FMT_UC8: MSD_AC_LAUNCH(MSD_FMT_UC8); break;
@@ -3473,8 +3449,8 @@ extern "C" int msd_launch_ac(const MsdScanParams *p, int format, const uint64_t 
 #undef MSD_AC_LAUNCH
     (void)d_offsets;
     if (phase != 1)
-        hipLaunchKernelGGL(msd_ac_gather_kernel, dim3(nblocks), dim3(256), 0, stream, d_counts, nblocks, d_regions, (uint32_t)cap, d_dense,
-                       dense_cap, d_totals);
+        hipLaunchKernelGGL(msd_ac_gather_kernel, dim3(a.nblocks), dim3(256), 0, stream, d_counts, a.nblocks, d_regions, (uint32_t)a.cap,
+                           d_dense, dense_cap, d_totals);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -3492,17 +3468,10 @@ extern "C" int msd_launch_group_ac(const MsdScanParams *p, int format, const uin
     const int use_float = (format == MSD_FMT_SC16 || format == MSD_FMT_SC16Q11);
     /* the same split as msd_launch_ac, over the listed buffers' tiles only */
     const uint32_t ntiles = nlist * AC_TILES_PER_BUFFER;
-    uint32_t tpw = (ntiles + max_wg - 1) / max_wg;
-    if (tpw == 0)
-        tpw = 1;
-    const uint32_t nwg = (ntiles + tpw - 1) / tpw;
-    const uint32_t nblocks = (nwg + ACNT / 64 - 1) / (ACNT / 64);
-    uint64_t cap = region_total / ((uint64_t)nblocks * (ACNT / 64));
-    if (cap > (uint64_t)tpw * ACW)
-        cap = (uint64_t)tpw * ACW;
-#define MSD_GROUP_AC_LAUNCH(F)                                                                                              \
-    hipLaunchKernelGGL((msd_ac_wave_kernel<F, true>), dim3(nblocks), dim3(ACNT), 0, stream, *p, ntiles, tpw, nullptr, d_sums, \
-                       d_fmeans, use_float, d_regions, (uint32_t)cap, d_counts, d_list, list_first)
+    const AcSplit a = ac_split(ntiles, max_wg, region_total);
+#define MSD_GROUP_AC_LAUNCH(F)                                                                                                  \
+    hipLaunchKernelGGL((msd_ac_wave_kernel<F, true>), dim3(a.nblocks), dim3(ACNT), 0, stream, *p, ntiles, a.tpw, nullptr, d_sums, \
+                       d_fmeans, use_float, d_regions, (uint32_t)a.cap, d_counts, d_list, list_first)
     switch (format) {
     case MSD_FMT_UC8: MSD_GROUP_AC_LAUNCH(MSD_FMT_UC8); break;
     case MSD_FMT_SC16: MSD_GROUP_AC_LAUNCH(MSD_FMT_SC16); break;
@@ -3510,7 +3479,7 @@ extern "C" int msd_launch_group_ac(const MsdScanParams *p, int format, const uin
     default: return -22;
     }
 #undef MSD_GROUP_AC_LAUNCH
-    hipLaunchKernelGGL(msd_ac_gather_kernel, dim3(nblocks), dim3(256), 0, stream, d_counts, nblocks, d_regions, (uint32_t)cap,
+    hipLaunchKernelGGL(msd_ac_gather_kernel, dim3(a.nblocks), dim3(256), 0, stream, d_counts, a.nblocks, d_regions, (uint32_t)a.cap,
                        d_dense, dense_cap, d_totals);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
