@@ -2057,7 +2057,11 @@ __global__ void __launch_bounds__(FM_THREADS) msd_float_means_kernel(const uint8
  *           summed exactly with fsum_block.  Bit-identical to the sequential sum by construction: every
  *           shortcut is verified against the exact state before it is used. */
 constexpr int FB_MAX = 128; /* blocks of FS_BLOCK elements per buffer (MSD_CHUNK_SAMPLES / 1024) */
-constexpr int FM_SLOTS = 24; /* slow blocks per sum whose sub-block totals are kept (about ten occur) */
+/* slow blocks per sum whose sub-block totals are kept (about ten occur on noise).  A buffer can want more: a sum that
+ * stagnates on a power of two starts every block on the edge (64 blocks at full scale, then 64 quiet ones: 75 such blocks
+ * in the power sum).  The slots go to the first FM_SLOTS of them in block order; the others get none (slot 0xff, ca SLOW)
+ * and the apply kernel sums them sample by sample, exactly (tests/test_gpu_fm_scenes.py, the stagnate-* scenes). */
+constexpr int FM_SLOTS = 24;
 
 /* s + x(lane 0) + x(lane 1) + ... + x(lane 63), one addition after the other (convert.c:241-242).  The 64 values go
  * through 256 bytes of the wavefront's LDS and come back to every lane, sixteen broadcast reads of four: the chain is

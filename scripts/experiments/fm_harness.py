@@ -1,5 +1,7 @@
 """Round-4 debugging aid (GPU box): the float-sum kernels alone on random SC16 samples, against numpy's sequential
-float32 accumulation.  Usage: python scripts/experiments/fm_harness.py [nbuffers] [amplitude]"""
+float32 accumulation.  Usage: python scripts/experiments/fm_harness.py [nbuffers] [amplitude]
+Kept as the record it is (it prints, it does not assert).  The test of these kernels is tests/test_gpu_fm_scenes.py:
+constructed buffers (tests/fm_scenes.py), every entry, predictions wrong on purpose, bit equality asserted."""
 import ctypes, os, sys
 import numpy as np
 import torch

@@ -36,7 +36,11 @@ def test_plain_run_prints_the_headline_alone(torch_cuda):
 
 @pytest.mark.gpu
 def test_full_run_adds_baselines_and_checks(torch_cuda):
-    d = bench_line("--full", "--no-dropin", samples=1 << 24)
+    # 2^24 samples are one batch per pass, three launches in the timed region: with the default interval of one timed
+    # launch in three, which of them it is depends on how many passes the (time-bound) settling took, and a timed launch
+    # is only recognised behind another collect of the region -- launches_timed came out 0 in one run of three.  Every
+    # launch timed: two of the three are always recognised.
+    d = bench_line("--full", "--no-dropin", "--timing-interval", "1", samples=1 << 24)
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
     assert d["cpu_baseline"]["two_threads_like_the_reference"]["messages"] > 0
     assert d["message_set_diff_vs_oracle"] == 0 and d["messages_checked"] == d["messages_per_step"]
