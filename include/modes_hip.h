@@ -559,6 +559,22 @@ int msd_group_submit_device(msd_group *g, const void *d_iq, const msd_group_entr
                             msd_group_message_fn sink, void *user);
 int msd_group_submit_host(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n,
                           msd_group_message_fn sink, void *user);
+/* The same two calls with the decoded fields of every message (msd_fields, as msd_collect_fields delivers them for a
+ * context): arguments, errors and delivery order are those of msd_group_submit_device / msd_group_submit_host, and so
+ * are the messages; within a buffer its Mode S messages come first and its Mode A/C replies after them.  *fields equals
+ * msd_decode_fields(mm, carry, ...): carry is non-NULL only for a Mode A/C reply, and is then the fields of the previous
+ * Mode A/C reply of the same buffer -- one receiver's one entry of one call --, never of the batch neighbour (another
+ * receiver's buffer) and never of the same receiver's previous call (the reference clears its message record once per
+ * buffer, demod_2400.c:523-528).  Each receiver's result is exactly what msd_collect_fields delivers for a context of
+ * its own fed the same buffers.  The fields come from the kernel that builds the records for the buffers resolved on
+ * the GPU and from the host decoder for the buffers resolved on host threads; mm and fields are valid until the sink
+ * returns.  The group must have been created with MSD_CFG_DECODE_FIELDS: otherwise -EINVAL with the group's state
+ * untouched.  Such a group may mix these calls with the two above, which do what they do on any group. */
+typedef void (*msd_group_fields_fn)(uint32_t receiver, const msd_message *mm, const msd_fields *fields, void *user);
+int msd_group_submit_device_fields(msd_group *g, const void *d_iq, const msd_group_entry *e, uint32_t n,
+                                   msd_group_fields_fn sink, void *user);
+int msd_group_submit_host_fields(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n,
+                                 msd_group_fields_fn sink, void *user);
 int msd_group_reset_receiver(msd_group *g, uint32_t receiver); /* filter, clock, counters, tail */
 int msd_group_get_stats(const msd_group *g, uint32_t receiver, msd_stats *st);
 int msd_group_set_preamble_threshold(msd_group *g, int threshold); /* group-wide: sets every receiver's threshold */

@@ -220,6 +220,7 @@ EXPORTS = [
     "msd_group_reset_receiver", "msd_group_get_stats", "msd_group_set_preamble_threshold", "msd_group_get_timing",
     "msd_group_set_receiver_options", "msd_group_get_receiver_options",
     "msd_group_set_receiver_mode_ac", "msd_group_get_receiver_mode_ac",
+    "msd_group_submit_device_fields", "msd_group_submit_host_fields",
 ]
 
 _lib = None
@@ -599,6 +600,7 @@ class GroupReceiverOptions(C.Structure):
 
 GROUP_MESSAGE_DTYPE = np.dtype([("receiver", "<u4"), ("m", MESSAGE_DTYPE)])
 _GROUP_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_void_p)
+_GROUP_FIELDS_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 def _group_lib():
@@ -610,7 +612,8 @@ def _group_lib():
         L.msd_group_destroy.argtypes = [C.c_void_p]
         L.msd_group_last_error.restype = C.c_char_p
         L.msd_group_last_error.argtypes = [C.c_void_p]
-        for f in (L.msd_group_submit_device, L.msd_group_submit_host):
+        for f in (L.msd_group_submit_device, L.msd_group_submit_host, L.msd_group_submit_device_fields,
+                  L.msd_group_submit_host_fields):
             f.restype = C.c_int
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.msd_group_reset_receiver.restype = C.c_int
@@ -668,24 +671,31 @@ class ReceiverGroup:
         if rc != 0:
             raise MsdError(f"{_group_lib().msd_group_last_error(self._h).decode()} ({os.strerror(-rc)}, {rc})")
 
-    def submit(self, iq, receivers, dropped=None, as_dict=False, deliver=True):
+    def submit(self, iq, receivers, dropped=None, as_dict=False, deliver=True, fields=False):
         """One buffer of CHUNK samples for each of `receivers`, entry i at iq[i * CHUNK * bytes_per_sample ...].
         iq: bytes, a numpy array, or a torch tensor on the GPU (read in place, after torch's current stream is done).  dropped[i]: samples receiver i lost
         in front of its buffer.  Returns a GROUP_MESSAGE_DTYPE array (receiver, m) in delivery order, or with
         as_dict=True {receiver: MESSAGE_DTYPE array} for the receivers of the call.  deliver=False passes no sink (the
-        counters still advance; for timing the library without the per-message Python callback)."""
+        counters still advance; for timing the library without the per-message Python callback).
+        fields=True (a group made with flags=CFG_DECODE_FIELDS) goes through msd_group_submit_*_fields and returns
+        (messages, fields): the same first result and a FIELDS_DTYPE array of the same length and order, or with
+        as_dict=True {receiver: (MESSAGE_DTYPE array, FIELDS_DTYPE array)}."""
         receivers = [int(r) for r in receivers]
         n = len(receivers)
         entries = (GroupEntry * max(n, 1))()
         for i, r in enumerate(receivers):
             entries[i] = GroupEntry(r, 0, int(dropped[i]) if dropped is not None else 0)
-        rx, raw = [], []
+        rx, raw, fraw = [], [], []
 
         def sink(receiver, mm, _user):
             rx.append(receiver)
             raw.append(C.string_at(mm, MESSAGE_DTYPE.itemsize))
 
-        fn = _GROUP_SINK(sink)  # (kept alive until the call returns)
+        def fields_sink(receiver, mm, ff, _user):
+            sink(receiver, mm, _user)
+            fraw.append(C.string_at(ff, FIELDS_DTYPE.itemsize))
+
+        fn = _GROUP_FIELDS_SINK(fields_sink) if fields else _GROUP_SINK(sink)  # (kept alive until the call returns)
         cb = C.cast(fn, C.c_void_p) if deliver else None
         need = n * CHUNK * self.bytes_per_sample
         L = _group_lib()
@@ -696,20 +706,30 @@ class ReceiverGroup:
                 raise ValueError(f"{n} buffers need {need} bytes")
             import torch
             torch.cuda.current_stream(iq.device).synchronize()  # the group reads it on its own stream
-            self._check(L.msd_group_submit_device(self._h, C.c_void_p(iq.data_ptr()), entries, n, cb, None))
+            call = L.msd_group_submit_device_fields if fields else L.msd_group_submit_device
+            self._check(call(self._h, C.c_void_p(iq.data_ptr()), entries, n, cb, None))
         else:
             arr = np.frombuffer(iq, dtype=np.uint8) if isinstance(iq, (bytes, bytearray, memoryview)) else \
                 np.ascontiguousarray(iq).view(np.uint8).reshape(-1)
             if arr.size < need:
                 raise ValueError(f"{n} buffers need {need} bytes")
-            self._check(L.msd_group_submit_host(self._h, arr.ctypes.data, entries, n, cb, None))
+            call = L.msd_group_submit_host_fields if fields else L.msd_group_submit_host
+            self._check(call(self._h, arr.ctypes.data, entries, n, cb, None))
         res = np.zeros(len(rx), dtype=GROUP_MESSAGE_DTYPE)
         if rx:
             res["receiver"] = rx
             res["m"] = np.frombuffer(b"".join(raw), dtype=MESSAGE_DTYPE)
+        by_rx = lambda a, r: _raw_copy(np.ascontiguousarray(a[res["receiver"] == r]))
+        if not fields:
+            return {r: by_rx(res["m"], r) for r in receivers} if as_dict else res
+        ff = np.frombuffer(b"".join(fraw), dtype=FIELDS_DTYPE).copy() if fraw else np.zeros(0, dtype=FIELDS_DTYPE)
         if not as_dict:
-            return res
-        return {r: _raw_copy(np.ascontiguousarray(res["m"][res["receiver"] == r])) for r in receivers}
+            return res, ff
+        return {r: (by_rx(res["m"], r), by_rx(ff, r)) for r in receivers}
+
+    def submit_fields(self, iq, receivers, **kw):
+        """submit(..., fields=True)."""
+        return self.submit(iq, receivers, fields=True, **kw)
 
     def stats(self, receiver):
         st = Stats()

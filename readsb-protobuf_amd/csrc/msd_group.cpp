@@ -33,6 +33,7 @@ struct GroupReceiver {
 struct GroupEntryOut {
     std::vector<msd_message> msgs;
     std::vector<uint64_t> req;
+    std::vector<msd_fields> fields; /* of msgs, for a fields call (msd_group_submit_*_fields) */
     std::vector<msd_hit> hits; /* the entry's hits, positions made buffer-relative */
     std::vector<msd_ac_hit> ac; /* its Mode A/C candidates, likewise */
     double means[2] = {0, 0};
@@ -224,8 +225,9 @@ constexpr uint32_t GROUP_FULL_GUARD = 6000u; /* occupied active slots above whic
 
 /* The entries idx[] on the host: each buffer through the host resolver's sequential path against its receiver's filter,
  * hit positions made buffer-relative; then the signal power of their messages with the group look-behind.  The
- * candidate lists must be in s.h_hits / s.h_tries. */
-int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const std::vector<uint32_t> &idx)
+ * candidate lists must be in s.h_hits / s.h_tries.  want_fields: the decoded fields of every entry's messages beside
+ * them, an entry on its own so that the Mode A/C altitude carry stays inside its buffer. */
+int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const std::vector<uint32_t> &idx, bool want_fields)
 {
     msd_ctx *c = g->ctx;
     const int format = c->cfg.format;
@@ -287,6 +289,10 @@ int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const st
         const std::vector<uint32_t> buf(o.msgs.size(), 0u);
         msd_resolve_power(&r.resolver, 1, &o.valid, o.means, o.msgs.data(), sizeof(msd_message), o.req.data(), buf.data(),
                           s.h_pow + pow_first[k], sizeof(uint64_t), o.msgs.size());
+        if (want_fields) { /* one buffer index for the whole entry: the carry starts empty and never leaves it */
+            o.fields.resize(o.msgs.size());
+            msd_fields_batch(o.msgs.data(), sizeof(msd_message), buf.data(), o.msgs.size(), o.fields.data());
+        }
     });
     g->host_buffers += idx.size();
     for (uint32_t i : idx) { /* the device copies follow the host filters */
@@ -300,9 +306,10 @@ int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const st
 /* The GPU resolve of one call: every buffer in one pass of msd_resolve_kernel against its own receiver's snapshot
  * (snap_idx = receiver), signal power and records on the device, then the receivers' filter changes applied to the host
  * filters and, by msd_group_filter_apply_kernel, to the device snapshots.  Buffers the kernel hands back (fallback) and
- * receivers whose active table is nearly full are returned in `host` for group_host_entries. */
+ * receivers whose active table is nearly full are returned in `host` for group_host_entries.  want_fields: the emit
+ * kernel also writes the decoded fields, s.h_fields[k] beside s.h_wire[k]. */
 int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vector<uint32_t> &gpu_idx,
-                      std::vector<uint32_t> &host, std::vector<uint32_t> &rec_first)
+                      std::vector<uint32_t> &host, std::vector<uint32_t> &rec_first, bool want_fields)
 {
     msd_ctx *c = g->ctx;
     const uint32_t n = s.nbuffers;
@@ -380,8 +387,9 @@ int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vect
         rc = ensure_req(c, s, total);
         if (rc)
             return gfail(g, rc, "records: %s", c->err);
-        rc = msd_launch_emit(&rp, n, reinterpret_cast<const unsigned long long *>(s.d_powr), s.h_side, s.h_wire, nullptr,
-                             (uint32_t)s.req_cap, c->stream);
+        /* (s.h_fields after ensure_req, which moves the arrays when it grows them) */
+        rc = msd_launch_emit(&rp, n, reinterpret_cast<const unsigned long long *>(s.d_powr), s.h_side, s.h_wire,
+                             want_fields ? s.h_fields : nullptr, (uint32_t)s.req_cap, c->stream);
         if (rc)
             return gfail(g, rc, "emit kernel launch failed");
     }
@@ -429,9 +437,18 @@ int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vect
     return 0;
 }
 
+/* where a call's messages go: `sink` for msd_group_submit_*, `fsink` with the decoded fields for
+ * msd_group_submit_*_fields (want_fields: a fields call, whether or not it has a sink) */
+struct GroupSink {
+    msd_group_message_fn sink = nullptr;
+    msd_group_fields_fn fsink = nullptr;
+    void *user = nullptr;
+    bool want_fields = false;
+};
+
 /* one call: scan (group instantiation); then every entry resolved against its own receiver's state -- on the GPU, or
  * on host threads (MSD_CFG_HOST_RESOLVE, a rescanned overflow, the kernel's fallback); tails; delivery in entry order */
-int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint32_t n, msd_group_message_fn sink, void *user)
+int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint32_t n, const GroupSink &to)
 {
     msd_ctx *c = g->ctx;
     const int format = c->cfg.format;
@@ -517,7 +534,7 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     }
     std::vector<uint32_t> gpu_idx, host, rec_first;
     if (s.gpu_resolve) {
-        rc = group_gpu_entries(g, s, e, gpu_idx, host, rec_first);
+        rc = group_gpu_entries(g, s, e, gpu_idx, host, rec_first, to.want_fields);
         if (rc)
             return rc;
         if (!host.empty()) { /* their candidate lists after all */
@@ -547,7 +564,7 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     c->timing.tries = s.h_totals[1];
     c->timing.resolve_passes = gpu_idx.empty() ? 0 : 1;
     if (!host.empty()) {
-        rc = group_host_entries(g, s, e, host);
+        rc = group_host_entries(g, s, e, host, to.want_fields);
         if (rc)
             return rc;
     }
@@ -559,21 +576,65 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     GHIPCHK(g, hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < n; ++i)
         g->rx[e[i].receiver].have_tail = true;
-    if (sink) {
+    if (to.sink || to.fsink) { /* each entry's records, and its fields, from wherever it was resolved */
         std::vector<bool> on_gpu(n, false);
         for (uint32_t i : gpu_idx)
             on_gpu[i] = true;
         for (uint32_t i = 0; i < n; ++i) {
+            const GroupEntryOut &o = g->out[i];
             if (on_gpu[i]) {
-                for (uint32_t k = rec_first[i]; k < rec_first[i + 1]; ++k)
-                    sink(e[i].receiver, &s.h_wire[k].mm, user);
+                for (uint32_t k = rec_first[i]; k < rec_first[i + 1]; ++k) {
+                    if (to.fsink)
+                        to.fsink(e[i].receiver, &s.h_wire[k].mm, &s.h_fields[k], to.user);
+                    else
+                        to.sink(e[i].receiver, &s.h_wire[k].mm, to.user);
+                }
             } else {
-                for (const msd_message &m : g->out[i].msgs)
-                    sink(e[i].receiver, &m, user);
+                for (size_t k = 0; k < o.msgs.size(); ++k) {
+                    if (to.fsink)
+                        to.fsink(e[i].receiver, &o.msgs[k], &o.fields[k], to.user);
+                    else
+                        to.sink(e[i].receiver, &o.msgs[k], to.user);
+                }
             }
         }
     }
     return 0;
+}
+
+/* the four submit entries: the checks that leave the group untouched, the copy of a host call's IQ to the staging
+ * buffer, then the call */
+int group_submit(msd_group *g, const void *iq, const msd_group_entry *e, uint32_t n, bool from_host, const GroupSink &to)
+{
+    if (!g)
+        return -EINVAL;
+    msd_ctx *c = g->ctx;
+    if (to.want_fields && !c->want_fields)
+        return gfail(g, -EINVAL, "the group was created without MSD_CFG_DECODE_FIELDS");
+    if (group_check(g, e, n))
+        return gfail(g, -EINVAL, "entries: a receiver out of range or given twice, nonzero flags, or more than max_receivers");
+    if (n && !iq)
+        return gfail(g, -EINVAL, from_host ? "IQ pointer must be non-null" : "IQ pointer must be non-null and 16-byte aligned");
+    if (n && !from_host && (reinterpret_cast<uintptr_t>(iq) & 15u))
+        return gfail(g, -EINVAL, "IQ pointer must be non-null and 16-byte aligned");
+    if (c->failed)
+        return gfail(g, -EIO, "an earlier call failed");
+    if (n == 0)
+        return 0;
+    auto run = [&]() -> int {
+        GHIPCHK(g, hipSetDevice(c->cfg.device));
+        if (from_host) {
+            if (!c->d_stage)
+                GHIPCHK(g, hipMalloc(reinterpret_cast<void **>(&c->d_stage), c->cfg.max_batch_samples * 4 + 64));
+            GHIPCHK(g, hipMemcpyAsync(c->d_stage, iq, (size_t)n * MSD_CHUNK_SAMPLES * c->bps, hipMemcpyHostToDevice, c->stream));
+            iq = c->d_stage;
+        }
+        return group_run(g, static_cast<const uint8_t *>(iq), e, n, to);
+    };
+    const int rc = run();
+    if (rc)
+        c->failed = true;
+    return rc;
 }
 
 } /* namespace */
@@ -666,50 +727,39 @@ const char *msd_group_last_error(const msd_group *g)
 int msd_group_submit_device(msd_group *g, const void *d_iq, const msd_group_entry *e, uint32_t n,
                             msd_group_message_fn sink, void *user)
 {
-    if (!g)
-        return -EINVAL;
-    if (group_check(g, e, n))
-        return gfail(g, -EINVAL, "entries: a receiver out of range or given twice, nonzero flags, or more than max_receivers");
-    if (n && (!d_iq || (reinterpret_cast<uintptr_t>(d_iq) & 15u)))
-        return gfail(g, -EINVAL, "IQ pointer must be non-null and 16-byte aligned");
-    if (g->ctx->failed)
-        return gfail(g, -EIO, "an earlier call failed");
-    if (n == 0)
-        return 0;
-    GHIPCHK(g, hipSetDevice(g->ctx->cfg.device));
-    const int rc = group_run(g, static_cast<const uint8_t *>(d_iq), e, n, sink, user);
-    if (rc)
-        g->ctx->failed = true;
-    return rc;
+    GroupSink to;
+    to.sink = sink;
+    to.user = user;
+    return group_submit(g, d_iq, e, n, false, to);
 }
 
 int msd_group_submit_host(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n,
                           msd_group_message_fn sink, void *user)
 {
-    if (!g)
-        return -EINVAL;
-    if (group_check(g, e, n))
-        return gfail(g, -EINVAL, "entries: a receiver out of range or given twice, nonzero flags, or more than max_receivers");
-    if (n && !h_iq)
-        return gfail(g, -EINVAL, "IQ pointer must be non-null");
-    msd_ctx *c = g->ctx;
-    if (c->failed)
-        return gfail(g, -EIO, "an earlier call failed");
-    if (n == 0)
-        return 0;
-    auto stage = [&]() -> int {
-        GHIPCHK(g, hipSetDevice(c->cfg.device));
-        if (!c->d_stage)
-            GHIPCHK(g, hipMalloc(reinterpret_cast<void **>(&c->d_stage), c->cfg.max_batch_samples * 4 + 64));
-        GHIPCHK(g, hipMemcpyAsync(c->d_stage, h_iq, (size_t)n * MSD_CHUNK_SAMPLES * c->bps, hipMemcpyHostToDevice, c->stream));
-        return 0;
-    };
-    const int rc = stage();
-    if (rc) {
-        c->failed = true;
-        return rc;
-    }
-    return msd_group_submit_device(g, c->d_stage, e, n, sink, user);
+    GroupSink to;
+    to.sink = sink;
+    to.user = user;
+    return group_submit(g, h_iq, e, n, true, to);
+}
+
+int msd_group_submit_device_fields(msd_group *g, const void *d_iq, const msd_group_entry *e, uint32_t n,
+                                   msd_group_fields_fn sink, void *user)
+{
+    GroupSink to;
+    to.fsink = sink;
+    to.user = user;
+    to.want_fields = true;
+    return group_submit(g, d_iq, e, n, false, to);
+}
+
+int msd_group_submit_host_fields(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n,
+                                 msd_group_fields_fn sink, void *user)
+{
+    GroupSink to;
+    to.fsink = sink;
+    to.user = user;
+    to.want_fields = true;
+    return group_submit(g, h_iq, e, n, true, to);
 }
 
 int msd_group_reset_receiver(msd_group *g, uint32_t receiver)

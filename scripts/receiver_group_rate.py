@@ -20,7 +20,16 @@ profiles/receiver_group_options_rate.json.
 times the K = 1024 call with Mode A/C off for every receiver, on for every other one, and on for all, alternating, in
 one process, over a capture with 2000 Mode A/C replies a second; writes profiles/receiver_group_modeac_rate.json.  Its
 kernel trace: rocprofv3 --kernel-trace --stats -- python scripts/receiver_group_rate.py --modeac --reps 3 --out
-/tmp/x.json (profiles/receiver_group_modeac_k1024_kernel_stats.csv)."""
+/tmp/x.json (profiles/receiver_group_modeac_k1024_kernel_stats.csv).
+
+    python scripts/receiver_group_rate.py --fields [--reps 20]
+
+times the K = 1024 call three ways, alternating, in one process: the plain call on a group made without
+MSD_CFG_DECODE_FIELDS, the plain call on a group made with it, and the fields call (msd_group_submit_*_fields) on
+that group, over a capture with 2000 Mode A/C replies a second and Mode A/C on for every other receiver; writes
+profiles/receiver_group_fields_rate.json.  Its kernel trace: rocprofv3 --kernel-trace --stats -- python
+scripts/receiver_group_rate.py --fields --reps 3 --out /tmp/x.json
+(profiles/receiver_group_fields_k1024_kernel_stats.csv)."""
 import argparse
 import json
 import os
@@ -41,16 +50,18 @@ def main():
     ap.add_argument("--only", type=int, default=0)
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--modeac", action="store_true")
+    ap.add_argument("--fields", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "receiver_group_options_rate.json" if a.mixed else
-                             "receiver_group_modeac_rate.json" if a.modeac else "receiver_group_rate.json")
+                             "receiver_group_modeac_rate.json" if a.modeac else
+                             "receiver_group_fields_rate.json" if a.fields else "receiver_group_rate.json")
     import __graft_entry__ as g
     pkg = g.load_package()
     import torch
     capi, siggen = pkg.capi, pkg.siggen
-    base = siggen.generate(siggen.make_cfg(seed=17, msgs_per_sec=3000, n_aircraft=60, ac_per_sec=2000 if a.modeac else 0),
+    base = siggen.generate(siggen.make_cfg(seed=17, msgs_per_sec=3000, n_aircraft=60, ac_per_sec=2000 if a.modeac or a.fields else 0),
                            64 * CHUNK)
     ks = [a.only] if a.only else [1, 16, 256, 1024]
     kmax = max(ks)
@@ -62,6 +73,8 @@ def main():
         return mixed(a, capi, dev, host)
     if a.modeac:
         return modeac(a, capi, dev, host)
+    if a.fields:
+        return fields(a, capi, dev, host)
     res = {"buffer_samples": CHUNK, "format": "uc8", "reps": a.reps, "group": {}}
     for k in ks:
         grp = capi.ReceiverGroup(k, fmt=capi.FMT_UC8)
@@ -134,15 +147,30 @@ def modeac(a, capi, dev, host):
     alternate(a, k, groups, dev, host, res, modeac=True)
 
 
-def alternate(a, k, groups, dev, host, res, modeac=False):
+def fields(a, capi, dev, host):
+    k = 1024
+    flagged = capi.ReceiverGroup(k, fmt=capi.FMT_UC8, flags=capi.CFG_DECODE_FIELDS)
+    groups = {"plain": capi.ReceiverGroup(k, fmt=capi.FMT_UC8), "plain_on_fields_group": flagged, "fields": flagged}
+    for grp in (groups["plain"], flagged):
+        for r in range(0, k, 2):
+            grp.set_receiver_mode_ac(r, 1)
+    res = {"buffer_samples": CHUNK, "format": "uc8", "receivers": k, "reps": a.reps,
+           "capture": "siggen seed 17, 3000 Mode S and 2000 Mode A/C replies a second; Mode A/C on for even receivers",
+           "groups": "plain: made without MSD_CFG_DECODE_FIELDS; plain_on_fields_group / fields: one group made with it, "
+                     "through msd_group_submit_* and msd_group_submit_*_fields; no sink in either (deliver=False)",
+           "calls": {}}
+    alternate(a, k, groups, dev, host, res, modeac=True, fields_of=("fields",))
+
+
+def alternate(a, k, groups, dev, host, res, modeac=False, fields_of=()):
     for where, iq in (("device", dev), ("host", host)):
         ts = {name: [] for name in groups}
-        for grp in groups.values():
-            grp.submit(iq, list(range(k)), deliver=False)  # warm-up
+        for name, grp in groups.items():
+            grp.submit(iq, list(range(k)), deliver=False, fields=name in fields_of)  # warm-up
         for _ in range(a.reps):  # alternating, so that drift of the box falls on both alike
             for name, grp in groups.items():
                 t0 = time.perf_counter()
-                grp.submit(iq, list(range(k)), deliver=False)
+                grp.submit(iq, list(range(k)), deliver=False, fields=name in fields_of)
                 ts[name].append(time.perf_counter() - t0)
         for name, v in ts.items():
             t = float(np.median(v))
@@ -156,6 +184,7 @@ def alternate(a, k, groups, dev, host, res, modeac=False):
         res["calls"][name]["accepted"] = int(sum(sum(grp.stats(r)["demod_accepted"]) for r in range(k)))
         if modeac:
             res["calls"][name]["demod_modeac"] = int(sum(grp.stats(r)["demod_modeac"] for r in range(k)))
+    for grp in groups.values():
         grp.close()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
