@@ -506,6 +506,28 @@ int msd_accept_frames(msd_ctx *ctx, const msd_message *frames, size_t n, int on_
                       msd_message_fn sink, void *user);
 int msd_get_remote_stats(const msd_ctx *ctx, msd_remote_stats *st);
 
+/* ---- wire output: accepted messages as the bytes readsb sends on -- Beast frames (modesSendBeastOutput,
+ * net_io.c:769-835) or AVR raw lines (modesSendRawOutput, net_io.c:870-896) -- written on the GPU.
+ *   MSD_WIRE_BEAST     0x1A, type '1' / '2' / '3' for 2 / 7 / 14 bytes, the low 48 bits of timestampMsg big-endian, the
+ *                      signal byte (int)round(sqrt(signalLevel) * 255) -- at least 1 for a level above zero, at most 255
+ *                      --, the payload; every 0x1A behind the type byte doubled.  Another length: no bytes.
+ *   MSD_WIRE_AVR       "*HEX;\n", upper case.
+ *   MSD_WIRE_AVR_MLAT  "@" + 12 hex digits of the timestamp + "HEX;\n" when the timestamp is not zero, else as above.
+ * A message with correctedbits == 2 goes out only with MSD_WIRE_VERBATIM (--net-verbatim, net_io.c:1272-1285), and with
+ * it every repaired message goes out with the bytes as they were received (net_io.c:775,874): the one or two
+ * positions in [5, msgbits) whose single-bit syndromes xor to `crc` (DF 11: crc & 0xffff80) flipped back; a record that
+ * no such pattern fits goes out as it is.  The bytes are those of msd_beast_frame_out / msd_avr_line_out
+ * (libmsd_host.so) applied to the same records in the same order; a message takes at most 44 bytes. ---- */
+enum { MSD_WIRE_BEAST = 0, MSD_WIRE_AVR = 1, MSD_WIRE_AVR_MLAT = 2 };
+#define MSD_WIRE_VERBATIM 1u /* --net-verbatim */
+/* n records from anywhere (msd_collect, msd_accept_beast, a file; device or host memory as msd_accept_frames takes them)
+ * -> out[0 .. *out_len), one dense stream in record order, and ends[i] (n entries, or NULL) = the end offset of record
+ * i in it -- a record that is not forwarded repeats the end before it.  Synchronous; out and ends are host arrays.
+ * -ENOSPC: cap is too small; *out_len is the size needed and nothing else was written.  -EINVAL: an unknown format or
+ * flag bit, n above 2^24, NULL.  -EBUSY while msd_launch_* batches are outstanding.  n == 0: 0 and *out_len = 0. */
+int msd_wire_encode(msd_ctx *ctx, const msd_message *msgs, size_t n, int on_device, int format, uint32_t flags,
+                    uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
+
 /* ---- receiver groups: many independent live receivers of one configuration decoded in one launch.
  * A group holds up to max_receivers receivers.  Each call takes exactly one full MSD_CHUNK_SAMPLES buffer from each
  * of any subset of them, runs one scan over all of them and delivers each receiver's messages.  For every receiver the
@@ -575,6 +597,21 @@ int msd_group_submit_device_fields(msd_group *g, const void *d_iq, const msd_gro
                                    msd_group_fields_fn sink, void *user);
 int msd_group_submit_host_fields(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n,
                                  msd_group_fields_fn sink, void *user);
+/* The same two calls with every entry's messages in wire format (MSD_WIRE_*, MSD_WIRE_VERBATIM: see msd_wire_encode):
+ * arguments, checks, errors and order are those of msd_group_submit_device / msd_group_submit_host, plus -EINVAL for an
+ * unknown format or flag bit, with the group's state untouched.  The sink is called exactly once per entry, in entry
+ * order, with that entry's bytes (nbytes may be 0) and the number of messages they carry; bytes is valid until the sink
+ * returns.  The bytes equal the concatenation, in delivery order, of msd_beast_frame_out / msd_avr_line_out over the
+ * messages the plain call delivers for that entry; filter, clocks, tails, every msd_stats counter and the power sums
+ * are exactly the plain call's.  For the buffers resolved on the GPU the bytes are written by kernels behind the record
+ * kernel, each entry contiguous in page-locked host memory (verbatim from the repaired positions of the winning try, no
+ * search); for the buffers resolved on host threads the host writers run on the entry's thread.  A group may mix all
+ * six submit calls. */
+typedef void (*msd_group_wire_fn)(uint32_t receiver, const uint8_t *bytes, size_t nbytes, uint32_t nmessages, void *user);
+int msd_group_submit_device_wire(msd_group *g, const void *d_iq, const msd_group_entry *e, uint32_t n, int format,
+                                 uint32_t flags, msd_group_wire_fn sink, void *user);
+int msd_group_submit_host_wire(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n, int format,
+                               uint32_t flags, msd_group_wire_fn sink, void *user);
 int msd_group_reset_receiver(msd_group *g, uint32_t receiver); /* filter, clock, counters, tail */
 int msd_group_get_stats(const msd_group *g, uint32_t receiver, msd_stats *st);
 int msd_group_set_preamble_threshold(msd_group *g, int threshold); /* group-wide: sets every receiver's threshold */

@@ -109,6 +109,9 @@ def layout_from_environment():
                   debug_flags=int(e("MSD_DEBUG_FLAGS", "0") or 0))
     return flags, fields
 INVALID_ALTITUDE = -9999
+WIRE_BEAST, WIRE_AVR, WIRE_AVR_MLAT = 0, 1, 2  # msd_wire_encode / msd_group_submit_*_wire formats
+WIRE_VERBATIM = 1  # --net-verbatim
+BEAST_MAX = 44  # most bytes one message takes in any of the formats
 
 
 class Config(C.Structure):
@@ -221,6 +224,7 @@ EXPORTS = [
     "msd_group_set_receiver_options", "msd_group_get_receiver_options",
     "msd_group_set_receiver_mode_ac", "msd_group_get_receiver_mode_ac",
     "msd_group_submit_device_fields", "msd_group_submit_host_fields",
+    "msd_wire_encode", "msd_group_submit_device_wire", "msd_group_submit_host_wire",
 ]
 
 _lib = None
@@ -300,6 +304,9 @@ def lib():
             getattr(L, name).restype = C.c_int
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p,
                                          C.c_void_p]
+        L.msd_wire_encode.restype = C.c_int
+        L.msd_wire_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_void_p,
+                                      C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
         L.msd_get_remote_stats.restype = C.c_int
         L.msd_get_remote_stats.argtypes = [C.c_void_p, C.POINTER(RemoteStats)]
         _lib = L
@@ -517,6 +524,31 @@ class Demodulator:
         return self._run(lambda fn, st: lib().msd_accept_frames(self._h, records.ctypes.data, records.size, 0, now_ms,
                                                                 fn, st))
 
+    def encode_wire(self, messages, format, verbatim=False, on_device=False):
+        """msd_wire_encode: the records as one stream of Beast frames (WIRE_BEAST) or AVR lines (WIRE_AVR,
+        WIRE_AVR_MLAT), written on the GPU.  messages: a MESSAGE_DTYPE array, or with on_device=True a contiguous torch
+        tensor on the GPU holding such records (read in place).  Returns (bytes, ends): ends[i] is the end offset of
+        record i in the stream (uint32); a record that is not forwarded repeats the end before it."""
+        flags = WIRE_VERBATIM if verbatim else 0
+        if on_device:
+            if not messages.is_contiguous():
+                raise ValueError("encode_wire needs a contiguous tensor")
+            nbytes = messages.numel() * messages.element_size()
+            if nbytes % MESSAGE_DTYPE.itemsize:
+                raise ValueError("encode_wire needs whole records")
+            import torch
+            torch.cuda.current_stream(messages.device).synchronize()  # the context reads it on its own stream
+            ptr, n = messages.data_ptr(), nbytes // MESSAGE_DTYPE.itemsize
+        else:
+            messages = np.ascontiguousarray(messages, dtype=MESSAGE_DTYPE)
+            ptr, n = messages.ctypes.data, messages.size
+        out = np.zeros(max(n * BEAST_MAX, 1), dtype=np.uint8)
+        ends = np.zeros(n, dtype=np.uint32)
+        used = C.c_size_t()
+        self._check(lib().msd_wire_encode(self._h, C.c_void_p(ptr), n, int(bool(on_device)), format, flags,
+                                          out.ctypes.data, out.size, C.byref(used), ends.ctypes.data))
+        return out[: used.value].tobytes(), ends
+
     def remote_stats(self):
         st = RemoteStats()
         self._check(lib().msd_get_remote_stats(self._h, C.byref(st)))
@@ -601,6 +633,7 @@ class GroupReceiverOptions(C.Structure):
 GROUP_MESSAGE_DTYPE = np.dtype([("receiver", "<u4"), ("m", MESSAGE_DTYPE)])
 _GROUP_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_void_p)
 _GROUP_FIELDS_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_GROUP_WIRE_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p)
 
 
 def _group_lib():
@@ -616,6 +649,9 @@ def _group_lib():
                   L.msd_group_submit_host_fields):
             f.restype = C.c_int
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        for f in (L.msd_group_submit_device_wire, L.msd_group_submit_host_wire):
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.msd_group_reset_receiver.restype = C.c_int
         L.msd_group_reset_receiver.argtypes = [C.c_void_p, C.c_uint32]
         L.msd_group_get_stats.restype = C.c_int
@@ -730,6 +766,45 @@ class ReceiverGroup:
     def submit_fields(self, iq, receivers, **kw):
         """submit(..., fields=True)."""
         return self.submit(iq, receivers, fields=True, **kw)
+
+    def _submit_wire(self, call, iq, receivers, format, verbatim, dropped, deliver):
+        receivers = [int(r) for r in receivers]
+        n = len(receivers)
+        entries = (GroupEntry * max(n, 1))()
+        for i, r in enumerate(receivers):
+            entries[i] = GroupEntry(r, 0, int(dropped[i]) if dropped is not None else 0)
+        got = []
+
+        def sink(receiver, data, nbytes, nmessages, _user):
+            got.append((receiver, C.string_at(data, nbytes) if nbytes else b"", nmessages))
+
+        fn = _GROUP_WIRE_SINK(sink)  # (kept alive until the call returns)
+        self._check(call(self._h, iq, entries, n, format, WIRE_VERBATIM if verbatim else 0,
+                         C.cast(fn, C.c_void_p) if deliver else None, None))
+        return got
+
+    def submit_device_wire(self, iq, receivers, format=WIRE_BEAST, verbatim=False, dropped=None, deliver=True):
+        """msd_group_submit_device_wire: as submit() with a torch tensor on the GPU, the result in wire format -- the
+        list of (receiver, bytes, nmessages), one per entry in entry order.  deliver=False passes no sink."""
+        n = len(receivers)
+        if not iq.is_contiguous():
+            raise ValueError("submit needs a contiguous tensor")
+        if iq.numel() * iq.element_size() < n * CHUNK * self.bytes_per_sample:
+            raise ValueError(f"{n} buffers need {n * CHUNK * self.bytes_per_sample} bytes")
+        import torch
+        torch.cuda.current_stream(iq.device).synchronize()  # the group reads it on its own stream
+        return self._submit_wire(_group_lib().msd_group_submit_device_wire, C.c_void_p(iq.data_ptr()), receivers, format,
+                                 verbatim, dropped, deliver)
+
+    def submit_host_wire(self, iq, receivers, format=WIRE_BEAST, verbatim=False, dropped=None, deliver=True):
+        """msd_group_submit_host_wire: the same for bytes or a numpy array in host memory."""
+        n = len(receivers)
+        arr = np.frombuffer(iq, dtype=np.uint8) if isinstance(iq, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(iq).view(np.uint8).reshape(-1)
+        if arr.size < n * CHUNK * self.bytes_per_sample:
+            raise ValueError(f"{n} buffers need {n * CHUNK * self.bytes_per_sample} bytes")
+        return self._submit_wire(_group_lib().msd_group_submit_host_wire, arr.ctypes.data, receivers, format, verbatim,
+                                 dropped, deliver)
 
     def stats(self, receiver):
         st = Stats()

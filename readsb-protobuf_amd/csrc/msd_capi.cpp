@@ -2315,6 +2315,85 @@ int msd_decode_fields_device(msd_ctx *c, const msd_message *msgs, size_t n, msd_
     return rc ? fail(c, rc, "field kernel launch failed") : 0;
 }
 
+/* Lengths and their scan, the stream's length to the host, then -- if it fits -- the store into a device array and two
+ * copies into the caller's. */
+int msd_wire_encode(msd_ctx *c, const msd_message *msgs, size_t n, int on_device, int format, uint32_t flags, uint8_t *out,
+                    size_t cap, size_t *out_len, uint32_t *ends)
+{
+    if (!c || !out_len)
+        return -EINVAL;
+    if (format != MSD_WIRE_BEAST && format != MSD_WIRE_AVR && format != MSD_WIRE_AVR_MLAT)
+        return fail(c, -EINVAL, "msd_wire_encode: unknown format %d", format);
+    if (flags & ~MSD_WIRE_VERBATIM)
+        return fail(c, -EINVAL, "msd_wire_encode: unknown flags 0x%x", flags);
+    if ((n && !msgs) || n > (1u << 24))
+        return fail(c, -EINVAL, "msd_wire_encode: no records, or more than 2^24");
+    if (c->failed)
+        return fail(c, -EIO, "an earlier call failed");
+    if (c->outstanding)
+        return fail(c, -EBUSY, "batches outstanding");
+    *out_len = 0;
+    if (n == 0)
+        return 0;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const int verbatim = (flags & MSD_WIRE_VERBATIM) ? 1 : 0;
+    const uint32_t nblocks = (uint32_t)((n + 255) / 256);
+    msd_message *d_in = nullptr;
+    uint8_t *d_lens = nullptr, *d_out = nullptr;
+    uint32_t *d_sums = nullptr, *d_ends = nullptr;
+    uint32_t total = 0;
+    int rc = 0;
+    bool nospc = false;
+    hipError_t e = hipSuccess;
+    if (!on_device) {
+        e = hipMalloc(reinterpret_cast<void **>(&d_in), n * sizeof *d_in);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_in, msgs, n * sizeof *d_in, hipMemcpyHostToDevice, c->aux_stream);
+        msgs = d_in;
+    }
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void **>(&d_lens), n);
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void **>(&d_sums), sizeof(uint32_t) * ((size_t)nblocks + 1));
+    if (e == hipSuccess)
+        rc = msd_launch_wire_lengths(msgs, (uint32_t)n, format, verbatim, d_lens, d_sums, c->aux_stream);
+    if (e == hipSuccess && !rc)
+        e = hipMemcpyAsync(&total, d_sums + nblocks, sizeof total, hipMemcpyDeviceToHost, c->aux_stream);
+    if (e == hipSuccess && !rc)
+        e = hipStreamSynchronize(c->aux_stream);
+    if (e == hipSuccess && !rc) {
+        *out_len = total;
+        nospc = total > cap || (total && !out);
+    }
+    if (e == hipSuccess && !rc && !nospc) {
+        e = hipMalloc(reinterpret_cast<void **>(&d_out), (size_t)total + 16);
+        if (e == hipSuccess && ends)
+            e = hipMalloc(reinterpret_cast<void **>(&d_ends), n * sizeof(uint32_t));
+        if (e == hipSuccess)
+            rc = msd_launch_wire_store(msgs, (uint32_t)n, format, verbatim, d_lens, d_sums, d_out, d_ends, c->aux_stream);
+        if (e == hipSuccess && !rc && total)
+            e = hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, c->aux_stream);
+        if (e == hipSuccess && !rc && ends)
+            e = hipMemcpyAsync(ends, d_ends, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->aux_stream);
+        if (e == hipSuccess && !rc)
+            e = hipStreamSynchronize(c->aux_stream);
+    }
+    (void)hipFree(d_in);
+    (void)hipFree(d_lens);
+    (void)hipFree(d_sums);
+    (void)hipFree(d_out);
+    (void)hipFree(d_ends);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, e == hipErrorOutOfMemory ? -ENOMEM : -EIO, "msd_wire_encode: %s", hipGetErrorString(e));
+    }
+    if (rc)
+        return fail(c, rc, "wire kernel launch failed");
+    if (nospc)
+        return fail(c, -ENOSPC, "msd_wire_encode: %u bytes needed, room for %zu", total, cap);
+    return 0;
+}
+
 int msd_restart(msd_ctx *c)
 {
     if (!c)

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "msd_ctx.h" /* the context, and with it modes_hip.h, msd_internal.h and msd_kernels.h */
+#include "host/msd_wire.h" /* the host writers, for the entries resolved on host threads */
 
 using namespace msd_impl;
 
@@ -36,6 +37,8 @@ struct GroupEntryOut {
     std::vector<msd_fields> fields; /* of msgs, for a fields call (msd_group_submit_*_fields) */
     std::vector<msd_hit> hits; /* the entry's hits, positions made buffer-relative */
     std::vector<msd_ac_hit> ac; /* its Mode A/C candidates, likewise */
+    std::vector<uint8_t> wire;  /* msgs in wire format, for a wire call (msd_group_submit_*_wire) */
+    uint32_t wire_msgs = 0;     /* the messages `wire` carries */
     double means[2] = {0, 0};
     uint32_t valid = MSD_CHUNK_SAMPLES;
 };
@@ -90,6 +93,11 @@ struct msd_group {
     uint64_t host_buffers = 0;     /* buffers resolved on the host (msd_timing.resolve_fallback) */
     std::vector<GroupEntryOut> out;
     std::vector<uint64_t> req_all;
+    /* wire calls, made by the first of them (group_make_wire) */
+    uint8_t *h_wire_out = nullptr; /* pinned: the entries' bytes of the buffers resolved on the GPU */
+    size_t wire_cap = 0;
+    uint32_t *h_wire_entries = nullptr; /* pinned [max_receivers][4]: offset, bytes, messages, 0 per buffer */
+    uint32_t *d_wire_counts = nullptr;  /* [max_receivers][2]: bytes and messages per buffer, between the two kernels */
     char err[256] = {0};
 };
 
@@ -220,15 +228,63 @@ int group_check(const msd_group *g, const msd_group_entry *e, uint32_t n)
     return 0;
 }
 
+/* where a call's messages go: `sink` for msd_group_submit_*, `fsink` with the decoded fields for
+ * msd_group_submit_*_fields (want_fields: a fields call, whether or not it has a sink), `wsink` with every entry's
+ * bytes in wire format for msd_group_submit_*_wire (want_wire, likewise) */
+struct GroupSink {
+    msd_group_message_fn sink = nullptr;
+    msd_group_fields_fn fsink = nullptr;
+    msd_group_wire_fn wsink = nullptr;
+    void *user = nullptr;
+    bool want_fields = false;
+    bool want_wire = false;
+    int wire_format = MSD_WIRE_BEAST;
+    uint32_t wire_flags = 0;
+};
+
+/* The buffers of the wire calls: the pinned array the kernels write the entries' bytes to -- at least `bytes`, grown
+ * when a call's worst case needs more --, the per-buffer results and the counts between the two kernels. */
+int group_make_wire(msd_group *g, size_t bytes)
+{
+    GHIPCHK(g, hipSetDevice(g->ctx->cfg.device));
+    if (!g->h_wire_entries) {
+        uint32_t *entries = nullptr, *counts = nullptr;
+        if (hipHostMalloc(reinterpret_cast<void **>(&entries), sizeof(uint32_t) * 4 * g->max_receivers, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&counts), sizeof(uint32_t) * 2 * g->max_receivers) != hipSuccess) {
+            (void)hipGetLastError();
+            if (entries)
+                (void)hipHostFree(entries);
+            return gfail(g, -ENOMEM, "wire output buffers: out of memory");
+        }
+        g->h_wire_entries = entries;
+        g->d_wire_counts = counts;
+    }
+    if (bytes > g->wire_cap) { /* (nothing of an earlier call is in flight: every call ends synchronised) */
+        const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 16);
+        uint8_t *p = nullptr;
+        if (hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return gfail(g, -ENOMEM, "wire output array: out of memory");
+        }
+        if (g->h_wire_out)
+            (void)hipHostFree(g->h_wire_out);
+        g->h_wire_out = p;
+        g->wire_cap = want;
+    }
+    return 0;
+}
+
 constexpr uint32_t GROUP_FULL_GUARD = 6000u; /* occupied active slots above which a buffer is resolved on the host (as the
                                                 context's replay does: a buffer adds at most 970 addresses, two slots each) */
 
 /* The entries idx[] on the host: each buffer through the host resolver's sequential path against its receiver's filter,
  * hit positions made buffer-relative; then the signal power of their messages with the group look-behind.  The
  * candidate lists must be in s.h_hits / s.h_tries.  want_fields: the decoded fields of every entry's messages beside
- * them, an entry on its own so that the Mode A/C altitude carry stays inside its buffer. */
-int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const std::vector<uint32_t> &idx, bool want_fields)
+ * them, an entry on its own so that the Mode A/C altitude carry stays inside its buffer.  to.want_wire: every entry's
+ * messages through the host writers (host/msd_wire.c), on the entry's thread. */
+int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const std::vector<uint32_t> &idx, const GroupSink &to)
 {
+    const bool want_fields = to.want_fields;
     msd_ctx *c = g->ctx;
     const int format = c->cfg.format;
     const uint64_t H = s.h_totals[0];
@@ -293,6 +349,21 @@ int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const st
             o.fields.resize(o.msgs.size());
             msd_fields_batch(o.msgs.data(), sizeof(msd_message), buf.data(), o.msgs.size(), o.fields.data());
         }
+        if (to.want_wire) {
+            const int verbatim = (to.wire_flags & MSD_WIRE_VERBATIM) ? 1 : 0;
+            o.wire.resize(o.msgs.size() * MSD_AVR_MAX); /* MSD_AVR_MAX > MSD_BEAST_MAX; the line's NUL is overwritten */
+            size_t used = 0;
+            o.wire_msgs = 0;
+            for (const msd_message &mm : o.msgs) {
+                const size_t len = to.wire_format == MSD_WIRE_BEAST
+                                       ? msd_beast_frame_out(&mm, verbatim, o.wire.data() + used)
+                                       : msd_avr_line_out(&mm, to.wire_format == MSD_WIRE_AVR_MLAT, verbatim,
+                                                          reinterpret_cast<char *>(o.wire.data()) + used);
+                used += len;
+                o.wire_msgs += len ? 1u : 0u;
+            }
+            o.wire.resize(used);
+        }
     });
     g->host_buffers += idx.size();
     for (uint32_t i : idx) { /* the device copies follow the host filters */
@@ -307,10 +378,12 @@ int group_host_entries(msd_group *g, Slot &s, const msd_group_entry *e, const st
  * (snap_idx = receiver), signal power and records on the device, then the receivers' filter changes applied to the host
  * filters and, by msd_group_filter_apply_kernel, to the device snapshots.  Buffers the kernel hands back (fallback) and
  * receivers whose active table is nearly full are returned in `host` for group_host_entries.  want_fields: the emit
- * kernel also writes the decoded fields, s.h_fields[k] beside s.h_wire[k]. */
+ * kernel also writes the decoded fields, s.h_fields[k] beside s.h_wire[k].  to.want_wire: behind the emit kernel the two
+ * wire kernels leave every such buffer's bytes in g->h_wire_out, as g->h_wire_entries says. */
 int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vector<uint32_t> &gpu_idx,
-                      std::vector<uint32_t> &host, std::vector<uint32_t> &rec_first, bool want_fields)
+                      std::vector<uint32_t> &host, std::vector<uint32_t> &rec_first, const GroupSink &to)
 {
+    const bool want_fields = to.want_fields;
     msd_ctx *c = g->ctx;
     const uint32_t n = s.nbuffers;
     const GpuCtl ctl = gpu_ctl(c, s);
@@ -393,6 +466,24 @@ int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vect
         if (rc)
             return gfail(g, rc, "emit kernel launch failed");
     }
+    if (to.want_wire) {
+        /* the worst case, known before the launch: 44 bytes per Mode S message and 20 per Mode A/C reply (a Beast frame
+         * of two bytes with every byte escaped; an AVR line of a reply is 19), every entry rounded up to 16 */
+        size_t worst = 0;
+        for (uint32_t i : gpu_idx)
+            worst += ((size_t)MSD_BEAST_MAX * s.h_rbuf[i].nmsgs + 20u * (size_t)s.h_rbuf[i].nac + 15u) & ~(size_t)15u;
+        rc = group_make_wire(g, worst);
+        if (rc)
+            return rc;
+        memset(g->h_wire_entries, 0, sizeof(uint32_t) * 4 * n);
+        if (total) {
+            rc = msd_launch_group_wire(&rp, n, reinterpret_cast<const unsigned long long *>(s.d_powr), to.wire_format,
+                                       (to.wire_flags & MSD_WIRE_VERBATIM) ? 1 : 0, g->d_wire_counts, g->h_wire_out,
+                                       g->wire_cap, g->h_wire_entries, c->stream);
+            if (rc)
+                return gfail(g, rc, "wire kernel launch failed");
+        }
+    }
     /* the filter changes, in each receiver's order: adds, then the flip (readsb.c:331) -- on the host filters here, on
      * the device snapshots by the filter kernel below */
     const uint32_t m = (uint32_t)gpu_idx.size();
@@ -436,15 +527,6 @@ int group_gpu_entries(msd_group *g, Slot &s, const msd_group_entry *e, std::vect
     });
     return 0;
 }
-
-/* where a call's messages go: `sink` for msd_group_submit_*, `fsink` with the decoded fields for
- * msd_group_submit_*_fields (want_fields: a fields call, whether or not it has a sink) */
-struct GroupSink {
-    msd_group_message_fn sink = nullptr;
-    msd_group_fields_fn fsink = nullptr;
-    void *user = nullptr;
-    bool want_fields = false;
-};
 
 /* one call: scan (group instantiation); then every entry resolved against its own receiver's state -- on the GPU, or
  * on host threads (MSD_CFG_HOST_RESOLVE, a rescanned overflow, the kernel's fallback); tails; delivery in entry order */
@@ -534,7 +616,7 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     }
     std::vector<uint32_t> gpu_idx, host, rec_first;
     if (s.gpu_resolve) {
-        rc = group_gpu_entries(g, s, e, gpu_idx, host, rec_first, to.want_fields);
+        rc = group_gpu_entries(g, s, e, gpu_idx, host, rec_first, to);
         if (rc)
             return rc;
         if (!host.empty()) { /* their candidate lists after all */
@@ -564,7 +646,7 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     c->timing.tries = s.h_totals[1];
     c->timing.resolve_passes = gpu_idx.empty() ? 0 : 1;
     if (!host.empty()) {
-        rc = group_host_entries(g, s, e, host, to.want_fields);
+        rc = group_host_entries(g, s, e, host, to);
         if (rc)
             return rc;
     }
@@ -576,7 +658,25 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     GHIPCHK(g, hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < n; ++i)
         g->rx[e[i].receiver].have_tail = true;
-    if (to.sink || to.fsink) { /* each entry's records, and its fields, from wherever it was resolved */
+    if (to.want_wire) { /* each entry's bytes from wherever it was resolved: one call per entry */
+        std::vector<bool> on_gpu(n, false);
+        for (uint32_t i : gpu_idx)
+            on_gpu[i] = true;
+        for (uint32_t i : gpu_idx) {
+            const uint32_t *we = g->h_wire_entries + 4 * (size_t)i;
+            if (we[1] == 0xffffffffu || (size_t)we[0] + we[1] > g->wire_cap)
+                return gfail(g, -EIO, "wire kernel: entry %u does not fit the output array", i);
+        }
+        for (uint32_t i = 0; i < n && to.wsink; ++i) {
+            const GroupEntryOut &o = g->out[i];
+            if (on_gpu[i]) {
+                const uint32_t *we = g->h_wire_entries + 4 * (size_t)i;
+                to.wsink(e[i].receiver, g->h_wire_out + we[0], we[1], we[2], to.user);
+            } else {
+                to.wsink(e[i].receiver, o.wire.data(), o.wire.size(), o.wire_msgs, to.user);
+            }
+        }
+    } else if (to.sink || to.fsink) { /* each entry's records, and its fields, from wherever it was resolved */
         std::vector<bool> on_gpu(n, false);
         for (uint32_t i : gpu_idx)
             on_gpu[i] = true;
@@ -602,7 +702,7 @@ int group_run(msd_group *g, const uint8_t *d_iq, const msd_group_entry *e, uint3
     return 0;
 }
 
-/* the four submit entries: the checks that leave the group untouched, the copy of a host call's IQ to the staging
+/* the six submit entries: the checks that leave the group untouched, the copy of a host call's IQ to the staging
  * buffer, then the call */
 int group_submit(msd_group *g, const void *iq, const msd_group_entry *e, uint32_t n, bool from_host, const GroupSink &to)
 {
@@ -611,6 +711,9 @@ int group_submit(msd_group *g, const void *iq, const msd_group_entry *e, uint32_
     msd_ctx *c = g->ctx;
     if (to.want_fields && !c->want_fields)
         return gfail(g, -EINVAL, "the group was created without MSD_CFG_DECODE_FIELDS");
+    if (to.want_wire && ((to.wire_format != MSD_WIRE_BEAST && to.wire_format != MSD_WIRE_AVR &&
+                          to.wire_format != MSD_WIRE_AVR_MLAT) || (to.wire_flags & ~MSD_WIRE_VERBATIM)))
+        return gfail(g, -EINVAL, "wire output: unknown format %d or flags 0x%x", to.wire_format, to.wire_flags);
     if (group_check(g, e, n))
         return gfail(g, -EINVAL, "entries: a receiver out of range or given twice, nonzero flags, or more than max_receivers");
     if (n && !iq)
@@ -715,6 +818,9 @@ void msd_group_destroy(msd_group *g)
     (void)hipHostFree(g->h_apply);
     (void)hipHostFree(g->h_adds);
     (void)hipHostFree(g->h_snap);
+    (void)hipHostFree(g->h_wire_out);
+    (void)hipHostFree(g->h_wire_entries);
+    (void)hipFree(g->d_wire_counts);
     msd_destroy(g->ctx);
     delete g;
 }
@@ -759,6 +865,30 @@ int msd_group_submit_host_fields(msd_group *g, const void *h_iq, const msd_group
     to.fsink = sink;
     to.user = user;
     to.want_fields = true;
+    return group_submit(g, h_iq, e, n, true, to);
+}
+
+int msd_group_submit_device_wire(msd_group *g, const void *d_iq, const msd_group_entry *e, uint32_t n, int format,
+                                 uint32_t flags, msd_group_wire_fn sink, void *user)
+{
+    GroupSink to;
+    to.wsink = sink;
+    to.user = user;
+    to.want_wire = true;
+    to.wire_format = format;
+    to.wire_flags = flags;
+    return group_submit(g, d_iq, e, n, false, to);
+}
+
+int msd_group_submit_host_wire(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n, int format,
+                               uint32_t flags, msd_group_wire_fn sink, void *user)
+{
+    GroupSink to;
+    to.wsink = sink;
+    to.user = user;
+    to.want_wire = true;
+    to.wire_format = format;
+    to.wire_flags = flags;
     return group_submit(g, h_iq, e, n, true, to);
 }
 

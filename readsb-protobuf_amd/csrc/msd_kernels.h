@@ -166,6 +166,21 @@ int msd_launch_power_buffers(const MsdScanParams *p, int format, const msd_acc *
  * from the counts) */
 int msd_launch_emit(const MsdResolveParams *p, uint32_t nbuffers, const unsigned long long *power, unsigned long long *side, msd_wire *dense,
                     msd_fields *fields /* NULL: no field decode */, uint32_t cap, hipStream_t stream);
+/* ---- wire output (msd_wire_kernels.hip): Beast frames / AVR lines, format MSD_WIRE_*, verbatim 0 / 1 ----
+ * msd_wire_encode in two steps.  lengths: d_lens[i] = bytes of record i (0: not forwarded), d_block_sums[k] = bytes in
+ * front of records 256 k .., d_block_sums[ceil(n / 256)] = the stream's length (ceil(n / 256) + 1 words).  store: the
+ * stream to out (device or page-locked host memory, that many bytes), ends[i] (or NULL) = the end offset of record i. */
+int msd_launch_wire_lengths(const msd_message *d_msgs, uint32_t n, int format, int verbatim, uint8_t *d_lens,
+                            uint32_t *d_block_sums, hipStream_t stream);
+int msd_launch_wire_store(const msd_message *d_msgs, uint32_t n, int format, int verbatim, const uint8_t *d_lens,
+                          const uint32_t *d_block_off, uint8_t *out, uint32_t *ends, hipStream_t stream);
+/* receiver groups: the messages msd_launch_emit writes as records, as wire bytes.  Buffer b's bytes are contiguous at
+ * out + entries[4 b] (a multiple of 16; out: page-locked host memory of cap bytes, at least the sum over the buffers of
+ * 44 nmsgs + 20 nac rounded up to 16), entries[4 b + 1] of them (0xffffffff: they would have passed cap, nothing
+ * written) carrying entries[4 b + 2] messages; d_counts: 2 nbuffers words of device memory.  Two kernels, no
+ * synchronisation between them. */
+int msd_launch_group_wire(const MsdResolveParams *p, uint32_t nbuffers, const unsigned long long *power, int format,
+                          int verbatim, uint32_t *d_counts, uint8_t *out, uint64_t cap, uint32_t *entries, hipStream_t stream);
 /* the field decoder of the emit kernel on its own: out[i] = fields of in[i] (device pointers) */
 int msd_launch_fields(const msd_message *d_in, msd_fields *d_out, uint32_t n, hipStream_t stream);
 uint32_t msd_scan_tile(int format); /* scan positions per tile of the scan kernel for this sample format */

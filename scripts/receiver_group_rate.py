@@ -29,7 +29,17 @@ MSD_CFG_DECODE_FIELDS, the plain call on a group made with it, and the fields ca
 that group, over a capture with 2000 Mode A/C replies a second and Mode A/C on for every other receiver; writes
 profiles/receiver_group_fields_rate.json.  Its kernel trace: rocprofv3 --kernel-trace --stats -- python
 scripts/receiver_group_rate.py --fields --reps 3 --out /tmp/x.json
-(profiles/receiver_group_fields_k1024_kernel_stats.csv)."""
+(profiles/receiver_group_fields_k1024_kernel_stats.csv).
+
+    python scripts/receiver_group_rate.py --wire [--reps 20]
+
+times the K = 1024 call three ways, alternating, in one process, over the --fields capture and with Mode A/C on for every
+other receiver: the plain call with a C sink that only counts; the plain call with a C sink that runs
+msd_beast_frame_out on every message into one array -- the only way to these bytes without the wire entries --; and the
+wire call (msd_group_submit_*_wire, Beast) with a C sink that adds up the sizes it is handed.  The three sinks are
+compiled by the script (gcc) against libmsd_host.so.  Writes profiles/receiver_group_wire_rate.json.  Its kernel trace:
+rocprofv3 --kernel-trace --stats -- python scripts/receiver_group_rate.py --wire --reps 3 --out /tmp/x.json
+(profiles/receiver_group_wire_k1024_kernel_stats.csv)."""
 import argparse
 import json
 import os
@@ -51,17 +61,19 @@ def main():
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--modeac", action="store_true")
     ap.add_argument("--fields", action="store_true")
+    ap.add_argument("--wire", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "receiver_group_options_rate.json" if a.mixed else
                              "receiver_group_modeac_rate.json" if a.modeac else
-                             "receiver_group_fields_rate.json" if a.fields else "receiver_group_rate.json")
+                             "receiver_group_fields_rate.json" if a.fields else
+                             "receiver_group_wire_rate.json" if a.wire else "receiver_group_rate.json")
     import __graft_entry__ as g
     pkg = g.load_package()
     import torch
     capi, siggen = pkg.capi, pkg.siggen
-    base = siggen.generate(siggen.make_cfg(seed=17, msgs_per_sec=3000, n_aircraft=60, ac_per_sec=2000 if a.modeac or a.fields else 0),
+    base = siggen.generate(siggen.make_cfg(seed=17, msgs_per_sec=3000, n_aircraft=60, ac_per_sec=2000 if a.modeac or a.fields or a.wire else 0),
                            64 * CHUNK)
     ks = [a.only] if a.only else [1, 16, 256, 1024]
     kmax = max(ks)
@@ -75,6 +87,8 @@ def main():
         return modeac(a, capi, dev, host)
     if a.fields:
         return fields(a, capi, dev, host)
+    if a.wire:
+        return wire(a, capi, dev, host)
     res = {"buffer_samples": CHUNK, "format": "uc8", "reps": a.reps, "group": {}}
     for k in ks:
         grp = capi.ReceiverGroup(k, fmt=capi.FMT_UC8)
@@ -160,6 +174,109 @@ def fields(a, capi, dev, host):
                      "through msd_group_submit_* and msd_group_submit_*_fields; no sink in either (deliver=False)",
            "calls": {}}
     alternate(a, k, groups, dev, host, res, modeac=True, fields_of=("fields",))
+
+
+WIRE_SINKS_C = r"""
+#include <stddef.h>
+#include <stdint.h>
+size_t msd_beast_frame_out(const void *mm, int net_verbatim, uint8_t *out);
+struct state { uint8_t *buf; size_t used, cap; uint64_t messages, calls; };
+void count_sink(uint32_t receiver, const void *mm, void *user)
+{
+    struct state *s = user;
+    (void)receiver; (void)mm;
+    s->calls++;
+}
+void beast_sink(uint32_t receiver, const void *mm, void *user)
+{
+    struct state *s = user;
+    (void)receiver;
+    s->calls++;
+    if (s->used + 44 <= s->cap) {
+        const size_t n = msd_beast_frame_out(mm, 0, s->buf + s->used);
+        s->used += n;
+        s->messages += n != 0;
+    }
+}
+void wire_sink(uint32_t receiver, const uint8_t *bytes, size_t nbytes, uint32_t nmessages, void *user)
+{
+    struct state *s = user;
+    (void)receiver; (void)bytes;
+    s->calls++;
+    s->used += nbytes;
+    s->messages += nmessages;
+}
+"""
+
+
+def wire(a, capi, dev, host):
+    import ctypes as C
+    import subprocess
+    import tempfile
+    k = 1024
+    libdir = os.path.dirname(capi.LIB_PATH)
+    tmp = tempfile.mkdtemp()
+    with open(os.path.join(tmp, "sinks.c"), "w") as f:
+        f.write(WIRE_SINKS_C)
+    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-o", os.path.join(tmp, "sinks.so"), os.path.join(tmp, "sinks.c"),
+                           "-L" + libdir, "-lmsd_host", "-Wl,-rpath," + libdir])
+    sinks = C.CDLL(os.path.join(tmp, "sinks.so"))
+
+    class State(C.Structure):
+        _fields_ = [("buf", C.c_void_p), ("used", C.c_size_t), ("cap", C.c_size_t), ("messages", C.c_uint64),
+                    ("calls", C.c_uint64)]
+
+    out = np.zeros(64 << 20, dtype=np.uint8)
+    L = capi._group_lib()
+    groups = {name: capi.ReceiverGroup(k, fmt=capi.FMT_UC8) for name in ("plain", "plain_host_beast", "wire")}
+    for grp in groups.values():
+        for r in range(0, k, 2):
+            grp.set_receiver_mode_ac(r, 1)
+    entries = (capi.GroupEntry * k)(*[capi.GroupEntry(r, 0, 0) for r in range(k)])
+    fn = {n: C.cast(getattr(sinks, n), C.c_void_p) for n in ("count_sink", "beast_sink", "wire_sink")}
+    last = {}
+
+    def call(name, where):
+        st = State(out.ctypes.data, 0, out.size, 0, 0)
+        iq = C.c_void_p(dev.data_ptr()) if where == "device" else host.ctypes.data
+        h = groups[name]._h
+        if name == "wire":
+            f = L.msd_group_submit_device_wire if where == "device" else L.msd_group_submit_host_wire
+            rc = f(h, iq, entries, k, capi.WIRE_BEAST, 0, fn["wire_sink"], C.byref(st))
+        else:
+            f = L.msd_group_submit_device if where == "device" else L.msd_group_submit_host
+            rc = f(h, iq, entries, k, fn["count_sink" if name == "plain" else "beast_sink"], C.byref(st))
+        if rc:
+            raise RuntimeError(f"{name}: {rc}")
+        last[name] = {"sink_calls": st.calls, "bytes": st.used, "messages": st.messages}
+
+    res = {"buffer_samples": CHUNK, "format": "uc8", "receivers": k, "reps": a.reps,
+           "capture": "siggen seed 17, 3000 Mode S and 2000 Mode A/C replies a second; Mode A/C on for even receivers",
+           "calls_timed": "plain: msd_group_submit_* with a sink that counts; plain_host_beast: the same with a sink that runs "
+                          "msd_beast_frame_out into one array; wire: msd_group_submit_*_wire (Beast) with a sink that adds up "
+                          "the sizes (it does not copy the bytes)", "calls": {}}
+    for where in ("device", "host"):
+        ts = {name: [] for name in groups}
+        for name in groups:
+            call(name, where)  # warm-up
+        for _ in range(a.reps):  # alternating, so that drift of the box falls on all alike
+            for name in groups:
+                t0 = time.perf_counter()
+                call(name, where)
+                ts[name].append(time.perf_counter() - t0)
+        for name, v in ts.items():
+            t = float(np.median(v))
+            res["calls"].setdefault(name, {})[where] = {
+                "call_ms_median": t * 1e3, "call_ms_min": min(v) * 1e3, "call_ms_max": max(v) * 1e3,
+                "call_ms_all": [x * 1e3 for x in v], "receivers_real_time": k * (CHUNK / 2.4e6) / t, "last_call": last[name]}
+        print(where, json.dumps({n: round(res["calls"][n][where]["call_ms_median"], 3) for n in groups}), flush=True)
+    for name, grp in groups.items():
+        t = grp.timing()
+        res["calls"][name]["timing"] = {x: t[x] for x in ("hits", "tries", "reruns", "resolve_passes", "resolve_fallback")}
+        grp.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
 
 
 def alternate(a, k, groups, dev, host, res, modeac=False, fields_of=()):
