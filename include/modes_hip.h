@@ -612,7 +612,7 @@ int msd_group_submit_device_wire(msd_group *g, const void *d_iq, const msd_group
                                  uint32_t flags, msd_group_wire_fn sink, void *user);
 int msd_group_submit_host_wire(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n, int format,
                                uint32_t flags, msd_group_wire_fn sink, void *user);
-int msd_group_reset_receiver(msd_group *g, uint32_t receiver); /* filter, clock, counters, tail */
+int msd_group_reset_receiver(msd_group *g, uint32_t receiver); /* filter, clock, counters, tail; its Beast framing state */
 int msd_group_get_stats(const msd_group *g, uint32_t receiver, msd_stats *st);
 int msd_group_set_preamble_threshold(msd_group *g, int threshold); /* group-wide: sets every receiver's threshold */
 /* of the most recent call: hits, tries, resolve_passes (1: the GPU resolve ran; 0: all on the host); since creation:
@@ -648,6 +648,53 @@ int msd_group_get_receiver_options(const msd_group *g, uint32_t receiver, msd_gr
  * the group's state untouched. */
 int msd_group_set_receiver_mode_ac(msd_group *g, uint32_t receiver, int on);
 int msd_group_get_receiver_mode_ac(const msd_group *g, uint32_t receiver, int *on);
+
+/* Beast input per receiver: one call takes a piece of the Beast byte stream of each of any subset of
+ * the group's receivers -- remote feeders next to the group's own SDRs -- and decides them on the GPU in a number of
+ * launches and host synchronisations that does not depend on n.  For every receiver the results are exactly those of a
+ * context of its own, given that receiver's options, fed the same bytes by msd_accept_beast in the same calls with the
+ * same now_ms: the records, every msd_remote_stats counter except the diagnostic tile_rewalks, and the filter
+ * afterwards.  The divergence noted there applies unchanged (a '2' frame whose DF implies 112 bits is bad).
+ *
+ * Per receiver: its own kept incomplete frame and pending gap, carried from call to call -- bytes of one entry never
+ * complete, start or charge a frame of another; its own repair level (msd_group_set_receiver_options) and Mode A/C
+ * switch (type '1' frames are delivered as Mode A/C records when it is on and only counted when it is off, as
+ * msd_config.mode_ac decides for a context); and its ICAO filter, the one its IQ buffers read and write, so that
+ * addresses learnt from either source make the other's address/parity replies acceptable for this receiver and for no
+ * other.  Within the call every frame sees the adds of the frames before it in its own entry; after the entry,
+ * icaoFilterExpire(now_ms) on that receiver.  The adds and the flip reach the host copy of the filter and, in a group
+ * that resolves on the GPU, the resident device snapshot, so the next msd_group_submit_* sees them without an upload;
+ * a MSD_CFG_HOST_RESOLVE group keeps no snapshots on the device, and the call uploads those of its own receivers.  A
+ * Beast entry is history for the repair-level rule (msd_group_set_receiver_options to another level is -EBUSY
+ * afterwards).  msd_group_reset_receiver also clears the receiver's remote counters, kept frame and pending gap.
+ *
+ * entry i's bytes are bytes[offset .. offset + nbytes), device memory (on_device = 1; it must stay valid until the call
+ * returns) or host memory (copied in).  An entry with nbytes = 0 runs only the receiver's icaoFilterExpire.  Delivery:
+ * before the call returns, by entry in the order of the call's entries, then in stream order within an entry;
+ * sysTimestampMsg is the entry's now_ms, the other fields are as msd_accept_beast sets them.
+ * -EINVAL, with the group's state untouched: a receiver out of range, the same receiver twice in one call,
+ * n > max_receivers, nonzero flags or reserved, nbytes > MSD_GROUP_BEAST_ENTRY_MAX, an offset above
+ * MSD_GROUP_BEAST_OFFSET_MAX, NULL bytes or entries with n > 0.  n == 0 returns 0.  A call that fails after its kernels
+ * were queued (-EIO, or -ENOMEM for its scratch) leaves the group accepting msd_group_destroy only.
+ * Memory: nothing until the first call.  Then 170 bytes of host memory per receiver of the group; and, grown to the
+ * largest piece seen (a call is cut into pieces of whole entries of at most 8 MiB of new bytes), about 40 bytes of
+ * device memory per byte of a piece, where every entry counts rounded up to a multiple of 4096 bytes (1024 entries of
+ * 4 KiB behind a kept frame: 8 MiB, about 330 MB), about 400 bytes of device and of page-locked host memory per entry,
+ * 56 bytes of page-locked memory per delivered message, for host input the piece's bytes once more on each side, and
+ * in a MSD_CFG_HOST_RESOLVE group 65.6 KB on each side per entry. */
+#define MSD_GROUP_BEAST_ENTRY_MAX (1u << 20)
+#define MSD_GROUP_BEAST_OFFSET_MAX ((uint64_t)1 << 47)
+typedef struct msd_group_beast_entry {
+    uint32_t receiver;  /* 0 .. max_receivers-1 */
+    uint32_t flags;     /* reserved, 0 */
+    uint64_t offset;    /* of this entry's bytes in `bytes` */
+    uint32_t nbytes;    /* may be 0; at most MSD_GROUP_BEAST_ENTRY_MAX */
+    uint32_t reserved;  /* 0 */
+    uint64_t now_ms;    /* mstime() for this receiver: sysTimestampMsg of its records, then icaoFilterExpire */
+} msd_group_beast_entry;
+int msd_group_accept_beast(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
+                           msd_group_message_fn sink, void *user);
+int msd_group_get_remote_stats(const msd_group *g, uint32_t receiver, msd_remote_stats *st);
 
 #ifdef __cplusplus
 }

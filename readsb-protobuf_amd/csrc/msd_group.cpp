@@ -16,6 +16,7 @@
 
 #include "msd_ctx.h" /* the context, and with it modes_hip.h, msd_internal.h and msd_kernels.h */
 #include "host/msd_wire.h" /* the host writers, for the entries resolved on host threads */
+#include "msd_group_beast.h" /* Beast input per receiver: msd_group_accept_beast */
 
 using namespace msd_impl;
 
@@ -98,6 +99,8 @@ struct msd_group {
     size_t wire_cap = 0;
     uint32_t *h_wire_entries = nullptr; /* pinned [max_receivers][4]: offset, bytes, messages, 0 per buffer */
     uint32_t *d_wire_counts = nullptr;  /* [max_receivers][2]: bytes and messages per buffer, between the two kernels */
+    void *beast = nullptr; /* Beast input (msd_group_beast.cpp): scratch and the receivers' framing state, made by the
+                              first msd_group_accept_beast */
     char err[256] = {0};
 };
 
@@ -821,6 +824,7 @@ void msd_group_destroy(msd_group *g)
     (void)hipHostFree(g->h_wire_out);
     (void)hipHostFree(g->h_wire_entries);
     (void)hipFree(g->d_wire_counts);
+    msd_gb_free(g->beast);
     msd_destroy(g->ctx);
     delete g;
 }
@@ -899,6 +903,7 @@ int msd_group_reset_receiver(msd_group *g, uint32_t receiver)
     if (g->ctx->failed)
         return gfail(g, -EIO, "an earlier call failed");
     group_receiver_reset(g->rx[receiver]);
+    msd_gb_reset_receiver(g->beast, receiver); /* its remote counters, kept frame and pending gap */
     const int rc = group_upload_snapshot(g, receiver);
     if (rc)
         g->ctx->failed = true;
@@ -985,6 +990,69 @@ int msd_group_get_timing(const msd_group *g, msd_timing *t)
     if (!g)
         return -EINVAL;
     return msd_get_timing(g->ctx, t);
+}
+
+/* Beast input per receiver: the checks that leave the group untouched, each entry's receiver options, then the call
+ * (msd_group_beast.cpp) */
+int msd_group_accept_beast(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
+                           msd_group_message_fn sink, void *user)
+{
+    if (!g)
+        return -EINVAL;
+    msd_ctx *c = g->ctx;
+    if (n > g->max_receivers)
+        return gfail(g, -EINVAL, "Beast entries: more than max_receivers");
+    if (n && (!e || !bytes))
+        return gfail(g, -EINVAL, "Beast entries: NULL bytes or entries");
+    std::vector<bool> seen(g->max_receivers, false);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (e[i].receiver >= g->max_receivers || seen[e[i].receiver] || e[i].flags || e[i].reserved)
+            return gfail(g, -EINVAL, "Beast entry %u: a receiver out of range or given twice, or nonzero flags or reserved", i);
+        if (e[i].nbytes > MSD_GROUP_BEAST_ENTRY_MAX || e[i].offset > MSD_GROUP_BEAST_OFFSET_MAX)
+            return gfail(g, -EINVAL, "Beast entry %u: more than %u bytes, or an offset above 2^47", i, MSD_GROUP_BEAST_ENTRY_MAX);
+        seen[e[i].receiver] = true;
+    }
+    if (c->failed)
+        return gfail(g, -EIO, "an earlier call failed");
+    if (n == 0)
+        return 0;
+    msd_frames_view fv;
+    int rc = msd_frames_get_view(c, &fv); /* the CRC and repair tables of the group's context */
+    if (rc)
+        return gfail(g, rc, "Beast input: no tables");
+    msd_gb_view v{};
+    v.stream = fv.stream;
+    v.device = fv.device;
+    v.max_receivers = g->max_receivers;
+    v.tables = fv.tables;
+    v.d_snaps = g->gpu ? g->d_snaps : nullptr;
+    v.state = &g->beast;
+    v.err = g->err;
+    v.errlen = sizeof g->err;
+    std::vector<msd_gb_input> in(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        GroupReceiver &r = g->rx[e[i].receiver];
+        in[i].receiver = e[i].receiver;
+        in[i].nbytes = e[i].nbytes;
+        in[i].offset = e[i].offset;
+        in[i].now_ms = e[i].now_ms;
+        in[i].filter = &r.resolver.filter;
+        in[i].nfix = r.opt.nfix_crc;
+        in[i].mode_ac = r.mode_ac ? 1 : 0;
+        r.history = true; /* the repair level is fixed from here on, as by a buffer */
+    }
+    rc = msd_gb_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, user);
+    if (rc)
+        c->failed = true;
+    return rc;
+}
+
+int msd_group_get_remote_stats(const msd_group *g, uint32_t receiver, msd_remote_stats *st)
+{
+    if (!g || !st || receiver >= g->max_receivers)
+        return -EINVAL;
+    msd_gb_get_stats(g->beast, receiver, st);
+    return 0;
 }
 
 } /* extern "C" */
