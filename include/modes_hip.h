@@ -506,6 +506,45 @@ int msd_accept_frames(msd_ctx *ctx, const msd_message *frames, size_t n, int on_
                       msd_message_fn sink, void *user);
 int msd_get_remote_stats(const msd_ctx *ctx, msd_remote_stats *st);
 
+/* ---- AVR raw text input (--net-ri-port: serviceInit(..., READ_MODE_ASCII, "\n", decodeHexMessage), net_io.c:501), a
+ * byte stream cut into lines and parsed into records on the GPU.
+ *   Lines.  The stream is cut at every '\n' (0x0A); a line is the bytes between two cuts.  The bytes behind the last
+ *   '\n' of a call are an incomplete line: they are kept and completed by the next call, so the results do not depend
+ *   on how a stream is cut into calls.
+ *   Long lines.  A line of more than MSD_AVR_LINE_MAX bytes, the '\n' not counted, is dropped whole and counted in
+ *   long_lines, whatever it holds; what is carried between calls is therefore at most MSD_AVR_LINE_MAX kept bytes, or
+ *   the flag "inside an overlong line: discard up to and including the next '\n'".  Divergence: the reference accepts
+ *   a message behind any amount of white space that fits its 64 KiB client buffer and drops the whole buffer when it
+ *   fills without a separator (net_io.c:2448-2455); a valid line is at most 44 characters plus white space.
+ *   Every other line is decided by msd_avr_parse_line(line + '\0', msd_config.mode_ac, keep_timestamp, &rec)
+ *   (libmsd_host.so), bit for bit: white space is space and 0x09..0x0D; the prefixes are * : @ % <; the payload is 4
+ *   (with mode_ac), 14 or 28 hex digits in front of a ';' that ends the text; signalLevel of a '<' line is
+ *   (((hi << 4) | lo) / 255)^2 with hi, lo = -1 for a non-hex digit, whatever the digits are; a non-hex timestamp digit
+ *   gives timestamp 0.  Dropped (dropped_lines): an empty or white-space-only line, no ';', an unknown prefix, a wrong
+ *   length, a non-hex payload digit, a Mode A/C length with mode_ac off.  A NUL byte ends the line's text as strlen
+ *   does; the rest up to the '\n' is ignored.  Divergences: the reference's strstr stalls on a NUL, it reads hex[-1]
+ *   on an empty line and past the end of a too-short prefixed line.
+ *   timestampMsg is the line's 12 digits with MSD_AVR_KEEP_TIMESTAMP and 0 without, as in the reference
+ *   (net_io.c:1698-1703).
+ * The records of a call are then decided in stream order exactly as one msd_accept_frames call over them decides them
+ * (filter, adds-before-tests order, msd_remote_stats, sysTimestampMsg = now_ms, the 56-bit divergence above), followed
+ * by one icaoFilterExpire(now_ms) per call -- also when n == 0 or no line was completed.
+ * bytes: device (on_device = 1) or host memory as msd_accept_beast takes them.  -EINVAL: an unknown flag bit, NULL.
+ * -EBUSY while msd_launch_* batches are outstanding.  msd_reset also clears the kept bytes, the discard flag and
+ * msd_avr_stats.  Device memory: a piece of at most 8 MiB is staged (host input), with 4 bytes per 4096 of them for the
+ * framing and 56 + about 30 bytes per record the piece yields. ---- */
+#define MSD_AVR_LINE_MAX 256u
+#define MSD_AVR_KEEP_TIMESTAMP 1u
+typedef struct msd_avr_stats {
+    uint64_t lines;         /* complete lines seen = frames + dropped_lines + long_lines */
+    uint64_t frames;        /* lines that became a record and were handed to decoding */
+    uint64_t dropped_lines; /* lines of at most MSD_AVR_LINE_MAX bytes that msd_avr_parse_line refuses */
+    uint64_t long_lines;    /* lines of more than MSD_AVR_LINE_MAX bytes */
+} msd_avr_stats;
+int msd_accept_avr(msd_ctx *ctx, const void *bytes, size_t n, int on_device, uint32_t flags, uint64_t now_ms,
+                   msd_message_fn sink, void *user);
+int msd_get_avr_stats(const msd_ctx *ctx, msd_avr_stats *st);
+
 /* ---- wire output: accepted messages as the bytes readsb sends on -- Beast frames (modesSendBeastOutput,
  * net_io.c:769-835) or AVR raw lines (modesSendRawOutput, net_io.c:870-896) -- written on the GPU.
  *   MSD_WIRE_BEAST     0x1A, type '1' / '2' / '3' for 2 / 7 / 14 bytes, the low 48 bits of timestampMsg big-endian, the

@@ -111,6 +111,8 @@ def layout_from_environment():
 INVALID_ALTITUDE = -9999
 WIRE_BEAST, WIRE_AVR, WIRE_AVR_MLAT = 0, 1, 2  # msd_wire_encode / msd_group_submit_*_wire formats
 WIRE_VERBATIM = 1  # --net-verbatim
+AVR_LINE_MAX = 256  # MSD_AVR_LINE_MAX
+AVR_KEEP_TIMESTAMP = 1  # MSD_AVR_KEEP_TIMESTAMP
 BEAST_MAX = 44  # most bytes one message takes in any of the formats
 
 
@@ -202,6 +204,14 @@ class RemoteStats(C.Structure):
         return out
 
 
+class AvrStats(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("frames", C.c_uint64), ("dropped_lines", C.c_uint64),
+                ("long_lines", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class _SinkState(C.Structure):
     _fields_ = [("out", C.c_void_p), ("cap", C.c_size_t), ("count", C.c_size_t)]
 
@@ -218,7 +228,7 @@ EXPORTS = [
     "msd_note_dropped", "msd_set_preamble_threshold", "msd_set_timing_interval", "msd_restart", "msd_decode_fields_device",
     "msd_arena_permille", "msd_host_register", "msd_host_unregister", "msd_demodulate_magbufs",
     "msd_convert_begin", "msd_convert_end", "msd_thread_attach", "msd_dc_filter_status",
-    "msd_accept_beast", "msd_accept_frames", "msd_get_remote_stats",
+    "msd_accept_beast", "msd_accept_frames", "msd_get_remote_stats", "msd_accept_avr", "msd_get_avr_stats",
     "msd_group_create", "msd_group_destroy", "msd_group_last_error", "msd_group_submit_device", "msd_group_submit_host",
     "msd_group_reset_receiver", "msd_group_get_stats", "msd_group_set_preamble_threshold", "msd_group_get_timing",
     "msd_group_set_receiver_options", "msd_group_get_receiver_options",
@@ -310,6 +320,11 @@ def lib():
                                       C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
         L.msd_get_remote_stats.restype = C.c_int
         L.msd_get_remote_stats.argtypes = [C.c_void_p, C.POINTER(RemoteStats)]
+        L.msd_accept_avr.restype = C.c_int
+        L.msd_accept_avr.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint64, C.c_void_p,
+                                     C.c_void_p]
+        L.msd_get_avr_stats.restype = C.c_int
+        L.msd_get_avr_stats.argtypes = [C.c_void_p, C.POINTER(AvrStats)]
         _lib = L
     return _lib
 
@@ -524,6 +539,26 @@ class Demodulator:
         records = np.ascontiguousarray(records, dtype=MESSAGE_DTYPE)
         return self._run(lambda fn, st: lib().msd_accept_frames(self._h, records.ctypes.data, records.size, 0, now_ms,
                                                                 fn, st))
+
+    def accept_avr(self, data, now_ms, keep_timestamp=False):
+        """msd_accept_avr: the messages readsb accepts from these bytes of an AVR raw text stream ("*hex;" lines cut at
+        '\\n'; an incomplete line is kept for the next call).  `data`: bytes, a numpy array, or a torch tensor on the
+        GPU (read in place through its device pointer).  keep_timestamp: MSD_AVR_KEEP_TIMESTAMP."""
+        flags = AVR_KEEP_TIMESTAMP if keep_timestamp else 0
+        if hasattr(data, "data_ptr") and getattr(data, "is_cuda", False):
+            if not data.is_contiguous():
+                raise ValueError("accept_avr needs a contiguous tensor")
+            ptr, n = data.data_ptr(), data.numel() * data.element_size()
+            return self._run(lambda fn, st: lib().msd_accept_avr(self._h, C.c_void_p(ptr), n, 1, flags, now_ms, fn, st))
+        arr = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        return self._run(lambda fn, st: lib().msd_accept_avr(self._h, arr.ctypes.data, arr.size, 0, flags, now_ms, fn,
+                                                             st))
+
+    def avr_stats(self):
+        st = AvrStats()
+        self._check(lib().msd_get_avr_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def encode_wire(self, messages, format, verbatim=False, on_device=False):
         """msd_wire_encode: the records as one stream of Beast frames (WIRE_BEAST) or AVR lines (WIRE_AVR,

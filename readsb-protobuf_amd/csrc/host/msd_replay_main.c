@@ -13,6 +13,10 @@
  * (default 65536) and each piece goes through msd_accept_beast (decodeBinMessage behind the READ_MODE_BEAST scanner,
  * net_io.c:1486-1627,2504-2569) with mstime() = --now-ms (default 0); the same outputs, and --stats prints the remote
  * counters (stats.h remote_*).
+ *
+ * `--avr-in F` does the same for an AVR raw text stream (the --net-ri-port input, "*hex;" lines): pieces of --avr-chunk
+ * bytes (default 65536) through msd_accept_avr; --mlat also keeps the lines' timestamps (MSD_AVR_KEEP_TIMESTAMP), and
+ * --stats adds the four line counters.
  */
 #define _GNU_SOURCE
 #include <inttypes.h>
@@ -74,9 +78,12 @@ static void write_beast(const msd_message *mm, void *user)
 enum { OptIfileName = 615, OptIfileFormat, OptIfileThrottle, OptIfilePath };
 static volatile int g_exit; /* Modes.exit */
 
-/* --beast-in: a Beast stream through msd_accept_beast on a context of its own */
-static int run_beast_in(const char *path, size_t chunk, uint64_t now_ms, const msd_receiver_options *rx, int want_stats)
+/* --beast-in / --avr-in: a Beast stream through msd_accept_beast, or AVR text through msd_accept_avr, on a context of
+ * its own */
+static int run_remote_in(const char *path, int avr, size_t chunk, uint64_t now_ms, const msd_receiver_options *rx,
+                         int want_stats)
 {
+    const char *entry = avr ? "msd_accept_avr" : "msd_accept_beast";
     FILE *f = fopen(path, "rb");
     if (!f) {
         fprintf(stderr, "cannot open %s\n", path);
@@ -105,9 +112,10 @@ static int run_beast_in(const char *path, size_t chunk, uint64_t now_ms, const m
     }
     size_t got;
     while ((got = fread(buf, 1, chunk, f)) > 0) {
-        rc = msd_accept_beast(ctx, buf, got, 0, now_ms, rx->sink, rx->sink_user);
+        rc = avr ? msd_accept_avr(ctx, buf, got, 0, g_mlat ? MSD_AVR_KEEP_TIMESTAMP : 0u, now_ms, rx->sink, rx->sink_user)
+                 : msd_accept_beast(ctx, buf, got, 0, now_ms, rx->sink, rx->sink_user);
         if (rc) {
-            fprintf(stderr, "msd_accept_beast: %s (%d)\n", msd_last_error(ctx), rc);
+            fprintf(stderr, "%s: %s (%d)\n", entry, msd_last_error(ctx), rc);
             break;
         }
     }
@@ -128,6 +136,11 @@ static int run_beast_in(const char *path, size_t chunk, uint64_t now_ms, const m
                     g_count, st.remote_received_modes, st.remote_received_modeac, st.remote_rejected_bad,
                     st.remote_rejected_unknown_icao, st.remote_accepted[0], st.remote_accepted[1], st.remote_accepted[2],
                     st.frames, st.other_frames, st.garbage_bytes);
+        msd_avr_stats as;
+        if (avr && msd_get_avr_stats(ctx, &as) == 0)
+            fprintf(stderr, "avr_lines %" PRIu64 "\navr_frames %" PRIu64 "\navr_dropped_lines %" PRIu64
+                            "\navr_long_lines %" PRIu64 "\n",
+                    as.lines, as.frames, as.dropped_lines, as.long_lines);
     }
     msd_destroy(ctx);
     return rc ? 1 : 0;
@@ -145,8 +158,8 @@ int main(int argc, char **argv)
     rx.sink = print_raw;
     rx.sink_user = stdout;
     int want_stats = 0, want_timing = 0;
-    const char *beast_in = NULL;
-    size_t beast_chunk = 65536;
+    const char *beast_in = NULL, *avr_in = NULL;
+    size_t beast_chunk = 65536, avr_chunk = 65536;
     uint64_t now_ms = 0;
 
     const msd_ifile_hooks hooks = {host_should_exit, NULL, host_at_eof, NULL};
@@ -173,6 +186,8 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--stats")) want_stats = 1;
         else if (!strcmp(a, "--beast-in") && next) { beast_in = next; ++i; }
         else if (!strcmp(a, "--beast-chunk") && next && strtoull(next, NULL, 10) > 0) { beast_chunk = (size_t)strtoull(next, NULL, 10); ++i; }
+        else if (!strcmp(a, "--avr-in") && next) { avr_in = next; ++i; }
+        else if (!strcmp(a, "--avr-chunk") && next && strtoull(next, NULL, 10) > 0) { avr_chunk = (size_t)strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--now-ms") && next) { now_ms = strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--timing")) want_timing = 1; /* one JSON line on stderr: what the run cost (msd_ifileGetTiming) */
         else if (!strcmp(a, "--no-output")) rx.sink = count_only;
@@ -192,12 +207,16 @@ int main(int argc, char **argv)
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
                             "[--device N] [--sc16q11-table-bits N]\n"
                             "       msd_replay --beast-in F [--beast-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
+                            "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n"
+                            "       msd_replay --avr-in F [--avr-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
                             "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n");
             return 2;
         }
     }
+    if (avr_in)
+        return run_remote_in(avr_in, 1, avr_chunk, now_ms, &rx, want_stats);
     if (beast_in)
-        return run_beast_in(beast_in, beast_chunk, now_ms, &rx, want_stats);
+        return run_remote_in(beast_in, 0, beast_chunk, now_ms, &rx, want_stats);
     msd_ifileSetReceiver(&rx);
     if (!msd_ifileOpen()) {
         fprintf(stderr, "%s\n", msd_ifileLastError());

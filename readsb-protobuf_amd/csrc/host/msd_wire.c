@@ -327,7 +327,7 @@ int msd_avr_parse_line(const char *line, int mode_ac, int keep_timestamp, msd_me
         }
         if (skip == 15) {
             const int hi = hexval(hex[13]), lo = hexval(hex[14]);
-            level = (double)((hi << 4) | lo) / 255.0; /* net_io.c:1690-1691, whatever the digits are */
+            level = (double)((hi * 16) | lo) / 255.0; /* net_io.c:1690-1691, whatever the digits are (-1: none) */
             level *= level;
         }
     }
@@ -346,4 +346,50 @@ int msd_avr_parse_line(const char *line, int mode_ac, int keep_timestamp, msd_me
     }
     wire_message(out, bytes, (int)(l / 2), keep_timestamp ? ts : 0, level);
     return 1;
+}
+
+void msd_avr_reader_init(msd_avr_reader *r, int mode_ac, int keep_timestamp)
+{
+    r->len = 0;
+    r->discard = 0;
+    r->mode_ac = mode_ac;
+    r->keep_timestamp = keep_timestamp;
+    r->lines = r->frames = r->dropped_lines = r->long_lines = 0;
+}
+
+size_t msd_avr_reader_feed(msd_avr_reader *r, const uint8_t *data, size_t n, msd_message_fn fn, void *user)
+{
+    size_t delivered = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint8_t ch = data[i];
+        if (ch != '\n') {
+            if (r->discard)
+                continue;
+            if (r->len == MSD_AVR_LINE_MAX) { /* the line has outgrown the bound: nothing of it is kept */
+                r->discard = 1;
+                r->len = 0;
+                continue;
+            }
+            r->buf[r->len++] = ch;
+            continue;
+        }
+        ++r->lines;
+        if (r->discard) {
+            r->discard = 0;
+            ++r->long_lines;
+            continue;
+        }
+        r->buf[r->len] = 0;
+        r->len = 0;
+        msd_message mm;
+        if (msd_avr_parse_line((const char *)r->buf, r->mode_ac, r->keep_timestamp, &mm)) {
+            ++r->frames;
+            ++delivered;
+            if (fn)
+                fn(&mm, user);
+        } else {
+            ++r->dropped_lines;
+        }
+    }
+    return delivered;
 }

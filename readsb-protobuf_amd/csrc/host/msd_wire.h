@@ -68,6 +68,24 @@ size_t msd_beast_reader_feed(msd_beast_reader *r, const uint8_t *data, size_t n,
  * out->timestampMsg for the caller that wants it (`keep_timestamp`). */
 int msd_avr_parse_line(const char *line, int mode_ac, int keep_timestamp, msd_message *out);
 
+/* An AVR text stream (--net-ri-port), the host twin of msd_accept_avr (modes_hip.h has the rules): cut at every '\n',
+ * the incomplete line kept between calls, a line of more than MSD_AVR_LINE_MAX bytes dropped whole (long_lines), every
+ * other line decided by msd_avr_parse_line on its text up to the first NUL. */
+typedef struct msd_avr_reader {
+    uint8_t buf[MSD_AVR_LINE_MAX + 1]; /* the incomplete line, and room for the NUL */
+    size_t len;
+    int discard;                       /* inside an overlong line: skip up to and including the next '\n' */
+    int mode_ac, keep_timestamp;
+    uint64_t lines;         /* complete lines = frames + dropped_lines + long_lines */
+    uint64_t frames;        /* records delivered */
+    uint64_t dropped_lines; /* lines msd_avr_parse_line refuses */
+    uint64_t long_lines;
+} msd_avr_reader;
+void msd_avr_reader_init(msd_avr_reader *r, int mode_ac, int keep_timestamp);
+/* Appends n bytes of the stream; the record of every complete line that has one goes to fn in order.  Returns the
+ * records delivered by this call. */
+size_t msd_avr_reader_feed(msd_avr_reader *r, const uint8_t *data, size_t n, msd_message_fn fn, void *user);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
 /*
- * msd_frames.cpp -- host side of the Beast / AVR input (msd_accept_beast, msd_accept_frames, msd_get_remote_stats):
- * pieces, device scratch, the three launches of msd_frames_kernels.hip per piece, and what stays on the host -- the
- * kept incomplete frame, the pending gap, the context's ICAO filter (the device inserts a piece's new addresses into a
- * copy; the same inserts are repeated here, in the same order) and the counters.  DESIGN.md 4.8.
+ * msd_frames.cpp -- host side of the Beast / AVR input (msd_accept_beast, msd_accept_frames, msd_accept_avr,
+ * msd_get_remote_stats, msd_get_avr_stats): pieces, device scratch, the three launches of msd_frames_kernels.hip per
+ * piece (AVR text: the framing launches of msd_avr_kernels.hip in front of the records path's), and what stays on the
+ * host -- the kept incomplete frame or line, the pending gap, the context's ICAO filter (the device inserts a piece's
+ * new addresses into a copy; the same inserts are repeated here, in the same order) and the counters.  DESIGN.md 4.8.
  */
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "modes_hip.h"
+#include "msd_avr.h"
 #include "msd_frames.h"
 #include "msd_internal.h"
 
@@ -37,6 +39,12 @@ struct State {
     uint32_t *h_snap = nullptr;
     std::vector<msd_message> recs;
     std::vector<uint32_t> newaddr_h;
+    /* msd_accept_avr: the incomplete line, or the flag that an overlong one is being discarded */
+    uint8_t avr_tail[MSD_AVR_LINE_MAX];
+    uint32_t avr_tl = 0;
+    int avr_discard = 0;
+    msd_avr_stats as{};
+    Buf avr_tailbuf, avr_wg, avr_rec;
 };
 
 int fail(const msd_frames_view &v, int code, const char *fmt, ...)
@@ -178,6 +186,27 @@ int prepare_hash(const msd_frames_view &v, State &s, uint32_t nadds, hipStream_t
     return 0;
 }
 
+/* decode, filter and finish n records in device memory: what both msd_accept_frames and msd_accept_avr do to a piece */
+int finish_piece(const msd_frames_view &v, State &s, hipStream_t st, msd_message_fn sink, void *user);
+int decide_records(const msd_frames_view &v, State &s, const msd_message *d_in, uint32_t n, uint64_t now_ms,
+                   hipStream_t st, msd_message_fn sink, void *user)
+{
+    int rc;
+    if ((rc = upload_filter(v, s, st)))
+        return rc;
+    msd_fr_scratch x = scratch(s);
+    if ((rc = msd_fr_launch_records_decode(d_in, n, &v.tables, &x, st)))
+        return fail(v, rc, "decode kernel failed to launch");
+    if ((rc = read_ctr(v, s, st)))
+        return rc;
+    const uint32_t nadds = (uint32_t)s.h_ctr[MSD_FR_CTR_ADDS];
+    if (nadds && (rc = prepare_hash(v, s, nadds, st, x)))
+        return rc;
+    if ((rc = msd_fr_launch_records_filter(d_in, n, nadds, now_ms, &v.tables, &x, st)))
+        return fail(v, rc, "filter kernels failed to launch");
+    return finish_piece(v, s, st, sink, user);
+}
+
 /* after stage 3: records and new addresses to the host; the filter, the counters, the sink */
 int finish_piece(const msd_frames_view &v, State &s, hipStream_t st, msd_message_fn sink, void *user)
 {
@@ -237,7 +266,7 @@ void msd_frames_free(void *state)
         return;
     Buf *all[] = {&s->stage, &s->tailbuf, &s->succ, &s->info, &s->mark, &s->first, &s->exitl, &s->entry, &s->good,
                   &s->cnt, &s->nodes, &s->cls, &s->addr, &s->flags, &s->scan_tmp, &s->newlist, &s->newaddr, &s->hash,
-                  &s->out, &s->snap, &s->in, &s->ctr};
+                  &s->out, &s->snap, &s->in, &s->ctr, &s->avr_tailbuf, &s->avr_wg, &s->avr_rec};
     for (Buf *b : all)
         (void)hipFree(b->p);
     if (s->h_ctr)
@@ -255,6 +284,9 @@ void msd_frames_reset(void *state)
     s->tl = 0;
     s->pending_gap = 0;
     memset(&s->rs, 0, sizeof s->rs);
+    s->avr_tl = 0;
+    s->avr_discard = 0;
+    memset(&s->as, 0, sizeof s->as);
 }
 
 int msd_get_remote_stats(const msd_ctx *ctx, msd_remote_stats *st)
@@ -369,20 +401,106 @@ int msd_accept_frames(msd_ctx *ctx, const msd_message *frames, size_t n, int on_
             HCK(v, hipMemcpyAsync(s->in.p, frames + pos, sizeof(msd_message) * take, hipMemcpyHostToDevice, st));
             d_in = as<msd_message>(s->in);
         }
-        if ((rc = upload_filter(v, *s, st)))
+        if ((rc = decide_records(v, *s, d_in, take, now_ms, st, sink, user)))
             return rc;
-        msd_fr_scratch x = scratch(*s);
-        if ((rc = msd_fr_launch_records_decode(d_in, take, &v.tables, &x, st)))
-            return fail(v, rc, "decode kernel failed to launch");
+        pos += take;
+    }
+    msd_filter_expire(v.filter, now_ms); /* readsb.c:331 */
+    return 0;
+}
+
+int msd_get_avr_stats(const msd_ctx *ctx, msd_avr_stats *st)
+{
+    if (!ctx || !st)
+        return -EINVAL;
+    msd_frames_view v;
+    int rc = msd_frames_get_view(const_cast<msd_ctx *>(ctx), &v);
+    if (rc)
+        return rc;
+    const State *s = static_cast<const State *>(*v.state);
+    if (s)
+        *st = s->as;
+    else
+        memset(st, 0, sizeof *st);
+    return 0;
+}
+
+int msd_accept_avr(msd_ctx *ctx, const void *bytes, size_t n, int on_device, uint32_t flags, uint64_t now_ms,
+                   msd_message_fn sink, void *user)
+{
+    if (!ctx || (n && !bytes) || (flags & ~MSD_AVR_KEEP_TIMESTAMP))
+        return -EINVAL;
+    msd_frames_view v;
+    State *s = nullptr;
+    int rc = enter(ctx, v, &s);
+    if (rc)
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(v.stream);
+    const uint8_t *src = static_cast<const uint8_t *>(bytes);
+    const int keep = (flags & MSD_AVR_KEEP_TIMESTAMP) != 0;
+    for (size_t pos = 0; pos < n;) {
+        const uint32_t take = (uint32_t)(n - pos < MSD_FR_PIECE ? n - pos : MSD_FR_PIECE);
+        const uint32_t tl = s->avr_tl, total = tl + take;
+        const uint32_t spans = (total + MSD_AVR_SPAN - 1u) / MSD_AVR_SPAN;
+        if ((rc = ensure(v, *s, 0, 0)) || (rc = grow(v, s->avr_tailbuf, MSD_AVR_LINE_MAX)) ||
+            (rc = grow(v, s->avr_wg, sizeof(uint32_t) * (spans + 1))))
+            return rc;
+        const uint8_t *d_data = src + pos;
+        if (!on_device) {
+            if ((rc = grow(v, s->stage, take)))
+                return rc;
+            HCK(v, hipMemcpyAsync(s->stage.p, src + pos, take, hipMemcpyHostToDevice, st));
+            d_data = as<uint8_t>(s->stage);
+        }
+        if (tl)
+            HCK(v, hipMemcpyAsync(s->avr_tailbuf.p, s->avr_tail, tl, hipMemcpyHostToDevice, st));
+        const uint8_t *d_tail = as<uint8_t>(s->avr_tailbuf);
+        const int discard = s->avr_discard;
+        if ((rc = msd_avr_launch_count(d_tail, tl, d_data, total, discard, v.tables.mode_ac, as<uint32_t>(s->avr_wg),
+                                       as<unsigned long long>(s->ctr), st)))
+            return fail(v, rc, "line kernels failed to launch");
         if ((rc = read_ctr(v, *s, st)))
             return rc;
-        const uint32_t nadds = (uint32_t)s->h_ctr[MSD_FR_CTR_ADDS];
-        if (nadds && (rc = prepare_hash(v, *s, nadds, st, x)))
-            return rc;
-        if ((rc = msd_fr_launch_records_filter(d_in, take, nadds, now_ms, &v.tables, &x, st)))
-            return fail(v, rc, "filter kernels failed to launch");
-        if ((rc = finish_piece(v, *s, st, sink, user)))
-            return rc;
+        const uint32_t nrec = (uint32_t)s->h_ctr[MSD_AVR_CTR_RECORDS];
+        const uint64_t lines = s->h_ctr[MSD_AVR_CTR_LINES], dropped = s->h_ctr[MSD_AVR_CTR_DROPPED],
+                       longl = s->h_ctr[MSD_AVR_CTR_LONG];
+        const uint32_t from = (uint32_t)s->h_ctr[MSD_AVR_CTR_LAST_NL]; /* where the incomplete line starts */
+        /* what the next piece starts with: the bytes behind the last '\n', unless they are too many already */
+        uint8_t newtail[MSD_AVR_LINE_MAX];
+        uint32_t ntl = 0;
+        int ndiscard = from ? 0 : discard;
+        if (!ndiscard && total - from > MSD_AVR_LINE_MAX)
+            ndiscard = 1;
+        if (!ndiscard) {
+            for (uint32_t i = from; i < tl; ++i)
+                newtail[ntl++] = s->avr_tail[i];
+            const uint32_t dfrom = from > tl ? from - tl : 0;
+            if (take > dfrom) {
+                if (on_device) {
+                    HCK(v, hipMemcpyAsync(newtail + ntl, d_data + dfrom, take - dfrom, hipMemcpyDeviceToHost, st));
+                    HCK(v, hipStreamSynchronize(st));
+                } else {
+                    memcpy(newtail + ntl, src + pos + dfrom, take - dfrom);
+                }
+                ntl += take - dfrom;
+            }
+        }
+        if (nrec) {
+            if ((rc = ensure(v, *s, 0, nrec)) || (rc = grow(v, s->avr_rec, sizeof(msd_message) * nrec)))
+                return rc;
+            if ((rc = msd_avr_launch_store(d_tail, tl, d_data, total, discard, v.tables.mode_ac, keep,
+                                           as<uint32_t>(s->avr_wg), as<msd_message>(s->avr_rec), st)))
+                return fail(v, rc, "line store kernel failed to launch");
+            if ((rc = decide_records(v, *s, as<msd_message>(s->avr_rec), nrec, now_ms, st, sink, user)))
+                return rc;
+        }
+        memcpy(s->avr_tail, newtail, ntl);
+        s->avr_tl = ntl;
+        s->avr_discard = ndiscard;
+        s->as.lines += lines;
+        s->as.frames += nrec;
+        s->as.dropped_lines += dropped;
+        s->as.long_lines += longl;
         pos += take;
     }
     msd_filter_expire(v.filter, now_ms); /* readsb.c:331 */
