@@ -651,7 +651,7 @@ int msd_group_submit_device_wire(msd_group *g, const void *d_iq, const msd_group
                                  uint32_t flags, msd_group_wire_fn sink, void *user);
 int msd_group_submit_host_wire(msd_group *g, const void *h_iq, const msd_group_entry *e, uint32_t n, int format,
                                uint32_t flags, msd_group_wire_fn sink, void *user);
-int msd_group_reset_receiver(msd_group *g, uint32_t receiver); /* filter, clock, counters, tail; its Beast framing state */
+int msd_group_reset_receiver(msd_group *g, uint32_t receiver); /* filter, clock, counters, tail; its Beast and AVR framing state */
 int msd_group_get_stats(const msd_group *g, uint32_t receiver, msd_stats *st);
 int msd_group_set_preamble_threshold(msd_group *g, int threshold); /* group-wide: sets every receiver's threshold */
 /* of the most recent call: hits, tries, resolve_passes (1: the GPU resolve ran; 0: all on the host); since creation:
@@ -715,7 +715,8 @@ int msd_group_get_receiver_mode_ac(const msd_group *g, uint32_t receiver, int *o
  * n > max_receivers, nonzero flags or reserved, nbytes > MSD_GROUP_BEAST_ENTRY_MAX, an offset above
  * MSD_GROUP_BEAST_OFFSET_MAX, NULL bytes or entries with n > 0.  n == 0 returns 0.  A call that fails after its kernels
  * were queued (-EIO, or -ENOMEM for its scratch) leaves the group accepting msd_group_destroy only.
- * Memory: nothing until the first call.  Then 170 bytes of host memory per receiver of the group; and, grown to the
+ * Memory: nothing until the first call (the remote counters, 88 bytes per receiver, are made with the group).  Then 80
+ * bytes of host memory per receiver of the group; and, grown to the
  * largest piece seen (a call is cut into pieces of whole entries of at most 8 MiB of new bytes), about 40 bytes of
  * device memory per byte of a piece, where every entry counts rounded up to a multiple of 4096 bytes (1024 entries of
  * 4 KiB behind a kept frame: 8 MiB, about 330 MB), about 400 bytes of device and of page-locked host memory per entry,
@@ -734,6 +735,59 @@ typedef struct msd_group_beast_entry {
 int msd_group_accept_beast(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
                            msd_group_message_fn sink, void *user);
 int msd_group_get_remote_stats(const msd_group *g, uint32_t receiver, msd_remote_stats *st);
+
+/* AVR raw text input per receiver: one call takes a piece of the AVR text stream ("*8D...;", "@...;",
+ * "<...;" lines, --net-ri-port) of each of any subset of the group's receivers and frames, parses and decides them on
+ * the GPU in a number of launches and host synchronisations that does not depend on n.  For every receiver the results
+ * are exactly those of a context of its own, given that receiver's repair level and Mode A/C switch, fed the same bytes
+ * by msd_accept_avr in the same calls with the same flags and now_ms: the records, every msd_remote_stats counter except
+ * the diagnostic tile_rewalks, every msd_avr_stats counter, and the filter afterwards.  Every rule of msd_accept_avr's
+ * comment applies unchanged, per receiver: MSD_AVR_LINE_MAX, NUL, white space, the five prefixes, the '<' signal
+ * arithmetic, the timestamp flag, and the 56-bit divergence.
+ *
+ * Per receiver, carried from call to call: its own kept incomplete line (at most MSD_AVR_LINE_MAX bytes) or the flag
+ * "inside an overlong line" -- bytes of one entry never complete, start or discard a line of another --; its
+ * msd_avr_stats; and its msd_remote_stats, the same counters msd_group_get_remote_stats returns and its Beast entries
+ * add to (in a context the two inputs share them as well).  The kept line and the Beast input's kept frame are separate
+ * states: a receiver may get Beast entries and AVR entries in different calls.  Its repair level is the one of
+ * msd_group_set_receiver_options; with its Mode A/C switch on, four-digit lines are delivered as Mode A/C records, and
+ * dropped (dropped_lines) with it off, as msd_config.mode_ac decides for a context.  Its ICAO filter is the one its IQ
+ * buffers and its Beast entries read and write.  Within the call every record sees the adds of the records before it in
+ * its own entry; after the entry, icaoFilterExpire(now_ms) on that receiver, also when no line was completed.  The adds
+ * and the flip reach the host copy of the filter and, in a group that resolves on the GPU, the resident device
+ * snapshot; a MSD_CFG_HOST_RESOLVE group keeps no snapshots on the device, and the call uploads those of its own
+ * receivers.  An AVR entry is history for the repair-level rule (msd_group_set_receiver_options to another level is
+ * -EBUSY afterwards).  msd_group_reset_receiver also clears the receiver's kept line, its discard flag and its
+ * msd_avr_stats (and the remote counters, as before).
+ *
+ * entry i's bytes are bytes[offset .. offset + nbytes), device memory (on_device = 1; it must stay valid until the call
+ * returns) or host memory (copied in).  flags is per entry, not per receiver: successive entries of one receiver may
+ * differ.  An entry with nbytes = 0 runs only the receiver's icaoFilterExpire and leaves its kept line alone.
+ * Delivery: before the call returns, by entry in the order of the call's entries, then in stream order within an entry;
+ * sysTimestampMsg is the entry's now_ms, the other fields are as msd_accept_avr sets them.
+ * -EINVAL, with the group's state untouched: a receiver out of range, the same receiver twice in one call,
+ * n > max_receivers, a flag bit other than MSD_AVR_KEEP_TIMESTAMP, nonzero reserved, nbytes > MSD_GROUP_AVR_ENTRY_MAX,
+ * an offset above MSD_GROUP_AVR_OFFSET_MAX, NULL bytes or entries with n > 0.  n == 0 returns 0.  A call that fails
+ * after its kernels were queued (-EIO, or -ENOMEM for its scratch) leaves the group accepting msd_group_destroy only.
+ * Memory: nothing until the first call.  Then about 300 bytes of host memory per receiver of the group; and, grown to
+ * the largest piece seen (a call is cut into pieces of whole entries of at most 8 MiB of new bytes), about 13 bytes of
+ * device memory per byte of a piece, where every entry counts rounded up to a multiple of 4096 bytes (1024 entries of
+ * 4 KiB behind a kept line: 8 MiB, about 110 MB), about 750 bytes of device and of page-locked host memory per entry,
+ * 56 bytes of device and of page-locked memory per delivered message, for host input the piece's bytes once more on
+ * each side, and in a MSD_CFG_HOST_RESOLVE group 65.6 KB on each side per entry. */
+#define MSD_GROUP_AVR_ENTRY_MAX (1u << 20)
+#define MSD_GROUP_AVR_OFFSET_MAX ((uint64_t)1 << 47)
+typedef struct msd_group_avr_entry {
+    uint32_t receiver;  /* 0 .. max_receivers-1 */
+    uint32_t flags;     /* 0 or MSD_AVR_KEEP_TIMESTAMP */
+    uint64_t offset;    /* of this entry's bytes in `bytes` */
+    uint32_t nbytes;    /* may be 0; at most MSD_GROUP_AVR_ENTRY_MAX */
+    uint32_t reserved;  /* 0 */
+    uint64_t now_ms;    /* mstime() for this receiver: sysTimestampMsg of its records, then icaoFilterExpire */
+} msd_group_avr_entry;
+int msd_group_accept_avr(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
+                         msd_group_message_fn sink, void *user);
+int msd_group_get_avr_stats(const msd_group *g, uint32_t receiver, msd_avr_stats *st);
 
 #ifdef __cplusplus
 }

@@ -235,7 +235,7 @@ EXPORTS = [
     "msd_group_set_receiver_mode_ac", "msd_group_get_receiver_mode_ac",
     "msd_group_submit_device_fields", "msd_group_submit_host_fields",
     "msd_wire_encode", "msd_group_submit_device_wire", "msd_group_submit_host_wire",
-    "msd_group_accept_beast", "msd_group_get_remote_stats",
+    "msd_group_accept_beast", "msd_group_get_remote_stats", "msd_group_accept_avr", "msd_group_get_avr_stats",
 ]
 
 _lib = None
@@ -675,6 +675,15 @@ class GroupBeastEntry(C.Structure):
 GROUP_BEAST_ENTRY_MAX = 1 << 20  # MSD_GROUP_BEAST_ENTRY_MAX
 
 
+class GroupAvrEntry(C.Structure):
+    """msd_group_avr_entry: one receiver's piece of its AVR text stream in a msd_group_accept_avr call."""
+    _fields_ = [("receiver", C.c_uint32), ("flags", C.c_uint32), ("offset", C.c_uint64), ("nbytes", C.c_uint32),
+                ("reserved", C.c_uint32), ("now_ms", C.c_uint64)]
+
+
+GROUP_AVR_ENTRY_MAX = 1 << 20  # MSD_GROUP_AVR_ENTRY_MAX
+
+
 GROUP_MESSAGE_DTYPE = np.dtype([("receiver", "<u4"), ("m", MESSAGE_DTYPE)])
 _GROUP_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_void_p)
 _GROUP_FIELDS_SINK = C.CFUNCTYPE(None, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -718,6 +727,11 @@ def _group_lib():
                                              C.c_void_p, C.c_void_p]
         L.msd_group_get_remote_stats.restype = C.c_int
         L.msd_group_get_remote_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RemoteStats)]
+        L.msd_group_accept_avr.restype = C.c_int
+        L.msd_group_accept_avr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroupAvrEntry), C.c_uint32,
+                                           C.c_void_p, C.c_void_p]
+        L.msd_group_get_avr_stats.restype = C.c_int
+        L.msd_group_get_avr_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(AvrStats)]
         L._group_bound = True
     return L
 
@@ -857,24 +871,68 @@ class ReceiverGroup:
                                  dropped, deliver)
 
     @staticmethod
-    def beast_entries(chunks, now_ms):
-        """The GroupBeastEntry array and the packed bytes of an accept_beast call: `chunks` is a list of
-        (receiver, bytes) pairs or a {receiver: bytes} dict (in its order), now_ms an int or one per entry.  Entry i's
-        bytes follow entry i - 1's in the packed array."""
+    def _remote_entries(Entry, chunks, now_ms, flags):
         pairs = list(chunks.items()) if isinstance(chunks, dict) else list(chunks)
         n = len(pairs)
         nows = [int(now_ms)] * n if isinstance(now_ms, (int, np.integer)) else [int(t) for t in now_ms]
         if len(nows) != n:
             raise ValueError(f"{n} entries need {n} now_ms values")
-        entries = (GroupBeastEntry * max(n, 1))()
+        entries = (Entry * max(n, 1))()
         parts, off = [], 0
         for i, (r, data) in enumerate(pairs):
             b = bytes(data) if isinstance(data, (bytes, bytearray, memoryview)) else \
                 np.ascontiguousarray(data).view(np.uint8).tobytes()
-            entries[i] = GroupBeastEntry(int(r), 0, off, len(b), 0, nows[i])
+            entries[i] = Entry(int(r), flags, off, len(b), 0, nows[i])
             parts.append(b)
             off += len(b)
         return entries, n, b"".join(parts)
+
+    @staticmethod
+    def beast_entries(chunks, now_ms):
+        """The GroupBeastEntry array and the packed bytes of an accept_beast call: `chunks` is a list of
+        (receiver, bytes) pairs or a {receiver: bytes} dict (in its order), now_ms an int or one per entry.  Entry i's
+        bytes follow entry i - 1's in the packed array."""
+        return ReceiverGroup._remote_entries(GroupBeastEntry, chunks, now_ms, 0)
+
+    @staticmethod
+    def avr_entries(chunks, now_ms, keep_timestamp=False):
+        """The GroupAvrEntry array and the packed bytes of an accept_avr call, as beast_entries builds them;
+        keep_timestamp sets MSD_AVR_KEEP_TIMESTAMP in every entry's flags."""
+        return ReceiverGroup._remote_entries(GroupAvrEntry, chunks, now_ms, AVR_KEEP_TIMESTAMP if keep_timestamp else 0)
+
+    def _accept_remote(self, call, what, ent, n, data, as_dict, deliver):
+        rx, raw = [], []
+
+        def sink(receiver, mm, _user):
+            rx.append(receiver)
+            raw.append(C.string_at(mm, MESSAGE_DTYPE.itemsize))
+
+        fn = _GROUP_SINK(sink)  # (kept alive until the call returns)
+        cb = C.cast(fn, C.c_void_p) if deliver else None
+        need = max((ent[i].offset + ent[i].nbytes for i in range(n)), default=0)
+        if hasattr(data, "data_ptr") and getattr(data, "is_cuda", False):
+            if not data.is_contiguous():
+                raise ValueError(f"{what} needs a contiguous tensor")
+            if data.numel() * data.element_size() < need:
+                raise ValueError(f"the entries need {need} bytes")
+            import torch
+            torch.cuda.current_stream(data.device).synchronize()  # the group reads it on its own stream
+            self._check(call(self._h, C.c_void_p(data.data_ptr()), 1, ent, n, cb, None))
+        else:
+            arr = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+            if arr.size < need:
+                raise ValueError(f"the entries need {need} bytes")
+            keep = arr if arr.size else np.zeros(1, dtype=np.uint8)  # a non-NULL pointer for entries that are all empty
+            self._check(call(self._h, keep.ctypes.data, 0, ent, n, cb, None))
+        res = np.zeros(len(rx), dtype=GROUP_MESSAGE_DTYPE)
+        if rx:
+            res["receiver"] = rx
+            res["m"] = np.frombuffer(b"".join(raw), dtype=MESSAGE_DTYPE)
+        if not as_dict:
+            return res
+        return {int(ent[i].receiver): _raw_copy(np.ascontiguousarray(res["m"][res["receiver"] == ent[i].receiver]))
+                for i in range(n)}
 
     def accept_beast(self, chunks, now_ms, as_dict=False, deliver=True, entries=None):
         """msd_group_accept_beast: a piece of the Beast stream of each of any subset of the receivers, decided against
@@ -887,42 +945,26 @@ class ReceiverGroup:
             ent, n, data = self.beast_entries(chunks, now_ms)
         else:
             (ent, n), data = entries, chunks
-        rx, raw = [], []
+        return self._accept_remote(_group_lib().msd_group_accept_beast, "accept_beast", ent, n, data, as_dict, deliver)
 
-        def sink(receiver, mm, _user):
-            rx.append(receiver)
-            raw.append(C.string_at(mm, MESSAGE_DTYPE.itemsize))
-
-        fn = _GROUP_SINK(sink)  # (kept alive until the call returns)
-        cb = C.cast(fn, C.c_void_p) if deliver else None
-        need = max((ent[i].offset + ent[i].nbytes for i in range(n)), default=0)
-        L = _group_lib()
-        if hasattr(data, "data_ptr") and getattr(data, "is_cuda", False):
-            if not data.is_contiguous():
-                raise ValueError("accept_beast needs a contiguous tensor")
-            if data.numel() * data.element_size() < need:
-                raise ValueError(f"the entries need {need} bytes")
-            import torch
-            torch.cuda.current_stream(data.device).synchronize()  # the group reads it on its own stream
-            self._check(L.msd_group_accept_beast(self._h, C.c_void_p(data.data_ptr()), 1, ent, n, cb, None))
+    def accept_avr(self, chunks, now_ms, keep_timestamp=False, as_dict=False, deliver=True, entries=None):
+        """msd_group_accept_avr: a piece of the AVR text stream of each of any subset of the receivers, in the forms
+        accept_beast takes: (receiver, bytes) pairs or a dict with now_ms (and keep_timestamp for every entry), or the
+        byte array with entries=(GroupAvrEntry array, n), whose flags then say which entries keep their timestamps."""
+        if entries is None:
+            ent, n, data = self.avr_entries(chunks, now_ms, keep_timestamp)
         else:
-            arr = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(data).view(np.uint8).reshape(-1)
-            if arr.size < need:
-                raise ValueError(f"the entries need {need} bytes")
-            keep = arr if arr.size else np.zeros(1, dtype=np.uint8)  # a non-NULL pointer for entries that are all empty
-            self._check(L.msd_group_accept_beast(self._h, keep.ctypes.data, 0, ent, n, cb, None))
-        res = np.zeros(len(rx), dtype=GROUP_MESSAGE_DTYPE)
-        if rx:
-            res["receiver"] = rx
-            res["m"] = np.frombuffer(b"".join(raw), dtype=MESSAGE_DTYPE)
-        if not as_dict:
-            return res
-        return {int(ent[i].receiver): _raw_copy(np.ascontiguousarray(res["m"][res["receiver"] == ent[i].receiver]))
-                for i in range(n)}
+            (ent, n), data = entries, chunks
+        return self._accept_remote(_group_lib().msd_group_accept_avr, "accept_avr", ent, n, data, as_dict, deliver)
+
+    def avr_stats(self, receiver):
+        """msd_group_get_avr_stats: one receiver's line counters (zeros before its first AVR entry)."""
+        st = AvrStats()
+        self._check(_group_lib().msd_group_get_avr_stats(self._h, receiver, C.byref(st)))
+        return st.as_dict()
 
     def remote_stats(self, receiver):
-        """msd_group_get_remote_stats: one receiver's remote counters (zeros before its first Beast entry)."""
+        """msd_group_get_remote_stats: one receiver's remote counters, of its Beast and its AVR entries (zeros before the first)."""
         st = RemoteStats()
         self._check(_group_lib().msd_group_get_remote_stats(self._h, receiver, C.byref(st)))
         return st.as_dict()

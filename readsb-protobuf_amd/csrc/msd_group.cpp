@@ -17,6 +17,7 @@
 #include "msd_ctx.h" /* the context, and with it modes_hip.h, msd_internal.h and msd_kernels.h */
 #include "host/msd_wire.h" /* the host writers, for the entries resolved on host threads */
 #include "msd_group_beast.h" /* Beast input per receiver: msd_group_accept_beast */
+#include "msd_group_avr.h"   /* AVR text input per receiver: msd_group_accept_avr */
 
 using namespace msd_impl;
 
@@ -101,6 +102,8 @@ struct msd_group {
     uint32_t *d_wire_counts = nullptr;  /* [max_receivers][2]: bytes and messages per buffer, between the two kernels */
     void *beast = nullptr; /* Beast input (msd_group_beast.cpp): scratch and the receivers' framing state, made by the
                               first msd_group_accept_beast */
+    void *avr = nullptr;   /* AVR text input (msd_group_avr.cpp), likewise, made by the first msd_group_accept_avr */
+    msd_remote_stats *remote = nullptr; /* [max_receivers] the remote counters both inputs add to */
     char err[256] = {0};
 };
 
@@ -773,8 +776,9 @@ int msd_group_create(const msd_config *cfg, uint32_t max_receivers, msd_group **
     const unsigned hw = std::thread::hardware_concurrency();
     g->threads = cfg->resolve_threads > 0 ? (uint32_t)cfg->resolve_threads : std::max(1u, std::min(16u, hw / 8u));
     g->rx = new (std::nothrow) GroupReceiver[max_receivers];
+    g->remote = new (std::nothrow) msd_remote_stats[max_receivers]();
     const size_t tail_bytes = (size_t)max_receivers * MSD_HALO_FRONT * g->ctx->bps;
-    if (!g->rx || hipMalloc(reinterpret_cast<void **>(&g->d_tails), tail_bytes) != hipSuccess ||
+    if (!g->rx || !g->remote || hipMalloc(reinterpret_cast<void **>(&g->d_tails), tail_bytes) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&g->d_ctl), sizeof(uint32_t) * 4 * max_receivers) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void **>(&g->h_ctl), sizeof(uint32_t) * 4 * max_receivers, hipHostMallocDefault) != hipSuccess ||
         (g->gpu && (hipMalloc(reinterpret_cast<void **>(&g->d_snaps), sizeof(uint32_t) * MSD_SNAP_WORDS * max_receivers) != hipSuccess ||
@@ -825,6 +829,8 @@ void msd_group_destroy(msd_group *g)
     (void)hipHostFree(g->h_wire_entries);
     (void)hipFree(g->d_wire_counts);
     msd_gb_free(g->beast);
+    msd_ga_free(g->avr);
+    delete[] g->remote;
     msd_destroy(g->ctx);
     delete g;
 }
@@ -903,7 +909,9 @@ int msd_group_reset_receiver(msd_group *g, uint32_t receiver)
     if (g->ctx->failed)
         return gfail(g, -EIO, "an earlier call failed");
     group_receiver_reset(g->rx[receiver]);
-    msd_gb_reset_receiver(g->beast, receiver); /* its remote counters, kept frame and pending gap */
+    memset(&g->remote[receiver], 0, sizeof g->remote[receiver]);
+    msd_gb_reset_receiver(g->beast, receiver); /* its kept frame and pending gap */
+    msd_ga_reset_receiver(g->avr, receiver);   /* its kept line, discard flag and msd_avr_stats */
     const int rc = group_upload_snapshot(g, receiver);
     if (rc)
         g->ctx->failed = true;
@@ -1026,6 +1034,7 @@ int msd_group_accept_beast(msd_group *g, const void *bytes, int on_device, const
     v.max_receivers = g->max_receivers;
     v.tables = fv.tables;
     v.d_snaps = g->gpu ? g->d_snaps : nullptr;
+    v.remote = g->remote;
     v.state = &g->beast;
     v.err = g->err;
     v.errlen = sizeof g->err;
@@ -1051,7 +1060,71 @@ int msd_group_get_remote_stats(const msd_group *g, uint32_t receiver, msd_remote
 {
     if (!g || !st || receiver >= g->max_receivers)
         return -EINVAL;
-    msd_gb_get_stats(g->beast, receiver, st);
+    *st = g->remote[receiver];
+    return 0;
+}
+
+/* AVR text input per receiver: the same checks, the entries' flags, then the call (msd_group_avr.cpp) */
+int msd_group_accept_avr(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
+                         msd_group_message_fn sink, void *user)
+{
+    if (!g)
+        return -EINVAL;
+    msd_ctx *c = g->ctx;
+    if (n > g->max_receivers)
+        return gfail(g, -EINVAL, "AVR entries: more than max_receivers");
+    if (n && (!e || !bytes))
+        return gfail(g, -EINVAL, "AVR entries: NULL bytes or entries");
+    std::vector<bool> seen(g->max_receivers, false);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (e[i].receiver >= g->max_receivers || seen[e[i].receiver] || (e[i].flags & ~MSD_AVR_KEEP_TIMESTAMP) || e[i].reserved)
+            return gfail(g, -EINVAL, "AVR entry %u: a receiver out of range or given twice, an unknown flag or nonzero reserved", i);
+        if (e[i].nbytes > MSD_GROUP_AVR_ENTRY_MAX || e[i].offset > MSD_GROUP_AVR_OFFSET_MAX)
+            return gfail(g, -EINVAL, "AVR entry %u: more than %u bytes, or an offset above 2^47", i, MSD_GROUP_AVR_ENTRY_MAX);
+        seen[e[i].receiver] = true;
+    }
+    if (c->failed)
+        return gfail(g, -EIO, "an earlier call failed");
+    if (n == 0)
+        return 0;
+    msd_frames_view fv;
+    int rc = msd_frames_get_view(c, &fv); /* the CRC and repair tables of the group's context */
+    if (rc)
+        return gfail(g, rc, "AVR input: no tables");
+    msd_gb_view v{};
+    v.stream = fv.stream;
+    v.device = fv.device;
+    v.max_receivers = g->max_receivers;
+    v.tables = fv.tables;
+    v.d_snaps = g->gpu ? g->d_snaps : nullptr;
+    v.remote = g->remote;
+    v.state = &g->avr;
+    v.err = g->err;
+    v.errlen = sizeof g->err;
+    std::vector<msd_ga_input> in(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        GroupReceiver &r = g->rx[e[i].receiver];
+        in[i].receiver = e[i].receiver;
+        in[i].nbytes = e[i].nbytes;
+        in[i].flags = e[i].flags;
+        in[i].offset = e[i].offset;
+        in[i].now_ms = e[i].now_ms;
+        in[i].filter = &r.resolver.filter;
+        in[i].nfix = r.opt.nfix_crc;
+        in[i].mode_ac = r.mode_ac ? 1 : 0;
+        r.history = true; /* the repair level is fixed from here on, as by a buffer */
+    }
+    rc = msd_ga_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, user);
+    if (rc)
+        c->failed = true;
+    return rc;
+}
+
+int msd_group_get_avr_stats(const msd_group *g, uint32_t receiver, msd_avr_stats *st)
+{
+    if (!g || !st || receiver >= g->max_receivers)
+        return -EINVAL;
+    msd_ga_get_stats(g->avr, receiver, st);
     return 0;
 }
 

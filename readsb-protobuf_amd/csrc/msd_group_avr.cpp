@@ -1,0 +1,292 @@
+/*
+ * msd_group_avr.cpp -- host side of msd_group_accept_avr ("AVR text input per receiver"): the pieces of
+ * whole entries, the device scratch (made by the first call), the launches of msd_group_avr_kernels.hip and of the
+ * Beast input's filter stage, and what stays on the host per receiver -- the kept incomplete line or the flag that an
+ * overlong one is being discarded, msd_avr_stats, and the host copy of the ICAO filter, on which every entry's new
+ * addresses are inserted again in the device's order before the flip.  The remote counters are the group's
+ * (msd_gb_view.remote), shared with the Beast input.  A piece costs two host synchronisations and a fixed number of
+ * launches and copies, whatever its number of entries.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "msd_group_avr.h"
+#include "msd_group_scratch.h"
+#include "msd_kernels.h"
+
+using namespace msd_group_scratch;
+
+namespace {
+
+constexpr uint32_t LM = MSD_AVR_LINE_MAX;
+
+struct Rx {
+    uint8_t line[LM];
+    uint32_t tl = 0;
+    uint32_t discard = 0;
+    msd_avr_stats as{};
+};
+
+struct State {
+    std::vector<Rx> rx;
+    Buf up, buf, cnt, nodes, cls, addr, flags, off, scan_tmp, newlist, newaddr, hash, snaps, add_first, rec, out, ctr, tot,
+        lines_out, stage;
+    Buf h_up{nullptr, 0, true}, h_ctr{nullptr, 0, true}, h_tot{nullptr, 0, true}, h_lines{nullptr, 0, true},
+        h_out{nullptr, 0, true}, h_new{nullptr, 0, true}, h_stage{nullptr, 0, true}, h_snaps{nullptr, 0, true};
+    Buf *all[28] = {&up,   &buf,   &cnt,       &nodes, &cls,  &addr,  &flags, &off,       &scan_tmp, &newlist,
+                    &newaddr, &hash, &snaps,   &add_first, &rec, &out, &ctr,  &tot,       &lines_out, &stage,
+                    &h_up, &h_ctr, &h_tot,     &h_lines, &h_out, &h_new, &h_stage, &h_snaps};
+};
+
+/* entries [a, b) of the call as one piece */
+int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_device, const msd_ga_input *in, uint32_t a,
+              uint32_t b, msd_group_message_fn sink, void *user)
+{
+    hipStream_t st = static_cast<hipStream_t>(v->stream);
+    const uint32_t n = b - a;
+    int rc = 0;
+
+    /* the upload block: entries | span -> entry | kept lines | snapshot slots | flips */
+    uint32_t nspans = 0;
+    size_t newbytes = 0;
+    for (uint32_t i = a; i < b; ++i) {
+        const uint32_t seg = in[i].nbytes ? s.rx[in[i].receiver].tl + in[i].nbytes : 0u;
+        nspans += (seg + MSD_AVR_SPAN - 1u) / MSD_AVR_SPAN;
+        newbytes += in[i].nbytes;
+    }
+    const uint32_t len = nspans * MSD_AVR_SPAN;
+    const size_t o_ent = 0, o_span = up8(sizeof(msd_gb_entry) * n), o_lines = o_span + up8(sizeof(uint32_t) * nspans),
+                 o_slot = o_lines + (size_t)LM * n, o_flip = o_slot + up8(sizeof(uint32_t) * n),
+                 up_bytes = o_flip + up8(sizeof(uint32_t) * n);
+    if ((rc = grow(v, s.h_up, up_bytes)) || (rc = grow(v, s.up, up_bytes)))
+        return rc;
+    if (!on_device && ((rc = grow(v, s.h_stage, newbytes + 1)) || (rc = grow(v, s.stage, newbytes + 1))))
+        return rc;
+    uint8_t *hu = as<uint8_t>(s.h_up);
+    msd_gb_entry *ent = reinterpret_cast<msd_gb_entry *>(hu + o_ent);
+    uint32_t *span_ent = reinterpret_cast<uint32_t *>(hu + o_span);
+    uint8_t *lines = hu + o_lines;
+    uint32_t *slot = reinterpret_cast<uint32_t *>(hu + o_slot), *flip = reinterpret_cast<uint32_t *>(hu + o_flip);
+    uint32_t t = 0;
+    size_t staged = 0;
+    for (uint32_t i = a; i < b; ++i) {
+        const msd_ga_input &I = in[i];
+        const Rx &r = s.rx[I.receiver];
+        msd_gb_entry &E = ent[i - a];
+        memset(&E, 0, sizeof E);
+        E.tl = I.nbytes ? r.tl : 0u; /* an empty entry leaves its receiver's kept line and discard flag alone */
+        E.now_ms = I.now_ms;
+        E.s0 = t * MSD_AVR_SPAN;
+        E.s1 = E.s0 + (I.nbytes ? E.tl + I.nbytes : 0u);
+        E.tile0 = t;
+        E.ntiles = (E.s1 - E.s0 + MSD_AVR_SPAN - 1u) / MSD_AVR_SPAN;
+        E.snap = v->d_snaps ? I.receiver : i - a;
+        E.opt = (uint32_t)I.nfix | (I.mode_ac ? MSD_GB_OPT_MODEAC : 0u) |
+                ((I.flags & MSD_AVR_KEEP_TIMESTAMP) ? MSD_GA_OPT_KEEP_TS : 0u) | (r.discard ? MSD_GA_OPT_DISCARD : 0u);
+        if (on_device) {
+            E.src = I.offset;
+        } else { /* the call's bytes packed densely into one page-locked array: one copy to the device */
+            E.src = staged;
+            memcpy(as<uint8_t>(s.h_stage) + staged, bytes + I.offset, I.nbytes);
+            staged += I.nbytes;
+        }
+        for (uint32_t k = 0; k < E.ntiles; ++k)
+            span_ent[t++] = i - a;
+        memcpy(lines + (size_t)LM * (i - a), r.line, LM);
+        slot[i - a] = I.receiver;
+        flip[i - a] = I.now_ms >= I.filter->next_flip ? 1u : 0u; /* icaoFilterExpire's own test (icao_filter.c:150-164) */
+    }
+
+    /* scratch: the piece's bytes, and the records by its shortest line that yields one (7 bytes) */
+    const size_t nrec_max = (size_t)len / 7u + 2;
+    if ((rc = grow(v, s.buf, (size_t)len + 16)) || (rc = grow(v, s.cnt, 4 * (size_t)(nspans + 2))) ||
+        (rc = grow(v, s.nodes, 4 * nrec_max)) || (rc = grow(v, s.cls, nrec_max)) || (rc = grow(v, s.addr, 4 * nrec_max)) ||
+        (rc = grow(v, s.flags, 4 * nrec_max)) || (rc = grow(v, s.off, 4 * (nrec_max + 1))) ||
+        (rc = grow(v, s.scan_tmp, 4 * msd_fr_scan_tmp_words((uint32_t)(nrec_max > nspans ? nrec_max : nspans)))) ||
+        (rc = grow(v, s.newlist, 4 * nrec_max)) || (rc = grow(v, s.newaddr, 4 * nrec_max)) ||
+        (rc = grow(v, s.rec, sizeof(msd_message) * nrec_max)) || (rc = grow(v, s.add_first, 4 * (size_t)(n + 1))) ||
+        (rc = grow(v, s.ctr, 8 * (size_t)MSD_FR_CTR_WORDS * n)) || (rc = grow(v, s.tot, 8 * MSD_GB_TOT_WORDS)) ||
+        (rc = grow(v, s.lines_out, (size_t)LM * n)) || (rc = grow(v, s.h_ctr, 8 * (size_t)MSD_FR_CTR_WORDS * n)) ||
+        (rc = grow(v, s.h_tot, 8 * MSD_GB_TOT_WORDS)) || (rc = grow(v, s.h_lines, (size_t)LM * n)))
+        return rc;
+    uint32_t *snaps = v->d_snaps;
+    if (!snaps) { /* a group that resolves on the host keeps no snapshots on the device: those of this piece */
+        const size_t sb = sizeof(uint32_t) * MSD_SNAP_WORDS * (size_t)n;
+        if ((rc = grow(v, s.h_snaps, sb)) || (rc = grow(v, s.snaps, sb)))
+            return rc;
+        uint32_t *h = as<uint32_t>(s.h_snaps);
+        for (uint32_t i = a; i < b; ++i, h += MSD_SNAP_WORDS)
+            snapshot_of(in[i].filter, h);
+        HCK(v, hipMemcpyAsync(s.snaps.p, s.h_snaps.p, sb, hipMemcpyHostToDevice, st));
+        snaps = as<uint32_t>(s.snaps);
+    }
+    HCK(v, hipMemcpyAsync(s.up.p, s.h_up.p, up_bytes, hipMemcpyHostToDevice, st));
+    if (!on_device && staged)
+        HCK(v, hipMemcpyAsync(s.stage.p, s.h_stage.p, staged, hipMemcpyHostToDevice, st));
+
+    msd_ga_scratch x{};
+    uint8_t *du = as<uint8_t>(s.up);
+    x.f.n = n;
+    x.f.ntiles = nspans;
+    x.f.len = len;
+    x.f.ent = reinterpret_cast<const msd_gb_entry *>(du + o_ent);
+    x.f.tile_ent = reinterpret_cast<const uint32_t *>(du + o_span);
+    x.f.buf = as<uint8_t>(s.buf);
+    x.f.cnt = as<uint32_t>(s.cnt);
+    x.f.nodes = as<uint32_t>(s.nodes);
+    x.f.cls = as<uint8_t>(s.cls);
+    x.f.addr = as<uint32_t>(s.addr);
+    x.f.flags = as<uint32_t>(s.flags);
+    x.f.off = as<uint32_t>(s.off);
+    x.f.scan_tmp = as<uint32_t>(s.scan_tmp);
+    x.f.newlist = as<uint32_t>(s.newlist);
+    x.f.newaddr = as<uint32_t>(s.newaddr);
+    x.f.snaps = snaps;
+    x.f.add_first = as<uint32_t>(s.add_first);
+    x.f.ctr = as<unsigned long long>(s.ctr);
+    x.f.tot = as<unsigned long long>(s.tot);
+    x.lines_in = du + o_lines;
+    x.lines_out = as<uint8_t>(s.lines_out);
+    x.rec = as<msd_message>(s.rec);
+
+    const uint8_t *src = on_device ? bytes : as<uint8_t>(s.stage);
+    if ((rc = msd_ga_launch_frame_decode(src, &v->tables, &x, st)))
+        return fail(v, rc, "AVR input: line and decode kernels failed to launch");
+    /* first synchronisation: the piece's records, adds and an upper bound of the records it delivers */
+    HCK(v, hipMemcpyAsync(s.h_tot.p, s.tot.p, 8 * MSD_GB_TOT_WORDS, hipMemcpyDeviceToHost, st));
+    HCK(v, hipStreamSynchronize(st));
+    const unsigned long long *tot = as<unsigned long long>(s.h_tot);
+    const uint32_t nrec = (uint32_t)tot[MSD_GB_TOT_NODES], nadds = (uint32_t)tot[MSD_GB_TOT_ADDS],
+                   ncand = (uint32_t)tot[MSD_GB_TOT_CAND];
+    if (tot[MSD_GB_TOT_NODES] + 2 > nrec_max || ncand > nrec || nadds > nrec)
+        return fail(v, -EIO, "AVR input: %llu records, %u messages in a piece of %u bytes", tot[MSD_GB_TOT_NODES], ncand, len);
+    if (nadds) {
+        uint32_t hs = 64;
+        while (hs < 2u * nadds)
+            hs <<= 1;
+        if ((rc = grow(v, s.hash, (size_t)16 * hs)))
+            return rc;
+        HCK(v, hipMemsetAsync(s.hash.p, 0xff, (size_t)16 * hs, st));
+        x.f.hash = as<unsigned long long>(s.hash);
+        x.f.hslots = hs;
+    }
+    if ((rc = grow(v, s.out, sizeof(msd_message) * ((size_t)ncand + 1))) ||
+        (rc = grow(v, s.h_out, sizeof(msd_message) * ((size_t)ncand + 1))) ||
+        (rc = grow(v, s.h_new, sizeof(uint32_t) * ((size_t)nadds + 1))))
+        return rc;
+    x.f.out = as<msd_message>(s.out);
+    if ((rc = msd_gb_launch_filter_records(x.rec, nrec, nadds, &v->tables, &x.f, st)))
+        return fail(v, rc, "AVR input: filter kernels failed to launch");
+    if (v->d_snaps && /* the resident snapshots: every entry's inserts, then its flip */
+        (rc = msd_launch_group_filter_apply(v->d_snaps, n, reinterpret_cast<const uint32_t *>(du + o_slot), x.f.add_first,
+                                            x.f.newaddr, reinterpret_cast<const uint32_t *>(du + o_flip), st)))
+        return fail(v, rc, "AVR input: group filter kernel launch failed");
+    /* second synchronisation: counters, kept lines and discard flags, records and the new-address lists */
+    HCK(v, hipMemcpyAsync(s.h_ctr.p, s.ctr.p, 8 * (size_t)MSD_FR_CTR_WORDS * n, hipMemcpyDeviceToHost, st));
+    HCK(v, hipMemcpyAsync(s.h_lines.p, s.lines_out.p, (size_t)LM * n, hipMemcpyDeviceToHost, st));
+    if (nrec && ncand)
+        HCK(v, hipMemcpyAsync(s.h_out.p, s.out.p, sizeof(msd_message) * ncand, hipMemcpyDeviceToHost, st));
+    if (nrec && nadds)
+        HCK(v, hipMemcpyAsync(s.h_new.p, s.newaddr.p, sizeof(uint32_t) * nadds, hipMemcpyDeviceToHost, st));
+    HCK(v, hipStreamSynchronize(st));
+
+    const unsigned long long *ctr = as<unsigned long long>(s.h_ctr);
+    for (uint32_t i = a; i < b; ++i) { /* nothing is committed before every entry has been looked at */
+        const unsigned long long *c = ctr + (size_t)MSD_FR_CTR_WORDS * (i - a);
+        if (c[MSD_GB_CTR_NTL] > LM || c[MSD_GA_CTR_DISCARD] > 1 || (c[MSD_GA_CTR_DISCARD] && c[MSD_GB_CTR_NTL]))
+            return fail(v, -EIO, "AVR input: receiver %u: incomplete line of %llu bytes", in[i].receiver, c[MSD_GB_CTR_NTL]);
+        if (c[MSD_GB_CTR_REC_FIRST] + c[MSD_FR_CTR_RECORDS] > ncand || c[MSD_GB_CTR_NEW_FIRST] + c[MSD_FR_CTR_NEW] > nadds)
+            return fail(v, -EIO, "AVR input: receiver %u: record or address range outside the piece's", in[i].receiver);
+    }
+    const msd_message *recs = as<msd_message>(s.h_out);
+    const uint32_t *newaddr = as<uint32_t>(s.h_new);
+    for (uint32_t i = a; i < b; ++i) {
+        const msd_ga_input &I = in[i];
+        const unsigned long long *c = ctr + (size_t)MSD_FR_CTR_WORDS * (i - a);
+        Rx &r = s.rx[I.receiver];
+        /* icaoFilterAdd of the entry's new addresses in order of first add, as the device inserted them; then the flip */
+        for (uint32_t k = 0; k < (uint32_t)c[MSD_FR_CTR_NEW]; ++k)
+            msd_filter_add(I.filter, newaddr[c[MSD_GB_CTR_NEW_FIRST] + k]);
+        msd_filter_expire(I.filter, I.now_ms); /* readsb.c:331 */
+        add_remote(v->remote[I.receiver], c);
+        r.as.lines += c[MSD_GA_CTR_LINES];
+        r.as.frames += c[MSD_FR_CTR_NODES];
+        r.as.dropped_lines += c[MSD_GA_CTR_DROPPED];
+        r.as.long_lines += c[MSD_GA_CTR_LONG];
+        if (I.nbytes) { /* what its next entry starts with */
+            r.tl = (uint32_t)c[MSD_GB_CTR_NTL];
+            r.discard = (uint32_t)c[MSD_GA_CTR_DISCARD];
+            memcpy(r.line, as<uint8_t>(s.h_lines) + (size_t)LM * (i - a), r.tl);
+        }
+        if (sink)
+            for (uint32_t k = 0; k < (uint32_t)c[MSD_FR_CTR_RECORDS]; ++k)
+                sink(I.receiver, recs + c[MSD_GB_CTR_REC_FIRST] + k, user);
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int msd_ga_accept(const msd_gb_view *v, const void *bytes, int on_device, const msd_ga_input *in, uint32_t n,
+                  msd_group_message_fn sink, void *user)
+{
+    State *s = static_cast<State *>(*v->state);
+    if (!s) {
+        s = new (std::nothrow) State();
+        if (!s)
+            return fail(v, -ENOMEM, "out of host memory");
+        try {
+            s->rx.resize(v->max_receivers);
+        } catch (...) {
+            delete s;
+            return fail(v, -ENOMEM, "out of host memory");
+        }
+        *v->state = s;
+    }
+    HCK(v, hipSetDevice(v->device));
+    /* pieces of whole entries: a piece is closed when the next entry would take its new bytes past MSD_FR_PIECE */
+    for (uint32_t a = 0; a < n;) {
+        uint32_t b = a;
+        size_t sum = 0;
+        while (b < n && (b == a || sum + in[b].nbytes <= MSD_FR_PIECE))
+            sum += in[b++].nbytes;
+        const int rc = run_piece(v, *s, static_cast<const uint8_t *>(bytes), on_device, in, a, b, sink, user);
+        if (rc)
+            return rc;
+        a = b;
+    }
+    return 0;
+}
+
+void msd_ga_reset_receiver(void *state, uint32_t receiver)
+{
+    State *s = static_cast<State *>(state);
+    if (s && receiver < s->rx.size())
+        s->rx[receiver] = Rx();
+}
+
+void msd_ga_get_stats(const void *state, uint32_t receiver, msd_avr_stats *st)
+{
+    const State *s = static_cast<const State *>(state);
+    if (s && receiver < s->rx.size())
+        *st = s->rx[receiver].as;
+    else
+        memset(st, 0, sizeof *st);
+}
+
+void msd_ga_free(void *state)
+{
+    State *s = static_cast<State *>(state);
+    if (!s)
+        return;
+    for (Buf *b : s->all)
+        release(*b);
+    delete s;
+}
+
+} // extern "C"

@@ -1,21 +1,21 @@
 /*
  * msd_group_beast.cpp -- host side of msd_group_accept_beast ("Beast input per receiver"): the pieces of
  * whole entries, the device scratch (made by the first call), the launches of msd_group_beast_kernels.hip, and what
- * stays on the host per receiver -- the kept incomplete frame, the pending gap, the remote counters, and the host copy
- * of the ICAO filter, on which every entry's new addresses are inserted again in the device's order before the flip.
- * A piece costs two host synchronisations and a fixed number of launches and copies, whatever its number of entries.
+ * stays on the host per receiver -- the kept incomplete frame, the pending gap, and the host copy of the ICAO filter,
+ * on which every entry's new addresses are inserted again in the device's order before the flip.  The remote counters
+ * are the group's (msd_gb_view.remote): the AVR input adds to the same ones.  A piece costs two host synchronisations and a fixed number of launches and copies, whatever its number of entries.
  */
 #include <hip/hip_runtime.h>
 
-#include <cerrno>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "msd_group_beast.h"
+#include "msd_group_scratch.h"
 #include "msd_kernels.h"
+
+using namespace msd_group_scratch;
 
 namespace {
 
@@ -23,13 +23,6 @@ struct Rx {
     uint8_t tail[MSD_FR_TAIL_MAX];
     uint32_t tl = 0;
     uint64_t pending_gap = 0;
-    msd_remote_stats rs{};
-};
-
-struct Buf { /* device (pinned = false) or page-locked host memory */
-    void *p = nullptr;
-    size_t cap = 0;
-    bool pinned = false;
 };
 
 struct State {
@@ -43,54 +36,6 @@ struct State {
                     &newaddr, &hash,  &snaps,   &add_first, &out,  &ctr,       &tot,   &tails_out, &stage,
                     &h_up,    &h_ctr, &h_tot,   &h_tails,   &h_out, &h_new,    &h_stage, &h_snaps};
 };
-
-int fail(const msd_gb_view *v, int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(v->err, v->errlen, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HCK(v, call)                                                                                                   \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-            return fail((v), -EIO, "%s failed: %s", #call, hipGetErrorString(e_));                                     \
-    } while (0)
-
-int grow(const msd_gb_view *v, Buf &b, size_t bytes)
-{
-    if (b.cap >= bytes)
-        return 0;
-    if (b.pinned)
-        (void)hipHostFree(b.p);
-    else
-        (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t cap = bytes + bytes / 4 + 256;
-    const hipError_t e = b.pinned ? hipHostMalloc(&b.p, cap, hipHostMallocDefault) : hipMalloc(&b.p, cap);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        return fail(v, -ENOMEM, "Beast input scratch: %zu bytes of %s memory: %s", cap, b.pinned ? "page-locked" : "device",
-                    hipGetErrorString(e));
-    }
-    b.cap = cap;
-    return 0;
-}
-
-template <class T> T *as(Buf &b)
-{
-    return static_cast<T *>(b.p);
-}
-
-size_t up8(size_t x)
-{
-    return (x + 7u) & ~(size_t)7u;
-}
 
 /* entries [a, b) of the call as one piece */
 int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_device, const msd_gb_input *in, uint32_t a,
@@ -174,14 +119,8 @@ int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_devic
         if ((rc = grow(v, s.h_snaps, sb)) || (rc = grow(v, s.snaps, sb)))
             return rc;
         uint32_t *h = as<uint32_t>(s.h_snaps);
-        for (uint32_t i = a; i < b; ++i, h += MSD_SNAP_WORDS) {
-            const msd_filter *f = in[i].filter;
-            for (uint32_t k = 0; k < 8192; ++k) {
-                h[2 * k] = f->slot[0][k];
-                h[2 * k + 1] = f->slot[1][k];
-            }
-            h[16384] = (uint32_t)f->active;
-        }
+        for (uint32_t i = a; i < b; ++i, h += MSD_SNAP_WORDS)
+            snapshot_of(in[i].filter, h);
         HCK(v, hipMemcpyAsync(s.snaps.p, s.h_snaps.p, sb, hipMemcpyHostToDevice, st));
         snaps = as<uint32_t>(s.snaps);
     }
@@ -280,16 +219,7 @@ int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_devic
         for (uint32_t k = 0; k < (uint32_t)c[MSD_FR_CTR_NEW]; ++k)
             msd_filter_add(I.filter, newaddr[c[MSD_GB_CTR_NEW_FIRST] + k]);
         msd_filter_expire(I.filter, I.now_ms); /* readsb.c:331 */
-        r.rs.remote_received_modes += c[MSD_FR_CTR_MODES];
-        r.rs.remote_received_modeac += c[MSD_FR_CTR_MODEAC];
-        r.rs.remote_rejected_bad += c[MSD_FR_CTR_BAD];
-        r.rs.remote_rejected_unknown_icao += c[MSD_FR_CTR_UNKNOWN];
-        for (int k = 0; k < 3; ++k)
-            r.rs.remote_accepted[k] += c[MSD_FR_CTR_ACC0 + k];
-        r.rs.frames += c[MSD_FR_CTR_FRAMES];
-        r.rs.other_frames += c[MSD_FR_CTR_OTHER];
-        r.rs.garbage_bytes += c[MSD_FR_CTR_GARBAGE];
-        r.rs.tile_rewalks += c[MSD_FR_CTR_REWALKS];
+        add_remote(v->remote[I.receiver], c);
         if (I.nbytes) { /* what its next entry starts with: the incomplete frame, or the bytes since the last frame as a gap */
             if ((uint32_t)c[MSD_FR_CTR_EXIT] & MSD_FR_INC) {
                 r.tl = (uint32_t)c[MSD_GB_CTR_NTL];
@@ -349,26 +279,13 @@ void msd_gb_reset_receiver(void *state, uint32_t receiver)
         s->rx[receiver] = Rx();
 }
 
-void msd_gb_get_stats(const void *state, uint32_t receiver, msd_remote_stats *st)
-{
-    const State *s = static_cast<const State *>(state);
-    if (s && receiver < s->rx.size())
-        *st = s->rx[receiver].rs;
-    else
-        memset(st, 0, sizeof *st);
-}
-
 void msd_gb_free(void *state)
 {
     State *s = static_cast<State *>(state);
     if (!s)
         return;
-    for (Buf *b : s->all) {
-        if (b->pinned)
-            (void)hipHostFree(b->p);
-        else
-            (void)hipFree(b->p);
-    }
+    for (Buf *b : s->all)
+        release(*b);
     delete s;
 }
 

@@ -86,6 +86,11 @@ int msd_gb_launch_chain_decode(const uint8_t *src, const msd_fr_tables *t, const
 /* Stage 3: first adds per (entry, address), the ordered inserts one workgroup per entry, verdicts and records.
  * hslots a power of two >= 2 * nadds when nadds > 0. */
 int msd_gb_launch_filter(uint32_t nnodes, uint32_t nadds, const msd_fr_tables *t, const msd_gb_scratch *s, void *stream);
+/* The same stage over records that are framed already (the AVR text input, msd_group_avr.h): record k is in[k], parsed
+ * as msd_avr_parse_line leaves it; nodes[k] is any position of its entry's segment (its line's '\n'), cnt[] the
+ * tiles' first records.  The records are written from `in`; buf, info and the chain arrays are not read. */
+int msd_gb_launch_filter_records(const msd_message *in, uint32_t nnodes, uint32_t nadds, const msd_fr_tables *t,
+                                 const msd_gb_scratch *s, void *stream);
 
 /* ---- the driver (msd_group_beast.cpp) ---- */
 typedef struct msd_gb_input { /* one entry of a call, checked by the caller */
@@ -105,7 +110,8 @@ typedef struct msd_gb_view { /* what the driver needs of a group */
     msd_fr_tables tables;
     uint32_t *d_snaps; /* the receivers' resident snapshots ([max_receivers][MSD_SNAP_WORDS]); NULL: a group that
                           resolves on the host, the call then uploads the snapshots of its own receivers */
-    void **state;      /* created by the first call */
+    msd_remote_stats *remote; /* [max_receivers] the receivers' remote counters, which both inputs add to */
+    void **state;      /* the driver's own, created by its first call */
     char *err;
     size_t errlen;
 } msd_gb_view;
@@ -114,7 +120,6 @@ typedef struct msd_gb_view { /* what the driver needs of a group */
 int msd_gb_accept(const msd_gb_view *v, const void *bytes, int on_device, const msd_gb_input *in, uint32_t n,
                   msd_group_message_fn sink, void *user);
 void msd_gb_reset_receiver(void *state, uint32_t receiver);
-void msd_gb_get_stats(const void *state, uint32_t receiver, msd_remote_stats *st);
 void msd_gb_free(void *state);
 
 #ifdef __cplusplus

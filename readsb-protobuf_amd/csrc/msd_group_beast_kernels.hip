@@ -560,6 +560,34 @@ __global__ void __launch_bounds__(NT) msd_gb_records_kernel(const uint8_t *buf, 
     finish_record(o, f.d, f.ts, f.level, E.now_ms, ctr + (size_t)ei * CW);
 }
 
+/* the records of an input that is framed already (AVR text): record k from in[k] instead of a frame of `buf`, with its
+ * entry's repair level, clock and counters */
+__global__ void __launch_bounds__(NT) msd_gb_records_in_kernel(const msd_message *in, uint32_t nnodes,
+                                                              const msd_gb_entry *ent, const uint32_t *tile_ent,
+                                                              msd_fr_tables T, const uint32_t *nodes, const uint8_t *cls,
+                                                              const uint32_t *off, msd_message *out,
+                                                              unsigned long long *ctr)
+{
+    const uint32_t k = blockIdx.x * NT + threadIdx.x;
+    if (k >= nnodes || off[k + 1] == off[k])
+        return;
+    const uint32_t ei = tile_ent[nodes[k] / FT];
+    const msd_gb_entry &E = ent[ei];
+    const msd_message &m = in[k];
+    msd_message &o = out[off[k]];
+    if (cls[k] == MSD_FR_C_MODEAC) {
+        modeac_record(o, m.msg, m.timestampMsg, m.signalLevel, E.now_ms);
+        return;
+    }
+    Decoded d;
+    const int nb = m.msgbits == 112 ? 14 : 7;
+    for (int j = 0; j < 14; ++j)
+        d.msg[j] = j < nb ? m.msg[j] : 0;
+    T.nfix = (int)MSD_GB_OPT_NFIX(E.opt);
+    decide(T, nb, d);
+    finish_record(o, d, m.timestampMsg, m.signalLevel, E.now_ms, ctr + (size_t)ei * CW);
+}
+
 /* every entry's range of `out` */
 __global__ void __launch_bounds__(NT) msd_gb_ranges_kernel(const msd_gb_entry *ent, uint32_t n, const uint32_t *cnt,
                                                           const uint32_t *off, unsigned long long *ctr)
@@ -612,12 +640,9 @@ extern "C" int msd_gb_launch_chain_decode(const uint8_t *src, const msd_fr_table
     return check(hipGetLastError());
 }
 
-extern "C" int msd_gb_launch_filter(uint32_t nnodes, uint32_t nadds, const msd_fr_tables *t, const msd_gb_scratch *s,
-                                    void *stream)
+/* stage 3 up to the flags of the records and their offsets: the same for frames of `buf` and for parsed records */
+static void filter_stage(uint32_t nnodes, uint32_t nadds, const msd_gb_scratch *s, hipStream_t st)
 {
-    hipStream_t st = (hipStream_t)stream;
-    if (nnodes == 0) /* no message: the counters stay as the decode left them */
-        return 0;
     const uint32_t n = s->n;
     if (nadds) {
         hipLaunchKernelGGL(msd_gb_first_add_kernel, dim3(blocks(nnodes)), dim3(NT), 0, st, nnodes, s->tile_ent, s->nodes,
@@ -633,8 +658,30 @@ extern "C" int msd_gb_launch_filter(uint32_t nnodes, uint32_t nadds, const msd_f
     hipLaunchKernelGGL(msd_gb_verdict_kernel, dim3(blocks(nnodes)), dim3(NT), 0, st, nnodes, s->ent, s->tile_ent,
                        s->nodes, s->cls, s->addr, s->hash, nadds ? s->hslots : 0u, s->snaps, s->flags, s->ctr);
     scan_excl(s->flags, s->off, nnodes, s->scan_tmp, st);
+}
+
+extern "C" int msd_gb_launch_filter(uint32_t nnodes, uint32_t nadds, const msd_fr_tables *t, const msd_gb_scratch *s,
+                                    void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (nnodes == 0) /* no message: the counters stay as the decode left them */
+        return 0;
+    filter_stage(nnodes, nadds, s, st);
     hipLaunchKernelGGL(msd_gb_records_kernel, dim3(blocks(nnodes)), dim3(NT), 0, st, s->buf, nnodes, s->ent, s->tile_ent,
                        *t, s->nodes, s->info, s->cls, s->off, s->out, s->ctr);
-    hipLaunchKernelGGL(msd_gb_ranges_kernel, dim3(blocks(n)), dim3(NT), 0, st, s->ent, n, s->cnt, s->off, s->ctr);
+    hipLaunchKernelGGL(msd_gb_ranges_kernel, dim3(blocks(s->n)), dim3(NT), 0, st, s->ent, s->n, s->cnt, s->off, s->ctr);
+    return check(hipGetLastError());
+}
+
+extern "C" int msd_gb_launch_filter_records(const msd_message *in, uint32_t nnodes, uint32_t nadds, const msd_fr_tables *t,
+                                            const msd_gb_scratch *s, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (nnodes == 0)
+        return 0;
+    filter_stage(nnodes, nadds, s, st);
+    hipLaunchKernelGGL(msd_gb_records_in_kernel, dim3(blocks(nnodes)), dim3(NT), 0, st, in, nnodes, s->ent, s->tile_ent,
+                       *t, s->nodes, s->cls, s->off, s->out, s->ctr);
+    hipLaunchKernelGGL(msd_gb_ranges_kernel, dim3(blocks(s->n)), dim3(NT), 0, st, s->ent, s->n, s->cnt, s->off, s->ctr);
     return check(hipGetLastError());
 }
