@@ -789,6 +789,50 @@ int msd_group_accept_avr(msd_group *g, const void *bytes, int on_device, const m
                          msd_group_message_fn sink, void *user);
 int msd_group_get_avr_stats(const msd_group *g, uint32_t receiver, msd_avr_stats *st);
 
+/* Decoded fields and wire output for the two remote inputs: the accept calls above with every record's
+ * msd_fields, or with every entry's records as Beast frames or AVR lines, made on the GPU from the records where the
+ * filter stage leaves them.  The sinks are those of msd_group_submit_*_fields and msd_group_submit_*_wire.
+ *
+ * Arguments, checks, errors, piece cutting and delivery order are those of msd_group_accept_beast /
+ * msd_group_accept_avr, and these calls leave exactly what the plain call leaves: the records decided, every
+ * msd_remote_stats and msd_avr_stats counter, the kept frame or line, the pending gap and the discard flag, the filter
+ * afterwards (host copy and resident snapshot), and the repair-level history rule.  A group may mix all six accept
+ * calls and all six submit calls.  Every error leaves the group's state untouched, as in the plain calls.
+ *
+ * Fields calls: the sink gets every record the plain call would deliver, with *fields == msd_decode_fields(mm, NULL,
+ * ...).  carry is always NULL, also for Mode A/C records: the reference decodes every remote frame into a freshly zeroed
+ * message (net_io.c:1538), so nothing carries from one type '1' frame to the next, unlike the demodulator's per-buffer
+ * record.  The group must have been created with MSD_CFG_DECODE_FIELDS: otherwise -EINVAL with the group's state
+ * untouched, the rule of msd_group_submit_*_fields.
+ *
+ * Wire calls: format is MSD_WIRE_BEAST, MSD_WIRE_AVR or MSD_WIRE_AVR_MLAT, flags 0 or MSD_WIRE_VERBATIM; any input
+ * format may go out in any output format.  The sink is called exactly once per entry, in entry order, also for entries
+ * with nbytes == 0 and entries that yield no record (nbytes 0 then).  bytes equals the concatenation, in delivery
+ * order, of msd_beast_frame_out / msd_avr_line_out (libmsd_host.so) over the records the plain call delivers for that
+ * entry, with the same format and verbatim flag; nmessages is the number of those records, forwarded or not, as
+ * msd_group_submit_*_wire counts.  A record with correctedbits == 2 produces bytes only with MSD_WIRE_VERBATIM.  An AVR
+ * entry without MSD_AVR_KEEP_TIMESTAMP has timestamp 0 and therefore goes out as a '*' line under MSD_WIRE_AVR_MLAT
+ * too.  -EINVAL for an unknown format or flag bit, with the group's state untouched.  bytes is valid until the sink
+ * returns.
+ *
+ * The number of launches and of host synchronisations per piece does not depend on n, and there is no synchronisation
+ * beyond the two a piece has in the plain calls: the kernels are queued between the filter stage and the second one;
+ * the fields cross in a copy of that synchronisation, the wire bytes are written to page-locked memory directly.
+ * Memory, made by the first such call and grown to the largest piece seen, per candidate record of a piece -- the
+ * frames and lines that pass the CRC, an upper bound of the delivered messages, by which the buffers and the fields'
+ * copy are sized: fields, 140 bytes of device and of page-locked memory; wire, at most 44 bytes (MSD_WIRE_MAX) of
+ * page-locked memory and 5 bytes of device memory, 2 more with MSD_WIRE_VERBATIM (the repaired bit positions, which the
+ * records kernel then leaves beside the records: no search); and 8 bytes of page-locked memory per entry for the
+ * per-entry range words. */
+int msd_group_accept_beast_fields(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
+                                  msd_group_fields_fn sink, void *user);
+int msd_group_accept_avr_fields(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
+                                msd_group_fields_fn sink, void *user);
+int msd_group_accept_beast_wire(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
+                                int format, uint32_t flags, msd_group_wire_fn sink, void *user);
+int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
+                              int format, uint32_t flags, msd_group_wire_fn sink, void *user);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,8 @@ EXPORTS = [
     "msd_group_submit_device_fields", "msd_group_submit_host_fields",
     "msd_wire_encode", "msd_group_submit_device_wire", "msd_group_submit_host_wire",
     "msd_group_accept_beast", "msd_group_get_remote_stats", "msd_group_accept_avr", "msd_group_get_avr_stats",
+    "msd_group_accept_beast_fields", "msd_group_accept_avr_fields", "msd_group_accept_beast_wire",
+    "msd_group_accept_avr_wire",
 ]
 
 _lib = None
@@ -730,6 +732,13 @@ def _group_lib():
         L.msd_group_accept_avr.restype = C.c_int
         L.msd_group_accept_avr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroupAvrEntry), C.c_uint32,
                                            C.c_void_p, C.c_void_p]
+        for f, E in ((L.msd_group_accept_beast_fields, GroupBeastEntry), (L.msd_group_accept_avr_fields, GroupAvrEntry)):
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(E), C.c_uint32, C.c_void_p, C.c_void_p]
+        for f, E in ((L.msd_group_accept_beast_wire, GroupBeastEntry), (L.msd_group_accept_avr_wire, GroupAvrEntry)):
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(E), C.c_uint32, C.c_int, C.c_uint32, C.c_void_p,
+                          C.c_void_p]
         L.msd_group_get_avr_stats.restype = C.c_int
         L.msd_group_get_avr_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(AvrStats)]
         L._group_bound = True
@@ -900,15 +909,8 @@ class ReceiverGroup:
         keep_timestamp sets MSD_AVR_KEEP_TIMESTAMP in every entry's flags."""
         return ReceiverGroup._remote_entries(GroupAvrEntry, chunks, now_ms, AVR_KEEP_TIMESTAMP if keep_timestamp else 0)
 
-    def _accept_remote(self, call, what, ent, n, data, as_dict, deliver):
-        rx, raw = [], []
-
-        def sink(receiver, mm, _user):
-            rx.append(receiver)
-            raw.append(C.string_at(mm, MESSAGE_DTYPE.itemsize))
-
-        fn = _GROUP_SINK(sink)  # (kept alive until the call returns)
-        cb = C.cast(fn, C.c_void_p) if deliver else None
+    def _remote_call(self, call, what, ent, n, data, cb, extra=()):
+        """One accept call: the byte array as a device or host pointer, `extra` between n and the sink."""
         need = max((ent[i].offset + ent[i].nbytes for i in range(n)), default=0)
         if hasattr(data, "data_ptr") and getattr(data, "is_cuda", False):
             if not data.is_contiguous():
@@ -917,14 +919,24 @@ class ReceiverGroup:
                 raise ValueError(f"the entries need {need} bytes")
             import torch
             torch.cuda.current_stream(data.device).synchronize()  # the group reads it on its own stream
-            self._check(call(self._h, C.c_void_p(data.data_ptr()), 1, ent, n, cb, None))
+            self._check(call(self._h, C.c_void_p(data.data_ptr()), 1, ent, n, *extra, cb, None))
         else:
             arr = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
                 np.ascontiguousarray(data).view(np.uint8).reshape(-1)
             if arr.size < need:
                 raise ValueError(f"the entries need {need} bytes")
             keep = arr if arr.size else np.zeros(1, dtype=np.uint8)  # a non-NULL pointer for entries that are all empty
-            self._check(call(self._h, keep.ctypes.data, 0, ent, n, cb, None))
+            self._check(call(self._h, keep.ctypes.data, 0, ent, n, *extra, cb, None))
+
+    def _accept_remote(self, call, what, ent, n, data, as_dict, deliver):
+        rx, raw = [], []
+
+        def sink(receiver, mm, _user):
+            rx.append(receiver)
+            raw.append(C.string_at(mm, MESSAGE_DTYPE.itemsize))
+
+        fn = _GROUP_SINK(sink)  # (kept alive until the call returns)
+        self._remote_call(call, what, ent, n, data, C.cast(fn, C.c_void_p) if deliver else None)
         res = np.zeros(len(rx), dtype=GROUP_MESSAGE_DTYPE)
         if rx:
             res["receiver"] = rx
@@ -933,6 +945,28 @@ class ReceiverGroup:
             return res
         return {int(ent[i].receiver): _raw_copy(np.ascontiguousarray(res["m"][res["receiver"] == ent[i].receiver]))
                 for i in range(n)}
+
+    def _accept_remote_fields(self, call, what, ent, n, data, deliver):
+        per = {int(ent[i].receiver): [] for i in range(n)}
+
+        def sink(receiver, mm, ff, _user):
+            per[receiver].append((np.frombuffer(C.string_at(mm, MESSAGE_DTYPE.itemsize), dtype=MESSAGE_DTYPE)[0],
+                                  np.frombuffer(C.string_at(ff, FIELDS_DTYPE.itemsize), dtype=FIELDS_DTYPE)[0]))
+
+        fn = _GROUP_FIELDS_SINK(sink)  # (kept alive until the call returns)
+        self._remote_call(call, what, ent, n, data, C.cast(fn, C.c_void_p) if deliver else None)
+        return per
+
+    def _accept_remote_wire(self, call, what, ent, n, data, format, verbatim, deliver):
+        got = []
+
+        def sink(receiver, b, nbytes, nmessages, _user):
+            got.append((receiver, C.string_at(b, nbytes) if nbytes else b"", nmessages))
+
+        fn = _GROUP_WIRE_SINK(sink)  # (kept alive until the call returns)
+        self._remote_call(call, what, ent, n, data, C.cast(fn, C.c_void_p) if deliver else None,
+                          (format, WIRE_VERBATIM if verbatim is True else int(verbatim)))
+        return got
 
     def accept_beast(self, chunks, now_ms, as_dict=False, deliver=True, entries=None):
         """msd_group_accept_beast: a piece of the Beast stream of each of any subset of the receivers, decided against
@@ -956,6 +990,34 @@ class ReceiverGroup:
         else:
             (ent, n), data = entries, chunks
         return self._accept_remote(_group_lib().msd_group_accept_avr, "accept_avr", ent, n, data, as_dict, deliver)
+
+    def accept_beast_fields(self, chunks, now_ms, deliver=True, entries=None):
+        """msd_group_accept_beast_fields (a group made with flags=CFG_DECODE_FIELDS): accept_beast with the decoded
+        fields of every record -- {receiver: [(message, fields), ...]} for the receivers of the call, each list in
+        delivery order, message a MESSAGE_DTYPE and fields a FIELDS_DTYPE record."""
+        ent, n, data = self.beast_entries(chunks, now_ms) if entries is None else (*entries, chunks)
+        return self._accept_remote_fields(_group_lib().msd_group_accept_beast_fields, "accept_beast_fields", ent, n, data,
+                                          deliver)
+
+    def accept_avr_fields(self, chunks, now_ms, keep_timestamp=False, deliver=True, entries=None):
+        """msd_group_accept_avr_fields: the same for accept_avr."""
+        ent, n, data = self.avr_entries(chunks, now_ms, keep_timestamp) if entries is None else (*entries, chunks)
+        return self._accept_remote_fields(_group_lib().msd_group_accept_avr_fields, "accept_avr_fields", ent, n, data,
+                                          deliver)
+
+    def accept_beast_wire(self, chunks, now_ms, format=WIRE_BEAST, verbatim=False, deliver=True, entries=None):
+        """msd_group_accept_beast_wire: accept_beast with every entry's records as Beast frames or AVR lines -- the list
+        of (receiver, bytes, nmessages), one per entry in entry order.  verbatim: a bool, or the flags word itself."""
+        ent, n, data = self.beast_entries(chunks, now_ms) if entries is None else (*entries, chunks)
+        return self._accept_remote_wire(_group_lib().msd_group_accept_beast_wire, "accept_beast_wire", ent, n, data,
+                                        format, verbatim, deliver)
+
+    def accept_avr_wire(self, chunks, now_ms, keep_timestamp=False, format=WIRE_BEAST, verbatim=False, deliver=True,
+                        entries=None):
+        """msd_group_accept_avr_wire: the same for accept_avr."""
+        ent, n, data = self.avr_entries(chunks, now_ms, keep_timestamp) if entries is None else (*entries, chunks)
+        return self._accept_remote_wire(_group_lib().msd_group_accept_avr_wire, "accept_avr_wire", ent, n, data, format,
+                                        verbatim, deliver)
 
     def avr_stats(self, receiver):
         """msd_group_get_avr_stats: one receiver's line counters (zeros before its first AVR entry)."""

@@ -163,12 +163,14 @@ struct Decoded {
     uint8_t msg[14];
     uint32_t crc, addr;
     uint8_t df, msgbits, corrected, cls;
+    uint8_t errbit[2]; /* the repaired bit positions, as diagnose names them (0xff: none) */
 };
 
 /* msg: nbytes (7 or 14) received bytes; the rest zero */
 __device__ void decide(const msd_fr_tables &T, int nbytes, Decoded &d)
 {
     d.corrected = 0;
+    d.errbit[0] = d.errbit[1] = 0xff;
     d.crc = 0;
     d.addr = 0;
     d.df = d.msg[0] >> 3;
@@ -202,6 +204,7 @@ __device__ void decide(const msd_fr_tables &T, int nbytes, Decoded &d)
             }
             d.msg[bit[0] >> 3] ^= (uint8_t)(0x80u >> (bit[0] & 7));
             d.corrected = 1;
+            d.errbit[0] = (uint8_t)bit[0];
             d.addr = ((uint32_t)d.msg[1] << 16) | ((uint32_t)d.msg[2] << 8) | d.msg[3];
             d.cls = MSD_FR_C_TEST;
             return;
@@ -216,8 +219,10 @@ __device__ void decide(const msd_fr_tables &T, int nbytes, Decoded &d)
                 d.cls = MSD_FR_C_BAD;
                 return;
             }
-            for (int j = 0; j < ne; ++j)
+            for (int j = 0; j < ne; ++j) {
                 d.msg[bit[j] >> 3] ^= (uint8_t)(0x80u >> (bit[j] & 7));
+                d.errbit[j] = (uint8_t)bit[j];
+            }
             d.corrected = (uint8_t)ne;
             d.addr = ((uint32_t)d.msg[1] << 16) | ((uint32_t)d.msg[2] << 8) | d.msg[3];
             d.cls = d.addr != aa ? MSD_FR_C_TEST : MSD_FR_C_ACC; /* mode_s.c:522-526 */

@@ -1000,14 +1000,48 @@ int msd_group_get_timing(const msd_group *g, msd_timing *t)
     return msd_get_timing(g->ctx, t);
 }
 
+/* the output of a fields or wire accept call (out = NULL: a plain call), checked as group_submit checks its own */
+static int group_check_out(msd_group *g, const msd_gb_out *out)
+{
+    if (!out)
+        return 0;
+    if (out->want_fields && !g->ctx->want_fields)
+        return gfail(g, -EINVAL, "the group was created without MSD_CFG_DECODE_FIELDS");
+    if (out->want_wire && ((out->format != MSD_WIRE_BEAST && out->format != MSD_WIRE_AVR && out->format != MSD_WIRE_AVR_MLAT) ||
+                           (out->verbatim & ~(int)MSD_WIRE_VERBATIM)))
+        return gfail(g, -EINVAL, "wire output: unknown format %d or flags 0x%x", out->format, (unsigned)out->verbatim);
+    return 0;
+}
+
+static msd_gb_out fields_out(msd_group_fields_fn sink)
+{
+    msd_gb_out o{};
+    o.want_fields = 1;
+    o.fsink = sink;
+    return o;
+}
+
+/* (verbatim carries the call's flags until group_check_out has seen them: MSD_WIRE_VERBATIM is 1) */
+static msd_gb_out wire_out(int format, uint32_t flags, msd_group_wire_fn sink)
+{
+    msd_gb_out o{};
+    o.want_wire = 1;
+    o.wsink = sink;
+    o.format = format;
+    o.verbatim = (int)flags;
+    return o;
+}
+
 /* Beast input per receiver: the checks that leave the group untouched, each entry's receiver options, then the call
  * (msd_group_beast.cpp) */
-int msd_group_accept_beast(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
-                           msd_group_message_fn sink, void *user)
+static int group_accept_beast(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
+                              msd_group_message_fn sink, const msd_gb_out *out, void *user)
 {
     if (!g)
         return -EINVAL;
     msd_ctx *c = g->ctx;
+    if (int rc = group_check_out(g, out))
+        return rc;
     if (n > g->max_receivers)
         return gfail(g, -EINVAL, "Beast entries: more than max_receivers");
     if (n && (!e || !bytes))
@@ -1050,10 +1084,30 @@ int msd_group_accept_beast(msd_group *g, const void *bytes, int on_device, const
         in[i].mode_ac = r.mode_ac ? 1 : 0;
         r.history = true; /* the repair level is fixed from here on, as by a buffer */
     }
-    rc = msd_gb_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, user);
+    rc = msd_gb_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, out, user);
     if (rc)
         c->failed = true;
     return rc;
+}
+
+int msd_group_accept_beast(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
+                           msd_group_message_fn sink, void *user)
+{
+    return group_accept_beast(g, bytes, on_device, e, n, sink, nullptr, user);
+}
+
+int msd_group_accept_beast_fields(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
+                                  msd_group_fields_fn sink, void *user)
+{
+    const msd_gb_out o = fields_out(sink);
+    return group_accept_beast(g, bytes, on_device, e, n, nullptr, &o, user);
+}
+
+int msd_group_accept_beast_wire(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
+                                int format, uint32_t flags, msd_group_wire_fn sink, void *user)
+{
+    const msd_gb_out o = wire_out(format, flags, sink);
+    return group_accept_beast(g, bytes, on_device, e, n, nullptr, &o, user);
 }
 
 int msd_group_get_remote_stats(const msd_group *g, uint32_t receiver, msd_remote_stats *st)
@@ -1065,12 +1119,14 @@ int msd_group_get_remote_stats(const msd_group *g, uint32_t receiver, msd_remote
 }
 
 /* AVR text input per receiver: the same checks, the entries' flags, then the call (msd_group_avr.cpp) */
-int msd_group_accept_avr(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
-                         msd_group_message_fn sink, void *user)
+static int group_accept_avr(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
+                            msd_group_message_fn sink, const msd_gb_out *out, void *user)
 {
     if (!g)
         return -EINVAL;
     msd_ctx *c = g->ctx;
+    if (int rc = group_check_out(g, out))
+        return rc;
     if (n > g->max_receivers)
         return gfail(g, -EINVAL, "AVR entries: more than max_receivers");
     if (n && (!e || !bytes))
@@ -1114,10 +1170,30 @@ int msd_group_accept_avr(msd_group *g, const void *bytes, int on_device, const m
         in[i].mode_ac = r.mode_ac ? 1 : 0;
         r.history = true; /* the repair level is fixed from here on, as by a buffer */
     }
-    rc = msd_ga_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, user);
+    rc = msd_ga_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, out, user);
     if (rc)
         c->failed = true;
     return rc;
+}
+
+int msd_group_accept_avr(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
+                         msd_group_message_fn sink, void *user)
+{
+    return group_accept_avr(g, bytes, on_device, e, n, sink, nullptr, user);
+}
+
+int msd_group_accept_avr_fields(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
+                                msd_group_fields_fn sink, void *user)
+{
+    const msd_gb_out o = fields_out(sink);
+    return group_accept_avr(g, bytes, on_device, e, n, nullptr, &o, user);
+}
+
+int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
+                              int format, uint32_t flags, msd_group_wire_fn sink, void *user)
+{
+    const msd_gb_out o = wire_out(format, flags, sink);
+    return group_accept_avr(g, bytes, on_device, e, n, nullptr, &o, user);
 }
 
 int msd_group_get_avr_stats(const msd_group *g, uint32_t receiver, msd_avr_stats *st)

@@ -63,9 +63,9 @@ typedef struct msd_ga_input { /* one entry of a call, checked by the caller */
     int mode_ac;        /* its Mode A/C switch */
 } msd_ga_input;
 
-/* 0, or a negative errno with the text in v->err; -EIO leaves the receivers' state undefined */
+/* 0, or a negative errno with the text in v->err; -EIO leaves the receivers' state undefined.  out: as msd_gb_accept */
 int msd_ga_accept(const msd_gb_view *v, const void *bytes, int on_device, const msd_ga_input *in, uint32_t n,
-                  msd_group_message_fn sink, void *user);
+                  msd_group_message_fn sink, const msd_gb_out *out, void *user);
 void msd_ga_reset_receiver(void *state, uint32_t receiver);
 void msd_ga_get_stats(const void *state, uint32_t receiver, msd_avr_stats *st);
 void msd_ga_free(void *state);

@@ -31,6 +31,7 @@ struct State {
         newaddr, hash, snaps, add_first, out, ctr, tot, tails_out, stage;
     Buf h_up{nullptr, 0, true}, h_ctr{nullptr, 0, true}, h_tot{nullptr, 0, true}, h_tails{nullptr, 0, true},
         h_out{nullptr, 0, true}, h_new{nullptr, 0, true}, h_stage{nullptr, 0, true}, h_snaps{nullptr, 0, true};
+    OutBufs ob; /* of the fields and wire calls, made by the first of them */
     Buf *all[35] = {&up,      &buf,   &first,   &nxt,  &succ,      &info,      &mark,  &exitl, &entry,
                     &good,    &cnt,   &nodes,   &cls,  &addr,      &flags,     &off,   &scan_tmp, &newlist,
                     &newaddr, &hash,  &snaps,   &add_first, &out,  &ctr,       &tot,   &tails_out, &stage,
@@ -39,7 +40,7 @@ struct State {
 
 /* entries [a, b) of the call as one piece */
 int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_device, const msd_gb_input *in, uint32_t a,
-              uint32_t b, msd_group_message_fn sink, void *user)
+              uint32_t b, msd_group_message_fn sink, const msd_gb_out *out, void *user)
 {
     hipStream_t st = static_cast<hipStream_t>(v->stream);
     const uint32_t n = b - a;
@@ -185,12 +186,18 @@ int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_devic
     if ((rc = grow(v, s.h_out, sizeof(msd_message) * ((size_t)ncand + 1))) ||
         (rc = grow(v, s.h_new, sizeof(uint32_t) * ((size_t)nadds + 1))))
         return rc;
+    if ((rc = out_errbits(v, s.ob, out, ncand, &x.errbits)))
+        return rc;
     if ((rc = msd_gb_launch_filter(nnodes, nadds, &v->tables, &x, st)))
         return fail(v, rc, "Beast input: filter kernels failed to launch");
     if (v->d_snaps && /* the resident snapshots: every entry's inserts, then its flip */
         (rc = msd_launch_group_filter_apply(v->d_snaps, n, reinterpret_cast<const uint32_t *>(du + o_slot), x.add_first,
                                             x.newaddr, reinterpret_cast<const uint32_t *>(du + o_flip), st)))
         return fail(v, rc, "Beast input: group filter kernel launch failed");
+    /* a fields or wire call: the output stage over the piece's records, whose number only the device knows */
+    const bool queued = out && nnodes && ncand;
+    if (queued && (rc = out_queue(v, s.ob, *out, x.out, x.off + nnodes, ncand, x.ctr, n, x.errbits, st)))
+        return rc;
     /* second synchronisation: counters, kept frames, records and the new-address lists */
     HCK(v, hipMemcpyAsync(s.h_ctr.p, s.ctr.p, 8 * (size_t)MSD_FR_CTR_WORDS * n, hipMemcpyDeviceToHost, st));
     HCK(v, hipMemcpyAsync(s.h_tails.p, s.tails_out.p, (size_t)MSD_FR_TAIL_MAX * n, hipMemcpyDeviceToHost, st));
@@ -207,6 +214,8 @@ int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_devic
             return fail(v, -EIO, "Beast input: receiver %u: incomplete frame of %llu bytes", in[i].receiver, c[MSD_GB_CTR_NTL]);
         if (c[MSD_GB_CTR_REC_FIRST] + c[MSD_FR_CTR_RECORDS] > ncand || c[MSD_GB_CTR_NEW_FIRST] + c[MSD_FR_CTR_NEW] > nadds)
             return fail(v, -EIO, "Beast input: receiver %u: record or address range outside the piece's", in[i].receiver);
+        if (out && !out_range_ok(s.ob, *out, queued, i - a, ncand))
+            return fail(v, -EIO, "Beast input: receiver %u: wire bytes outside the piece's", in[i].receiver);
     }
     const msd_message *recs = as<msd_message>(s.h_out);
     const uint32_t *newaddr = as<uint32_t>(s.h_new);
@@ -230,7 +239,10 @@ int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_devic
                 r.pending_gap = (c[MSD_FR_CTR_NODES] ? 0 : r.pending_gap) + ((E.s1 - E.s0) - c[MSD_FR_CTR_LAST_END]);
             }
         }
-        if (sink)
+        if (out)
+            out_deliver(s.ob, *out, queued, I.receiver, i - a, recs, (uint32_t)c[MSD_GB_CTR_REC_FIRST],
+                        (uint32_t)c[MSD_FR_CTR_RECORDS], user);
+        else if (sink)
             for (uint32_t k = 0; k < (uint32_t)c[MSD_FR_CTR_RECORDS]; ++k)
                 sink(I.receiver, recs + c[MSD_GB_CTR_REC_FIRST] + k, user);
     }
@@ -242,7 +254,7 @@ int run_piece(const msd_gb_view *v, State &s, const uint8_t *bytes, int on_devic
 extern "C" {
 
 int msd_gb_accept(const msd_gb_view *v, const void *bytes, int on_device, const msd_gb_input *in, uint32_t n,
-                  msd_group_message_fn sink, void *user)
+                  msd_group_message_fn sink, const msd_gb_out *out, void *user)
 {
     State *s = static_cast<State *>(*v->state);
     if (!s) {
@@ -264,7 +276,7 @@ int msd_gb_accept(const msd_gb_view *v, const void *bytes, int on_device, const 
         size_t sum = 0;
         while (b < n && (b == a || sum + in[b].nbytes <= MSD_FR_PIECE))
             sum += in[b++].nbytes;
-        const int rc = run_piece(v, *s, static_cast<const uint8_t *>(bytes), on_device, in, a, b, sink, user);
+        const int rc = run_piece(v, *s, static_cast<const uint8_t *>(bytes), on_device, in, a, b, sink, out, user);
         if (rc)
             return rc;
         a = b;
@@ -285,6 +297,8 @@ void msd_gb_free(void *state)
     if (!s)
         return;
     for (Buf *b : s->all)
+        release(*b);
+    for (Buf *b : s->ob.all)
         release(*b);
     delete s;
 }

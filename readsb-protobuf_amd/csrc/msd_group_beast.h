@@ -75,6 +75,8 @@ typedef struct msd_gb_scratch {
     uint32_t *snaps;         /* the receivers' filter snapshots */
     uint32_t *add_first;     /* [n + 1] the entries' ranges in newaddr, for msd_group_filter_apply_kernel */
     msd_message *out;        /* [records] entry after entry, stream order within one */
+    uint8_t *errbits;        /* [records][2] the repaired bit positions of out[k] (0xff: none), for a verbatim wire call;
+                                NULL in every other call */
     unsigned long long *ctr; /* [n][MSD_FR_CTR_WORDS] */
     unsigned long long *tot; /* [MSD_GB_TOT_WORDS] */
 } msd_gb_scratch;
@@ -91,6 +93,31 @@ int msd_gb_launch_filter(uint32_t nnodes, uint32_t nadds, const msd_fr_tables *t
  * tiles' first records.  The records are written from `in`; buf, info and the chain arrays are not read. */
 int msd_gb_launch_filter_records(const msd_message *in, uint32_t nnodes, uint32_t nadds, const msd_fr_tables *t,
                                  const msd_gb_scratch *s, void *stream);
+
+/* ---- the output stage of both remote inputs (msd_group_remote_out_kernels.hip) ---- */
+/* The records of a piece are out[0 .. *count), *count <= bound: `count` is the last word of the filter stage's scan
+ * (off + nnodes), device memory; `bound` what the host knows after the first synchronisation (MSD_GB_TOT_CAND).
+ * fields[k] = msd_decode_fields(out[k], NULL). */
+int msd_gro_launch_fields(const msd_message *out, const uint32_t *count, uint32_t bound, msd_fields *fields, void *stream);
+/* The records as one dense stream of Beast frames or AVR lines in `bytes` (page-locked host memory, at least
+ * MSD_GRO_WIRE_MAX * bound bytes), and every entry's part of it from its counter row: ranges[2 e] its first byte,
+ * ranges[2 e + 1] its bytes (0xffffffff: its records are not among the piece's); ranges is page-locked memory as well.
+ * errbits: NULL, or for verbatim output the repaired positions beside the records (msd_gb_scratch.errbits).
+ * lens [bound], block_sums [bound / 256 + 2] and starts [bound] are device scratch. */
+#define MSD_GRO_WIRE_MAX 44u /* MSD_WIRE_MAX of msd_wire_impl.h */
+int msd_gro_launch_wire(const msd_message *out, const uint32_t *count, uint32_t bound, const unsigned long long *ctr,
+                        uint32_t n, int format, const uint8_t *errbits, uint8_t *lens, uint32_t *block_sums, uint32_t *starts,
+                        uint8_t *bytes, uint32_t *ranges, void *stream);
+
+/* what a call delivers instead of bare records: msd_group_accept_*_fields (want_fields) or _wire (want_wire); a sink
+ * may be NULL */
+typedef struct msd_gb_out {
+    int want_fields, want_wire;
+    msd_group_fields_fn fsink;
+    msd_group_wire_fn wsink;
+    int format;   /* MSD_WIRE_* */
+    int verbatim; /* MSD_WIRE_VERBATIM */
+} msd_gb_out;
 
 /* ---- the driver (msd_group_beast.cpp) ---- */
 typedef struct msd_gb_input { /* one entry of a call, checked by the caller */
@@ -116,9 +143,10 @@ typedef struct msd_gb_view { /* what the driver needs of a group */
     size_t errlen;
 } msd_gb_view;
 
-/* 0, or a negative errno with the text in v->err; -EIO leaves the receivers' state undefined */
+/* 0, or a negative errno with the text in v->err; -EIO leaves the receivers' state undefined.  out: NULL for the plain
+ * call (records to `sink`), else the fields or wire call (`sink` is not used) */
 int msd_gb_accept(const msd_gb_view *v, const void *bytes, int on_device, const msd_gb_input *in, uint32_t n,
-                  msd_group_message_fn sink, void *user);
+                  msd_group_message_fn sink, const msd_gb_out *out, void *user);
 void msd_gb_reset_receiver(void *state, uint32_t receiver);
 void msd_gb_free(void *state);
 

@@ -537,10 +537,21 @@ __global__ void __launch_bounds__(NT) msd_gb_verdict_kernel(uint32_t nnodes, con
     flags[k] = c == MSD_FR_C_ACC || c == MSD_FR_C_ADD || c == MSD_FR_C_TEST || c == MSD_FR_C_MODEAC;
 }
 
+/* for a verbatim wire call (errbits not NULL; msd_group_remote_out_kernels.hip): the one or two bit positions decide
+ * repaired in record r, 0xff for none; every other call passes NULL and stores what it always stored */
+__device__ __forceinline__ void leave_errbits(uint8_t *errbits, uint32_t r, uint32_t e0, uint32_t e1)
+{
+    if (errbits) {
+        errbits[2 * (size_t)r] = (uint8_t)e0;
+        errbits[2 * (size_t)r + 1] = (uint8_t)e1;
+    }
+}
+
 __global__ void __launch_bounds__(NT) msd_gb_records_kernel(const uint8_t *buf, uint32_t nnodes, const msd_gb_entry *ent,
                                                            const uint32_t *tile_ent, msd_fr_tables T,
                                                            const uint32_t *nodes, const uint16_t *info, const uint8_t *cls,
-                                                           const uint32_t *off, msd_message *out, unsigned long long *ctr)
+                                                           const uint32_t *off, msd_message *out, unsigned long long *ctr,
+                                                           uint8_t *errbits)
 {
     const uint32_t k = blockIdx.x * NT + threadIdx.x;
     if (k >= nnodes || off[k + 1] == off[k])
@@ -553,11 +564,13 @@ __global__ void __launch_bounds__(NT) msd_gb_records_kernel(const uint8_t *buf, 
     msd_message &o = out[off[k]];
     if (cls[k] == MSD_FR_C_MODEAC) {
         modeac_record(o, f.d.msg, f.ts, f.level, E.now_ms);
+        leave_errbits(errbits, off[k], 0xffu, 0xffu);
         return;
     }
     T.nfix = (int)MSD_GB_OPT_NFIX(E.opt);
     decide(T, f.nbytes, f.d);
     finish_record(o, f.d, f.ts, f.level, E.now_ms, ctr + (size_t)ei * CW);
+    leave_errbits(errbits, off[k], f.d.errbit[0], f.d.errbit[1]);
 }
 
 /* the records of an input that is framed already (AVR text): record k from in[k] instead of a frame of `buf`, with its
@@ -566,7 +579,7 @@ __global__ void __launch_bounds__(NT) msd_gb_records_in_kernel(const msd_message
                                                               const msd_gb_entry *ent, const uint32_t *tile_ent,
                                                               msd_fr_tables T, const uint32_t *nodes, const uint8_t *cls,
                                                               const uint32_t *off, msd_message *out,
-                                                              unsigned long long *ctr)
+                                                              unsigned long long *ctr, uint8_t *errbits)
 {
     const uint32_t k = blockIdx.x * NT + threadIdx.x;
     if (k >= nnodes || off[k + 1] == off[k])
@@ -577,6 +590,7 @@ __global__ void __launch_bounds__(NT) msd_gb_records_in_kernel(const msd_message
     msd_message &o = out[off[k]];
     if (cls[k] == MSD_FR_C_MODEAC) {
         modeac_record(o, m.msg, m.timestampMsg, m.signalLevel, E.now_ms);
+        leave_errbits(errbits, off[k], 0xffu, 0xffu);
         return;
     }
     Decoded d;
@@ -586,6 +600,7 @@ __global__ void __launch_bounds__(NT) msd_gb_records_in_kernel(const msd_message
     T.nfix = (int)MSD_GB_OPT_NFIX(E.opt);
     decide(T, nb, d);
     finish_record(o, d, m.timestampMsg, m.signalLevel, E.now_ms, ctr + (size_t)ei * CW);
+    leave_errbits(errbits, off[k], d.errbit[0], d.errbit[1]);
 }
 
 /* every entry's range of `out` */
@@ -668,7 +683,7 @@ extern "C" int msd_gb_launch_filter(uint32_t nnodes, uint32_t nadds, const msd_f
         return 0;
     filter_stage(nnodes, nadds, s, st);
     hipLaunchKernelGGL(msd_gb_records_kernel, dim3(blocks(nnodes)), dim3(NT), 0, st, s->buf, nnodes, s->ent, s->tile_ent,
-                       *t, s->nodes, s->info, s->cls, s->off, s->out, s->ctr);
+                       *t, s->nodes, s->info, s->cls, s->off, s->out, s->ctr, s->errbits);
     hipLaunchKernelGGL(msd_gb_ranges_kernel, dim3(blocks(s->n)), dim3(NT), 0, st, s->ent, s->n, s->cnt, s->off, s->ctr);
     return check(hipGetLastError());
 }
@@ -681,7 +696,7 @@ extern "C" int msd_gb_launch_filter_records(const msd_message *in, uint32_t nnod
         return 0;
     filter_stage(nnodes, nadds, s, st);
     hipLaunchKernelGGL(msd_gb_records_in_kernel, dim3(blocks(nnodes)), dim3(NT), 0, st, in, nnodes, s->ent, s->tile_ent,
-                       *t, s->nodes, s->cls, s->off, s->out, s->ctr);
+                       *t, s->nodes, s->cls, s->off, s->out, s->ctr, s->errbits);
     hipLaunchKernelGGL(msd_gb_ranges_kernel, dim3(blocks(s->n)), dim3(NT), 0, st, s->ent, s->n, s->cnt, s->off, s->ctr);
     return check(hipGetLastError());
 }

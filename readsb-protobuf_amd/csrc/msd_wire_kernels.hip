@@ -10,69 +10,19 @@
  *   msd_group_wire_count_kernel leaves the bytes per buffer, msd_group_wire_kernel sums them over the buffers in
  *   front and stores.
  *
- * Both store through wire_store_run: the bytes of up to 256 messages are put together in LDS and leave as
- * whole-wavefront runs of consecutive aligned dwords, for the reason msd_emit_kernel gives for its rows -- the
- * destination may be host memory, where a store per message byte would cost a PCIe write each.
+ * Both store through wire_store_run (msd_wire_store_impl.h): the bytes of up to 256 messages are put together in LDS
+ * and leave as whole-wavefront runs of consecutive aligned dwords, for the reason msd_emit_kernel gives for its rows --
+ * the destination may be host memory, where a store per message byte would cost a PCIe write each.
  */
 #include <hip/hip_runtime.h>
 
 #include "msd_emit_impl.h"
 #include "msd_wire_impl.h"
+#include "msd_wire_store_impl.h"
 
 namespace {
 
-constexpr uint32_t WT = 256;                           /* threads, and messages per LDS image */
-constexpr uint32_t IMAGE_WORDS = WT * MSD_WIRE_MAX / 4 + 2; /* the image starts at the destination's offset in its dword */
-
-/* exclusive prefix of v over the workgroup's 256 threads, and the total; `part`: 4 words of LDS */
-__device__ inline uint32_t block_scan(uint32_t v, uint32_t *part, uint32_t &total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d)
-            incl += up;
-    }
-    __syncthreads(); /* part may still be read from the call before */
-    if (lane == 63)
-        part[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4; ++w)
-        before += w < wave ? part[w] : 0u;
-    total = part[0] + part[1] + part[2] + part[3];
-    return before + incl - v;
-}
-
-/* Where thread t's bytes go in the image of a run that will be stored at dst: the image mirrors the destination's
- * alignment, byte j of it is byte j - (dst & 3) of the run. */
-__device__ __forceinline__ uint8_t *image_at(uint32_t *image, const uint8_t *dst, uint32_t off)
-{
-    return reinterpret_cast<uint8_t *>(image) + (reinterpret_cast<uintptr_t>(dst) & 3u) + off;
-}
-
-/* The len bytes of the image to dst .. dst + len: the aligned dwords inside the run by the whole workgroup, lane after
- * lane; the bytes in front of the first and behind the last of them one by one (at most three each).  Needs a barrier
- * between the image's writes and the call, and one before the image is written again. */
-__device__ inline void wire_store_run(uint8_t *dst, const uint32_t *image, uint32_t len)
-{
-    const uint32_t start = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u), end = start + len;
-    const uint32_t w0 = (start + 3u) / 4u, w1 = end / 4u;
-    const uint32_t head_end = min(4u * w0, end), tail_begin = max(4u * w1, head_end);
-    uint8_t *base = dst - start; /* dword-aligned */
-    uint32_t *d32 = reinterpret_cast<uint32_t *>(base);
-    for (uint32_t w = w0 + threadIdx.x; w < w1; w += WT)
-        d32[w] = image[w];
-    const uint8_t *ib = reinterpret_cast<const uint8_t *>(image);
-    const uint32_t j = threadIdx.x;
-    if (start + j < head_end)
-        base[start + j] = ib[start + j];
-    if (j >= 4 && tail_begin + (j - 4) < end) /* (other lanes than the head's) */
-        base[tail_begin + (j - 4)] = ib[tail_begin + (j - 4)];
-}
+using namespace msd_wire_store; /* WT, IMAGE_WORDS, block_scan, block_sums_scan, image_at, wire_store_run */
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* msd_wire_encode */
@@ -98,18 +48,7 @@ __global__ void __launch_bounds__(WT) msd_wire_len_kernel(const msd_message *msg
 __global__ void __launch_bounds__(WT) msd_wire_scan_kernel(uint32_t *block_sums, uint32_t nblocks)
 {
     __shared__ uint32_t part[4];
-    uint32_t run = 0;
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += WT) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t v = b < nblocks ? block_sums[b] : 0u;
-        uint32_t total;
-        const uint32_t before = block_scan(v, part, total);
-        if (b < nblocks)
-            block_sums[b] = run + before;
-        run += total;
-    }
-    if (threadIdx.x == 0)
-        block_sums[nblocks] = run;
+    block_sums_scan(block_sums, nblocks, part);
 }
 
 __global__ void __launch_bounds__(WT) msd_wire_store_kernel(const msd_message *msgs, uint32_t n, int format, int verbatim,

@@ -1,0 +1,89 @@
+/* msd_wire_store_impl.h -- how the wire kernels lay a stream out and store it: the workgroup scan over the messages'
+ * lengths, the scan over the workgroups' sums, and the LDS image of up to 256 messages that leaves as whole-wavefront
+ * runs of consecutive aligned dwords (the destination may be host memory, where a store per message byte would cost a
+ * PCIe write each).  Shared by msd_wire_kernels.hip and msd_group_remote_out_kernels.hip.  Device code only. */
+#ifndef MSD_WIRE_STORE_IMPL_H
+#define MSD_WIRE_STORE_IMPL_H
+
+#include <hip/hip_runtime.h>
+
+#include "msd_wire_impl.h"
+
+namespace msd_wire_store {
+
+/* threads, and messages per LDS image; tests/test_gpu_receiver_group_remote_wire.py sizes its entries around this value
+ * (its B) to meet the workgroup seams: change both together */
+constexpr uint32_t WT = 256;
+constexpr uint32_t IMAGE_WORDS = WT * MSD_WIRE_MAX / 4 + 2; /* the image starts at the destination's offset in its dword */
+
+/* exclusive prefix of v over the workgroup's 256 threads, and the total; `part`: 4 words of LDS */
+__device__ inline uint32_t block_scan(uint32_t v, uint32_t *part, uint32_t &total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d)
+            incl += up;
+    }
+    __syncthreads(); /* part may still be read from the call before */
+    if (lane == 63)
+        part[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 4; ++w)
+        before += w < wave ? part[w] : 0u;
+    total = part[0] + part[1] + part[2] + part[3];
+    return before + incl - v;
+}
+
+/* block_sums[0 .. nblocks) -> their exclusive prefix in place, block_sums[nblocks] = the stream's length.  The body of
+ * a kernel of one workgroup. */
+__device__ inline void block_sums_scan(uint32_t *block_sums, uint32_t nblocks, uint32_t *part)
+{
+    uint32_t run = 0;
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += WT) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint32_t v = b < nblocks ? block_sums[b] : 0u;
+        uint32_t total;
+        const uint32_t before = block_scan(v, part, total);
+        if (b < nblocks)
+            block_sums[b] = run + before;
+        run += total;
+    }
+    if (threadIdx.x == 0)
+        block_sums[nblocks] = run;
+}
+
+/* Where thread t's bytes go in the image of a run that will be stored at dst: the image mirrors the destination's
+ * alignment, byte j of it is byte j - (dst & 3) of the run. */
+__device__ __forceinline__ uint8_t *image_at(uint32_t *image, const uint8_t *dst, uint32_t off)
+{
+    return reinterpret_cast<uint8_t *>(image) + (reinterpret_cast<uintptr_t>(dst) & 3u) + off;
+}
+
+/* The len bytes of the image to dst .. dst + len: the aligned dwords inside the run by the whole workgroup, lane after
+ * lane; the bytes in front of the first and behind the last of them one by one (at most three each).  Needs a barrier
+ * between the image's writes and the call, and one before the image is written again. */
+__device__ inline void wire_store_run(uint8_t *dst, const uint32_t *image, uint32_t len)
+{
+    const uint32_t start = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u), end = start + len;
+    const uint32_t w0 = (start + 3u) / 4u, w1 = end / 4u;
+    const uint32_t head_end = min(4u * w0, end), tail_begin = max(4u * w1, head_end);
+    uint8_t *base = dst - start; /* dword-aligned */
+    uint32_t *d32 = reinterpret_cast<uint32_t *>(base);
+    for (uint32_t w = w0 + threadIdx.x; w < w1; w += WT)
+        d32[w] = image[w];
+    const uint8_t *ib = reinterpret_cast<const uint8_t *>(image);
+    const uint32_t j = threadIdx.x;
+    if (start + j < head_end)
+        base[start + j] = ib[start + j];
+    if (j >= 4 && tail_begin + (j - 4) < end) /* (other lanes than the head's) */
+        base[tail_begin + (j - 4)] = ib[tail_begin + (j - 4)];
+}
+
+} // namespace msd_wire_store
+
+#endif
