@@ -833,6 +833,92 @@ int msd_group_accept_beast_wire(msd_group *g, const void *bytes, int on_device, 
 int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
                               int format, uint32_t flags, msd_group_wire_fn sink, void *user);
 
+/* ---- positions: where the aircraft is.  A tracker object of its own -- not tied to a context or a group -- that takes
+ * accepted records with their msd_fields from anywhere (msd_collect_fields, the *_fields group calls, msd_accept_* with
+ * msd_decode_fields, a file) in stream order and says for every record whether readsb would have decoded a position
+ * from it, and which one: struct modesMessage's cpr_decoded, decoded_lat, decoded_lon and cpr_relative as
+ * trackUpdateFromMessage leaves them.  On the GPU; libmsd_host.so has the same object on the host
+ * (msd_pos_host_*, same signatures without the device), compiled from the same two headers.
+ *
+ * The rules are the position path of track.c: the whole of cpr.c; accept_data / trackDataValid / trackDataAge
+ * (track.c:170-196, track.h:217-235); speed_check, greatcircle, doGlobalCPR, doLocalCPR and updatePosition up to the
+ * assignment of a->meta.lat/lon and the pos_reliable counters (:260-279, :313-688); the CPR, gs, ias and tas stores and
+ * the per-source ADS-B versions that select gs.v0 or gs.v2 (:1032-1075, :1222-1235, :1313-1329); messageNow() is the
+ * record's sysTimestampMsg (:1010); Mode A/C records and records with msd_fields.addr == 0 are skipped (:999-1008).
+ * Aircraft are keyed by (receiver index, the 25 low bits of msd_fields.addr, MSD_NON_ICAO_ADDRESS included); a record's
+ * receiver index also selects the receiver location and --max-range its checks use.  Not built: decoded_nic /
+ * decoded_rc, the declination, the polar range, SBS and MLAT positions, and every other member of struct aircraft.
+ *
+ * What is exact.  The coordinates: double + - * / floor fmod in the reference's order, nothing contracted; delivered
+ * lat / lon are bit-identical to the reference's whenever the decisions are.
+ * What is not.  greatcircle's sin, cos, acos and atan2 are the device's, not glibc's.  Its distances are never
+ * delivered; they feed three comparisons (the --max-range check, the local range limit, the speed check).  The host
+ * object records the smallest |distance - limit| over every such comparison since its creation or reset as
+ * msd_pos_stats.min_gate_margin_m (+infinity when there was none).  CONTRACT: the device and the host object agree on
+ * every record, bit for bit, of a stream in which no gate comes closer to its limit than 1e-3 m on the host object.
+ * The device reports its own margin, computed with its own distances; it need not equal the host's.
+ *
+ * Parallelism is across aircraft: a call finds or inserts every record's aircraft in an open-addressing table in device
+ * memory, groups the records by aircraft with stable counting passes (stream order kept; no result depends on the order
+ * in which atomic operations land), and one lane per aircraft walks its records in order with the state in registers.
+ * A call whose records all belong to one aircraft is a serial walk by one lane.  Results do not depend on how a stream
+ * is cut into calls. ---- */
+typedef struct msd_pos_receiver {
+    double lat, lon;       /* --lat / --lon, degrees */
+    double max_range_m;    /* Modes.maxRange in metres (--max-range is in nautical miles: x 1852); 0 = no limit */
+    int32_t latlon_valid;  /* MODES_USER_LATLON_VALID */
+    int32_t reserved;      /* 0 */
+} msd_pos_receiver;
+typedef struct msd_pos_config {
+    int32_t device;             /* HIP device ordinal */
+    int32_t filter_persistence; /* --filter-persistence, Modes.filter_persistence (readsb.h:281); 0 = 8, the reference's default */
+    uint32_t capacity;          /* slots of the aircraft table: a power of two, 64 .. 2^24; 136 bytes each, twice */
+    uint32_t receivers;         /* receiver indices 0 .. receivers-1; at least 1, at most 65536 */
+    const msd_pos_receiver *receiver; /* `receivers` entries, or NULL: no receiver has a location or a range limit */
+} msd_pos_config;
+#define MSD_POS_NOT_TRIED (-3)
+typedef struct msd_position { /* 24 bytes */
+    double lat, lon;   /* decoded_lat / decoded_lon; 0 unless decoded */
+    uint8_t decoded;   /* cpr_decoded */
+    uint8_t relative;  /* 0 global CPR, 1 relative to the aircraft's last position, 2 relative to the receiver (cpr_relative
+                          is relative != 0) */
+    uint8_t surface;   /* the record carries a surface position */
+    int8_t result;     /* updatePosition's location_result: 0 / 1 / 2 as `relative`, -1 nothing decoded, -2 the global
+                          decode was implausible or not accepted; MSD_POS_NOT_TRIED: the record brought no new CPR half
+                          (or was skipped) */
+    uint8_t pad[4];
+} msd_position;
+typedef struct msd_pos_stats { /* stats.h: the cpr_* counters updatePosition, doGlobalCPR and doLocalCPR touch */
+    uint64_t cpr_surface, cpr_airborne;
+    uint64_t cpr_global_ok, cpr_global_bad, cpr_global_skipped, cpr_global_range_checks, cpr_global_speed_checks;
+    uint64_t cpr_local_ok, cpr_local_aircraft_relative, cpr_local_receiver_relative, cpr_local_skipped;
+    uint64_t cpr_local_range_checks, cpr_local_speed_checks;
+    uint64_t aircraft;        /* live: slots of the table in use */
+    double min_gate_margin_m; /* see above */
+} msd_pos_stats;
+typedef struct msd_pos msd_pos;
+/* -EINVAL: NULL, a capacity that is no power of two in range, receivers out of range, a negative filter_persistence.
+ * -ENODEV: no GPU (there is no CPU fallback in this library; the host object is msd_pos_host_create). */
+int msd_pos_create(const msd_pos_config *cfg, msd_pos **out);
+void msd_pos_destroy(msd_pos *p);
+const char *msd_pos_last_error(const msd_pos *p);
+int msd_pos_reset(msd_pos *p); /* forget every aircraft and the counters; the receivers keep their locations */
+/* a receiver's location and range from now on; rx == NULL: none */
+int msd_pos_set_receiver(msd_pos *p, uint32_t receiver, const msd_pos_receiver *rx);
+/* n records in stream order: msgs[i] (sysTimestampMsg and msgtype are read), fields[i], and receiver[i] (NULL: all 0).
+ * The three arrays are device memory (on_device = 1; they stay valid until the call returns) or host memory; out is a
+ * host array of n.  Synchronous.  The tracker works on a stream of its own and orders nothing against the caller's:
+ * whatever produces device arrays (a kernel, a copy on another stream) must have completed before the call.  -ENOSPC, with nothing changed: the call's new aircraft do not fit the free slots.
+ * -EINVAL, with nothing changed: NULL with n > 0, n above 2^24, a receiver index out of range.  n == 0 returns 0. */
+int msd_pos_update(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                   int on_device, msd_position *out);
+/* trackRemoveStaleAircraft(now_ms) for these members (track.c:1494-1570; the reference runs it once per second): an
+ * aircraft not seen for 10 minutes, or for 60 s with a single message, is removed and its slot is free again; of the
+ * others, gs / ias / tas / cpr_odd / cpr_even / position expire 70 s after their last update, and pos_reliable is reset
+ * with an expired position. */
+int msd_pos_expire(msd_pos *p, uint64_t now_ms);
+int msd_pos_get_stats(const msd_pos *p, msd_pos_stats *st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -238,6 +238,8 @@ EXPORTS = [
     "msd_group_accept_beast", "msd_group_get_remote_stats", "msd_group_accept_avr", "msd_group_get_avr_stats",
     "msd_group_accept_beast_fields", "msd_group_accept_avr_fields", "msd_group_accept_beast_wire",
     "msd_group_accept_avr_wire",
+    "msd_pos_create", "msd_pos_destroy", "msd_pos_last_error", "msd_pos_reset", "msd_pos_set_receiver", "msd_pos_update",
+    "msd_pos_expire", "msd_pos_get_stats",
 ]
 
 _lib = None
@@ -1071,3 +1073,157 @@ class ReceiverGroup:
     def set_receiver_mode_ac(self, receiver, on):
         """Switch one receiver's Mode A/C on (1) or off (0), from its next buffer; reset_receiver keeps it."""
         self._check(_group_lib().msd_group_set_receiver_mode_ac(self._h, receiver, int(on)))
+
+
+# ---- positions (modes_hip.h "positions"): the tracker on the GPU and its host twin in libmsd_host.so ----
+POSITION_DTYPE = np.dtype([("lat", "<f8"), ("lon", "<f8"), ("decoded", "u1"), ("relative", "u1"), ("surface", "u1"),
+                           ("result", "i1"), ("pad", "u1", (4,))], align=True)
+assert POSITION_DTYPE.itemsize == 24
+POS_NOT_TRIED = -3  # MSD_POS_NOT_TRIED
+HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmsd_host.so")
+
+
+class PosReceiver(C.Structure):
+    _fields_ = [("lat", C.c_double), ("lon", C.c_double), ("max_range_m", C.c_double), ("latlon_valid", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class PosConfig(C.Structure):
+    _fields_ = [("device", C.c_int32), ("filter_persistence", C.c_int32), ("capacity", C.c_uint32),
+                ("receivers", C.c_uint32), ("receiver", C.POINTER(PosReceiver))]
+
+
+class PosStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in (
+        "cpr_surface", "cpr_airborne", "cpr_global_ok", "cpr_global_bad", "cpr_global_skipped", "cpr_global_range_checks",
+        "cpr_global_speed_checks", "cpr_local_ok", "cpr_local_aircraft_relative", "cpr_local_receiver_relative",
+        "cpr_local_skipped", "cpr_local_range_checks", "cpr_local_speed_checks", "aircraft")] + [
+        ("min_gate_margin_m", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _pos_receivers(receivers):
+    """A list of dicts (lat, lon, max_range_m, latlon_valid) -> a PosReceiver array."""
+    arr = (PosReceiver * len(receivers))()
+    for a, r in zip(arr, receivers):
+        r = r or {}
+        a.lat, a.lon = r.get("lat", 0.0), r.get("lon", 0.0)
+        a.max_range_m, a.latlon_valid = r.get("max_range_m", 0.0), int(r.get("latlon_valid", 0))
+    return arr
+
+
+_pos_libs = {}
+
+
+def _pos_lib(host):
+    """The msd_pos_* entries of libmodes_hip.so, or the msd_pos_host_* twin of libmsd_host.so, under common names."""
+    if host not in _pos_libs:
+        L = C.CDLL(HOST_LIB_PATH) if host else lib()
+        pre = "msd_pos_host_" if host else "msd_pos_"
+        f = {k: getattr(L, pre + k) for k in ("create", "destroy", "reset", "set_receiver", "update", "expire", "get_stats")}
+        f["create"].argtypes = [C.POINTER(PosConfig), C.POINTER(C.c_void_p)]
+        f["destroy"].argtypes = [C.c_void_p]
+        f["destroy"].restype = None
+        f["reset"].argtypes = [C.c_void_p]
+        f["set_receiver"].argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PosReceiver)]
+        f["update"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + (
+            [] if host else [C.c_int]) + [C.c_void_p]
+        f["expire"].argtypes = [C.c_void_p, C.c_uint64]
+        f["get_stats"].argtypes = [C.c_void_p, C.POINTER(PosStats)]
+        for k, fn in f.items():
+            if k != "destroy":
+                fn.restype = C.c_int
+        if host:
+            L.msd_pos_host_home_slot.restype = C.c_uint32
+            L.msd_pos_host_home_slot.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+            for name, n_ref, n_int in (("airborne", 0, 5), ("surface", 2, 5), ("relative", 2, 4)):
+                fn = getattr(L, "msd_cpr_host_" + name)
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_double] * n_ref + [C.c_int] * n_int + [C.POINTER(C.c_double)] * 2
+        else:
+            L.msd_pos_last_error.restype = C.c_char_p
+            L.msd_pos_last_error.argtypes = [C.c_void_p]
+        _pos_libs[host] = (L, f)
+    return _pos_libs[host]
+
+
+class PositionTracker:
+    """msd_pos on the GPU (host=False) or its twin on the host (host=True): the same calls, the same results on every
+    stream whose min_gate_margin_m on the twin stays above 1e-3 m."""
+
+    def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False):
+        self.host = host
+        self.L, self.f = _pos_lib(host)
+        receivers = receivers if receivers is not None else [None]
+        self._rx = _pos_receivers(receivers)
+        cfg = PosConfig(device=device, filter_persistence=filter_persistence, capacity=capacity,
+                        receivers=len(receivers), receiver=self._rx)
+        self.h = C.c_void_p()
+        rc = self.f["create"](C.byref(cfg), C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            raise MsdError(f"msd_pos{'_host' if host else ''}_create failed: {rc} ({os.strerror(-rc)})")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.f["destroy"](self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != 0:
+            err = MsdError(f"{what} failed: {rc} ({os.strerror(-rc)})")
+            err.code = rc
+            raise err
+
+    def update(self, messages, fields, receiver=None):
+        """Host record arrays (MESSAGE_DTYPE, FIELDS_DTYPE, optional uint32 receiver indices) -> POSITION_DTYPE array."""
+        n = len(messages)
+        assert len(fields) == n and messages.dtype == MESSAGE_DTYPE and fields.dtype == FIELDS_DTYPE
+        messages, fields = np.ascontiguousarray(messages), np.ascontiguousarray(fields)
+        rx = None if receiver is None else np.ascontiguousarray(receiver, dtype=np.uint32)
+        out = np.zeros(n, dtype=POSITION_DTYPE)
+        args = [self.h, messages.ctypes.data, fields.ctypes.data, None if rx is None else rx.ctypes.data, n]
+        self._check(self.f["update"](*args, *([] if self.host else [0]), out.ctypes.data), "msd_pos_update")
+        return out
+
+    def update_device(self, d_messages, d_fields, n, d_receiver=None):
+        """The same with the records in device memory (pointers); GPU tracker only."""
+        assert not self.host
+        out = np.zeros(n, dtype=POSITION_DTYPE)
+        self._check(self.f["update"](self.h, d_messages, d_fields, d_receiver, n, 1, out.ctypes.data), "msd_pos_update")
+        return out
+
+    def expire(self, now_ms):
+        self._check(self.f["expire"](self.h, now_ms), "msd_pos_expire")
+
+    def reset(self):
+        self._check(self.f["reset"](self.h), "msd_pos_reset")
+
+    def set_receiver(self, receiver, lat=0.0, lon=0.0, max_range_m=0.0, latlon_valid=1):
+        r = PosReceiver(lat=lat, lon=lon, max_range_m=max_range_m, latlon_valid=latlon_valid)
+        self._check(self.f["set_receiver"](self.h, receiver, C.byref(r)), "msd_pos_set_receiver")
+
+    def stats(self):
+        st = PosStats()
+        self._check(self.f["get_stats"](self.h, C.byref(st)), "msd_pos_get_stats")
+        return st.as_dict()
+
+
+def cpr_host(kind, *args):
+    """libmsd_host.so's msd_cpr_host_airborne / _surface / _relative -> (result, lat, lon)."""
+    L, _ = _pos_lib(True)
+    lat, lon = C.c_double(0), C.c_double(0)
+    r = getattr(L, "msd_cpr_host_" + kind)(*args, C.byref(lat), C.byref(lon))
+    return r, lat.value, lon.value
+
+
+def pos_home_slot(receiver, addr, capacity):
+    return _pos_lib(True)[0].msd_pos_host_home_slot(receiver, addr, capacity)

@@ -1,0 +1,219 @@
+/* msd_pos_host.c -- the host twin of the position tracker: msd_cpr_impl.h and msd_pos_impl.h compiled for the host,
+ * the same open-addressing table in host memory, records fed one after the other. */
+#include "msd_pos_host.h"
+
+#include <errno.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "msd_pos_impl.h"
+
+struct msd_pos_host {
+    uint32_t cap, nrx;
+    int fp;
+    uint64_t *keys;
+    msd_pos_aircraft *st;
+    msd_pos_receiver *rx;
+    uint64_t live;
+    msd_pos_acc acc;
+};
+
+int msd_cpr_host_airborne(int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag, double *lat, double *lon)
+{
+    return msd_cpr_airborne(even_lat, even_lon, odd_lat, odd_lon, fflag, lat, lon);
+}
+
+int msd_cpr_host_surface(double reflat, double reflon, int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag,
+                         double *lat, double *lon)
+{
+    return msd_cpr_surface(reflat, reflon, even_lat, even_lon, odd_lat, odd_lon, fflag, lat, lon);
+}
+
+int msd_cpr_host_relative(double reflat, double reflon, int cprlat, int cprlon, int fflag, int surface, double *lat,
+                          double *lon)
+{
+    return msd_cpr_relative(reflat, reflon, cprlat, cprlon, fflag, surface, lat, lon);
+}
+
+uint32_t msd_pos_host_home_slot(uint32_t receiver, uint32_t addr, uint32_t capacity)
+{
+    return msd_pos_hash(msd_pos_key(receiver, addr)) & (capacity - 1u);
+}
+
+static void clear(msd_pos_host *p)
+{
+    for (uint32_t i = 0; i < p->cap; ++i)
+        p->keys[i] = MSD_POS_EMPTY;
+    p->live = 0;
+    memset(&p->acc, 0, sizeof p->acc);
+    p->acc.margin = INFINITY;
+}
+
+int msd_pos_host_create(const msd_pos_config *cfg, msd_pos_host **out)
+{
+    if (!out || !msd_pos_config_ok(cfg))
+        return -EINVAL;
+    msd_pos_host *p = calloc(1, sizeof *p);
+    if (!p)
+        return -ENOMEM;
+    p->cap = cfg->capacity;
+    p->nrx = cfg->receivers;
+    p->fp = cfg->filter_persistence ? cfg->filter_persistence : 8;
+    p->keys = malloc(sizeof(uint64_t) * p->cap);
+    p->st = malloc(sizeof(msd_pos_aircraft) * p->cap);
+    p->rx = calloc(p->nrx, sizeof(msd_pos_receiver));
+    if (!p->keys || !p->st || !p->rx) {
+        msd_pos_host_destroy(p);
+        return -ENOMEM;
+    }
+    if (cfg->receiver)
+        memcpy(p->rx, cfg->receiver, sizeof(msd_pos_receiver) * p->nrx);
+    clear(p);
+    *out = p;
+    return 0;
+}
+
+void msd_pos_host_destroy(msd_pos_host *p)
+{
+    if (!p)
+        return;
+    free(p->keys);
+    free(p->st);
+    free(p->rx);
+    free(p);
+}
+
+int msd_pos_host_reset(msd_pos_host *p)
+{
+    if (!p)
+        return -EINVAL;
+    clear(p);
+    return 0;
+}
+
+int msd_pos_host_set_receiver(msd_pos_host *p, uint32_t receiver, const msd_pos_receiver *rx)
+{
+    if (!p || receiver >= p->nrx)
+        return -EINVAL;
+    if (rx)
+        p->rx[receiver] = *rx;
+    else
+        memset(&p->rx[receiver], 0, sizeof p->rx[receiver]);
+    return 0;
+}
+
+/* the slot of key, inserted when absent (*fresh = 1); -1: the table is full */
+static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
+{
+    uint32_t s = msd_pos_hash(key) & (p->cap - 1u);
+    for (uint32_t probes = 0; probes < p->cap; ++probes, s = (s + 1u) & (p->cap - 1u)) {
+        if (p->keys[s] == key)
+            return s;
+        if (p->keys[s] == MSD_POS_EMPTY) {
+            p->keys[s] = key;
+            msd_pos_aircraft_init(&p->st[s]);
+            *fresh = 1;
+            return s;
+        }
+    }
+    return -1;
+}
+
+int msd_pos_host_update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                        size_t n, msd_position *out)
+{
+    if (!p)
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!msgs || !fields || !out || n > ((size_t)1 << 24))
+        return -EINVAL;
+    if (receiver)
+        for (size_t i = 0; i < n; ++i)
+            if (receiver[i] >= p->nrx)
+                return -EINVAL;
+    uint32_t *slot = malloc(sizeof(uint32_t) * n), *added = malloc(sizeof(uint32_t) * n);
+    size_t nadded = 0;
+    if (!slot || !added) {
+        free(slot);
+        free(added);
+        return -ENOMEM;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        slot[i] = UINT32_MAX;
+        if (msgs[i].msgtype == 32 || fields[i].addr == 0) /* track.c:999-1008 */
+            continue;
+        int fresh = 0;
+        const int64_t s = find_or_insert(p, msd_pos_key(receiver ? receiver[i] : 0u, fields[i].addr), &fresh);
+        if (s < 0) { /* nothing changes: the aircraft this call added leave again */
+            for (size_t k = 0; k < nadded; ++k)
+                p->keys[added[k]] = MSD_POS_EMPTY;
+            free(slot);
+            free(added);
+            return -ENOSPC;
+        }
+        if (fresh)
+            added[nadded++] = (uint32_t)s;
+        slot[i] = (uint32_t)s;
+    }
+    p->live += nadded;
+    for (size_t i = 0; i < n; ++i) {
+        if (slot[i] == UINT32_MAX) {
+            memset(&out[i], 0, sizeof out[i]);
+            out[i].result = MSD_POS_NOT_TRIED;
+            continue;
+        }
+        memset(&out[i], 0, sizeof out[i]);
+        msd_pos_feed(&p->st[slot[i]], &p->rx[receiver ? receiver[i] : 0u], p->fp, msgs[i].sysTimestampMsg, &fields[i],
+                     &out[i], &p->acc);
+    }
+    free(slot);
+    free(added);
+    return 0;
+}
+
+int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
+{
+    if (!p)
+        return -EINVAL;
+    uint64_t removed = 0;
+    for (uint32_t s = 0; s < p->cap; ++s)
+        if (p->keys[s] != MSD_POS_EMPTY && msd_pos_expire_one(&p->st[s], now_ms)) {
+            p->keys[s] = MSD_POS_EMPTY - 1u; /* marked; no key is that large */
+            ++removed;
+        }
+    if (!removed)
+        return 0;
+    /* linear probing has no holes to leave: the survivors are inserted again into an empty table */
+    uint64_t *keys = malloc(sizeof(uint64_t) * p->cap);
+    msd_pos_aircraft *st = malloc(sizeof(msd_pos_aircraft) * p->cap);
+    if (!keys || !st) {
+        free(keys);
+        free(st);
+        return -ENOMEM;
+    }
+    memcpy(keys, p->keys, sizeof(uint64_t) * p->cap);
+    memcpy(st, p->st, sizeof(msd_pos_aircraft) * p->cap);
+    for (uint32_t s = 0; s < p->cap; ++s)
+        p->keys[s] = MSD_POS_EMPTY;
+    for (uint32_t s = 0; s < p->cap; ++s)
+        if (keys[s] < MSD_POS_EMPTY - 1u) {
+            int fresh = 0;
+            p->st[find_or_insert(p, keys[s], &fresh)] = st[s];
+        }
+    p->live -= removed;
+    free(keys);
+    free(st);
+    return 0;
+}
+
+int msd_pos_host_get_stats(const msd_pos_host *p, msd_pos_stats *st)
+{
+    if (!p || !st)
+        return -EINVAL;
+    memcpy(st, p->acc.c, sizeof p->acc.c);
+    st->aircraft = p->live;
+    st->min_gate_margin_m = p->acc.margin;
+    return 0;
+}

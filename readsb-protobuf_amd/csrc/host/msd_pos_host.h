@@ -1,0 +1,34 @@
+/* msd_pos_host.h -- the host twin of the position tracker (modes_hip.h, "positions"): the same object compiled for the
+ * host from msd_cpr_impl.h and msd_pos_impl.h, fed record by record in stream order.  Same signatures as msd_pos_*
+ * without the device; msd_pos_stats.min_gate_margin_m is the margin the contract in modes_hip.h speaks of. */
+#ifndef MSD_POS_HOST_H
+#define MSD_POS_HOST_H
+
+#include "modes_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct msd_pos_host msd_pos_host;
+int msd_pos_host_create(const msd_pos_config *cfg, msd_pos_host **out); /* cfg->device is ignored */
+void msd_pos_host_destroy(msd_pos_host *p);
+int msd_pos_host_reset(msd_pos_host *p);
+int msd_pos_host_set_receiver(msd_pos_host *p, uint32_t receiver, const msd_pos_receiver *rx);
+int msd_pos_host_update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                        size_t n, msd_position *out);
+int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms);
+int msd_pos_host_get_stats(const msd_pos_host *p, msd_pos_stats *st);
+/* the home slot of (receiver, addr) in a table of `capacity` slots (tests build collisions with it) */
+uint32_t msd_pos_host_home_slot(uint32_t receiver, uint32_t addr, uint32_t capacity);
+/* cpr.c's three decoders as msd_cpr_impl.h states them */
+int msd_cpr_host_airborne(int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag, double *lat, double *lon);
+int msd_cpr_host_surface(double reflat, double reflon, int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag,
+                         double *lat, double *lon);
+int msd_cpr_host_relative(double reflat, double reflon, int cprlat, int cprlon, int fflag, int surface, double *lat,
+                          double *lon);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

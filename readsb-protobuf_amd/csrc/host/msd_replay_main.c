@@ -30,6 +30,7 @@
 
 static int g_mlat, g_net_verbatim; /* Modes.mlat, Modes.net_verbatim */
 static uint64_t g_count;
+static int g_pos_failed;
 
 static void print_raw(const msd_message *mm, void *user)
 {
@@ -41,6 +42,33 @@ static void print_raw(const msd_message *mm, void *user)
     for (int j = 0; j < mm->msgbits / 8; j++)
         fprintf(out, "%02x", mm->msg[j]);
     fputs(";\n", out);
+    g_count++;
+}
+
+/* --positions: the --raw line, and behind it "lat,lon" where readsb's tracker would have decoded a position from this
+ * message (msd_pos_update on the GPU, one record at a time, with the fields of msd_decode_fields) */
+static msd_pos *g_pos;
+static void print_raw_positions(const msd_message *mm, void *user)
+{
+    FILE *out = user;
+    msd_fields f;
+    msd_position p;
+    if (g_mlat && mm->timestampMsg)
+        fprintf(out, "@%012" PRIX64, mm->timestampMsg);
+    else
+        fputc('*', out);
+    for (int j = 0; j < mm->msgbits / 8; j++)
+        fprintf(out, "%02x", mm->msg[j]);
+    fputc(';', out);
+    msd_decode_fields(mm, NULL, &f);
+    const int rc = msd_pos_update(g_pos, mm, &f, NULL, 1, 0, &p);
+    if (rc) {
+        fprintf(stderr, "msd_pos_update: %s (%d)\n", msd_pos_last_error(g_pos), rc);
+        g_pos_failed = 1;
+    } else if (p.decoded) {
+        fprintf(out, "%.6f,%.6f", p.lat, p.lon);
+    }
+    fputc('\n', out);
     g_count++;
 }
 
@@ -161,6 +189,10 @@ int main(int argc, char **argv)
     const char *beast_in = NULL, *avr_in = NULL;
     size_t beast_chunk = 65536, avr_chunk = 65536;
     uint64_t now_ms = 0;
+    int want_positions = 0, other_sink = 0;
+    msd_pos_receiver home; /* --lat / --lon / --max-range as readsb spells them (readsb.c: Modes.receiver, Modes.maxRange) */
+    memset(&home, 0, sizeof home);
+    int have_lat = 0, have_lon = 0;
 
     const msd_ifile_hooks hooks = {host_should_exit, NULL, host_at_eof, NULL};
     msd_ifileSetOptionKeys(OptIfileName, OptIfileFormat, OptIfileThrottle, OptIfilePath);
@@ -184,15 +216,19 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--mlat")) g_mlat = 1;
         else if (!strcmp(a, "--net-verbatim")) g_net_verbatim = 1; /* readsb.c: Modes.net_verbatim */
         else if (!strcmp(a, "--stats")) want_stats = 1;
+        else if (!strcmp(a, "--positions")) want_positions = 1;
+        else if (!strcmp(a, "--lat") && next) { home.lat = atof(next); have_lat = 1; ++i; }
+        else if (!strcmp(a, "--lon") && next) { home.lon = atof(next); have_lon = 1; ++i; }
+        else if (!strcmp(a, "--max-range") && next) { home.max_range_m = atof(next) * 1852.0; ++i; } /* nautical miles -> metres */
         else if (!strcmp(a, "--beast-in") && next) { beast_in = next; ++i; }
         else if (!strcmp(a, "--beast-chunk") && next && strtoull(next, NULL, 10) > 0) { beast_chunk = (size_t)strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--avr-in") && next) { avr_in = next; ++i; }
         else if (!strcmp(a, "--avr-chunk") && next && strtoull(next, NULL, 10) > 0) { avr_chunk = (size_t)strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--now-ms") && next) { now_ms = strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--timing")) want_timing = 1; /* one JSON line on stderr: what the run cost (msd_ifileGetTiming) */
-        else if (!strcmp(a, "--no-output")) rx.sink = count_only;
-        else if (!strcmp(a, "--net-raw")) rx.sink = print_net_raw;
-        else if (!strcmp(a, "--beast")) rx.sink = write_beast;
+        else if (!strcmp(a, "--no-output")) { rx.sink = count_only; other_sink = 1; }
+        else if (!strcmp(a, "--net-raw")) { rx.sink = print_net_raw; other_sink = 1; }
+        else if (!strcmp(a, "--beast")) { rx.sink = write_beast; other_sink = 1; }
         else if (!strcmp(a, "--raw") || !strcmp(a, "--quiet")) { /* this tool only has the raw dump */ }
         else if (!strcmp(a, "--device-type") && next) { ++i; /* always ifile */ }
         else if (!strcmp(a, "--device") && next) { rx.device = atoi(next); ++i; }
@@ -205,7 +241,12 @@ int main(int argc, char **argv)
         } else {
             fprintf(stderr, "usage: msd_replay --ifile F [--iformat uc8|sc16|sc16q11] [--fix|--no-fix|--aggressive] [--dcfilter] "
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
-                            "[--device N] [--sc16q11-table-bits N]\n"
+                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM]]\n"
+                            "       --positions: the --raw lines, with \"lat,lon\" behind the ';' of every message from which readsb's tracker\n"
+                            "       would have decoded a position (CPR global and local, its range and speed checks; the coordinates are exact, the\n"
+                            "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
+                            "       receiver's location (both, or neither); --max-range: the absolute maximum range in nautical miles, 0 = none.\n"
+                            "       Also with --beast-in and --avr-in; not with --net-raw, --beast or --no-output.\n"
                             "       msd_replay --beast-in F [--beast-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
                             "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n"
                             "       msd_replay --avr-in F [--avr-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
@@ -213,10 +254,35 @@ int main(int argc, char **argv)
             return 2;
         }
     }
-    if (avr_in)
-        return run_remote_in(avr_in, 1, avr_chunk, now_ms, &rx, want_stats);
-    if (beast_in)
-        return run_remote_in(beast_in, 0, beast_chunk, now_ms, &rx, want_stats);
+    if (want_positions) {
+        if (other_sink) {
+            fprintf(stderr, "--positions prints the --raw lines: not with --net-raw, --beast or --no-output\n");
+            return 2;
+        }
+        if (have_lat != have_lon) {
+            fprintf(stderr, "--lat and --lon go together\n");
+            return 2;
+        }
+        home.latlon_valid = have_lat;
+        msd_pos_config pc;
+        memset(&pc, 0, sizeof pc);
+        pc.device = rx.device;
+        pc.capacity = 1u << 16;
+        pc.receivers = 1;
+        pc.receiver = &home;
+        const int prc = msd_pos_create(&pc, &g_pos);
+        if (prc) {
+            fprintf(stderr, "msd_pos_create failed (%d)\n", prc);
+            return 1;
+        }
+        rx.sink = print_raw_positions;
+    }
+    if (avr_in || beast_in) {
+        const int rc = avr_in ? run_remote_in(avr_in, 1, avr_chunk, now_ms, &rx, want_stats)
+                              : run_remote_in(beast_in, 0, beast_chunk, now_ms, &rx, want_stats);
+        msd_pos_destroy(g_pos);
+        return rc ? rc : g_pos_failed;
+    }
     msd_ifileSetReceiver(&rx);
     if (!msd_ifileOpen()) {
         fprintf(stderr, "%s\n", msd_ifileLastError());
@@ -256,5 +322,6 @@ int main(int argc, char **argv)
         }
     }
     msd_ifileClose();
-    return 0;
+    msd_pos_destroy(g_pos);
+    return g_pos_failed ? 1 : 0;
 }

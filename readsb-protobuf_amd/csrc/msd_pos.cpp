@@ -1,0 +1,276 @@
+/* msd_pos.cpp -- C-ABI of the position tracker (modes_hip.h "positions"): the object, its device memory and the order
+ * in which a call queues the kernels of msd_pos_kernels.hip. */
+#include <errno.h>
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <new>
+#include <vector>
+
+#include "msd_pos.h"
+
+struct msd_pos {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    msd_pos_table tab[2] = {}; /* tab[cur] is live; expiry rebuilds into the other */
+    int cur = 0;
+    uint32_t nrx = 0;
+    int fp = 8;
+    uint64_t live = 0;
+    msd_pos_receiver *d_rx = nullptr;
+    unsigned long long *d_stats = nullptr;
+    uint32_t *d_ctl = nullptr;
+    /* per-call buffers, grown to the largest call seen */
+    size_t cap_n = 0, cap_in = 0;
+    uint32_t *d_slot = nullptr;
+    uint8_t *d_fresh = nullptr;
+    msd_position *d_out = nullptr;
+    uint32_t *d_idx[2] = {nullptr, nullptr}, *d_hist = nullptr;
+    msd_message *d_msgs = nullptr;
+    msd_fields *d_fields = nullptr;
+    uint32_t *d_receiver = nullptr;
+    char err[256] = "";
+};
+
+namespace {
+
+int fail(msd_pos *p, int code, const char *what, hipError_t e)
+{
+    snprintf(p->err, sizeof p->err, "%s: %s", what, hipGetErrorString(e));
+    return code;
+}
+
+#define POS_HIP(p, call)                                                                                              \
+    do {                                                                                                              \
+        const hipError_t e_ = (call);                                                                                 \
+        if (e_ != hipSuccess)                                                                                         \
+            return fail(p, e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO, #call, e_);                                    \
+    } while (0)
+
+int clear(msd_pos *p)
+{
+    unsigned long long init[MSD_POS_DSTATS] = {};
+    const double inf = INFINITY;
+    memcpy(&init[MSD_PC_N], &inf, sizeof inf);
+    msd_pos_launch_fill(p->stream, p->tab[p->cur].keys, p->tab[p->cur].cap);
+    POS_HIP(p, hipGetLastError());
+    POS_HIP(p, hipMemcpyAsync(p->d_stats, init, sizeof init, hipMemcpyHostToDevice, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    p->live = 0;
+    return 0;
+}
+
+template <typename T> void release(T *&ptr)
+{
+    if (ptr)
+        (void)hipFree(ptr);
+    ptr = nullptr;
+}
+
+/* room for a call of n records (and for its inputs, when they come from the host) */
+int reserve(msd_pos *p, size_t n, bool host_input)
+{
+    if (n > p->cap_n) {
+        release(p->d_slot), release(p->d_fresh), release(p->d_out), release(p->d_idx[0]), release(p->d_idx[1]), release(p->d_hist);
+        p->cap_n = 0;
+        const size_t piece = n < MSD_POS_PIECE ? n : MSD_POS_PIECE;
+        const size_t tiles = (piece + MSD_POS_TILE - 1) / MSD_POS_TILE;
+        POS_HIP(p, hipMalloc(&p->d_slot, n * sizeof(uint32_t)));
+        POS_HIP(p, hipMalloc(&p->d_fresh, n));
+        POS_HIP(p, hipMalloc(&p->d_out, n * sizeof(msd_position)));
+        POS_HIP(p, hipMalloc(&p->d_idx[0], piece * sizeof(uint32_t)));
+        POS_HIP(p, hipMalloc(&p->d_idx[1], piece * sizeof(uint32_t)));
+        POS_HIP(p, hipMalloc(&p->d_hist, 256 * tiles * sizeof(uint32_t)));
+        p->cap_n = n;
+    }
+    if (host_input && n > p->cap_in) {
+        release(p->d_msgs), release(p->d_fields), release(p->d_receiver);
+        p->cap_in = 0;
+        POS_HIP(p, hipMalloc(&p->d_msgs, n * sizeof(msd_message)));
+        POS_HIP(p, hipMalloc(&p->d_fields, n * sizeof(msd_fields)));
+        POS_HIP(p, hipMalloc(&p->d_receiver, n * sizeof(uint32_t)));
+        p->cap_in = n;
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int msd_pos_create(const msd_pos_config *cfg, msd_pos **out)
+{
+    if (!out || !msd_pos_config_ok(cfg))
+        return -EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device < 0 || cfg->device >= ndev)
+        return -ENODEV;
+    msd_pos *p = new (std::nothrow) msd_pos;
+    if (!p)
+        return -ENOMEM;
+    p->device = cfg->device;
+    p->nrx = cfg->receivers;
+    p->fp = cfg->filter_persistence ? cfg->filter_persistence : 8;
+    std::vector<msd_pos_receiver> rx(p->nrx);
+    memset(rx.data(), 0, rx.size() * sizeof(msd_pos_receiver));
+    if (cfg->receiver)
+        memcpy(rx.data(), cfg->receiver, rx.size() * sizeof(msd_pos_receiver));
+    const auto build = [&]() -> int {
+        POS_HIP(p, hipSetDevice(p->device));
+        POS_HIP(p, hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+        for (int k = 0; k < 2; ++k) {
+            p->tab[k].cap = cfg->capacity;
+            POS_HIP(p, hipMalloc(&p->tab[k].keys, sizeof(uint64_t) * cfg->capacity));
+            POS_HIP(p, hipMalloc(&p->tab[k].st, sizeof(msd_pos_aircraft) * cfg->capacity));
+        }
+        POS_HIP(p, hipMalloc(&p->d_rx, sizeof(msd_pos_receiver) * p->nrx));
+        POS_HIP(p, hipMalloc(&p->d_stats, sizeof(unsigned long long) * MSD_POS_DSTATS));
+        POS_HIP(p, hipMalloc(&p->d_ctl, sizeof(uint32_t) * MSD_POS_CTL_N));
+        POS_HIP(p, hipMemcpy(p->d_rx, rx.data(), sizeof(msd_pos_receiver) * p->nrx, hipMemcpyHostToDevice));
+        return clear(p);
+    };
+    const int rc = build();
+    if (rc) {
+        msd_pos_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return 0;
+}
+
+void msd_pos_destroy(msd_pos *p)
+{
+    if (!p)
+        return;
+    (void)hipSetDevice(p->device);
+    if (p->stream)
+        (void)hipStreamSynchronize(p->stream);
+    for (int k = 0; k < 2; ++k)
+        release(p->tab[k].keys), release(p->tab[k].st);
+    release(p->d_rx), release(p->d_stats), release(p->d_ctl), release(p->d_slot), release(p->d_fresh), release(p->d_out);
+    release(p->d_idx[0]), release(p->d_idx[1]), release(p->d_hist), release(p->d_msgs), release(p->d_fields),
+        release(p->d_receiver);
+    if (p->stream)
+        (void)hipStreamDestroy(p->stream);
+    delete p;
+}
+
+const char *msd_pos_last_error(const msd_pos *p)
+{
+    return p ? p->err : "no tracker";
+}
+
+int msd_pos_reset(msd_pos *p)
+{
+    if (!p)
+        return -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    return clear(p);
+}
+
+int msd_pos_set_receiver(msd_pos *p, uint32_t receiver, const msd_pos_receiver *rx)
+{
+    if (!p || receiver >= p->nrx)
+        return -EINVAL;
+    msd_pos_receiver r;
+    memset(&r, 0, sizeof r);
+    if (rx)
+        r = *rx;
+    POS_HIP(p, hipSetDevice(p->device));
+    POS_HIP(p, hipMemcpy(p->d_rx + receiver, &r, sizeof r, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int msd_pos_update(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                   int on_device, msd_position *out)
+{
+    if (!p)
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!msgs || !fields || !out || n > MSD_POS_MAX_N)
+        return -EINVAL;
+    if (!on_device && receiver)
+        for (size_t i = 0; i < n; ++i)
+            if (receiver[i] >= p->nrx)
+                return -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    const int rc = reserve(p, n, !on_device);
+    if (rc)
+        return rc;
+    if (!on_device) {
+        POS_HIP(p, hipMemcpyAsync(p->d_msgs, msgs, n * sizeof(msd_message), hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipMemcpyAsync(p->d_fields, fields, n * sizeof(msd_fields), hipMemcpyHostToDevice, p->stream));
+        if (receiver)
+            POS_HIP(p, hipMemcpyAsync(p->d_receiver, receiver, n * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+        msgs = p->d_msgs;
+        fields = p->d_fields;
+        receiver = receiver ? p->d_receiver : nullptr;
+    }
+    const msd_pos_table t = p->tab[p->cur];
+    uint32_t ctl[MSD_POS_CTL_N] = {};
+    POS_HIP(p, hipMemsetAsync(p->d_ctl, 0, sizeof ctl, p->stream));
+    msd_pos_launch_find(p->stream, t, msgs, fields, receiver, p->nrx, (uint32_t)n, p->d_slot, p->d_fresh, p->d_out, p->d_ctl);
+    POS_HIP(p, hipGetLastError());
+    POS_HIP(p, hipMemcpyAsync(ctl, p->d_ctl, sizeof ctl, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    if (ctl[MSD_POS_CTL_FULL] || ctl[MSD_POS_CTL_BAD_RECEIVER]) { /* nothing changes: this call's aircraft leave again */
+        msd_pos_launch_rollback(p->stream, t, p->d_slot, p->d_fresh, (uint32_t)n);
+        POS_HIP(p, hipGetLastError());
+        POS_HIP(p, hipStreamSynchronize(p->stream));
+        snprintf(p->err, sizeof p->err, "%s", ctl[MSD_POS_CTL_BAD_RECEIVER] ? "a receiver index is out of range"
+                                                                           : "the aircraft table is full");
+        return ctl[MSD_POS_CTL_BAD_RECEIVER] ? -EINVAL : -ENOSPC;
+    }
+    p->live += ctl[MSD_POS_CTL_INSERTED];
+    for (size_t base = 0; base < n; base += MSD_POS_PIECE) {
+        const size_t m = n - base < MSD_POS_PIECE ? n - base : MSD_POS_PIECE;
+        msd_pos_launch_piece(p->stream, t, msgs, fields, receiver, p->d_rx, p->fp, (uint32_t)base, (uint32_t)m, p->d_slot,
+                             p->d_idx[0], p->d_idx[1], p->d_hist, p->d_out, p->d_stats);
+        POS_HIP(p, hipGetLastError());
+    }
+    POS_HIP(p, hipMemcpyAsync(out, p->d_out, n * sizeof(msd_position), hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int msd_pos_expire(msd_pos *p, uint64_t now_ms)
+{
+    if (!p)
+        return -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    uint32_t ctl[MSD_POS_CTL_N] = {};
+    POS_HIP(p, hipMemsetAsync(p->d_ctl, 0, sizeof ctl, p->stream));
+    msd_pos_launch_expire(p->stream, p->tab[p->cur], now_ms, p->d_ctl);
+    POS_HIP(p, hipGetLastError());
+    POS_HIP(p, hipMemcpyAsync(ctl, p->d_ctl, sizeof ctl, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    if (!ctl[MSD_POS_CTL_REMOVED])
+        return 0;
+    /* linear probing has no holes to leave: the survivors are inserted again into the other, empty table */
+    const int other = p->cur ^ 1;
+    msd_pos_launch_fill(p->stream, p->tab[other].keys, p->tab[other].cap);
+    msd_pos_launch_rebuild(p->stream, p->tab[p->cur], p->tab[other]);
+    POS_HIP(p, hipGetLastError());
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    p->cur = other;
+    p->live -= ctl[MSD_POS_CTL_REMOVED];
+    return 0;
+}
+
+int msd_pos_get_stats(const msd_pos *p, msd_pos_stats *st)
+{
+    if (!p || !st)
+        return -EINVAL;
+    unsigned long long d[MSD_POS_DSTATS];
+    if (hipSetDevice(p->device) != hipSuccess ||
+        hipMemcpy(d, p->d_stats, sizeof d, hipMemcpyDeviceToHost) != hipSuccess)
+        return -EIO;
+    memcpy(st, d, sizeof(uint64_t) * MSD_PC_N);
+    st->aircraft = p->live;
+    memcpy(&st->min_gate_margin_m, &d[MSD_PC_N], sizeof(double));
+    return 0;
+}
+
+} // extern "C"

@@ -1,0 +1,41 @@
+/* msd_pos.h -- what msd_pos.cpp (the C-ABI of the position tracker) launches from msd_pos_kernels.hip.  Every function
+ * queues kernels on `stream` and returns; all pointers are device memory. */
+#ifndef MSD_POS_H
+#define MSD_POS_H
+
+#include <hip/hip_runtime.h>
+
+#include "msd_pos_impl.h"
+
+#define MSD_POS_TILE 256u          /* records per workgroup of a counting pass */
+#define MSD_POS_PIECE (1u << 20)   /* records grouped and walked at a time; a call of more is cut into pieces */
+#define MSD_POS_MAX_N (1u << 24)   /* records per call */
+/* ctl words of a call */
+enum { MSD_POS_CTL_FULL = 0, MSD_POS_CTL_BAD_RECEIVER = 1, MSD_POS_CTL_INSERTED = 2, MSD_POS_CTL_REMOVED = 3, MSD_POS_CTL_N = 4 };
+/* device counters: MSD_PC_N sums, then the bits of the smallest gate margin (a non-negative double orders as its bits) */
+#define MSD_POS_DSTATS (MSD_PC_N + 1)
+
+typedef struct msd_pos_table {
+    uint64_t *keys;        /* cap entries; MSD_POS_EMPTY = free */
+    msd_pos_aircraft *st;  /* cap entries */
+    uint32_t cap;          /* a power of two */
+} msd_pos_table;
+
+void msd_pos_launch_fill(hipStream_t stream, uint64_t *keys, uint32_t cap);
+/* step 1: slot[i] of every record (cap for a skipped one, whose out[i] is written here), fresh[i] = 1 where this record
+ * inserted its aircraft; ctl says whether the table overflowed or a receiver index was out of range */
+void msd_pos_launch_find(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
+                         const uint32_t *receiver, uint32_t nrx, uint32_t n, uint32_t *slot, uint8_t *fresh, msd_position *out,
+                         uint32_t *ctl);
+void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t *slot, const uint8_t *fresh, uint32_t n);
+/* steps 2 to 4 for records base .. base + n (n <= MSD_POS_PIECE): idx_a / idx_b hold n words each, hist
+ * 256 * ceil(n / MSD_POS_TILE) words */
+void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
+                          const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
+                          uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
+                          msd_position *out, unsigned long long *dstats);
+/* expiry: marks and counts the aircraft to remove (ctl[MSD_POS_CTL_REMOVED]); rebuild inserts the others into `to` */
+void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl);
+void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_table to);
+
+#endif

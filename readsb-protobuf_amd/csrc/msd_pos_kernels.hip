@@ -1,0 +1,290 @@
+/*
+ * msd_pos_kernels.hip -- the position tracker's kernels for gfx950 (modes_hip.h "positions").
+ *
+ * A call over n records runs four steps:
+ *   1. find: one lane per record finds or inserts its aircraft's slot in the open-addressing table (compare-and-swap on
+ *      the key word, linear probing).  Which slot a new aircraft lands in depends on the order the swaps arrive; nothing
+ *      that is delivered depends on the slot, only on the aircraft's own state.
+ *   2. group: the record indices are sorted by slot with least-significant-digit counting passes of 8 bits.  Every pass
+ *      is stable: a record's place is (digit's total in the tiles before) + (its rank among the same digit in its tile),
+ *      the rank from wave ballots and per-wave counts, the totals from integer sums -- no place is handed out by an
+ *      atomic's return value.  After the passes each aircraft's records are contiguous and in stream order.
+ *   3. walk: one lane per aircraft -- the lane at the first record of its run -- loads the state into registers, feeds
+ *      msd_pos_feed one record after the other, stores the state.  A batch of one aircraft is a serial walk by one lane.
+ *   4. each result is written at the record's own index; the counters are summed with integer atomics, the gate margin
+ *      with an integer minimum over the double's bits, both independent of arrival order.
+ * Wave64 throughout: ballots are 64 bits wide and a workgroup of 256 threads is four waves.  The walk is double
+ * precision arithmetic with long dependent chains and divergent branches per aircraft; its rate comes from the number of
+ * aircraft in flight, not from the vector width.
+ */
+#include "msd_pos.h"
+
+namespace {
+
+constexpr uint32_t NT = MSD_POS_TILE;
+constexpr uint64_t TOMB = MSD_POS_EMPTY - 1u; /* a slot whose aircraft expired, until the table is rebuilt */
+
+__global__ void __launch_bounds__(NT) msd_pos_fill_kernel(uint64_t *keys, uint32_t cap)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i < cap)
+        keys[i] = MSD_POS_EMPTY;
+}
+
+/* the slot of key, inserted when absent (*fresh = 1); cap: the table is full */
+__device__ uint32_t find_or_insert(const msd_pos_table &t, uint64_t key, int *fresh)
+{
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(t.keys);
+    uint32_t s = msd_pos_hash(key) & (t.cap - 1u);
+    for (uint32_t probes = 0; probes < t.cap; ++probes, s = (s + 1u) & (t.cap - 1u)) {
+        unsigned long long k = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == MSD_POS_EMPTY) {
+            k = atomicCAS(&keys[s], (unsigned long long)MSD_POS_EMPTY, (unsigned long long)key);
+            if (k == MSD_POS_EMPTY) {
+                *fresh = 1;
+                return s;
+            }
+        }
+        if (k == key)
+            return s;
+    }
+    return t.cap;
+}
+
+__global__ void __launch_bounds__(NT)
+msd_pos_find_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                    uint32_t nrx, uint32_t n, uint32_t *slot, uint8_t *fresh, msd_position *out, uint32_t *ctl)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint32_t r = receiver ? receiver[i] : 0u;
+    const uint32_t addr = fields[i].addr;
+    uint32_t s = t.cap;
+    int f = 0;
+    if (r >= nrx) {
+        atomicOr(&ctl[MSD_POS_CTL_BAD_RECEIVER], 1u);
+    } else if (msgs[i].msgtype != 32 && addr != 0) { /* track.c:999-1008 */
+        s = find_or_insert(t, msd_pos_key(r, addr), &f);
+        if (s == t.cap)
+            atomicOr(&ctl[MSD_POS_CTL_FULL], 1u);
+        if (f) {
+            msd_pos_aircraft_init(&t.st[s]);
+            atomicAdd(&ctl[MSD_POS_CTL_INSERTED], 1u);
+        }
+    }
+    if (s == t.cap) { /* a skipped record; the walk never sees it */
+        msd_position o = {};
+        o.result = MSD_POS_NOT_TRIED;
+        out[i] = o;
+    }
+    slot[i] = s;
+    fresh[i] = (uint8_t)f;
+}
+
+__global__ void __launch_bounds__(NT) msd_pos_rollback_kernel(msd_pos_table t, const uint32_t *slot, const uint8_t *fresh, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i < n && fresh[i])
+        t.keys[slot[i]] = MSD_POS_EMPTY;
+}
+
+/* ---- one counting pass over the piece's n indices: digit = (slot >> shift) & 255 ---- */
+/* the record (relative to the piece) at place e < n.  Every pass writes a permutation of 0 .. n-1: a tile's 256 counts
+ * cover each of its records once, so the scanned counts plus a record's rank among its tile's records of the same digit
+ * are n distinct places below n. */
+__device__ __forceinline__ uint32_t element(const uint32_t *idx_in, uint32_t e)
+{
+    return idx_in ? idx_in[e] : e;
+}
+
+/* hist[d * ntiles + tile] = records of digit d in the tile */
+__global__ void __launch_bounds__(NT)
+msd_pos_hist_kernel(const uint32_t *idx_in, const uint32_t *slot, uint32_t n, uint32_t shift, uint32_t *hist)
+{
+    __shared__ uint32_t cnt[256];
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t e = blockIdx.x * NT + threadIdx.x;
+    if (e < n)
+        atomicAdd(&cnt[(slot[element(idx_in, e)] >> shift) & 255u], 1u); /* a sum: the order does not matter */
+    __syncthreads();
+    hist[threadIdx.x * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
+}
+
+/* exclusive prefix sum of a[0 .. total) in place, one workgroup */
+__global__ void __launch_bounds__(1024) msd_pos_scan_kernel(uint32_t *a, uint32_t total)
+{
+    __shared__ uint32_t sh[1024];
+    __shared__ uint32_t carry;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0)
+        carry = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < total; base += 1024u) {
+        const uint32_t i = base + tid;
+        const uint32_t x = i < total ? a[i] : 0u;
+        sh[tid] = x;
+        __syncthreads();
+        for (uint32_t d = 1; d < 1024u; d <<= 1) {
+            const uint32_t y = tid >= d ? sh[tid - d] : 0u;
+            __syncthreads();
+            sh[tid] += y;
+            __syncthreads();
+        }
+        const uint32_t incl = sh[tid], c = carry;
+        if (i < total)
+            a[i] = c + incl - x;
+        __syncthreads();
+        if (tid == 1023u)
+            carry = c + incl;
+        __syncthreads();
+    }
+}
+
+/* idx_out[hist[d][tile] + rank of the record among the tile's records of digit d] = the record: stable */
+__global__ void __launch_bounds__(NT)
+msd_pos_scatter_kernel(const uint32_t *idx_in, const uint32_t *slot, uint32_t n, uint32_t shift, const uint32_t *hist,
+                       uint32_t *idx_out)
+{
+    __shared__ uint32_t wcnt[NT / 64][256];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    for (uint32_t w = 0; w < NT / 64; ++w)
+        wcnt[w][tid] = 0;
+    __syncthreads();
+    const uint32_t e = blockIdx.x * NT + tid;
+    const bool valid = e < n;
+    const uint32_t rec = valid ? element(idx_in, e) : 0u;
+    const uint32_t d = valid ? (slot[rec] >> shift) & 255u : 0u;
+    /* the lanes of this wave with the same digit */
+    unsigned long long peers = __ballot(valid);
+    for (uint32_t b = 0; b < 8; ++b) {
+        const bool bit = (d >> b) & 1u;
+        const unsigned long long m = __ballot(valid && bit);
+        peers &= bit ? m : ~m;
+    }
+    const uint32_t rank = __popcll(peers & ((1ull << lane) - 1ull));
+    if (valid && rank == 0)
+        wcnt[wave][d] = __popcll(peers);
+    __syncthreads();
+    if (valid) {
+        uint32_t before = 0;
+        for (uint32_t w = 0; w < wave; ++w)
+            before += wcnt[w][d];
+        idx_out[hist[d * gridDim.x + blockIdx.x] + before + rank] = rec;
+    }
+}
+
+/* step 3 and 4: the lane at the head of an aircraft's run walks it */
+__global__ void __launch_bounds__(NT)
+msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                    const msd_pos_receiver *rx, int filter_persistence, uint32_t base, uint32_t n, const uint32_t *slot,
+                    const uint32_t *idx, msd_position *out, unsigned long long *dstats)
+{
+    const uint32_t j = blockIdx.x * NT + threadIdx.x;
+    if (j >= n)
+        return;
+    const uint32_t s = slot[base + element(idx, j)];
+    if (s >= t.cap || (j > 0 && slot[base + element(idx, j - 1u)] == s))
+        return;
+    msd_pos_aircraft a = t.st[s];
+    msd_pos_acc acc = {};
+    acc.margin = INFINITY;
+    for (uint32_t k = j; k < n; ++k) {
+        const uint32_t i = base + element(idx, k);
+        if (slot[i] != s)
+            break;
+        const msd_fields f = fields[i];
+        const msd_pos_receiver r = rx[receiver ? receiver[i] : 0u];
+        msd_position o = {};
+        msd_pos_feed(&a, &r, filter_persistence, msgs[i].sysTimestampMsg, &f, &o, &acc);
+        out[i] = o;
+    }
+    t.st[s] = a;
+    for (int c = 0; c < MSD_PC_N; ++c)
+        if (acc.c[c])
+            atomicAdd(&dstats[c], (unsigned long long)acc.c[c]);
+    if (acc.margin < INFINITY)
+        atomicMin(&dstats[MSD_PC_N], (unsigned long long)__double_as_longlong(acc.margin));
+}
+
+__global__ void __launch_bounds__(NT) msd_pos_expire_kernel(msd_pos_table t, uint64_t now, uint32_t *ctl)
+{
+    const uint32_t s = blockIdx.x * NT + threadIdx.x;
+    if (s >= t.cap || t.keys[s] == MSD_POS_EMPTY)
+        return;
+    msd_pos_aircraft a = t.st[s];
+    if (msd_pos_expire_one(&a, now)) {
+        t.keys[s] = TOMB;
+        atomicAdd(&ctl[MSD_POS_CTL_REMOVED], 1u);
+    } else {
+        t.st[s] = a;
+    }
+}
+
+__global__ void __launch_bounds__(NT) msd_pos_rebuild_kernel(msd_pos_table from, msd_pos_table to)
+{
+    const uint32_t s = blockIdx.x * NT + threadIdx.x;
+    if (s >= from.cap || from.keys[s] >= TOMB)
+        return;
+    int fresh = 0;
+    to.st[find_or_insert(to, from.keys[s], &fresh)] = from.st[s]; /* found: `to` is as large as `from` and was empty */
+}
+
+uint32_t blocks(uint32_t n)
+{
+    return (n + NT - 1u) / NT;
+}
+
+} // namespace
+
+void msd_pos_launch_fill(hipStream_t stream, uint64_t *keys, uint32_t cap)
+{
+    msd_pos_fill_kernel<<<blocks(cap), NT, 0, stream>>>(keys, cap);
+}
+
+void msd_pos_launch_find(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
+                         const uint32_t *receiver, uint32_t nrx, uint32_t n, uint32_t *slot, uint8_t *fresh, msd_position *out,
+                         uint32_t *ctl)
+{
+    msd_pos_find_kernel<<<blocks(n), NT, 0, stream>>>(t, msgs, fields, receiver, nrx, n, slot, fresh, out, ctl);
+}
+
+void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t *slot, const uint8_t *fresh, uint32_t n)
+{
+    msd_pos_rollback_kernel<<<blocks(n), NT, 0, stream>>>(t, slot, fresh, n);
+}
+
+void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
+                          const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
+                          uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
+                          msd_position *out, unsigned long long *dstats)
+{
+    const uint32_t tiles = blocks(n);
+    /* slots run from 0 to cap inclusive (cap = skipped) */
+    uint32_t bits = 1;
+    while ((1u << bits) <= t.cap)
+        ++bits;
+    const uint32_t *in = nullptr; /* the first pass reads the identity */
+    uint32_t *bufs[2] = {idx_a, idx_b};
+    int w = 0;
+    for (uint32_t shift = 0; shift < bits; shift += 8) {
+        msd_pos_hist_kernel<<<tiles, NT, 0, stream>>>(in, slot + base, n, shift, hist);
+        msd_pos_scan_kernel<<<1, 1024, 0, stream>>>(hist, 256u * tiles);
+        msd_pos_scatter_kernel<<<tiles, NT, 0, stream>>>(in, slot + base, n, shift, hist, bufs[w]);
+        in = bufs[w];
+        w ^= 1;
+    }
+    msd_pos_walk_kernel<<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out,
+                                                  dstats);
+}
+
+void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl)
+{
+    msd_pos_expire_kernel<<<blocks(t.cap), NT, 0, stream>>>(t, now_ms, ctl);
+}
+
+void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_table to)
+{
+    msd_pos_rebuild_kernel<<<blocks(from.cap), NT, 0, stream>>>(from, to);
+}

@@ -18,7 +18,7 @@ typedef struct msd_siggen_cfg {
     uint32_t n_aircraft;       /* address pool size */
     uint32_t flip_permille;    /* frames with one flipped bit */
     uint32_t overlap_permille; /* frames placed on top of the previous one */
-    uint32_t reserved;
+    uint32_t reserved;         /* MSD_SIGGEN_SCENE_*; 0 = random payloads */
 } msd_siggen_cfg;
 
 /* One block of up to MSD_SIGGEN_BLOCK samples starting at sample block_index*MSD_SIGGEN_BLOCK. */
@@ -27,6 +27,11 @@ void msd_siggen_block(const msd_siggen_cfg *cfg, uint64_t block_index, uint32_t 
  * Returns 0 or a negative errno value. */
 int msd_siggen_generate(const msd_siggen_cfg *cfg, uint64_t first_sample, uint64_t nsamples,
                         void *out, unsigned nthreads);
+/* msd_siggen_cfg.reserved: every DF17 frame is an airborne position squitter (ME type 11) of its aircraft, which stands
+ * still at msd_siggen_position(); even and odd frames alternate at random.  Everything else is as without the flag. */
+#define MSD_SIGGEN_SCENE_POSITIONS 1u
+/* where the scene puts the k-th aircraft of the pool, degrees (|lat| < 70) */
+void msd_siggen_position(const msd_siggen_cfg *cfg, uint32_t k, double *lat, double *lon);
 /* k-th address of the pool */
 uint32_t msd_siggen_aircraft(const msd_siggen_cfg *cfg, uint32_t k);
 

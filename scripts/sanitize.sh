@@ -26,7 +26,7 @@ asan) SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omi
 tsan) SAN="-fsanitize=thread -fno-omit-frame-pointer"; CC=/opt/rocm/lib/llvm/bin/clang; CXX=/opt/rocm/lib/llvm/bin/clang++ ;;
 *) echo "usage: $0 asan|tsan OUTDIR" >&2; exit 2 ;;
 esac
-test -f msd_kernels.o -a -f msd_dc_kernels.o -a -f msd_resolve_kernels.o -a -f msd_frames_kernels.o -a -f msd_wire_kernels.o -a -f msd_avr_kernels.o -a -f msd_group_beast_kernels.o -a -f msd_group_avr_kernels.o -a -f msd_group_remote_out_kernels.o -a -f msd_capi.o -a -f msd_group.o -a -f msd_frames.o || { echo "run build.sh first (the HIP objects are reused)" >&2; exit 1; }
+test -f msd_kernels.o -a -f msd_dc_kernels.o -a -f msd_resolve_kernels.o -a -f msd_frames_kernels.o -a -f msd_wire_kernels.o -a -f msd_avr_kernels.o -a -f msd_group_beast_kernels.o -a -f msd_group_avr_kernels.o -a -f msd_group_remote_out_kernels.o -a -f msd_pos_kernels.o -a -f msd_capi.o -a -f msd_group.o -a -f msd_frames.o || { echo "run build.sh first (the HIP objects are reused)" >&2; exit 1; }
 INC="-I. -I../../include -Ihost"
 CF="-std=c11 -O1 -g -Wall -Wextra -fPIC $SAN $INC"
 $CC $CF -ffp-contract=off -c msd_tables.c -o "$OUT/msd_tables.o"
@@ -42,16 +42,18 @@ $CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $IN
 $CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_group.cpp -o "$OUT/msd_group.o"
 $CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_group_beast.cpp -o "$OUT/msd_group_beast.o"
 $CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_group_avr.cpp -o "$OUT/msd_group_avr.o"
-CAPI_OBJ="$CAPI_OBJ $OUT/msd_frames.o $OUT/msd_group.o $OUT/msd_group_beast.o $OUT/msd_group_avr.o"
+$CXX -std=c++17 -O1 -g -fPIC $SAN -ffp-contract=off -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_pos.cpp -o "$OUT/msd_pos.o"
+CAPI_OBJ="$CAPI_OBJ $OUT/msd_frames.o $OUT/msd_group.o $OUT/msd_group_beast.o $OUT/msd_group_avr.o $OUT/msd_pos.o"
 # (the sanitizer runtime comes from LD_PRELOAD or from the instrumented executable: the shared objects leave it undefined)
 # (the wire writers are in both libraries, as in build.sh)
 $CC $CF -c host/msd_wire.c -o "$OUT/msd_wire.o"
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmodes_hip.so" msd_kernels.o msd_dc_kernels.o msd_resolve_kernels.o msd_frames_kernels.o msd_wire_kernels.o msd_avr_kernels.o msd_group_beast_kernels.o msd_group_avr_kernels.o msd_group_remote_out_kernels.o $CAPI_OBJ \
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmodes_hip.so" msd_kernels.o msd_dc_kernels.o msd_resolve_kernels.o msd_frames_kernels.o msd_wire_kernels.o msd_avr_kernels.o msd_group_beast_kernels.o msd_group_avr_kernels.o msd_group_remote_out_kernels.o msd_pos_kernels.o $CAPI_OBJ \
     "$OUT/msd_tables.o" "$OUT/msd_resolve.o" "$OUT/msd_fields.o" "$OUT/msd_wire.o" -lm -lpthread
 for f in msd_fifo msd_sdr_ifile msd_converter msd_demod; do
     $CC $CF -c host/$f.c -o "$OUT/$f.o"
 done
-$CC -shared -fPIC $SAN -o "$OUT/libmsd_host.so" "$OUT"/msd_fifo.o "$OUT"/msd_sdr_ifile.o "$OUT"/msd_wire.o "$OUT"/msd_converter.o "$OUT"/msd_demod.o \
+$CC $CF -ffp-contract=off -c host/msd_pos_host.c -o "$OUT/msd_pos_host.o"
+$CC -shared -fPIC $SAN -o "$OUT/libmsd_host.so" "$OUT"/msd_pos_host.o "$OUT"/msd_fifo.o "$OUT"/msd_sdr_ifile.o "$OUT"/msd_wire.o "$OUT"/msd_converter.o "$OUT"/msd_demod.o \
     -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
 $CC $CF host/msd_replay_main.c "$OUT"/msd_sdr_ifile.o "$OUT"/msd_fifo.o "$OUT"/msd_wire.o "$OUT"/msd_converter.o -o "$OUT/msd_replay" \
     -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm

@@ -1,0 +1,235 @@
+"""Constructed record streams for the position tracker's tests (test_positions_model.py on the CPU,
+test_gpu_positions.py on the GPU): a builder that writes msd_message / msd_fields rows the way the field decoder would
+have left them, the named scenarios of the issue, a 2000-record mixed stream, and runners for the three
+implementations (the GPU object, the host twin, the second reading of tests/indep_positions.py).
+
+A scenario is (receivers, filter_persistence, steps); a step is ("update", msgs, fields, receiver) or ("expire", now_ms).
+Every scenario keeps every plausibility gate at least 1 m from its limit (asserted on the twin by the tests)."""
+import numpy as np
+
+import indep_positions as ip
+
+T0 = 1_600_000_000_000  # ms: a wall clock, as readsb's sysTimestampMsg is
+NM = 1852.0
+HOME = dict(lat=52.0, lon=4.0, latlon_valid=1)
+
+
+class Builder:
+    def __init__(self, pkg):
+        self.pkg, self.m, self.f, self.r = pkg, [], [], []
+
+    def rec(self, t, addr, rx=0, source=ip.ADSB, msgtype=17, **kw):
+        m = np.zeros((), dtype=self.pkg.capi.MESSAGE_DTYPE)
+        f = np.zeros((), dtype=self.pkg.capi.FIELDS_DTYPE)
+        m["sysTimestampMsg"], m["msgtype"], m["addr"], m["msgbits"] = t, msgtype, addr & 0xFFFFFF, 112
+        f["addr"], f["source"] = addr, source
+        for k, v in kw.items():
+            f[k] = v
+        self.m.append(m), self.f.append(f), self.r.append(rx)
+        return self
+
+    def pos(self, t, addr, lat, lon, odd, surface=False, movement=0, **kw):
+        y, x = ip.cpr_encode(lat, lon, odd, surface)
+        return self.rec(t, addr, cpr_valid=1, cpr_type=0 if surface else 1, cpr_odd=odd, cpr_lat=y, cpr_lon=x,
+                        movement=movement, metype=7 if surface else 11, **kw)
+
+    def raw(self, t, addr, y, x, odd, **kw):
+        return self.rec(t, addr, cpr_valid=1, cpr_type=1, cpr_odd=odd, cpr_lat=y, cpr_lon=x, metype=11, **kw)
+
+    def vel(self, t, addr, ew, ns, **kw):
+        return self.rec(t, addr, velocity_valid=1, ew_vel=ew, ns_vel=ns, metype=19, **kw)
+
+    def opstatus(self, t, addr, version, **kw):
+        return self.rec(t, addr, opstatus=1 | (version << 1), metype=31, **kw)
+
+    def step(self):
+        out = ("update", np.array(self.m, dtype=self.pkg.capi.MESSAGE_DTYPE), np.array(self.f, dtype=self.pkg.capi.FIELDS_DTYPE),
+               np.array(self.r, dtype=np.uint32))
+        self.m, self.f, self.r = [], [], []
+        return out
+
+
+def scenarios(pkg):
+    S = {}
+    B = lambda: Builder(pkg)  # noqa: E731
+
+    # even / odd pair inside and just outside 10 s (no receiver location: the late half decodes nothing)
+    b = B()
+    b.pos(T0, 0x100001, 51.5, 3.5, 0).pos(T0 + 10000, 0x100001, 51.5, 3.5, 1)
+    b.pos(T0, 0x100002, 51.5, 3.5, 0).pos(T0 + 10001, 0x100002, 51.5, 3.5, 1)
+    S["pair_10s"] = ([None], 0, [b.step()])
+
+    # the same with the demodulator's clock, which starts at 0: position_valid.updated == 0 is then "recent" and the
+    # unpaired half is tried relative to (0, 0) (track.c:466)
+    b = B()
+    b.pos(1000, 0x100003, 0.3, 0.4, 0).pos(12000, 0x100003, 0.3, 0.4, 1).pos(13000, 0x100004, 51.5, 3.5, 0)
+    S["clock_from_zero"] = ([None], 0, [b.step()])
+
+    # surface: 25 s with gs > 25 kt or unknown, 50 s with gs <= 25 kt (movement 48 = 24.5 kt, 49 = 25.5 kt)
+    b = B()
+    for k, (gap, mov) in enumerate(((25000, 49), (25001, 49), (50000, 48), (50001, 48), (25001, 0), (25000, 0))):
+        a = 0x200000 + k
+        b.pos(T0, a, 52.3, 4.76, 0, surface=True, movement=mov).pos(T0 + gap, a, 52.3, 4.76, 1, surface=True, movement=mov)
+    S["surface_windows"] = ([HOME], 0, [b.step()])
+
+    # surface movement read by version: 3 is 0.1875 kt as v0 and 0.1979 kt as v2 -- both slow; and a surface pair
+    # without any reference
+    b = B()
+    b.opstatus(T0, 0x210000, 2).pos(T0 + 100, 0x210000, 52.3, 4.76, 0, surface=True, movement=3)
+    b.pos(T0 + 40000, 0x210000, 52.3, 4.76, 1, surface=True, movement=3)
+    b.pos(T0, 0x210001, 52.3, 4.76, 0, surface=True, rx=1).pos(T0 + 1000, 0x210001, 52.3, 4.76, 1, surface=True, rx=1)
+    S["surface_version_and_no_reference"] = ([HOME, None], 0, [b.step()])
+
+    # type mismatch between the halves; source mismatch (ADS-B against TIS-B)
+    b = B()
+    b.pos(T0, 0x300001, 52.3, 4.76, 0).pos(T0 + 500, 0x300001, 52.3, 4.76, 1, surface=True)
+    b.pos(T0, 0x300002, 52.3, 4.76, 0).pos(T0 + 500, 0x300002, 52.3, 4.76, 1, source=ip.TISB)
+    b.pos(T0 + 900, 0x300002, 52.3, 4.76, 0, source=ip.TISB)      # a lesser source while ADS-B is fresh: not accepted
+    b.pos(T0 + 60000, 0x300002, 52.3, 4.76, 0, source=ip.TISB)    # stale by now: accepted, but 59.5 s from its odd half
+    b.pos(T0 + 60400, 0x300002, 52.3, 4.76, 1, source=ip.TISB)    # both TIS-B: global
+    S["type_and_source_mismatch"] = ([None], 0, [b.step()])
+
+    # global failure -> pos_reliable decrement -> position invalidated; with more good pairs first it survives one
+    b = B()
+    for a, good in ((0x400001, 1), (0x400002, 4)):
+        t = T0
+        for k in range(good):
+            b.pos(t, a, 50.0 + 0.001 * k, 8.0, 0).pos(t + 400, a, 50.0 + 0.001 * k, 8.0, 1)
+            t += 1000
+        b.pos(t, a, 40.0, 20.0, 0).pos(t + 400, a, 40.0, 20.0, 1)       # implausible: both halves dropped
+        b.pos(t + 12000, a, 50.01, 8.0, 0).pos(t + 12400, a, 50.01, 8.0, 1)  # the bad odd half is 11.6 s old by now
+    S["global_failure"] = ([None], 3, [b.step()])
+
+    # local, relative to the aircraft's last position, within 10 minutes and after them
+    b = B()
+    b.pos(T0, 0x500001, 48.0, 11.0, 0).pos(T0 + 500, 0x500001, 48.0, 11.0, 1)
+    b.pos(T0 + 30000, 0x500001, 48.05, 11.05, 0).pos(T0 + 300000, 0x500001, 48.4, 11.4, 1)
+    b.pos(T0 + 300000 + 599999, 0x500001, 48.5, 11.5, 0).pos(T0 + 1600000, 0x500001, 48.6, 11.6, 1)
+    S["aircraft_relative"] = ([None], 0, [b.step()])
+
+    # receiver-relative for each --max-range branch: 0, <= 180 NM, between, >= 360 NM; inside and outside the limit
+    rx = [dict(HOME, max_range_m=0.0), dict(HOME, max_range_m=150 * NM), dict(HOME, max_range_m=250 * NM),
+          dict(HOME, max_range_m=400 * NM)]
+    b = B()
+    for r in range(4):
+        b.pos(T0, 0x600000 + r, 52.5, 5.0, 0, rx=r)       # about 40 NM away
+        b.pos(T0, 0x610000 + r, 52.0, 7.5, 1, rx=r)       # about 129 NM: outside 360 - 250 = 110 NM
+        b.pos(T0, 0x620000 + r, 53.0, 9.0, 0, rx=r).pos(T0 + 300, 0x620000 + r, 53.0, 9.0, 1, rx=r)  # global, 190 NM
+    S["receiver_relative"] = (rx, 0, [b.step()])
+
+    # speed check with gs, tas, ias and none: a jump of about 5.6 km in 10 s passes at 700 kt (none) and fails at
+    # 100 kt; the odd half is 10.1 s old by then, so only the local decode is tried
+    b = B()
+    for k, kw in enumerate((dict(), dict(velocity_valid=1, ew_vel=60, ns_vel=80), dict(tas_valid=1, tas=100),
+                            dict(ias_valid=1, ias=80), dict(velocity_valid=1, ew_vel=600, ns_vel=800))):
+        a = 0x700000 + k
+        b.pos(T0, a, 45.0, 9.0, 0).pos(T0 + 500, a, 45.0, 9.0, 1)
+        if kw:
+            b.rec(T0 + 600, a, metype=19, **kw)
+        b.pos(T0 + 10600, a, 45.05, 9.0, 0)
+        b.pos(T0 + 11100, a, 45.05, 9.0, 1)   # the global decode of the new pair meets the same check
+    S["speed_check"] = ([None], 0, [b.step()])
+
+    # timestamps running backwards: every member has its own `updated`, so an older odd half is accepted while the odd
+    # member is new, an older even half is not, and a good global decode older than the position is skipped (-2)
+    b = B()
+    b.pos(T0 + 5000, 0x800001, 47.0, 8.0, 0).pos(T0 + 4000, 0x800001, 47.0, 8.0, 1).pos(T0 + 3000, 0x800001, 47.0, 8.0, 0)
+    b.pos(T0 + 5500, 0x800001, 47.0, 8.0, 1).pos(T0 + 5200, 0x800001, 47.001, 8.0, 0)
+    S["backwards"] = ([None], 0, [b.step()])
+
+    # expiry and TTL: a one-message aircraft goes after 60 s, the others after 10 minutes; a position expires after
+    # 70 s and takes pos_reliable with it; Mode A/C records and address 0 are skipped
+    steps = []
+    b = B()
+    b.pos(T0, 0x900001, 47.0, 8.0, 0).pos(T0 + 300, 0x900001, 47.0, 8.0, 1).pos(T0, 0x900002, 47.0, 8.0, 0)
+    b.rec(T0, 0x001234, msgtype=32, source=ip.MODE_AC).rec(T0, 0, msgtype=11, source=ip.MODE_S)
+    steps += [b.step(), ("expire", T0 + 60000), ("expire", T0 + 60001), ("expire", T0 + 70300)]
+    b.pos(T0 + 80000, 0x900001, 47.2, 8.2, 0).pos(T0 + 80400, 0x900001, 47.2, 8.2, 1).pos(T0 + 80500, 0x900002, 47.0, 8.0, 1)
+    steps += [b.step(), ("expire", T0 + 80400 + 600000), ("expire", T0 + 80400 + 600001), ("expire", T0 + 80500 + 600001)]
+    b.pos(T0 + 900000, 0x900001, 47.2, 8.2, 0)
+    steps += [b.step()]
+    S["expiry_and_ttl"] = ([None], 0, steps)
+    return S
+
+
+def mixed_stream(pkg, n=2000, seed=7):
+    """n records of 40 aircraft on two receivers: straight flights with a position every 400 to 600 ms alternating even
+    and odd, velocities, airspeeds, operational status, a few surface targets, jumps to implausible places, Mode A/C
+    records and address 0 in between; in time order.  -> (receivers, msgs, fields, receiver)."""
+    rng = np.random.default_rng(seed)
+    rxs = [dict(lat=52.0, lon=4.0, latlon_valid=1, max_range_m=300 * NM), dict(lat=48.0, lon=11.0, latlon_valid=1)]
+    b = Builder(pkg)
+    planes = []
+    for k in range(40):
+        r = k % 2
+        planes.append(dict(addr=0x3C0000 + 97 * k + (1 << 24 if k % 13 == 0 else 0), rx=r, lat=rxs[r]["lat"] + rng.uniform(-1.5, 1.5),
+                           lon=rxs[r]["lon"] + rng.uniform(-2, 2), vlat=rng.uniform(-2e-6, 2e-6), vlon=rng.uniform(-3e-6, 3e-6),
+                           surface=k % 10 == 9, odd=int(rng.integers(0, 2)), source=ip.TISB if k % 13 == 0 else ip.ADSB))
+    t = T0
+    while len(b.m) < n:
+        t += int(rng.integers(5, 40))
+        p = planes[int(rng.integers(0, len(planes)))]
+        dt = t - T0
+        lat, lon = p["lat"] + p["vlat"] * dt, p["lon"] + p["vlon"] * dt
+        u = rng.uniform()
+        kw = dict(rx=p["rx"], source=p["source"])
+        if p["surface"]:
+            lat, lon = p["lat"] + p["vlat"] * dt * 0.02, p["lon"] + p["vlon"] * dt * 0.02
+        if u < 0.70:
+            p["odd"] ^= 1
+            if rng.uniform() < 0.04:
+                k = 0.1 if rng.uniform() < 0.5 else 1.0                          # bad data, near (speed) or far (range)
+                lat, lon = lat + k * rng.uniform(3, 6), lon - k * rng.uniform(3, 6)
+            b.pos(t, p["addr"], lat, lon, p["odd"], surface=p["surface"], movement=int(rng.integers(0, 60)) if p["surface"] else 0, **kw)
+        elif u < 0.85:
+            b.vel(t, p["addr"], int(p["vlon"] * 2.4e8), int(p["vlat"] * 3.6e8), **kw)
+        elif u < 0.90:
+            b.rec(t, p["addr"], tas_valid=1, tas=int(rng.integers(100, 500)), msgtype=21, **dict(kw, source=ip.MODE_S))
+        elif u < 0.93:
+            b.rec(t, p["addr"], ias_valid=1, ias=int(rng.integers(100, 400)), msgtype=21, **dict(kw, source=ip.MODE_S))
+        elif u < 0.96:
+            b.opstatus(t, p["addr"], int(rng.integers(0, 3)), **kw)
+        elif u < 0.98:
+            b.rec(t, 0x7000 + int(rng.integers(0, 8)), msgtype=32, source=ip.MODE_AC, rx=p["rx"])
+        else:
+            b.rec(t, 0, msgtype=0, source=ip.MODE_S, rx=p["rx"])
+    _, m, f, r = b.step()
+    return rxs, m[:n], f[:n], r[:n]
+
+
+# ---- runners -------------------------------------------------------------------------------------------------------
+def run_library(tracker, steps, pieces=None):
+    """steps through a capi.PositionTracker -> POSITION_DTYPE rows of all update steps, in order; pieces: cut every
+    update into calls of that many records."""
+    outs = []
+    for s in steps:
+        if s[0] == "expire":
+            tracker.expire(s[1])
+            continue
+        _, m, f, r = s
+        k = pieces or max(len(m), 1)
+        for i in range(0, len(m), k):
+            outs.append(tracker.update(m[i:i + k], f[i:i + k], r[i:i + k]))
+    return np.concatenate(outs) if outs else np.zeros(0)
+
+
+def run_model(receivers, filter_persistence, steps):
+    t = ip.Tracker(receivers, filter_persistence or 8)
+    rows = []
+    for s in steps:
+        if s[0] == "expire":
+            t.expire(s[1])
+        else:
+            rows += t.update(s[1], s[2], s[3])
+    return rows, t.get_stats()
+
+
+def rows_of(out):
+    """POSITION_DTYPE -> comparable tuples with the coordinates as bit patterns."""
+    return [(int(o["decoded"]), int(o["relative"]), int(o["surface"]), int(o["result"]),
+             int(o["lat"].view(np.uint64)), int(o["lon"].view(np.uint64))) for o in out]
+
+
+def rows_of_model(rows):
+    return [(d, rel, s, res, int(np.float64(lat).view(np.uint64)), int(np.float64(lon).view(np.uint64)))
+            for d, rel, s, res, lat, lon in rows]

@@ -1,0 +1,135 @@
+"""The host twin of the position tracker (libmsd_host.so, msd_pos_host_*) against the second reading of track.c in
+tests/indep_positions.py, record by record and bit by bit, on the constructed streams of tests/pos_streams.py; the
+counters and the gate margin as well (both sides use the C library's sin / cos / acos / atan2).  Every stream must keep
+every plausibility gate at least 1 m from its limit: a stream that sits on a gate fails here, loudly, instead of
+making a comparison between two libms flake."""
+import math
+
+import numpy as np
+import pytest
+
+import pos_streams as ps
+
+
+@pytest.fixture(scope="module")
+def scen(pkg):
+    return ps.scenarios(pkg)
+
+
+NAMES = ["pair_10s", "clock_from_zero", "surface_windows", "surface_version_and_no_reference", "type_and_source_mismatch",
+         "global_failure", "aircraft_relative", "receiver_relative", "speed_check", "backwards", "expiry_and_ttl"]
+
+
+def twin_run(pkg, receivers, fp, steps, pieces=None):
+    t = pkg.capi.PositionTracker(capacity=1024, receivers=receivers, filter_persistence=fp, host=True)
+    out = ps.run_library(t, steps, pieces)
+    st = t.stats()
+    t.close()
+    return out, st
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_twin_equals_the_second_reading(pkg, scen, name):
+    receivers, fp, steps = scen[name]
+    out, st = twin_run(pkg, receivers, fp, steps)
+    rows, mst = ps.run_model(receivers, fp, steps)
+    assert ps.rows_of(out) == ps.rows_of_model(rows)
+    assert st == mst
+    assert st["min_gate_margin_m"] >= 1.0, st["min_gate_margin_m"]
+
+
+def results(pkg, scen, name):
+    receivers, fp, steps = scen[name]
+    out, st = twin_run(pkg, receivers, fp, steps)
+    return [int(x) for x in out["result"]], out, st
+
+
+def test_the_scenarios_reach_what_they_are_named_for(pkg, scen):
+    """Known answers, so that the two readings cannot agree on streams that never reach the rules in question."""
+    r, out, st = results(pkg, scen, "pair_10s")
+    assert r == [-1, 0, -1, -1] and st["cpr_global_ok"] == 1
+    assert abs(out["lat"][1] - 51.5) < 1e-4 and abs(out["lon"][1] - 3.5) < 1e-4
+    r, out, st = results(pkg, scen, "clock_from_zero")
+    assert r == [1, 1, -1] and st["cpr_local_aircraft_relative"] == 2
+    assert st["cpr_local_range_checks"] == 1  # 51.5 N 3.5 E decoded in the cell around (0, 0): more than 100 NM away
+    r, out, st = results(pkg, scen, "surface_windows")
+    assert r == [-1, 0, -1, -1, -1, 0, -1, -1, -1, -1, -1, 0] and st["cpr_surface"] == 12
+    assert abs(out["lat"][1] - 52.3) < 1e-4 and abs(out["lon"][1] - 4.76) < 1e-4 and out["surface"].all()
+    r, out, st = results(pkg, scen, "surface_version_and_no_reference")
+    assert r == [-3, -1, 0, -1, -1]
+    r, out, st = results(pkg, scen, "type_and_source_mismatch")
+    assert r == [-1, -1, -1, -1, -3, -1, 0] and st["cpr_global_ok"] == 1
+    r, out, st = results(pkg, scen, "global_failure")
+    #          one good pair, the bad pair invalidates the position       four good pairs, the position survives
+    assert r == [-1, 0, -2, -1, 1, 0] + [-1, 0, 0, 0, 0, 0, 0, 0, -2, -1, 1, 0]
+    assert st["cpr_global_bad"] == 2  # the mixed halves decode to a latitude out of range or fail the speed check
+    r, out, st = results(pkg, scen, "aircraft_relative")
+    assert r == [-1, 0, 1, 1, 1, -1]
+    r, out, st = results(pkg, scen, "receiver_relative")
+    #           no range          150 NM: the 190 NM pair is out    250 NM: 110 NM locally    400 NM: no local
+    assert r == [-1, -1, -1, 0] + [2, 2, -1, -2] + [2, -1, -1, 0] + [-1, -1, -1, 0]
+    assert st["cpr_local_receiver_relative"] == 3 and st["cpr_local_range_checks"] == 3 and st["cpr_global_range_checks"] == 1
+    r, out, st = results(pkg, scen, "speed_check")
+    #           none: 700 kt     gs 100, tas 100 and ias 80 kt: at most 213 kt x 4/3 -- too slow for 5.6 km in 11 s      gs 1000 kt
+    assert r == [-1, 0, 1, 0] + [-1, 0, -3, -1, -2] + [-1, 0, -3, -1, -2] + [-1, 0, -3, -1, -2] + [-1, 0, -3, 1, 0]
+    assert st["cpr_local_speed_checks"] == 3 and st["cpr_global_speed_checks"] == 3
+    r, out, st = results(pkg, scen, "backwards")
+    assert r == [-1, 0, -3, 0, -2] and st["cpr_global_skipped"] == 1 and st["cpr_global_bad"] == 0
+    r, out, st = results(pkg, scen, "expiry_and_ttl")
+    assert r == [-1, 0, -1, -3, -3] + [1, 0, -1] + [-1] and st["aircraft"] == 1
+    # the aircraft alive after each step: the one-message aircraft leaves after more than 60 s, the other after 10 min
+    receivers, fp, steps = scen["expiry_and_ttl"]
+    t = pkg.capi.PositionTracker(capacity=64, receivers=receivers, host=True)
+    alive = []
+    for s in steps:
+        ps.run_library(t, [s])
+        alive.append(t.stats()["aircraft"])
+    assert alive == [2, 2, 1, 1, 2, 1, 0, 0, 1]
+    t.close()
+
+
+def test_margin_is_reported_and_resets(pkg, scen):
+    receivers, fp, steps = scen["speed_check"]
+    t = pkg.capi.PositionTracker(capacity=64, receivers=receivers, filter_persistence=fp, host=True)
+    assert t.stats()["min_gate_margin_m"] == math.inf
+    ps.run_library(t, steps)
+    assert 1.0 <= t.stats()["min_gate_margin_m"] < 1e6
+    t.reset()
+    assert t.stats()["min_gate_margin_m"] == math.inf and t.stats()["aircraft"] == 0 and t.stats()["cpr_airborne"] == 0
+    t.close()
+
+
+def test_mixed_stream_and_cutting_invariance(pkg):
+    receivers, m, f, r = ps.mixed_stream(pkg)
+    steps = [("update", m, f, r)]
+    whole, st = twin_run(pkg, receivers, 0, steps)
+    rows, mst = ps.run_model(receivers, 0, steps)
+    assert ps.rows_of(whole) == ps.rows_of_model(rows) and st == mst
+    assert st["min_gate_margin_m"] >= 1.0, st["min_gate_margin_m"]
+    # the stream reaches every counter
+    for k, v in st.items():
+        assert v > 0, k
+    for pieces in (1, 7, 64):
+        cut, cst = twin_run(pkg, receivers, 0, steps, pieces)
+        assert np.array_equal(cut.view(np.uint8), whole.view(np.uint8)) and cst == st
+
+
+def test_table_full_changes_nothing(pkg, scen):
+    receivers, fp, steps = scen["pair_10s"]
+    t = pkg.capi.PositionTracker(capacity=64, receivers=[None], host=True)
+    b = ps.Builder(pkg)
+    for k in range(64):
+        b.pos(ps.T0, 0x100 + k, 10.0, 10.0, 0)
+    _, m, f, r = b.step()
+    t.update(m[:60], f[:60], r[:60])
+    before = t.stats()
+    with pytest.raises(pkg.MsdError) as e:
+        b2 = ps.Builder(pkg)
+        for k in range(5):
+            b2.pos(ps.T0 + 1, 0x900 + k, 10.0, 10.0, 1)
+        _, m2, f2, r2 = b2.step()
+        t.update(m2, f2, r2)
+    assert e.value.code == -28 and t.stats() == before  # -ENOSPC
+    t.update(m[60:], f[60:], r[60:])                    # exactly full is fine
+    assert t.stats()["aircraft"] == 64
+    t.close()
