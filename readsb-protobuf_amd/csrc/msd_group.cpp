@@ -16,8 +16,7 @@
 
 #include "msd_ctx.h" /* the context, and with it modes_hip.h, msd_internal.h and msd_kernels.h */
 #include "host/msd_wire.h" /* the host writers, for the entries resolved on host threads */
-#include "msd_group_beast.h" /* Beast input per receiver: msd_group_accept_beast */
-#include "msd_group_avr.h"   /* AVR text input per receiver: msd_group_accept_avr */
+#include "msd_group_avr.h" /* Beast and AVR input per receiver (with msd_group_beast.h): msd_group_accept_* */
 
 using namespace msd_impl;
 
@@ -100,9 +99,9 @@ struct msd_group {
     size_t wire_cap = 0;
     uint32_t *h_wire_entries = nullptr; /* pinned [max_receivers][4]: offset, bytes, messages, 0 per buffer */
     uint32_t *d_wire_counts = nullptr;  /* [max_receivers][2]: bytes and messages per buffer, between the two kernels */
-    void *beast = nullptr; /* Beast input (msd_group_beast.cpp): scratch and the receivers' framing state, made by the
+    void *beast = nullptr; /* Beast input (msd_group_remote.cpp): scratch and the receivers' framing state, made by the
                               first msd_group_accept_beast */
-    void *avr = nullptr;   /* AVR text input (msd_group_avr.cpp), likewise, made by the first msd_group_accept_avr */
+    void *avr = nullptr;   /* AVR text input, likewise, made by the first msd_group_accept_avr */
     msd_remote_stats *remote = nullptr; /* [max_receivers] the remote counters both inputs add to */
     char err[256] = {0};
 };
@@ -746,6 +745,117 @@ int group_submit(msd_group *g, const void *iq, const msd_group_entry *e, uint32_
     return rc;
 }
 
+/* the output of a fields or wire accept call (out = NULL: a plain call), checked as group_submit checks its own */
+int group_check_out(msd_group *g, const msd_gb_out *out)
+{
+    if (!out)
+        return 0;
+    if (out->want_fields && !g->ctx->want_fields)
+        return gfail(g, -EINVAL, "the group was created without MSD_CFG_DECODE_FIELDS");
+    if (out->want_wire && ((out->format != MSD_WIRE_BEAST && out->format != MSD_WIRE_AVR && out->format != MSD_WIRE_AVR_MLAT) ||
+                           (out->verbatim & ~(int)MSD_WIRE_VERBATIM)))
+        return gfail(g, -EINVAL, "wire output: unknown format %d or flags 0x%x", out->format, (unsigned)out->verbatim);
+    return 0;
+}
+
+msd_gb_out fields_out(msd_group_fields_fn sink)
+{
+    msd_gb_out o{};
+    o.want_fields = 1;
+    o.fsink = sink;
+    return o;
+}
+
+/* (verbatim carries the call's flags until group_check_out has seen them: MSD_WIRE_VERBATIM is 1) */
+msd_gb_out wire_out(int format, uint32_t flags, msd_group_wire_fn sink)
+{
+    msd_gb_out o{};
+    o.want_wire = 1;
+    o.wsink = sink;
+    o.format = format;
+    o.verbatim = (int)flags;
+    return o;
+}
+
+/* what differs between the remote inputs in group_accept_remote, by the public entry type of each */
+template <class Entry> struct RemoteInput;
+template <> struct RemoteInput<msd_group_beast_entry> {
+    static constexpr int FORMAT = MSD_GR_BEAST;
+    static constexpr const char *NAME = "Beast", *BAD_ENTRY = "or nonzero flags or reserved"; /* in the error texts */
+    static constexpr uint32_t FLAGS_OK = 0, ENTRY_MAX = MSD_GROUP_BEAST_ENTRY_MAX;
+    static constexpr uint64_t OFFSET_MAX = MSD_GROUP_BEAST_OFFSET_MAX;
+    static void **state(msd_group *g) { return &g->beast; }
+};
+template <> struct RemoteInput<msd_group_avr_entry> {
+    static constexpr int FORMAT = MSD_GR_AVR;
+    static constexpr const char *NAME = "AVR", *BAD_ENTRY = "an unknown flag or nonzero reserved";
+    static constexpr uint32_t FLAGS_OK = MSD_AVR_KEEP_TIMESTAMP, ENTRY_MAX = MSD_GROUP_AVR_ENTRY_MAX;
+    static constexpr uint64_t OFFSET_MAX = MSD_GROUP_AVR_OFFSET_MAX;
+    static void **state(msd_group *g) { return &g->avr; }
+};
+
+/* Beast or AVR input per receiver (Entry: msd_group_beast_entry or msd_group_avr_entry, of one layout): the checks that
+ * leave the group untouched, each entry's receiver options, then the call (msd_group_remote.cpp) */
+template <class Entry>
+int group_accept_remote(msd_group *g, const void *bytes, int on_device, const Entry *e, uint32_t n, msd_group_message_fn sink,
+                        const msd_gb_out *out, void *user)
+{
+    using F = RemoteInput<Entry>;
+    if (!g)
+        return -EINVAL;
+    msd_ctx *c = g->ctx;
+    if (int rc = group_check_out(g, out))
+        return rc;
+    if (n > g->max_receivers)
+        return gfail(g, -EINVAL, "%s entries: more than max_receivers", F::NAME);
+    if (n && (!e || !bytes))
+        return gfail(g, -EINVAL, "%s entries: NULL bytes or entries", F::NAME);
+    std::vector<bool> seen(g->max_receivers, false);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (e[i].receiver >= g->max_receivers || seen[e[i].receiver] || (e[i].flags & ~F::FLAGS_OK) || e[i].reserved)
+            return gfail(g, -EINVAL, "%s entry %u: a receiver out of range or given twice, %s", F::NAME, i, F::BAD_ENTRY);
+        if (e[i].nbytes > F::ENTRY_MAX || e[i].offset > F::OFFSET_MAX)
+            return gfail(g, -EINVAL, "%s entry %u: more than %u bytes, or an offset above 2^47", F::NAME, i, F::ENTRY_MAX);
+        seen[e[i].receiver] = true;
+    }
+    if (c->failed)
+        return gfail(g, -EIO, "an earlier call failed");
+    if (n == 0)
+        return 0;
+    msd_frames_view fv;
+    int rc = msd_frames_get_view(c, &fv); /* the CRC and repair tables of the group's context */
+    if (rc)
+        return gfail(g, rc, "%s input: no tables", F::NAME);
+    msd_gb_view v{};
+    v.format = F::FORMAT;
+    v.stream = fv.stream;
+    v.device = fv.device;
+    v.max_receivers = g->max_receivers;
+    v.tables = fv.tables;
+    v.d_snaps = g->gpu ? g->d_snaps : nullptr;
+    v.remote = g->remote;
+    v.state = F::state(g);
+    v.err = g->err;
+    v.errlen = sizeof g->err;
+    std::vector<msd_gr_input> in(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        GroupReceiver &r = g->rx[e[i].receiver];
+        in[i].receiver = e[i].receiver;
+        in[i].nbytes = e[i].nbytes;
+        in[i].flags = e[i].flags;
+        in[i].offset = e[i].offset;
+        in[i].now_ms = e[i].now_ms;
+        in[i].filter = &r.resolver.filter;
+        in[i].nfix = r.opt.nfix_crc;
+        in[i].mode_ac = r.mode_ac ? 1 : 0;
+        r.history = true; /* the repair level is fixed from here on, as by a buffer */
+    }
+    rc = msd_gr_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, out, user);
+    if (rc)
+        c->failed = true;
+    return rc;
+}
+
 } /* namespace */
 
 extern "C" {
@@ -828,8 +938,8 @@ void msd_group_destroy(msd_group *g)
     (void)hipHostFree(g->h_wire_out);
     (void)hipHostFree(g->h_wire_entries);
     (void)hipFree(g->d_wire_counts);
-    msd_gb_free(g->beast);
-    msd_ga_free(g->avr);
+    msd_gr_free(g->beast);
+    msd_gr_free(g->avr);
     delete[] g->remote;
     msd_destroy(g->ctx);
     delete g;
@@ -910,8 +1020,8 @@ int msd_group_reset_receiver(msd_group *g, uint32_t receiver)
         return gfail(g, -EIO, "an earlier call failed");
     group_receiver_reset(g->rx[receiver]);
     memset(&g->remote[receiver], 0, sizeof g->remote[receiver]);
-    msd_gb_reset_receiver(g->beast, receiver); /* its kept frame and pending gap */
-    msd_ga_reset_receiver(g->avr, receiver);   /* its kept line, discard flag and msd_avr_stats */
+    msd_gr_reset_receiver(g->beast, receiver); /* its kept frame and pending gap */
+    msd_gr_reset_receiver(g->avr, receiver);   /* its kept line, discard flag and msd_avr_stats */
     const int rc = group_upload_snapshot(g, receiver);
     if (rc)
         g->ctx->failed = true;
@@ -1000,114 +1110,24 @@ int msd_group_get_timing(const msd_group *g, msd_timing *t)
     return msd_get_timing(g->ctx, t);
 }
 
-/* the output of a fields or wire accept call (out = NULL: a plain call), checked as group_submit checks its own */
-static int group_check_out(msd_group *g, const msd_gb_out *out)
-{
-    if (!out)
-        return 0;
-    if (out->want_fields && !g->ctx->want_fields)
-        return gfail(g, -EINVAL, "the group was created without MSD_CFG_DECODE_FIELDS");
-    if (out->want_wire && ((out->format != MSD_WIRE_BEAST && out->format != MSD_WIRE_AVR && out->format != MSD_WIRE_AVR_MLAT) ||
-                           (out->verbatim & ~(int)MSD_WIRE_VERBATIM)))
-        return gfail(g, -EINVAL, "wire output: unknown format %d or flags 0x%x", out->format, (unsigned)out->verbatim);
-    return 0;
-}
-
-static msd_gb_out fields_out(msd_group_fields_fn sink)
-{
-    msd_gb_out o{};
-    o.want_fields = 1;
-    o.fsink = sink;
-    return o;
-}
-
-/* (verbatim carries the call's flags until group_check_out has seen them: MSD_WIRE_VERBATIM is 1) */
-static msd_gb_out wire_out(int format, uint32_t flags, msd_group_wire_fn sink)
-{
-    msd_gb_out o{};
-    o.want_wire = 1;
-    o.wsink = sink;
-    o.format = format;
-    o.verbatim = (int)flags;
-    return o;
-}
-
-/* Beast input per receiver: the checks that leave the group untouched, each entry's receiver options, then the call
- * (msd_group_beast.cpp) */
-static int group_accept_beast(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
-                              msd_group_message_fn sink, const msd_gb_out *out, void *user)
-{
-    if (!g)
-        return -EINVAL;
-    msd_ctx *c = g->ctx;
-    if (int rc = group_check_out(g, out))
-        return rc;
-    if (n > g->max_receivers)
-        return gfail(g, -EINVAL, "Beast entries: more than max_receivers");
-    if (n && (!e || !bytes))
-        return gfail(g, -EINVAL, "Beast entries: NULL bytes or entries");
-    std::vector<bool> seen(g->max_receivers, false);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (e[i].receiver >= g->max_receivers || seen[e[i].receiver] || e[i].flags || e[i].reserved)
-            return gfail(g, -EINVAL, "Beast entry %u: a receiver out of range or given twice, or nonzero flags or reserved", i);
-        if (e[i].nbytes > MSD_GROUP_BEAST_ENTRY_MAX || e[i].offset > MSD_GROUP_BEAST_OFFSET_MAX)
-            return gfail(g, -EINVAL, "Beast entry %u: more than %u bytes, or an offset above 2^47", i, MSD_GROUP_BEAST_ENTRY_MAX);
-        seen[e[i].receiver] = true;
-    }
-    if (c->failed)
-        return gfail(g, -EIO, "an earlier call failed");
-    if (n == 0)
-        return 0;
-    msd_frames_view fv;
-    int rc = msd_frames_get_view(c, &fv); /* the CRC and repair tables of the group's context */
-    if (rc)
-        return gfail(g, rc, "Beast input: no tables");
-    msd_gb_view v{};
-    v.stream = fv.stream;
-    v.device = fv.device;
-    v.max_receivers = g->max_receivers;
-    v.tables = fv.tables;
-    v.d_snaps = g->gpu ? g->d_snaps : nullptr;
-    v.remote = g->remote;
-    v.state = &g->beast;
-    v.err = g->err;
-    v.errlen = sizeof g->err;
-    std::vector<msd_gb_input> in(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        GroupReceiver &r = g->rx[e[i].receiver];
-        in[i].receiver = e[i].receiver;
-        in[i].nbytes = e[i].nbytes;
-        in[i].offset = e[i].offset;
-        in[i].now_ms = e[i].now_ms;
-        in[i].filter = &r.resolver.filter;
-        in[i].nfix = r.opt.nfix_crc;
-        in[i].mode_ac = r.mode_ac ? 1 : 0;
-        r.history = true; /* the repair level is fixed from here on, as by a buffer */
-    }
-    rc = msd_gb_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, out, user);
-    if (rc)
-        c->failed = true;
-    return rc;
-}
-
 int msd_group_accept_beast(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
                            msd_group_message_fn sink, void *user)
 {
-    return group_accept_beast(g, bytes, on_device, e, n, sink, nullptr, user);
+    return group_accept_remote(g, bytes, on_device, e, n, sink, nullptr, user);
 }
 
 int msd_group_accept_beast_fields(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
                                   msd_group_fields_fn sink, void *user)
 {
     const msd_gb_out o = fields_out(sink);
-    return group_accept_beast(g, bytes, on_device, e, n, nullptr, &o, user);
+    return group_accept_remote(g, bytes, on_device, e, n, nullptr, &o, user);
 }
 
 int msd_group_accept_beast_wire(msd_group *g, const void *bytes, int on_device, const msd_group_beast_entry *e, uint32_t n,
                                 int format, uint32_t flags, msd_group_wire_fn sink, void *user)
 {
     const msd_gb_out o = wire_out(format, flags, sink);
-    return group_accept_beast(g, bytes, on_device, e, n, nullptr, &o, user);
+    return group_accept_remote(g, bytes, on_device, e, n, nullptr, &o, user);
 }
 
 int msd_group_get_remote_stats(const msd_group *g, uint32_t receiver, msd_remote_stats *st)
@@ -1118,89 +1138,31 @@ int msd_group_get_remote_stats(const msd_group *g, uint32_t receiver, msd_remote
     return 0;
 }
 
-/* AVR text input per receiver: the same checks, the entries' flags, then the call (msd_group_avr.cpp) */
-static int group_accept_avr(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
-                            msd_group_message_fn sink, const msd_gb_out *out, void *user)
-{
-    if (!g)
-        return -EINVAL;
-    msd_ctx *c = g->ctx;
-    if (int rc = group_check_out(g, out))
-        return rc;
-    if (n > g->max_receivers)
-        return gfail(g, -EINVAL, "AVR entries: more than max_receivers");
-    if (n && (!e || !bytes))
-        return gfail(g, -EINVAL, "AVR entries: NULL bytes or entries");
-    std::vector<bool> seen(g->max_receivers, false);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (e[i].receiver >= g->max_receivers || seen[e[i].receiver] || (e[i].flags & ~MSD_AVR_KEEP_TIMESTAMP) || e[i].reserved)
-            return gfail(g, -EINVAL, "AVR entry %u: a receiver out of range or given twice, an unknown flag or nonzero reserved", i);
-        if (e[i].nbytes > MSD_GROUP_AVR_ENTRY_MAX || e[i].offset > MSD_GROUP_AVR_OFFSET_MAX)
-            return gfail(g, -EINVAL, "AVR entry %u: more than %u bytes, or an offset above 2^47", i, MSD_GROUP_AVR_ENTRY_MAX);
-        seen[e[i].receiver] = true;
-    }
-    if (c->failed)
-        return gfail(g, -EIO, "an earlier call failed");
-    if (n == 0)
-        return 0;
-    msd_frames_view fv;
-    int rc = msd_frames_get_view(c, &fv); /* the CRC and repair tables of the group's context */
-    if (rc)
-        return gfail(g, rc, "AVR input: no tables");
-    msd_gb_view v{};
-    v.stream = fv.stream;
-    v.device = fv.device;
-    v.max_receivers = g->max_receivers;
-    v.tables = fv.tables;
-    v.d_snaps = g->gpu ? g->d_snaps : nullptr;
-    v.remote = g->remote;
-    v.state = &g->avr;
-    v.err = g->err;
-    v.errlen = sizeof g->err;
-    std::vector<msd_ga_input> in(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        GroupReceiver &r = g->rx[e[i].receiver];
-        in[i].receiver = e[i].receiver;
-        in[i].nbytes = e[i].nbytes;
-        in[i].flags = e[i].flags;
-        in[i].offset = e[i].offset;
-        in[i].now_ms = e[i].now_ms;
-        in[i].filter = &r.resolver.filter;
-        in[i].nfix = r.opt.nfix_crc;
-        in[i].mode_ac = r.mode_ac ? 1 : 0;
-        r.history = true; /* the repair level is fixed from here on, as by a buffer */
-    }
-    rc = msd_ga_accept(&v, bytes, on_device ? 1 : 0, in.data(), n, sink, out, user);
-    if (rc)
-        c->failed = true;
-    return rc;
-}
-
 int msd_group_accept_avr(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
                          msd_group_message_fn sink, void *user)
 {
-    return group_accept_avr(g, bytes, on_device, e, n, sink, nullptr, user);
+    return group_accept_remote(g, bytes, on_device, e, n, sink, nullptr, user);
 }
 
 int msd_group_accept_avr_fields(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
                                 msd_group_fields_fn sink, void *user)
 {
     const msd_gb_out o = fields_out(sink);
-    return group_accept_avr(g, bytes, on_device, e, n, nullptr, &o, user);
+    return group_accept_remote(g, bytes, on_device, e, n, nullptr, &o, user);
 }
 
 int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, const msd_group_avr_entry *e, uint32_t n,
                               int format, uint32_t flags, msd_group_wire_fn sink, void *user)
 {
     const msd_gb_out o = wire_out(format, flags, sink);
-    return group_accept_avr(g, bytes, on_device, e, n, nullptr, &o, user);
+    return group_accept_remote(g, bytes, on_device, e, n, nullptr, &o, user);
 }
 
 int msd_group_get_avr_stats(const msd_group *g, uint32_t receiver, msd_avr_stats *st)
 {
     if (!g || !st || receiver >= g->max_receivers)
         return -EINVAL;
-    msd_ga_get_stats(g->avr, receiver, st);
+    msd_gr_get_avr_stats(g->avr, receiver, st);
     return 0;
 }
 

@@ -1,6 +1,6 @@
 /*
  * msd_group_avr.h -- AVR raw text input per receiver of a group (msd_group_accept_avr): what
- * msd_group.cpp (the entry, its checks), msd_group_avr.cpp (pieces, scratch, the receivers' kept lines) and
+ * msd_group.cpp (the entry, its checks), msd_group_remote.cpp (pieces, scratch, the receivers' kept lines) and
  * msd_group_avr_kernels.hip share.
  *
  * The layout is the Beast input's (msd_group_beast.h): a call is cut into pieces of whole entries, and in a piece every
@@ -51,24 +51,7 @@ typedef struct msd_ga_scratch {
  * segment and the class of every record.  Leaves the totals in f.tot and the per-entry counters in f.ctr. */
 int msd_ga_launch_frame_decode(const uint8_t *src, const msd_fr_tables *t, const msd_ga_scratch *s, void *stream);
 
-/* ---- the driver (msd_group_avr.cpp) ---- */
-typedef struct msd_ga_input { /* one entry of a call, checked by the caller */
-    uint32_t receiver;
-    uint32_t nbytes;
-    uint32_t flags; /* MSD_AVR_KEEP_TIMESTAMP */
-    uint64_t offset;
-    uint64_t now_ms;
-    msd_filter *filter; /* the receiver's host filter */
-    int nfix;           /* its repair level */
-    int mode_ac;        /* its Mode A/C switch */
-} msd_ga_input;
-
-/* 0, or a negative errno with the text in v->err; -EIO leaves the receivers' state undefined.  out: as msd_gb_accept */
-int msd_ga_accept(const msd_gb_view *v, const void *bytes, int on_device, const msd_ga_input *in, uint32_t n,
-                  msd_group_message_fn sink, const msd_gb_out *out, void *user);
-void msd_ga_reset_receiver(void *state, uint32_t receiver);
-void msd_ga_get_stats(const void *state, uint32_t receiver, msd_avr_stats *st);
-void msd_ga_free(void *state);
+/* the driver is the Beast input's: msd_gr_accept (msd_group_beast.h, msd_group_remote.cpp) */
 
 #ifdef __cplusplus
 }

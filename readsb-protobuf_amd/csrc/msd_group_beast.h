@@ -1,6 +1,6 @@
 /*
  * msd_group_beast.h -- Beast input per receiver of a group (msd_group_accept_beast): what
- * msd_group.cpp (the entry, its checks), msd_group_beast.cpp (pieces, scratch, the receivers' framing state) and
+ * msd_group.cpp (the entry, its checks), msd_group_remote.cpp (pieces, scratch, the receivers' framing state) and
  * msd_group_beast_kernels.hip share.
  *
  * A call is laid out as pieces of whole entries.  In a piece every entry has a segment [s0, s1): its kept incomplete
@@ -119,18 +119,22 @@ typedef struct msd_gb_out {
     int verbatim; /* MSD_WIRE_VERBATIM */
 } msd_gb_out;
 
-/* ---- the driver (msd_group_beast.cpp) ---- */
-typedef struct msd_gb_input { /* one entry of a call, checked by the caller */
+/* ---- the driver of both remote inputs (msd_group_remote.cpp) ---- */
+enum { MSD_GR_BEAST = 0, MSD_GR_AVR = 1 };
+
+typedef struct msd_gr_input { /* one entry of a call, checked by the caller */
     uint32_t receiver;
     uint32_t nbytes;
+    uint32_t flags; /* AVR: MSD_AVR_KEEP_TIMESTAMP; Beast: 0 */
     uint64_t offset;
     uint64_t now_ms;
     msd_filter *filter; /* the receiver's host filter */
     int nfix;           /* its repair level */
     int mode_ac;        /* its Mode A/C switch */
-} msd_gb_input;
+} msd_gr_input;
 
 typedef struct msd_gb_view { /* what the driver needs of a group */
+    int format; /* MSD_GR_* */
     void *stream;
     int device;
     uint32_t max_receivers;
@@ -138,17 +142,19 @@ typedef struct msd_gb_view { /* what the driver needs of a group */
     uint32_t *d_snaps; /* the receivers' resident snapshots ([max_receivers][MSD_SNAP_WORDS]); NULL: a group that
                           resolves on the host, the call then uploads the snapshots of its own receivers */
     msd_remote_stats *remote; /* [max_receivers] the receivers' remote counters, which both inputs add to */
-    void **state;      /* the driver's own, created by its first call */
+    void **state;      /* the driver's own of this format (scratch and the receivers' carries), created by its first call */
     char *err;
     size_t errlen;
 } msd_gb_view;
 
 /* 0, or a negative errno with the text in v->err; -EIO leaves the receivers' state undefined.  out: NULL for the plain
  * call (records to `sink`), else the fields or wire call (`sink` is not used) */
-int msd_gb_accept(const msd_gb_view *v, const void *bytes, int on_device, const msd_gb_input *in, uint32_t n,
+int msd_gr_accept(const msd_gb_view *v, const void *bytes, int on_device, const msd_gr_input *in, uint32_t n,
                   msd_group_message_fn sink, const msd_gb_out *out, void *user);
-void msd_gb_reset_receiver(void *state, uint32_t receiver);
-void msd_gb_free(void *state);
+/* state: NULL, or what a call left in *v->state (it knows its format); avr_state: of MSD_GR_AVR calls */
+void msd_gr_reset_receiver(void *state, uint32_t receiver);
+void msd_gr_get_avr_stats(const void *avr_state, uint32_t receiver, msd_avr_stats *st);
+void msd_gr_free(void *state); /* with the group's device current: releases the scratch */
 
 #ifdef __cplusplus
 }

@@ -40,10 +40,9 @@ fi
 # HIP headers, instrumented in both modes (their kernels stay in msd_frames_kernels.o / msd_kernels.o)
 $CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_frames.cpp -o "$OUT/msd_frames.o"
 $CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_group.cpp -o "$OUT/msd_group.o"
-$CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_group_beast.cpp -o "$OUT/msd_group_beast.o"
-$CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_group_avr.cpp -o "$OUT/msd_group_avr.o"
+$CXX -std=c++17 -O1 -g -fPIC $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_group_remote.cpp -o "$OUT/msd_group_remote.o"
 $CXX -std=c++17 -O1 -g -fPIC $SAN -ffp-contract=off -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $INC -c msd_pos.cpp -o "$OUT/msd_pos.o"
-CAPI_OBJ="$CAPI_OBJ $OUT/msd_frames.o $OUT/msd_group.o $OUT/msd_group_beast.o $OUT/msd_group_avr.o $OUT/msd_pos.o"
+CAPI_OBJ="$CAPI_OBJ $OUT/msd_frames.o $OUT/msd_group.o $OUT/msd_group_remote.o $OUT/msd_pos.o"
 # (the sanitizer runtime comes from LD_PRELOAD or from the instrumented executable: the shared objects leave it undefined)
 # (the wire writers are in both libraries, as in build.sh)
 $CC $CF -c host/msd_wire.c -o "$OUT/msd_wire.o"

@@ -386,3 +386,24 @@ def test_arguments_and_reset(pkg, rig):
     R.g.set_receiver_options(0, nfix_crc=1)  # unchanged level: allowed
     R.g.reset_receiver(0)
     R.g.set_receiver_options(0, nfix_crc=0)  # after the reset the level may change again
+
+
+# 12. a call of two pieces: nine entries of just under 1 MiB, mostly filler without a 0x1A
+def test_a_call_of_two_pieces(pkg, rig, torch_cuda):
+    rng = random.Random(12)
+    R = rig(9)
+    big = []
+    for r in range(9):
+        head = corrupted_corpus(rng, 40)
+        tail = corrupted_corpus(rng, 40) + frame(ord("3"), df17(r + 1))[:9]  # a frame cut across the call's end
+        room = (1 << 20) - 8 - r - len(head) - len(tail)
+        big.append((r, head + bytes([0x40 + r]) * room + tail))
+    sizes = [len(b) for _, b in big]
+    assert sum(sizes) > (8 << 20) >= sum(sizes[:8]) and all(s <= pkg.capi.GROUP_BEAST_ENTRY_MAX for s in sizes)
+    out = R.call(big, 20, device=torch_cuda)  # eight entries are the first piece, the ninth is the second
+    assert all(len(v) > 0 for v in out.values())
+    out = R.call([(r, frame(ord("3"), df17(r + 1))[9:]) for r in range(9)], 21)
+    assert all([int(m["addr"]) for m in out[r]] == [r + 1] for r in range(9))  # completed across the piece boundary too
+    R.check_stats()
+    assert all(ch.stats["garbage_bytes"] > 1000000 for ch in R.chk)  # the filler, charged to no frame
+    R.probe(30, rng, decoys=4)
