@@ -19,37 +19,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as g  # noqa: E402
-import indep_positions as ip  # noqa: E402
+import pos_streams as ps  # noqa: E402
 
 
-def encode(lat, lon, odd):
-    """tests/indep_positions.cpr_encode (airborne) over arrays."""
-    table = np.array(ip.NL_TABLE)
-    dlat = 360.0 / np.where(odd, 59.0, 60.0)
-    yz = np.floor(131072 * np.mod(lat, dlat) / dlat + 0.5)
-    rlat = dlat * (yz / 131072 + np.floor(lat / dlat))
-    nl = 59 - np.searchsorted(table, np.abs(rlat), side="right")
-    dlon = 360.0 / np.maximum(nl - odd, 1)
-    xz = np.floor(131072 * np.mod(lon, dlon) / dlon + 0.5)
-    return yz.astype(np.int64) & 0x1FFFF, xz.astype(np.int64) & 0x1FFFF
-
-
-def stream(pkg, aircraft, records, seed=1):
-    rng = np.random.default_rng(seed)
-    lat0, lon0 = rng.uniform(-60, 60, aircraft), rng.uniform(-180, 180, aircraft)
-    vlat, vlon = rng.uniform(-1.5e-6, 1.5e-6, aircraft), rng.uniform(-1.5e-6, 1.5e-6, aircraft)  # degrees per ms
-    i = np.arange(records)
-    a, k = i % aircraft, i // aircraft
-    t = 1_600_000_000_000 + k * 500 + (a * 500) // aircraft
-    odd = (k & 1).astype(np.int64)
-    dt = (k * 500).astype(np.float64)
-    y, x = encode(lat0[a] + vlat[a] * dt, lon0[a] + vlon[a] * dt, odd)
-    m = np.zeros(records, dtype=pkg.capi.MESSAGE_DTYPE)
-    f = np.zeros(records, dtype=pkg.capi.FIELDS_DTYPE)
-    m["sysTimestampMsg"], m["msgtype"], m["msgbits"], m["addr"] = t, 17, 112, 0x100000 + a
-    f["addr"], f["source"], f["metype"] = 0x100000 + a, 7, 11
-    f["cpr_valid"], f["cpr_type"], f["cpr_odd"], f["cpr_lat"], f["cpr_lon"] = 1, 1, odd, y, x
-    return m, f
+def stream(pkg, aircraft, records):
+    return ps.wide_stream(pkg, aircraft, records)[1:3]
 
 
 def median_rate(call, reset, n, repeat):

@@ -1,7 +1,9 @@
 """Constructed record streams for the position tracker's tests (test_positions_model.py on the CPU,
 test_gpu_positions.py on the GPU): a builder that writes msd_message / msd_fields rows the way the field decoder would
 have left them, the named scenarios of the issue, a 2000-record mixed stream, and runners for the three
-implementations (the GPU object, the host twin, the second reading of tests/indep_positions.py).
+implementations (the GPU object, the host twin, the second reading of tests/indep_positions.py).  For the machinery
+around the per-record logic (tests/test_gpu_positions_machinery.py): wide_stream, a vectorised stream of any length, and
+chain_scenario, five aircraft in one probe chain that runs across the end of the table.
 
 A scenario is (receivers, filter_persistence, steps); a step is ("update", msgs, fields, receiver) or ("expire", now_ms).
 Every scenario keeps every plausibility gate at least 1 m from its limit (asserted on the twin by the tests)."""
@@ -195,6 +197,109 @@ def mixed_stream(pkg, n=2000, seed=7):
             b.rec(t, 0, msgtype=0, source=ip.MODE_S, rx=p["rx"])
     _, m, f, r = b.step()
     return rxs, m[:n], f[:n], r[:n]
+
+
+def cpr_encode_array(lat, lon, odd):
+    """indep_positions.cpr_encode (airborne) over arrays."""
+    table = np.array(ip.NL_TABLE)
+    dlat = 360.0 / np.where(odd, 59.0, 60.0)
+    yz = np.floor(131072 * np.mod(lat, dlat) / dlat + 0.5)
+    rlat = dlat * (yz / 131072 + np.floor(lat / dlat))
+    nl = 59 - np.searchsorted(table, np.abs(rlat), side="right")
+    dlon = 360.0 / np.maximum(nl - odd, 1)
+    xz = np.floor(131072 * np.mod(lon, dlon) / dlon + 0.5)
+    return yz.astype(np.int64) & 0x1FFFF, xz.astype(np.int64) & 0x1FFFF
+
+
+def wide_stream(pkg, aircraft, records, receivers=1, skipped_every=0, seed=1):
+    """records airborne position squitters, round robin over `aircraft` aircraft (addresses 0x100000 + a, aircraft a on
+    receiver a % receivers, no receiver has a location), even and odd alternating, 500 ms between two positions of one
+    aircraft, each flying straight at up to about 450 kt: nearly every record is a global decode with a speed check, whose
+    limit of 500 m + 1.5 s x 933 kt stays about 1100 m from the at most 120 m flown.  skipped_every = k > 0 turns every
+    k-th record into one the tracker skips, in turn a Mode A/C record (msgtype 32) and address 0; the aircraft whose
+    record that was pairs its next half with one 1.5 s old.  In time order, no Python loop over the records.
+    -> (receivers, msgs, fields, receiver)."""
+    rng = np.random.default_rng(seed)
+    lat0, lon0 = rng.uniform(-60, 60, aircraft), rng.uniform(-180, 180, aircraft)
+    vlat, vlon = rng.uniform(-1.5e-6, 1.5e-6, aircraft), rng.uniform(-1.5e-6, 1.5e-6, aircraft)  # degrees per ms
+    i = np.arange(records)
+    a, k = i % aircraft, i // aircraft
+    t = T0 + k * 500 + (a * 500) // aircraft
+    odd = (k & 1).astype(np.int64)
+    dt = (k * 500).astype(np.float64)
+    y, x = cpr_encode_array(lat0[a] + vlat[a] * dt, lon0[a] + vlon[a] * dt, odd)
+    m = np.zeros(records, dtype=pkg.capi.MESSAGE_DTYPE)
+    f = np.zeros(records, dtype=pkg.capi.FIELDS_DTYPE)
+    m["sysTimestampMsg"], m["msgtype"], m["msgbits"], m["addr"] = t, 17, 112, 0x100000 + a
+    f["addr"], f["source"], f["metype"] = 0x100000 + a, ip.ADSB, 11
+    f["cpr_valid"], f["cpr_type"], f["cpr_odd"], f["cpr_lat"], f["cpr_lon"] = 1, 1, odd, y, x
+    if skipped_every:
+        skipped = i % skipped_every == skipped_every - 1
+        ac = skipped & ((i // skipped_every) % 2 == 0)
+        zero = skipped & ~ac
+        m["msgtype"][ac], f["source"][ac] = 32, ip.MODE_AC
+        m["msgtype"][zero], m["addr"][zero], f["addr"][zero], f["source"][zero] = 11, 0, 0, ip.MODE_S
+        for name in ("metype", "cpr_valid", "cpr_type", "cpr_odd", "cpr_lat", "cpr_lon"):
+            f[name][skipped] = 0
+    return [None] * receivers, m, f, (a % receivers).astype(np.uint32)
+
+
+def chain_addresses(pkg, capacity=64):
+    """Five addresses of receiver 0 with the home slots capacity - 1 (three), 0 and 1: inserted into an empty table they
+    occupy capacity - 1, 0, 1, 2, 3, one probe chain across the table's end."""
+    want = [capacity - 1] * 3 + [0, 1]
+    got = [None] * 5
+    a = 0x480000
+    while None in got:
+        s = pkg.capi.pos_home_slot(0, a, capacity)
+        for j in range(5):
+            if got[j] is None and want[j] == s:
+                got[j] = a
+                break
+        a += 1
+    return got
+
+
+CHAIN_VARIANTS = ("whole", "two_calls", "reversed")
+CHAIN_ALIVE = {"whole": [5, 5, 3, 3], "two_calls": [2, 5, 5, 3, 3], "reversed": [5, 5, 3, 3]}  # aircraft after each step
+
+
+def chain_place(j):
+    return 50.0 + 0.5 * j, 8.0 + 0.3 * j
+
+
+def chain_scenario(pkg, capacity=64, variant="whole"):
+    """The aircraft of chain_addresses: the first and third of the three that wrap and the one at home in slot 1 survive,
+    the two between them are heard once and leave from the middle of the chain.
+      1. at T0 a good even / odd pair for the survivors and one record for the others (two_calls: the first two aircraft
+         in one call, the rest in the next; reversed: the five in the opposite order);
+      2. at T0 + 61000 an even half per survivor: its odd half is 60.6 s old, so it decodes relative to the position of
+         step 1, through the speed check against that position, and becomes the position;
+      3. expiry at T0 + 61001: the others are more than 60 s old, the survivors move into the other table;
+      4. at T0 + 61400 the survivors' odd halves: global against the even half that was stored before the rebuild,
+         through the speed check against the position that was."""
+    assert variant in CHAIN_VARIANTS
+    addrs = chain_addresses(pkg, capacity)
+    order = [4, 3, 2, 1, 0] if variant == "reversed" else [0, 1, 2, 3, 4]
+    survivors = [j for j in order if j in (0, 2, 4)]
+    b = Builder(pkg)
+
+    def first(js):
+        for j in js:
+            b.pos(T0 + j, addrs[j], *chain_place(j), 0)
+        for j in js:
+            if j in survivors:
+                b.pos(T0 + 400 + j, addrs[j], *chain_place(j), 1)
+        return b.step()
+
+    steps = [first(order[:2]), first(order[2:])] if variant == "two_calls" else [first(order)]
+    for j in survivors:
+        b.pos(T0 + 61000, addrs[j], *chain_place(j), 0)
+    steps += [b.step(), ("expire", T0 + 61001)]
+    for j in survivors:
+        b.pos(T0 + 61400, addrs[j], *chain_place(j), 1)
+    steps.append(b.step())
+    return [None], 0, steps
 
 
 # ---- runners -------------------------------------------------------------------------------------------------------

@@ -156,6 +156,8 @@ def test_cutting_invariance(pkg, torch_cuda, mixed):
         t.close()
         assert cut.tobytes() == whole.tobytes(), pieces
         assert {k: cst[k] for k in COUNTERS} == {k: st[k] for k in COUNTERS}
+        # the same device arithmetic, reduced over one walker at a time here and over dozens at once there
+        assert np.float64(cst["min_gate_margin_m"]).tobytes() == np.float64(st["min_gate_margin_m"]).tobytes(), pieces
 
 
 def test_device_records_and_bad_receiver_index(pkg, torch_cuda, mixed):

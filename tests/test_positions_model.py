@@ -133,3 +133,96 @@ def test_table_full_changes_nothing(pkg, scen):
     t.update(m[60:], f[60:], r[60:])                    # exactly full is fine
     assert t.stats()["aircraft"] == 64
     t.close()
+
+
+# ---- the streams of tests/test_gpu_positions_machinery.py, fixed here before they meet the device ----
+def twin_at(pkg, capacity, receivers, fp, steps, pieces=None):
+    t = pkg.capi.PositionTracker(capacity=capacity, receivers=receivers, filter_persistence=fp, host=True)
+    out = ps.run_library(t, steps, pieces)
+    st = t.stats()
+    t.close()
+    return out, st
+
+
+def test_wide_stream_twin_equals_the_second_reading(pkg):
+    receivers, m, f, r = ps.wide_stream(pkg, aircraft=700, records=5600, receivers=3, skipped_every=17)
+    steps = [("update", m, f, r)]
+    out, st = twin_run(pkg, receivers, 0, steps)
+    rows, mst = ps.run_model(receivers, 0, steps)
+    assert ps.rows_of(out) == ps.rows_of_model(rows)
+    assert st == mst
+    assert st["min_gate_margin_m"] >= 1.0, st["min_gate_margin_m"]
+    # what the stream is: round robin in time order, three receivers, every 17th record skipped in both ways, and
+    # nearly every other record from the second round on a global decode
+    assert (np.diff(m["sysTimestampMsg"].astype(np.int64)) >= 0).all() and set(r.tolist()) == {0, 1, 2}
+    skipped = (m["msgtype"] == 32) | (f["addr"] == 0)
+    assert (f["addr"][~skipped] == 0x100000 + (np.arange(5600) % 700)[~skipped]).all()
+    assert skipped.sum() == 5600 // 17 and skipped[16::17].all() and (m["msgtype"] == 32).sum() == 165 and (f["addr"] == 0).sum() == 164
+    assert (out["result"][skipped] == pkg.capi.POS_NOT_TRIED).all()
+    assert st["aircraft"] == 700 and st["cpr_global_ok"] > 4400 and st["cpr_airborne"] == 5600 - skipped.sum()
+
+
+def test_wide_stream_without_options_is_one_receiver_and_all_positions(pkg):
+    receivers, m, f, r = ps.wide_stream(pkg, aircraft=7, records=70)
+    assert receivers == [None] and not r.any() and f["cpr_valid"].all() and (m["msgtype"] == 17).all()
+    assert (f["cpr_odd"] == (np.arange(70) // 7) % 2).all()
+    assert (np.diff(m["sysTimestampMsg"][::7].astype(np.int64)) == 500).all()
+    out, st = twin_run(pkg, receivers, 0, [("update", m, f, r)])
+    assert st["cpr_global_ok"] == 63 and st["min_gate_margin_m"] >= 1.0
+
+
+@pytest.mark.parametrize("kw", [dict(aircraft=300, records=2048, skipped_every=17),
+                                dict(aircraft=5000, records=20000, receivers=3, skipped_every=17)])
+def test_wide_streams_of_the_gpu_tests_keep_their_margin_and_cut_anywhere(pkg, kw):
+    receivers, m, f, r = ps.wide_stream(pkg, **kw)
+    steps = [("update", m, f, r)]
+    whole, st = twin_at(pkg, 8192, receivers, 0, steps)
+    assert st["min_gate_margin_m"] >= 1.0, st["min_gate_margin_m"]
+    assert st["aircraft"] == kw["aircraft"] and st["cpr_global_ok"] > len(m) // 2
+    cut, cst = twin_at(pkg, 8192, receivers, 0, steps, pieces=257)
+    assert cut.tobytes() == whole.tobytes() and cst == st
+
+
+def test_chain_addresses_share_one_chain_across_the_end(pkg):
+    for cap in (64, 256):
+        addrs = ps.chain_addresses(pkg, cap)
+        assert len(set(addrs)) == 5
+        assert [pkg.capi.pos_home_slot(0, a, cap) for a in addrs] == [cap - 1, cap - 1, cap - 1, 0, 1]
+
+
+@pytest.mark.parametrize("variant", ps.CHAIN_VARIANTS)
+def test_chain_scenario(pkg, variant):
+    receivers, fp, steps = ps.chain_scenario(pkg, 64, variant)
+    out, st = twin_at(pkg, 64, receivers, fp, steps)
+    rows, mst = ps.run_model(receivers, fp, steps)
+    assert ps.rows_of(out) == ps.rows_of_model(rows)
+    assert st == mst
+    assert st["min_gate_margin_m"] >= 1.0, st["min_gate_margin_m"]
+    # known answers: step 1 pairs the survivors, step 2 is aircraft-relative, step 4 global at the survivors' places
+    n1 = 8
+    first, even, late = out[:n1], out[n1:n1 + 3], out[n1 + 3:]
+    assert sorted(int(x) for x in first["result"]) == [-1] * 5 + [0] * 3
+    assert [int(x) for x in even["result"]] == [1, 1, 1]
+    assert [int(x) for x in late["result"]] == [0, 0, 0] and late["decoded"].all() and not late["relative"].any()
+    survivors = [4, 2, 0] if variant == "reversed" else [0, 2, 4]
+    for o, j in zip(late, survivors):
+        lat, lon = ps.chain_place(j)
+        assert abs(o["lat"] - lat) < 1e-4 and abs(o["lon"] - lon) < 1e-4
+    assert st["cpr_global_ok"] == 6 and st["cpr_local_aircraft_relative"] == 3 and st["cpr_global_speed_checks"] == 0
+    # the aircraft alive after each step
+    t = pkg.capi.PositionTracker(capacity=64, receivers=receivers, host=True)
+    alive = []
+    for s in steps:
+        ps.run_library(t, [s])
+        alive.append(t.stats()["aircraft"])
+    t.close()
+    assert alive == ps.CHAIN_ALIVE[variant]
+
+
+def test_nothing_delivered_depends_on_the_capacity(pkg):
+    receivers, m, f, r = ps.mixed_stream(pkg)
+    steps = [("update", m, f, r)]
+    small, sst = twin_at(pkg, 64, receivers, 0, steps)
+    large, lst = twin_at(pkg, 1024, receivers, 0, steps)
+    assert small.tobytes() == large.tobytes() and sst == lst
+    assert sst["min_gate_margin_m"] >= 1.0
