@@ -846,8 +846,9 @@ int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, co
  * the per-source ADS-B versions that select gs.v0 or gs.v2 (:1032-1075, :1222-1235, :1313-1329); messageNow() is the
  * record's sysTimestampMsg (:1010); Mode A/C records and records with msd_fields.addr == 0 are skipped (:999-1008).
  * Aircraft are keyed by (receiver index, the 25 low bits of msd_fields.addr, MSD_NON_ICAO_ADDRESS included); a record's
- * receiver index also selects the receiver location and --max-range its checks use.  Not built: decoded_nic /
- * decoded_rc, the declination, the polar range, SBS and MLAT positions, and every other member of struct aircraft.
+ * receiver index also selects the receiver location and --max-range its checks use.  The other members of struct
+ * aircraft, with decoded_nic / decoded_rc, are kept by a tracker made with msd_pos_create_table ("the aircraft table"
+ * below).  Not built: the Mode A/C matching, the declination, the polar range, SBS and MLAT positions.
  *
  * What is exact.  The coordinates: double + - * / floor fmod in the reference's order, nothing contracted; delivered
  * lat / lon are bit-identical to the reference's whenever the decisions are.
@@ -918,6 +919,97 @@ int msd_pos_update(msd_pos *p, const msd_message *msgs, const msd_fields *fields
  * with an expired position. */
 int msd_pos_expire(msd_pos *p, uint64_t now_ms);
 int msd_pos_get_stats(const msd_pos *p, msd_pos_stats *st);
+
+/* ---- the aircraft table: the rest of trackUpdateFromMessage (track.c:1020-1378) kept per aircraft beside the position
+ * state, for a tracker made with msd_pos_create_table, and a way to read it out.  Members: the signal
+ * ring, addr_type, category, the per-source versions, HRD / TAH, the barometric altitude with its plausibility gate and
+ * altitude_baro_reliable (:1091-1151), squawk, emergency, geometric altitude and delta, the three headings, track rate,
+ * roll, Mach, the rates, air / ground (:1249-1258), callsign, the navigation state, QNH, alert, SPI, the accuracy
+ * members with the v0 NACp / SIL fill-in (:894-967, :1074-1089) and the sil_type rule (:1355-1360), the derived
+ * geometric altitude (:1373-1378), and NIC / Rc (:690-892, :969-976) as doGlobalCPR and doLocalCPR apply them (:378-379,
+ * :458-473).  accept_data's stale interval is 15 s for altitude_baro, squawk and airground and 60 s for the others; every
+ * member expires 70 s after its update, so a member keeps `source` and `updated` only -- except altitude_geom, whose
+ * validity combine_validity can make from two others and which keeps its stale and expiry times.
+ * Not built: the reduce_forward half of accept_data, FATSV state, the declination (geomag_calc), the polar range,
+ * Mode A/C matching (trackMatchAC, modeA_hit / modeC_hit), SBS and MLAT input.
+ *
+ * Everything in a table entry is an integer the message carried or a copy of a double; no float is computed on the
+ * device.  A heading is the raw value plus the kind that says which of msd_fields_to_float's expressions turns it into
+ * degrees; roll, track rate, Mach, QNH and the selected heading stay raw.  msd_aircraft_to_float applies the expressions
+ * on the host.  CONTRACT: the device and the host object deliver the same bytes -- msd_aircraft entries and msd_pos_nicrc
+ * records -- on every stream on which they deliver the same msd_position records. ---- */
+enum { /* the members of msd_aircraft.source / .updated: struct aircraft's data_validity records */
+    MSD_AC_CALLSIGN = 0, MSD_AC_ALTITUDE_BARO, MSD_AC_ALTITUDE_GEOM, MSD_AC_GEOM_DELTA, MSD_AC_GS, MSD_AC_IAS, MSD_AC_TAS,
+    MSD_AC_MACH, MSD_AC_TRACK, MSD_AC_TRACK_RATE, MSD_AC_ROLL, MSD_AC_MAG_HEADING, MSD_AC_TRUE_HEADING, MSD_AC_BARO_RATE,
+    MSD_AC_GEOM_RATE, MSD_AC_SQUAWK, MSD_AC_AIRGROUND, MSD_AC_NAV_QNH, MSD_AC_NAV_ALTITUDE_MCP, MSD_AC_NAV_ALTITUDE_FMS,
+    MSD_AC_NAV_ALTITUDE_SRC, MSD_AC_NAV_HEADING, MSD_AC_NAV_MODES, MSD_AC_CPR_ODD, MSD_AC_CPR_EVEN, MSD_AC_POSITION,
+    MSD_AC_NIC_A, MSD_AC_NIC_C, MSD_AC_NIC_BARO, MSD_AC_NAC_P, MSD_AC_NAC_V, MSD_AC_SIL, MSD_AC_GVA, MSD_AC_SDA,
+    MSD_AC_EMERGENCY, MSD_AC_ALERT, MSD_AC_SPI, MSD_AC_N
+};
+/* msd_aircraft_heading.kind: which expression of msd_fields_to_float gives the degrees */
+enum { MSD_HDG_NONE = 0, MSD_HDG_COMMB = 1 /* BDS 5,0 / 6,0: (raw & 1023) * 90 / 512, + 180 with bit 10 */,
+       MSD_HDG_ES19 = 2 /* raw * 360 / 1024 */, MSD_HDG_SURFACE = 3 /* raw * 360 / 128 */,
+       MSD_HDG_VELOCITY = 4 /* atan2(ew, ns), the ground track of an airborne velocity */ };
+typedef struct msd_aircraft_heading { /* 8 bytes */
+    uint16_t raw;
+    int16_t ew, ns;
+    uint8_t kind;
+    uint8_t pad;
+} msd_aircraft_heading;
+typedef struct msd_aircraft { /* 592 bytes, no implicit padding; one per slot of a table tracker, in both tables */
+    uint32_t receiver, addr;       /* the key: receiver index, the 25 low bits of msd_fields.addr */
+    uint64_t seen, messages;       /* meta.seen / meta.messages */
+    double lat, lon;               /* meta.lat / meta.lon, with MSD_AC_POSITION */
+    uint32_t gs, ias, tas;
+    int32_t pos_reliable_odd, pos_reliable_even;
+    int32_t altitude_baro_reliable;
+    double signal_level[8];        /* signalLevel[8], 1e-5 until written */
+    uint64_t updated[MSD_AC_N];    /* data_validity.updated; stale = updated + 15 s (altitude_baro, squawk, airground) or
+                                      60 s, expires = updated + 70 s, altitude_geom aside */
+    uint64_t altitude_geom_stale, altitude_geom_expires;
+    int32_t alt_baro, alt_geom, geom_delta, baro_rate, geom_rate, nav_altitude_mcp, nav_altitude_fms; /* feet, ft/min */
+    msd_aircraft_heading track, mag_heading, true_heading;
+    uint16_t squawk;
+    uint16_t mach_raw;             /* Mach = mach_raw * 2.048 / 512 */
+    uint16_t nav_qnh_raw;          /* 800 + raw * 0.1 hPa with nav_qnh_commb, else 800 + (raw - 1) * 0.8 */
+    uint16_t nav_heading_raw;      /* x 180 / 256 with nav_heading_v2, else degrees */
+    uint16_t rc, cpr_odd_rc, cpr_even_rc; /* metres, 0 = unknown */
+    int16_t roll_q, track_rate_q;  /* as msd_fields */
+    uint8_t source[MSD_AC_N];      /* data_validity.source; 0 = invalid */
+    char callsign[8];
+    uint8_t signal_next, addr_type, category, adsb_hrd, adsb_tah, heading_type, air_ground, emergency, alert, spi,
+        nav_altitude_src, nav_modes, nav_qnh_commb, nav_heading_v2, nic, cpr_odd_nic, cpr_even_nic, nic_a, nic_c, nic_baro,
+        nac_p, nac_v, sil, sil_type, gva, sda;
+    int8_t adsb_version, tisb_version, adsr_version; /* -1 until a message of that source was seen */
+    uint8_t altitude_geom_stale_15s; /* altitude_geom's validity was last copied whole from altitude_baro's (combine_validity
+                                        with an invalid geom_delta): its stale interval is 15 s from then on */
+    uint8_t pad[7];                  /* 0 */
+} msd_aircraft;
+typedef struct msd_aircraft_float { /* the float-valued members of a table entry; 0 where the member was never set */
+    float track, mag_heading, true_heading, track_rate, roll, nav_qnh, nav_heading;
+    float pad;
+    double mach;
+} msd_aircraft_float;
+typedef struct msd_pos_nicrc { /* struct modesMessage's decoded_nic / decoded_rc */
+    uint16_t rc;
+    uint8_t nic;
+    uint8_t set; /* 1 exactly where msd_position.decoded is 1 */
+} msd_pos_nicrc;
+/* msd_pos_create plus one msd_aircraft per slot: 136 + 592 bytes per slot, twice.  -ENOMEM when that does not fit.  A
+ * tracker from msd_pos_create has no table: it allocates and launches what it did before the table existed. */
+int msd_pos_create_table(const msd_pos_config *cfg, msd_pos **out);
+/* msd_pos_update with decoded_nic / decoded_rc per record in the host array nicrc (n entries).  -EINVAL on a tracker
+ * without a table.  msd_pos_update itself feeds the table of a table tracker too. */
+int msd_pos_update_nicrc(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                         int on_device, msd_position *out, msd_pos_nicrc *nicrc);
+/* Every live aircraft, in ascending (receiver, addr) order -- compacted and ordered on the device, whatever slots the
+ * aircraft are in --, into out[0 .. *n): device memory (on_device = 1) or host memory of cap entries.  -ENOSPC, with *n
+ * the number of live aircraft and nothing written: cap is too small.  -EINVAL: no table, NULL n, NULL out with cap > 0. */
+int msd_pos_snapshot(msd_pos *p, msd_aircraft *out, size_t cap, int on_device, size_t *n);
+/* trackDataValid for one member of an entry at messageNow() = now_ms */
+int msd_aircraft_valid(const msd_aircraft *a, int member, uint64_t now_ms);
+/* the reference's floats of an entry, by msd_fields_to_float's expressions, on the host */
+void msd_aircraft_to_float(const msd_aircraft *a, msd_aircraft_float *out);
 
 #ifdef __cplusplus
 }

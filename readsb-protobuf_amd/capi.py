@@ -7,6 +7,7 @@ The binding mirrors the reference's interfaces for this path:
 There is no CPU fallback: loading or creating a context without the HIP library / a GPU raises.
 """
 import ctypes as C
+import errno
 import os
 
 import numpy as np
@@ -240,6 +241,7 @@ EXPORTS = [
     "msd_group_accept_avr_wire",
     "msd_pos_create", "msd_pos_destroy", "msd_pos_last_error", "msd_pos_reset", "msd_pos_set_receiver", "msd_pos_update",
     "msd_pos_expire", "msd_pos_get_stats",
+    "msd_pos_create_table", "msd_pos_update_nicrc", "msd_pos_snapshot", "msd_aircraft_valid", "msd_aircraft_to_float",
 ]
 
 _lib = None
@@ -1080,6 +1082,33 @@ POSITION_DTYPE = np.dtype([("lat", "<f8"), ("lon", "<f8"), ("decoded", "u1"), ("
                            ("result", "i1"), ("pad", "u1", (4,))], align=True)
 assert POSITION_DTYPE.itemsize == 24
 POS_NOT_TRIED = -3  # MSD_POS_NOT_TRIED
+# the aircraft table: msd_pos_nicrc, msd_aircraft and its member indices (MSD_AC_*)
+NICRC_DTYPE = np.dtype([("rc", "<u2"), ("nic", "u1"), ("set", "u1")])
+AC_MEMBERS = ("callsign", "altitude_baro", "altitude_geom", "geom_delta", "gs", "ias", "tas", "mach", "track", "track_rate",
+              "roll", "mag_heading", "true_heading", "baro_rate", "geom_rate", "squawk", "airground", "nav_qnh",
+              "nav_altitude_mcp", "nav_altitude_fms", "nav_altitude_src", "nav_heading", "nav_modes", "cpr_odd", "cpr_even",
+              "position", "nic_a", "nic_c", "nic_baro", "nac_p", "nac_v", "sil", "gva", "sda", "emergency", "alert", "spi")
+AC = {k: i for i, k in enumerate(AC_MEMBERS)}
+HEADING_DTYPE = np.dtype([("raw", "<u2"), ("ew", "<i2"), ("ns", "<i2"), ("kind", "u1"), ("pad", "u1")])
+AIRCRAFT_DTYPE = np.dtype(
+    [("receiver", "<u4"), ("addr", "<u4"), ("seen", "<u8"), ("messages", "<u8"), ("lat", "<f8"), ("lon", "<f8"),
+     ("gs", "<u4"), ("ias", "<u4"), ("tas", "<u4"), ("pos_reliable_odd", "<i4"), ("pos_reliable_even", "<i4"),
+     ("altitude_baro_reliable", "<i4"), ("signal_level", "<f8", (8,)), ("updated", "<u8", (len(AC_MEMBERS),)),
+     ("altitude_geom_stale", "<u8"), ("altitude_geom_expires", "<u8"), ("alt_baro", "<i4"), ("alt_geom", "<i4"),
+     ("geom_delta", "<i4"), ("baro_rate", "<i4"), ("geom_rate", "<i4"), ("nav_altitude_mcp", "<i4"),
+     ("nav_altitude_fms", "<i4"), ("track", HEADING_DTYPE), ("mag_heading", HEADING_DTYPE), ("true_heading", HEADING_DTYPE),
+     ("squawk", "<u2"), ("mach_raw", "<u2"), ("nav_qnh_raw", "<u2"), ("nav_heading_raw", "<u2"), ("rc", "<u2"),
+     ("cpr_odd_rc", "<u2"), ("cpr_even_rc", "<u2"), ("roll_q", "<i2"), ("track_rate_q", "<i2"),
+     ("source", "u1", (len(AC_MEMBERS),)), ("callsign", "S8")]
+    + [(k, "u1") for k in ("signal_next", "addr_type", "category", "adsb_hrd", "adsb_tah", "heading_type", "air_ground",
+                           "emergency", "alert", "spi", "nav_altitude_src", "nav_modes", "nav_qnh_commb", "nav_heading_v2",
+                           "nic", "cpr_odd_nic", "cpr_even_nic", "nic_a", "nic_c", "nic_baro", "nac_p", "nac_v", "sil",
+                           "sil_type", "gva", "sda")]
+    + [("adsb_version", "i1"), ("tisb_version", "i1"), ("adsr_version", "i1"), ("altitude_geom_stale_15s", "u1"),
+       ("pad", "u1", (7,))])
+assert AIRCRAFT_DTYPE.itemsize == 592 and NICRC_DTYPE.itemsize == 4
+AIRCRAFT_FLOAT_DTYPE = np.dtype([(k, "<f4") for k in ("track", "mag_heading", "true_heading", "track_rate", "roll", "nav_qnh",
+                                                      "nav_heading", "pad")] + [("mach", "<f8")])
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmsd_host.so")
 
 
@@ -1122,7 +1151,12 @@ def _pos_lib(host):
     if host not in _pos_libs:
         L = C.CDLL(HOST_LIB_PATH) if host else lib()
         pre = "msd_pos_host_" if host else "msd_pos_"
-        f = {k: getattr(L, pre + k) for k in ("create", "destroy", "reset", "set_receiver", "update", "expire", "get_stats")}
+        f = {k: getattr(L, pre + k) for k in ("create", "destroy", "reset", "set_receiver", "update", "expire", "get_stats",
+                                              "create_table", "update_nicrc", "snapshot")}
+        f["create_table"].argtypes = [C.POINTER(PosConfig), C.POINTER(C.c_void_p)]
+        f["update_nicrc"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + (
+            [] if host else [C.c_int]) + [C.c_void_p, C.c_void_p]
+        f["snapshot"].argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + ([] if host else [C.c_int]) + [C.POINTER(C.c_size_t)]
         f["create"].argtypes = [C.POINTER(PosConfig), C.POINTER(C.c_void_p)]
         f["destroy"].argtypes = [C.c_void_p]
         f["destroy"].restype = None
@@ -1153,15 +1187,16 @@ class PositionTracker:
     """msd_pos on the GPU (host=False) or its twin on the host (host=True): the same calls, the same results on every
     stream whose min_gate_margin_m on the twin stays above 1e-3 m."""
 
-    def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False):
-        self.host = host
+    def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False, table=False):
+        """table=True: msd_pos_create_table -- the tracker also keeps the aircraft table (update_nicrc, snapshot)."""
+        self.host, self.table = host, table
         self.L, self.f = _pos_lib(host)
         receivers = receivers if receivers is not None else [None]
         self._rx = _pos_receivers(receivers)
         cfg = PosConfig(device=device, filter_persistence=filter_persistence, capacity=capacity,
                         receivers=len(receivers), receiver=self._rx)
         self.h = C.c_void_p()
-        rc = self.f["create"](C.byref(cfg), C.byref(self.h))
+        rc = self.f["create_table" if table else "create"](C.byref(cfg), C.byref(self.h))
         if rc != 0:
             self.h = None
             raise MsdError(f"msd_pos{'_host' if host else ''}_create failed: {rc} ({os.strerror(-rc)})")
@@ -1194,6 +1229,44 @@ class PositionTracker:
         self._check(self.f["update"](*args, *([] if self.host else [0]), out.ctypes.data), "msd_pos_update")
         return out
 
+    def update_nicrc(self, messages, fields, receiver=None):
+        """update() with decoded_nic / decoded_rc per record -> (POSITION_DTYPE array, NICRC_DTYPE array)."""
+        n = len(messages)
+        assert len(fields) == n and messages.dtype == MESSAGE_DTYPE and fields.dtype == FIELDS_DTYPE
+        messages, fields = np.ascontiguousarray(messages), np.ascontiguousarray(fields)
+        rx = None if receiver is None else np.ascontiguousarray(receiver, dtype=np.uint32)
+        out, nicrc = np.zeros(n, dtype=POSITION_DTYPE), np.zeros(n, dtype=NICRC_DTYPE)
+        args = [self.h, messages.ctypes.data, fields.ctypes.data, None if rx is None else rx.ctypes.data, n]
+        self._check(self.f["update_nicrc"](*args, *([] if self.host else [0]), out.ctypes.data, nicrc.ctypes.data),
+                    "msd_pos_update_nicrc")
+        return out, nicrc
+
+    def live(self):
+        """The number of aircraft a snapshot would deliver."""
+        n = C.c_size_t(0)
+        rc = self.f["snapshot"](self.h, None, 0, *([] if self.host else [0]), C.byref(n))
+        if rc not in (0, -errno.ENOSPC):
+            self._check(rc, "msd_pos_snapshot")
+        return n.value
+
+    def snapshot(self, cap=None):
+        """Every live aircraft in ascending (receiver, addr) order -> AIRCRAFT_DTYPE array.  cap: the entries offered
+        (default: as many as are live)."""
+        cap = self.live() if cap is None else cap
+        out = np.zeros(cap, dtype=AIRCRAFT_DTYPE)
+        n = C.c_size_t(0)
+        rc = self.f["snapshot"](self.h, out.ctypes.data if cap else None, cap, *([] if self.host else [0]), C.byref(n))
+        self.snapshot_count = n.value
+        self._check(rc, "msd_pos_snapshot")
+        return out[:n.value]
+
+    def snapshot_device(self, d_out, cap):
+        """The same into device memory of cap entries (a pointer); GPU tracker only -> the number written."""
+        assert not self.host
+        n = C.c_size_t(0)
+        self._check(self.f["snapshot"](self.h, d_out, cap, 1, C.byref(n)), "msd_pos_snapshot")
+        return n.value
+
     def update_device(self, d_messages, d_fields, n, d_receiver=None):
         """The same with the records in device memory (pointers); GPU tracker only."""
         assert not self.host
@@ -1223,6 +1296,26 @@ def cpr_host(kind, *args):
     lat, lon = C.c_double(0), C.c_double(0)
     r = getattr(L, "msd_cpr_host_" + kind)(*args, C.byref(lat), C.byref(lon))
     return r, lat.value, lon.value
+
+
+def aircraft_valid(entry, member, now_ms):
+    """msd_aircraft_valid (trackDataValid) for one AIRCRAFT_DTYPE entry; member: a name of AC_MEMBERS or its index."""
+    L = lib()
+    L.msd_aircraft_valid.restype = C.c_int
+    L.msd_aircraft_valid.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+    e = np.ascontiguousarray(entry, dtype=AIRCRAFT_DTYPE).reshape(1)
+    return bool(L.msd_aircraft_valid(e.ctypes.data, AC[member] if isinstance(member, str) else member, now_ms))
+
+
+def aircraft_to_float(entry):
+    """msd_aircraft_to_float for one AIRCRAFT_DTYPE entry -> AIRCRAFT_FLOAT_DTYPE scalar."""
+    L = lib()
+    L.msd_aircraft_to_float.restype = None
+    L.msd_aircraft_to_float.argtypes = [C.c_void_p, C.c_void_p]
+    e = np.ascontiguousarray(entry, dtype=AIRCRAFT_DTYPE).reshape(1)
+    out = np.zeros(1, dtype=AIRCRAFT_FLOAT_DTYPE)
+    L.msd_aircraft_to_float(e.ctypes.data, out.ctypes.data)
+    return out[0]
 
 
 def pos_home_slot(receiver, addr, capacity):

@@ -7,13 +7,14 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "msd_pos_impl.h"
+#include "msd_trk_impl.h"
 
 struct msd_pos_host {
     uint32_t cap, nrx;
     int fp;
     uint64_t *keys;
     msd_pos_aircraft *st;
+    msd_trk_aircraft *trk; /* a table tracker's entries, else NULL */
     msd_pos_receiver *rx;
     uint64_t live;
     msd_pos_acc acc;
@@ -50,7 +51,7 @@ static void clear(msd_pos_host *p)
     p->acc.margin = INFINITY;
 }
 
-int msd_pos_host_create(const msd_pos_config *cfg, msd_pos_host **out)
+static int create(const msd_pos_config *cfg, msd_pos_host **out, int table)
 {
     if (!out || !msd_pos_config_ok(cfg))
         return -EINVAL;
@@ -63,7 +64,9 @@ int msd_pos_host_create(const msd_pos_config *cfg, msd_pos_host **out)
     p->keys = malloc(sizeof(uint64_t) * p->cap);
     p->st = malloc(sizeof(msd_pos_aircraft) * p->cap);
     p->rx = calloc(p->nrx, sizeof(msd_pos_receiver));
-    if (!p->keys || !p->st || !p->rx) {
+    if (table)
+        p->trk = malloc(sizeof(msd_trk_aircraft) * p->cap);
+    if (!p->keys || !p->st || !p->rx || (table && !p->trk)) {
         msd_pos_host_destroy(p);
         return -ENOMEM;
     }
@@ -74,10 +77,21 @@ int msd_pos_host_create(const msd_pos_config *cfg, msd_pos_host **out)
     return 0;
 }
 
+int msd_pos_host_create(const msd_pos_config *cfg, msd_pos_host **out)
+{
+    return create(cfg, out, 0);
+}
+
+int msd_pos_host_create_table(const msd_pos_config *cfg, msd_pos_host **out)
+{
+    return create(cfg, out, 1);
+}
+
 void msd_pos_host_destroy(msd_pos_host *p)
 {
     if (!p)
         return;
+    free(p->trk);
     free(p->keys);
     free(p->st);
     free(p->rx);
@@ -113,6 +127,8 @@ static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
         if (p->keys[s] == MSD_POS_EMPTY) {
             p->keys[s] = key;
             msd_pos_aircraft_init(&p->st[s]);
+            if (p->trk)
+                msd_trk_init(&p->trk[s]);
             *fresh = 1;
             return s;
         }
@@ -120,14 +136,14 @@ static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
     return -1;
 }
 
-int msd_pos_host_update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
-                        size_t n, msd_position *out)
+static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                  msd_position *out, msd_pos_nicrc *nicrc, int want_nicrc)
 {
-    if (!p)
+    if (!p || (want_nicrc && !p->trk))
         return -EINVAL;
     if (n == 0)
         return 0;
-    if (!msgs || !fields || !out || n > ((size_t)1 << 24))
+    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || n > ((size_t)1 << 24))
         return -EINVAL;
     if (receiver)
         for (size_t i = 0; i < n; ++i)
@@ -159,17 +175,69 @@ int msd_pos_host_update(msd_pos_host *p, const msd_message *msgs, const msd_fiel
     }
     p->live += nadded;
     for (size_t i = 0; i < n; ++i) {
+        msd_pos_nicrc q = {0, 0, 0};
         if (slot[i] == UINT32_MAX) {
             memset(&out[i], 0, sizeof out[i]);
             out[i].result = MSD_POS_NOT_TRIED;
+            if (want_nicrc)
+                nicrc[i] = q;
             continue;
         }
         memset(&out[i], 0, sizeof out[i]);
         msd_pos_feed(&p->st[slot[i]], &p->rx[receiver ? receiver[i] : 0u], p->fp, msgs[i].sysTimestampMsg, &fields[i],
                      &out[i], &p->acc);
+        if (p->trk)
+            msd_trk_feed(&p->trk[slot[i]], msgs[i].sysTimestampMsg, &msgs[i], &fields[i], &out[i], &q);
+        if (want_nicrc)
+            nicrc[i] = q;
     }
     free(slot);
     free(added);
+    return 0;
+}
+
+int msd_pos_host_update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                        size_t n, msd_position *out)
+{
+    return update(p, msgs, fields, receiver, n, out, NULL, 0);
+}
+
+int msd_pos_host_update_nicrc(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                              size_t n, msd_position *out, msd_pos_nicrc *nicrc)
+{
+    return update(p, msgs, fields, receiver, n, out, nicrc, 1);
+}
+
+static int by_key(const void *a, const void *b)
+{
+    const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+    return x < y ? -1 : x > y;
+}
+
+int msd_pos_host_snapshot(msd_pos_host *p, msd_aircraft *out, size_t cap, size_t *n)
+{
+    if (!p || !p->trk || !n || (!out && cap > 0))
+        return -EINVAL;
+    *n = (size_t)p->live;
+    if (p->live > cap)
+        return -ENOSPC;
+    if (p->live == 0)
+        return 0;
+    /* (key, slot) pairs in key order: keys are unique */
+    uint64_t *ks = malloc(sizeof(uint64_t) * 2 * p->live);
+    if (!ks)
+        return -ENOMEM;
+    size_t k = 0;
+    for (uint32_t s = 0; s < p->cap; ++s)
+        if (p->keys[s] != MSD_POS_EMPTY) {
+            ks[2 * k] = p->keys[s];
+            ks[2 * k + 1] = s;
+            ++k;
+        }
+    qsort(ks, k, 2 * sizeof(uint64_t), by_key);
+    for (size_t j = 0; j < k; ++j)
+        msd_trk_export(ks[2 * j], &p->st[ks[2 * j + 1]], &p->trk[ks[2 * j + 1]], &out[j]);
+    free(ks);
     return 0;
 }
 
@@ -179,20 +247,28 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
         return -EINVAL;
     uint64_t removed = 0;
     for (uint32_t s = 0; s < p->cap; ++s)
-        if (p->keys[s] != MSD_POS_EMPTY && msd_pos_expire_one(&p->st[s], now_ms)) {
-            p->keys[s] = MSD_POS_EMPTY - 1u; /* marked; no key is that large */
-            ++removed;
+        if (p->keys[s] != MSD_POS_EMPTY) {
+            if (msd_pos_expire_one(&p->st[s], now_ms)) {
+                p->keys[s] = MSD_POS_EMPTY - 1u; /* marked; no key is that large */
+                ++removed;
+            } else if (p->trk) {
+                msd_trk_expire_one(&p->trk[s], now_ms);
+            }
         }
     if (!removed)
         return 0;
     /* linear probing has no holes to leave: the survivors are inserted again into an empty table */
     uint64_t *keys = malloc(sizeof(uint64_t) * p->cap);
     msd_pos_aircraft *st = malloc(sizeof(msd_pos_aircraft) * p->cap);
-    if (!keys || !st) {
+    msd_trk_aircraft *trk = p->trk ? malloc(sizeof(msd_trk_aircraft) * p->cap) : NULL;
+    if (!keys || !st || (p->trk && !trk)) {
         free(keys);
         free(st);
+        free(trk);
         return -ENOMEM;
     }
+    if (trk)
+        memcpy(trk, p->trk, sizeof(msd_trk_aircraft) * p->cap);
     memcpy(keys, p->keys, sizeof(uint64_t) * p->cap);
     memcpy(st, p->st, sizeof(msd_pos_aircraft) * p->cap);
     for (uint32_t s = 0; s < p->cap; ++s)
@@ -200,11 +276,15 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
     for (uint32_t s = 0; s < p->cap; ++s)
         if (keys[s] < MSD_POS_EMPTY - 1u) {
             int fresh = 0;
-            p->st[find_or_insert(p, keys[s], &fresh)] = st[s];
+            const int64_t d = find_or_insert(p, keys[s], &fresh);
+            p->st[d] = st[s];
+            if (trk)
+                p->trk[d] = trk[s];
         }
     p->live -= removed;
     free(keys);
     free(st);
+    free(trk);
     return 0;
 }
 

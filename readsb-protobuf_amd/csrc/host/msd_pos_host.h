@@ -18,6 +18,12 @@ int msd_pos_host_set_receiver(msd_pos_host *p, uint32_t receiver, const msd_pos_
 int msd_pos_host_update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                         size_t n, msd_position *out);
 int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms);
+/* the aircraft table (modes_hip.h, "the aircraft table"): msd_pos_create_table, msd_pos_update_nicrc and
+ * msd_pos_snapshot on the host, from msd_trk_impl.h; the same bytes */
+int msd_pos_host_create_table(const msd_pos_config *cfg, msd_pos_host **out);
+int msd_pos_host_update_nicrc(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                              size_t n, msd_position *out, msd_pos_nicrc *nicrc);
+int msd_pos_host_snapshot(msd_pos_host *p, msd_aircraft *out, size_t cap, size_t *n);
 int msd_pos_host_get_stats(const msd_pos_host *p, msd_pos_stats *st);
 /* the home slot of (receiver, addr) in a table of `capacity` slots (tests build collisions with it) */
 uint32_t msd_pos_host_home_slot(uint32_t receiver, uint32_t addr, uint32_t capacity);

@@ -19,6 +19,7 @@
  * --stats adds the four line counters.
  */
 #define _GNU_SOURCE
+#include <errno.h>
 #include <inttypes.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -48,11 +49,16 @@ static void print_raw(const msd_message *mm, void *user)
 /* --positions: the --raw line, and behind it "lat,lon" where readsb's tracker would have decoded a position from this
  * message (msd_pos_update on the GPU, one record at a time, with the fields of msd_decode_fields) */
 static msd_pos *g_pos;
+static uint64_t g_clock_start_ms; /* --clock-start-ms: added to sysTimestampMsg in front of the tracker ("The clock") */
+static uint64_t g_last_ms;        /* the last record's timestamp as the tracker saw it */
 static void print_raw_positions(const msd_message *mm, void *user)
 {
     FILE *out = user;
     msd_fields f;
     msd_position p;
+    msd_message tm = *mm;
+    tm.sysTimestampMsg += g_clock_start_ms;
+    g_last_ms = tm.sysTimestampMsg;
     if (g_mlat && mm->timestampMsg)
         fprintf(out, "@%012" PRIX64, mm->timestampMsg);
     else
@@ -61,7 +67,7 @@ static void print_raw_positions(const msd_message *mm, void *user)
         fprintf(out, "%02x", mm->msg[j]);
     fputc(';', out);
     msd_decode_fields(mm, NULL, &f);
-    const int rc = msd_pos_update(g_pos, mm, &f, NULL, 1, 0, &p);
+    const int rc = msd_pos_update(g_pos, &tm, &f, NULL, 1, 0, &p);
     if (rc) {
         fprintf(stderr, "msd_pos_update: %s (%d)\n", msd_pos_last_error(g_pos), rc);
         g_pos_failed = 1;
@@ -70,6 +76,50 @@ static void print_raw_positions(const msd_message *mm, void *user)
     }
     fputc('\n', out);
     g_count++;
+}
+
+/* --aircraft: after the last message, one line per aircraft of the table's snapshot, in (receiver, address) order:
+ * "aircraft ADDR,messages,callsign,squawk,altitude_baro,gs,lat,lon"; a member that is not valid at the last record's
+ * timestamp (msd_aircraft_valid) stays empty */
+static int print_aircraft(FILE *out)
+{
+    size_t n = 0;
+    int rc = msd_pos_snapshot(g_pos, NULL, 0, 0, &n);
+    if (rc != 0 && rc != -ENOSPC) {
+        fprintf(stderr, "msd_pos_snapshot: %s (%d)\n", msd_pos_last_error(g_pos), rc);
+        return 1;
+    }
+    if (n == 0)
+        return 0;
+    msd_aircraft *ac = calloc(n, sizeof *ac);
+    if (!ac || (rc = msd_pos_snapshot(g_pos, ac, n, 0, &n)) != 0) {
+        fprintf(stderr, "msd_pos_snapshot: %s (%d)\n", ac ? msd_pos_last_error(g_pos) : "out of memory", rc);
+        free(ac);
+        return 1;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const msd_aircraft *a = &ac[i];
+        fprintf(out, "aircraft %06x,%" PRIu64 ",", a->addr, a->messages);
+        if (msd_aircraft_valid(a, MSD_AC_CALLSIGN, g_last_ms))
+            fprintf(out, "%.8s", a->callsign);
+        fputc(',', out);
+        if (msd_aircraft_valid(a, MSD_AC_SQUAWK, g_last_ms))
+            fprintf(out, "%04x", a->squawk);
+        fputc(',', out);
+        if (msd_aircraft_valid(a, MSD_AC_ALTITUDE_BARO, g_last_ms))
+            fprintf(out, "%d", a->alt_baro);
+        fputc(',', out);
+        if (msd_aircraft_valid(a, MSD_AC_GS, g_last_ms))
+            fprintf(out, "%u", a->gs);
+        fputc(',', out);
+        if (msd_aircraft_valid(a, MSD_AC_POSITION, g_last_ms))
+            fprintf(out, "%.6f,%.6f", a->lat, a->lon);
+        else
+            fputc(',', out);
+        fputc('\n', out);
+    }
+    free(ac);
+    return 0;
 }
 
 static void print_net_raw(const msd_message *mm, void *user)
@@ -189,7 +239,7 @@ int main(int argc, char **argv)
     const char *beast_in = NULL, *avr_in = NULL;
     size_t beast_chunk = 65536, avr_chunk = 65536;
     uint64_t now_ms = 0;
-    int want_positions = 0, other_sink = 0;
+    int want_positions = 0, want_aircraft = 0, other_sink = 0;
     msd_pos_receiver home; /* --lat / --lon / --max-range as readsb spells them (readsb.c: Modes.receiver, Modes.maxRange) */
     memset(&home, 0, sizeof home);
     int have_lat = 0, have_lon = 0;
@@ -217,6 +267,8 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--net-verbatim")) g_net_verbatim = 1; /* readsb.c: Modes.net_verbatim */
         else if (!strcmp(a, "--stats")) want_stats = 1;
         else if (!strcmp(a, "--positions")) want_positions = 1;
+        else if (!strcmp(a, "--aircraft")) want_aircraft = 1;
+        else if (!strcmp(a, "--clock-start-ms") && next) { g_clock_start_ms = strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--lat") && next) { home.lat = atof(next); have_lat = 1; ++i; }
         else if (!strcmp(a, "--lon") && next) { home.lon = atof(next); have_lon = 1; ++i; }
         else if (!strcmp(a, "--max-range") && next) { home.max_range_m = atof(next) * 1852.0; ++i; } /* nautical miles -> metres */
@@ -241,18 +293,25 @@ int main(int argc, char **argv)
         } else {
             fprintf(stderr, "usage: msd_replay --ifile F [--iformat uc8|sc16|sc16q11] [--fix|--no-fix|--aggressive] [--dcfilter] "
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
-                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM]]\n"
+                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft] [--clock-start-ms N]]\n"
                             "       --positions: the --raw lines, with \"lat,lon\" behind the ';' of every message from which readsb's tracker\n"
                             "       would have decoded a position (CPR global and local, its range and speed checks; the coordinates are exact, the\n"
                             "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
                             "       receiver's location (both, or neither); --max-range: the absolute maximum range in nautical miles, 0 = none.\n"
                             "       Also with --beast-in and --avr-in; not with --net-raw, --beast or --no-output.\n"
+                            "       --aircraft (with --positions): after the last message one line per tracked aircraft,\n"
+                            "       \"aircraft ADDR,messages,callsign,squawk,altitude_baro,gs,lat,lon\", a member empty when it is not valid at the\n"
+                            "       last message's time.  --clock-start-ms: milliseconds added to every message's time in front of the tracker.\n"
                             "       msd_replay --beast-in F [--beast-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
                             "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n"
                             "       msd_replay --avr-in F [--avr-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
                             "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n");
             return 2;
         }
+    }
+    if (want_aircraft && !want_positions) {
+        fprintf(stderr, "--aircraft goes with --positions\n");
+        return 2;
     }
     if (want_positions) {
         if (other_sink) {
@@ -270,7 +329,7 @@ int main(int argc, char **argv)
         pc.capacity = 1u << 16;
         pc.receivers = 1;
         pc.receiver = &home;
-        const int prc = msd_pos_create(&pc, &g_pos);
+        const int prc = want_aircraft ? msd_pos_create_table(&pc, &g_pos) : msd_pos_create(&pc, &g_pos);
         if (prc) {
             fprintf(stderr, "msd_pos_create failed (%d)\n", prc);
             return 1;
@@ -280,6 +339,8 @@ int main(int argc, char **argv)
     if (avr_in || beast_in) {
         const int rc = avr_in ? run_remote_in(avr_in, 1, avr_chunk, now_ms, &rx, want_stats)
                               : run_remote_in(beast_in, 0, beast_chunk, now_ms, &rx, want_stats);
+        if (want_aircraft && !rc && print_aircraft(stdout))
+            g_pos_failed = 1;
         msd_pos_destroy(g_pos);
         return rc ? rc : g_pos_failed;
     }
@@ -322,6 +383,8 @@ int main(int argc, char **argv)
         }
     }
     msd_ifileClose();
+    if (want_aircraft && print_aircraft(stdout))
+        g_pos_failed = 1;
     msd_pos_destroy(g_pos);
     return g_pos_failed ? 1 : 0;
 }

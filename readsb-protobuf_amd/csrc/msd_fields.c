@@ -137,3 +137,54 @@ void msd_fields_to_float(const msd_fields *f, msd_fields_float *o)
         o->nav_heading_valid = 1;
     }
 }
+
+/* a table entry's floats: the expressions above applied to what msd_trk_feed kept raw */
+static float aircraft_heading(const msd_aircraft_heading *h)
+{
+    switch (h->kind) {
+    case MSD_HDG_COMMB: {
+        float v = (float)((h->raw & 1023u) * 90.0 / 512.0);
+        if (h->raw & 1024u)
+            v = (float)(v + 180.0);
+        return v;
+    }
+    case MSD_HDG_ES19:
+        return (float)(h->raw * 360.0 / 1024.0);
+    case MSD_HDG_SURFACE:
+        return (float)(h->raw * 360.0 / 128.0);
+    case MSD_HDG_VELOCITY: {
+        float ground_track = (float)(atan2(h->ew, h->ns) * 180.0 / M_PI);
+        if (ground_track < 0)
+            ground_track += 360;
+        return ground_track;
+    }
+    default:
+        return 0;
+    }
+}
+
+void msd_aircraft_to_float(const msd_aircraft *a, msd_aircraft_float *o)
+{
+    memset(o, 0, sizeof *o);
+    o->track = aircraft_heading(&a->track);
+    o->mag_heading = aircraft_heading(&a->mag_heading);
+    o->true_heading = aircraft_heading(&a->true_heading);
+    if (a->updated[MSD_AC_ROLL] || a->source[MSD_AC_ROLL]) {
+        float roll = (float)((unsigned)(a->roll_q & 511) * 45.0 / 256.0);
+        if (a->roll_q < 0)
+            roll = (float)(roll - 90.0);
+        o->roll = roll;
+    }
+    if (a->updated[MSD_AC_TRACK_RATE] || a->source[MSD_AC_TRACK_RATE]) {
+        float r = (float)((unsigned)(a->track_rate_q & 511) * 8.0 / 256.0);
+        if (a->track_rate_q < 0)
+            r = r - 16;
+        o->track_rate = r;
+    }
+    if (a->updated[MSD_AC_MACH] || a->source[MSD_AC_MACH])
+        o->mach = (float)(a->mach_raw * 2.048 / 512);
+    if (a->updated[MSD_AC_NAV_QNH] || a->source[MSD_AC_NAV_QNH])
+        o->nav_qnh = a->nav_qnh_commb ? (float)(800 + a->nav_qnh_raw * 0.1) : (float)(800.0 + (a->nav_qnh_raw - 1) * 0.8);
+    if (a->updated[MSD_AC_NAV_HEADING] || a->source[MSD_AC_NAV_HEADING])
+        o->nav_heading = a->nav_heading_v2 ? (float)(a->nav_heading_raw * 180.0 / 256.0) : (float)a->nav_heading_raw;
+}

@@ -26,6 +26,12 @@ struct msd_pos {
     uint32_t *d_slot = nullptr;
     uint8_t *d_fresh = nullptr;
     msd_position *d_out = nullptr;
+    /* a table tracker (msd_pos_create_table): tab[k].trk, the per-record NIC / Rc and the snapshot's buffers */
+    bool table = false;
+    msd_pos_nicrc *d_nicrc = nullptr;
+    uint32_t *s_idx[2] = {nullptr, nullptr}, *s_hist = nullptr;
+    msd_aircraft *d_snap = nullptr;
+    size_t cap_snap = 0;
     uint32_t *d_idx[2] = {nullptr, nullptr}, *d_hist = nullptr;
     msd_message *d_msgs = nullptr;
     msd_fields *d_fields = nullptr;
@@ -73,6 +79,7 @@ int reserve(msd_pos *p, size_t n, bool host_input)
 {
     if (n > p->cap_n) {
         release(p->d_slot), release(p->d_fresh), release(p->d_out), release(p->d_idx[0]), release(p->d_idx[1]), release(p->d_hist);
+        release(p->d_nicrc);
         p->cap_n = 0;
         const size_t piece = n < MSD_POS_PIECE ? n : MSD_POS_PIECE;
         const size_t tiles = (piece + MSD_POS_TILE - 1) / MSD_POS_TILE;
@@ -82,6 +89,8 @@ int reserve(msd_pos *p, size_t n, bool host_input)
         POS_HIP(p, hipMalloc(&p->d_idx[0], piece * sizeof(uint32_t)));
         POS_HIP(p, hipMalloc(&p->d_idx[1], piece * sizeof(uint32_t)));
         POS_HIP(p, hipMalloc(&p->d_hist, 256 * tiles * sizeof(uint32_t)));
+        if (p->table)
+            POS_HIP(p, hipMalloc(&p->d_nicrc, n * sizeof(msd_pos_nicrc)));
         p->cap_n = n;
     }
     if (host_input && n > p->cap_in) {
@@ -95,11 +104,8 @@ int reserve(msd_pos *p, size_t n, bool host_input)
     return 0;
 }
 
-} // namespace
 
-extern "C" {
-
-int msd_pos_create(const msd_pos_config *cfg, msd_pos **out)
+int create(const msd_pos_config *cfg, msd_pos **out, bool table)
 {
     if (!out || !msd_pos_config_ok(cfg))
         return -EINVAL;
@@ -110,6 +116,7 @@ int msd_pos_create(const msd_pos_config *cfg, msd_pos **out)
     if (!p)
         return -ENOMEM;
     p->device = cfg->device;
+    p->table = table;
     p->nrx = cfg->receivers;
     p->fp = cfg->filter_persistence ? cfg->filter_persistence : 8;
     std::vector<msd_pos_receiver> rx(p->nrx);
@@ -123,6 +130,8 @@ int msd_pos_create(const msd_pos_config *cfg, msd_pos **out)
             p->tab[k].cap = cfg->capacity;
             POS_HIP(p, hipMalloc(&p->tab[k].keys, sizeof(uint64_t) * cfg->capacity));
             POS_HIP(p, hipMalloc(&p->tab[k].st, sizeof(msd_pos_aircraft) * cfg->capacity));
+            if (table)
+                POS_HIP(p, hipMalloc(&p->tab[k].trk, sizeof(msd_trk_aircraft) * cfg->capacity));
         }
         POS_HIP(p, hipMalloc(&p->d_rx, sizeof(msd_pos_receiver) * p->nrx));
         POS_HIP(p, hipMalloc(&p->d_stats, sizeof(unsigned long long) * MSD_POS_DSTATS));
@@ -139,6 +148,20 @@ int msd_pos_create(const msd_pos_config *cfg, msd_pos **out)
     return 0;
 }
 
+} // namespace
+
+extern "C" {
+
+int msd_pos_create(const msd_pos_config *cfg, msd_pos **out)
+{
+    return create(cfg, out, false);
+}
+
+int msd_pos_create_table(const msd_pos_config *cfg, msd_pos **out)
+{
+    return create(cfg, out, true);
+}
+
 void msd_pos_destroy(msd_pos *p)
 {
     if (!p)
@@ -147,7 +170,8 @@ void msd_pos_destroy(msd_pos *p)
     if (p->stream)
         (void)hipStreamSynchronize(p->stream);
     for (int k = 0; k < 2; ++k)
-        release(p->tab[k].keys), release(p->tab[k].st);
+        release(p->tab[k].keys), release(p->tab[k].st), release(p->tab[k].trk);
+    release(p->d_nicrc), release(p->s_idx[0]), release(p->s_idx[1]), release(p->s_hist), release(p->d_snap);
     release(p->d_rx), release(p->d_stats), release(p->d_ctl), release(p->d_slot), release(p->d_fresh), release(p->d_out);
     release(p->d_idx[0]), release(p->d_idx[1]), release(p->d_hist), release(p->d_msgs), release(p->d_fields),
         release(p->d_receiver);
@@ -182,14 +206,14 @@ int msd_pos_set_receiver(msd_pos *p, uint32_t receiver, const msd_pos_receiver *
     return 0;
 }
 
-int msd_pos_update(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
-                   int on_device, msd_position *out)
+static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                  int on_device, msd_position *out, msd_pos_nicrc *nicrc, bool want_nicrc)
 {
-    if (!p)
+    if (!p || (want_nicrc && !p->table))
         return -EINVAL;
     if (n == 0)
         return 0;
-    if (!msgs || !fields || !out || n > MSD_POS_MAX_N)
+    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || n > MSD_POS_MAX_N)
         return -EINVAL;
     if (!on_device && receiver)
         for (size_t i = 0; i < n; ++i)
@@ -224,15 +248,74 @@ int msd_pos_update(msd_pos *p, const msd_message *msgs, const msd_fields *fields
         return ctl[MSD_POS_CTL_BAD_RECEIVER] ? -EINVAL : -ENOSPC;
     }
     p->live += ctl[MSD_POS_CTL_INSERTED];
+    if (p->table) /* a skipped record's entry stays zero */
+        POS_HIP(p, hipMemsetAsync(p->d_nicrc, 0, n * sizeof(msd_pos_nicrc), p->stream));
     for (size_t base = 0; base < n; base += MSD_POS_PIECE) {
         const size_t m = n - base < MSD_POS_PIECE ? n - base : MSD_POS_PIECE;
         msd_pos_launch_piece(p->stream, t, msgs, fields, receiver, p->d_rx, p->fp, (uint32_t)base, (uint32_t)m, p->d_slot,
-                             p->d_idx[0], p->d_idx[1], p->d_hist, p->d_out, p->d_stats);
+                             p->d_idx[0], p->d_idx[1], p->d_hist, p->d_out, p->d_stats, p->d_nicrc);
         POS_HIP(p, hipGetLastError());
     }
     POS_HIP(p, hipMemcpyAsync(out, p->d_out, n * sizeof(msd_position), hipMemcpyDeviceToHost, p->stream));
+    if (want_nicrc)
+        POS_HIP(p, hipMemcpyAsync(nicrc, p->d_nicrc, n * sizeof(msd_pos_nicrc), hipMemcpyDeviceToHost, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
+}
+
+int msd_pos_update(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                   int on_device, msd_position *out)
+{
+    return update(p, msgs, fields, receiver, n, on_device, out, nullptr, false);
+}
+
+int msd_pos_update_nicrc(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                         int on_device, msd_position *out, msd_pos_nicrc *nicrc)
+{
+    return update(p, msgs, fields, receiver, n, on_device, out, nicrc, true);
+}
+
+int msd_pos_snapshot(msd_pos *p, msd_aircraft *out, size_t cap, int on_device, size_t *n)
+{
+    if (!p || !p->table || !n || (!out && cap > 0))
+        return -EINVAL;
+    *n = (size_t)p->live;
+    if (p->live > cap) {
+        snprintf(p->err, sizeof p->err, "%llu aircraft do not fit %zu entries", (unsigned long long)p->live, cap);
+        return -ENOSPC;
+    }
+    if (p->live == 0)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    const msd_pos_table t = p->tab[p->cur];
+    if (!p->s_hist) {
+        const size_t tiles = (t.cap + MSD_POS_TILE - 1) / MSD_POS_TILE;
+        POS_HIP(p, hipMalloc(&p->s_idx[0], t.cap * sizeof(uint32_t)));
+        POS_HIP(p, hipMalloc(&p->s_idx[1], t.cap * sizeof(uint32_t)));
+        POS_HIP(p, hipMalloc(&p->s_hist, 256 * tiles * sizeof(uint32_t)));
+    }
+    if (!on_device && p->live > p->cap_snap) {
+        release(p->d_snap);
+        p->cap_snap = 0;
+        POS_HIP(p, hipMalloc(&p->d_snap, p->live * sizeof(msd_aircraft)));
+        p->cap_snap = (size_t)p->live;
+    }
+    /* the key is receiver << 25 | address: the passes above the highest receiver index's top bit have nothing to order */
+    uint32_t key_bits = 25;
+    while (key_bits < 64 && ((uint64_t)(p->nrx - 1u) >> (key_bits - 25)) != 0)
+        ++key_bits;
+    msd_aircraft *dst = on_device ? out : p->d_snap;
+    msd_pos_launch_snapshot(p->stream, t, (uint32_t)p->live, key_bits, p->s_idx[0], p->s_idx[1], p->s_hist, dst);
+    POS_HIP(p, hipGetLastError());
+    if (!on_device)
+        POS_HIP(p, hipMemcpyAsync(out, p->d_snap, p->live * sizeof(msd_aircraft), hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int msd_aircraft_valid(const msd_aircraft *a, int member, uint64_t now_ms)
+{
+    return a && member >= 0 && member < MSD_AC_N && msd_trk_valid(a, member, now_ms);
 }
 
 int msd_pos_expire(msd_pos *p, uint64_t now_ms)

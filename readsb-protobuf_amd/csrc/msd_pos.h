@@ -5,7 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "msd_pos_impl.h"
+#include "msd_trk_impl.h"
 
 #define MSD_POS_TILE 256u          /* records per workgroup of a counting pass */
 #define MSD_POS_PIECE (1u << 20)   /* records grouped and walked at a time; a call of more is cut into pieces */
@@ -18,6 +18,7 @@ enum { MSD_POS_CTL_FULL = 0, MSD_POS_CTL_BAD_RECEIVER = 1, MSD_POS_CTL_INSERTED 
 typedef struct msd_pos_table {
     uint64_t *keys;        /* cap entries; MSD_POS_EMPTY = free */
     msd_pos_aircraft *st;  /* cap entries */
+    msd_trk_aircraft *trk; /* cap entries of a table tracker (msd_pos_create_table), else NULL */
     uint32_t cap;          /* a power of two */
 } msd_pos_table;
 
@@ -29,13 +30,19 @@ void msd_pos_launch_find(hipStream_t stream, msd_pos_table t, const msd_message 
                          uint32_t *ctl);
 void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t *slot, const uint8_t *fresh, uint32_t n);
 /* steps 2 to 4 for records base .. base + n (n <= MSD_POS_PIECE): idx_a / idx_b hold n words each, hist
- * 256 * ceil(n / MSD_POS_TILE) words */
+ * 256 * ceil(n / MSD_POS_TILE) words.  With t.trk, step 5: the table walk over the same grouped order, which reads the
+ * out[] of step 3 and writes nicrc[] (n entries from base) */
 void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
                           const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
                           uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
-                          msd_position *out, unsigned long long *dstats);
+                          msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc);
 /* expiry: marks and counts the aircraft to remove (ctl[MSD_POS_CTL_REMOVED]); rebuild inserts the others into `to` */
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl);
 void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_table to);
+/* snapshot of a table tracker: the slots of the `live` aircraft in ascending key order end up in one of idx_a / idx_b
+ * (cap words each; hist: 256 * ceil(cap / MSD_POS_TILE) words), from where their entries are gathered into out[0 .. live).
+ * key_bits: no key has a bit set at or above it */
+void msd_pos_launch_snapshot(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
+                             uint32_t *idx_b, uint32_t *hist, msd_aircraft *out);
 
 #endif

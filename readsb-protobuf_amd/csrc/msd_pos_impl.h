@@ -6,7 +6,8 @@
  *   the assignment of a->meta.lat/lon, the part of trackUpdateFromMessage that reaches them -- seen / messages
  *   :1024-1025, the per-source versions :1032-1075, the gs / ias / tas stores :1222-1235, the CPR stores :1313-1329,
  *   :1381-1383 -- and the part of trackRemoveStaleAircraft :1494-1570 that concerns these members.
- * Not here: NIC / Rc, geomag_calc, update_polar_range, SBS and MLAT input, every other member of struct aircraft.
+ * Not here: geomag_calc, update_polar_range, SBS and MLAT input.  NIC / Rc and the other members of struct aircraft are
+ * msd_trk_impl.h's, for a tracker with the aircraft table.
  *
  * Every validity of the six kept members has stale_interval 60 s and expire_interval 70 s (track.c:113-115,132-134), so
  * the state keeps `source` and `updated` and derives stale = updated + 60000, expires = updated + 70000: accept_data is

@@ -13,6 +13,9 @@
  *      msd_pos_feed one record after the other, stores the state.  A batch of one aircraft is a serial walk by one lane.
  *   4. each result is written at the record's own index; the counters are summed with integer atomics, the gate margin
  *      with an integer minimum over the double's bits, both independent of arrival order.
+ * A table tracker (msd_pos_create_table) adds, per piece, 5. a second walk by the same heads over the same runs that feeds
+ * the aircraft table entry (msd_trk_impl.h) from each record and from what step 3 wrote for it; and msd_pos_snapshot
+ * reuses step 2's passes with the digit taken from the slots' keys to deliver the table in key order.
  * Wave64 throughout: ballots are 64 bits wide and a workgroup of 256 threads is four waves.  The walk is double
  * precision arithmetic with long dependent chains and divergent branches per aircraft; its rate comes from the number of
  * aircraft in flight, not from the vector width.
@@ -70,6 +73,8 @@ msd_pos_find_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
             atomicOr(&ctl[MSD_POS_CTL_FULL], 1u);
         if (f) {
             msd_pos_aircraft_init(&t.st[s]);
+            if (t.trk)
+                msd_trk_init(&t.trk[s]);
             atomicAdd(&ctl[MSD_POS_CTL_INSERTED], 1u);
         }
     }
@@ -98,16 +103,32 @@ __device__ __forceinline__ uint32_t element(const uint32_t *idx_in, uint32_t e)
     return idx_in ? idx_in[e] : e;
 }
 
+/* where a pass takes its digit from: a record's slot (the grouping of a call), or a slot's 64-bit key (the snapshot) */
+struct SlotDigit {
+    const uint32_t *slot;
+    uint32_t shift;
+    __device__ __forceinline__ uint32_t operator()(uint32_t rec) const { return (slot[rec] >> shift) & 255u; }
+};
+struct KeyDigit {
+    const uint64_t *keys;
+    uint32_t shift;
+    __device__ __forceinline__ uint32_t operator()(uint32_t s) const { return (uint32_t)(keys[s] >> shift) & 255u; }
+};
+struct FreeDigit { /* 0 for a slot in use, 1 for a free one: the stable pass that compacts the live slots to the front */
+    const uint64_t *keys;
+    __device__ __forceinline__ uint32_t operator()(uint32_t s) const { return keys[s] >= MSD_POS_EMPTY - 1u ? 1u : 0u; }
+};
+
 /* hist[d * ntiles + tile] = records of digit d in the tile */
-__global__ void __launch_bounds__(NT)
-msd_pos_hist_kernel(const uint32_t *idx_in, const uint32_t *slot, uint32_t n, uint32_t shift, uint32_t *hist)
+template <typename Digit>
+__global__ void __launch_bounds__(NT) msd_pos_hist_kernel(const uint32_t *idx_in, Digit digit, uint32_t n, uint32_t *hist)
 {
     __shared__ uint32_t cnt[256];
     cnt[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t e = blockIdx.x * NT + threadIdx.x;
     if (e < n)
-        atomicAdd(&cnt[(slot[element(idx_in, e)] >> shift) & 255u], 1u); /* a sum: the order does not matter */
+        atomicAdd(&cnt[digit(element(idx_in, e))], 1u); /* a sum: the order does not matter */
     __syncthreads();
     hist[threadIdx.x * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
 }
@@ -143,9 +164,9 @@ __global__ void __launch_bounds__(1024) msd_pos_scan_kernel(uint32_t *a, uint32_
 }
 
 /* idx_out[hist[d][tile] + rank of the record among the tile's records of digit d] = the record: stable */
+template <typename Digit>
 __global__ void __launch_bounds__(NT)
-msd_pos_scatter_kernel(const uint32_t *idx_in, const uint32_t *slot, uint32_t n, uint32_t shift, const uint32_t *hist,
-                       uint32_t *idx_out)
+msd_pos_scatter_kernel(const uint32_t *idx_in, Digit digit, uint32_t n, const uint32_t *hist, uint32_t *idx_out)
 {
     __shared__ uint32_t wcnt[NT / 64][256];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -155,7 +176,7 @@ msd_pos_scatter_kernel(const uint32_t *idx_in, const uint32_t *slot, uint32_t n,
     const uint32_t e = blockIdx.x * NT + tid;
     const bool valid = e < n;
     const uint32_t rec = valid ? element(idx_in, e) : 0u;
-    const uint32_t d = valid ? (slot[rec] >> shift) & 255u : 0u;
+    const uint32_t d = valid ? digit(rec) : 0u;
     /* the lanes of this wave with the same digit */
     unsigned long long peers = __ballot(valid);
     for (uint32_t b = 0; b < 8; ++b) {
@@ -208,6 +229,33 @@ msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
         atomicMin(&dstats[MSD_PC_N], (unsigned long long)__double_as_longlong(acc.margin));
 }
 
+/* step 5, table trackers: the same heads walk the same runs again and feed the table entry, in place in device memory --
+ * a record touches a few members of the 592 bytes, and only those are loaded and stored.  Reads what step 3 wrote for
+ * each record (out[i].result) and writes its NIC / Rc. */
+__global__ void __launch_bounds__(NT)
+msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, uint32_t base, uint32_t n,
+                    const uint32_t *slot, const uint32_t *idx, const msd_position *out, msd_pos_nicrc *nicrc)
+{
+    const uint32_t j = blockIdx.x * NT + threadIdx.x;
+    if (j >= n)
+        return;
+    const uint32_t s = slot[base + element(idx, j)];
+    if (s >= t.cap || (j > 0 && slot[base + element(idx, j - 1u)] == s))
+        return;
+    msd_trk_aircraft *a = &t.trk[s];
+    for (uint32_t k = j; k < n; ++k) {
+        const uint32_t i = base + element(idx, k);
+        if (slot[i] != s)
+            break;
+        const msd_message m = msgs[i];
+        const msd_fields f = fields[i];
+        const msd_position o = out[i];
+        msd_pos_nicrc q;
+        msd_trk_feed(a, m.sysTimestampMsg, &m, &f, &o, &q);
+        nicrc[i] = q;
+    }
+}
+
 __global__ void __launch_bounds__(NT) msd_pos_expire_kernel(msd_pos_table t, uint64_t now, uint32_t *ctl)
 {
     const uint32_t s = blockIdx.x * NT + threadIdx.x;
@@ -219,6 +267,8 @@ __global__ void __launch_bounds__(NT) msd_pos_expire_kernel(msd_pos_table t, uin
         atomicAdd(&ctl[MSD_POS_CTL_REMOVED], 1u);
     } else {
         t.st[s] = a;
+        if (t.trk)
+            msd_trk_expire_one(&t.trk[s], now);
     }
 }
 
@@ -228,7 +278,31 @@ __global__ void __launch_bounds__(NT) msd_pos_rebuild_kernel(msd_pos_table from,
     if (s >= from.cap || from.keys[s] >= TOMB)
         return;
     int fresh = 0;
-    to.st[find_or_insert(to, from.keys[s], &fresh)] = from.st[s]; /* found: `to` is as large as `from` and was empty */
+    const uint32_t d = find_or_insert(to, from.keys[s], &fresh); /* found: `to` is as large as `from` and was empty */
+    to.st[d] = from.st[s];
+    if (from.trk)
+        to.trk[d] = from.trk[s];
+}
+
+/* snapshot: entry j of the output is the aircraft in slot idx[j] */
+__global__ void __launch_bounds__(NT) msd_trk_gather_kernel(msd_pos_table t, const uint32_t *idx, uint32_t live, msd_aircraft *out)
+{
+    const uint32_t j = blockIdx.x * NT + threadIdx.x;
+    if (j >= live)
+        return;
+    const uint32_t s = idx[j];
+    if (s < t.cap)
+        msd_trk_export(t.keys[s], &t.st[s], &t.trk[s], &out[j]);
+}
+
+/* one stable counting pass over n elements */
+template <typename Digit>
+void counting_pass(hipStream_t stream, const uint32_t *in, Digit digit, uint32_t n, uint32_t *hist, uint32_t *out)
+{
+    const uint32_t tiles = (n + NT - 1u) / NT;
+    msd_pos_hist_kernel<<<tiles, NT, 0, stream>>>(in, digit, n, hist);
+    msd_pos_scan_kernel<<<1, 1024, 0, stream>>>(hist, 256u * tiles);
+    msd_pos_scatter_kernel<<<tiles, NT, 0, stream>>>(in, digit, n, hist, out);
 }
 
 uint32_t blocks(uint32_t n)
@@ -258,7 +332,7 @@ void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t
 void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
                           const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
                           uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
-                          msd_position *out, unsigned long long *dstats)
+                          msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc)
 {
     const uint32_t tiles = blocks(n);
     /* slots run from 0 to cap inclusive (cap = skipped) */
@@ -269,14 +343,14 @@ void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message
     uint32_t *bufs[2] = {idx_a, idx_b};
     int w = 0;
     for (uint32_t shift = 0; shift < bits; shift += 8) {
-        msd_pos_hist_kernel<<<tiles, NT, 0, stream>>>(in, slot + base, n, shift, hist);
-        msd_pos_scan_kernel<<<1, 1024, 0, stream>>>(hist, 256u * tiles);
-        msd_pos_scatter_kernel<<<tiles, NT, 0, stream>>>(in, slot + base, n, shift, hist, bufs[w]);
+        counting_pass(stream, in, SlotDigit{slot + base, shift}, n, hist, bufs[w]);
         in = bufs[w];
         w ^= 1;
     }
     msd_pos_walk_kernel<<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out,
                                                   dstats);
+    if (t.trk)
+        msd_trk_walk_kernel<<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc);
 }
 
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl)
@@ -287,4 +361,18 @@ void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms,
 void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_table to)
 {
     msd_pos_rebuild_kernel<<<blocks(from.cap), NT, 0, stream>>>(from, to);
+}
+
+void msd_pos_launch_snapshot(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
+                             uint32_t *idx_b, uint32_t *hist, msd_aircraft *out)
+{
+    /* the live slots to the front, in slot order; then least-significant-digit passes over those by their keys */
+    counting_pass(stream, (const uint32_t *)nullptr, FreeDigit{t.keys}, t.cap, hist, idx_a);
+    uint32_t *bufs[2] = {idx_a, idx_b};
+    int w = 0;
+    for (uint32_t shift = 0; shift < key_bits; shift += 8) {
+        counting_pass(stream, (const uint32_t *)bufs[w], KeyDigit{t.keys, shift}, live, hist, bufs[w ^ 1]);
+        w ^= 1;
+    }
+    msd_trk_gather_kernel<<<blocks(live), NT, 0, stream>>>(t, bufs[w], live, out);
 }

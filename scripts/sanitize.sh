@@ -9,6 +9,8 @@
 #                           and its C++ launcher are not gcc's to instrument)
 #   OUTDIR/msd_replay       the replay tool
 #   OUTDIR/fifo_stress      tests/c/fifo_stress.c: producer twelve buffers ahead, consumer, a halt in mid-stream
+#   OUTDIR/aircraft_table_units  tests/c/aircraft_table_units.c: the aircraft table's host twin and msd_aircraft_to_float
+#                           under a main of their own; run it as it is
 # Run the python tests against them with MSD_LIBMODES_HIP=OUTDIR/libmodes_hip.so and LD_PRELOAD=$(gcc -print-file-name=libasan.so)
 # (tests/test_sanitizers.py does).
 set -e
@@ -59,4 +61,7 @@ $CC $CF host/msd_replay_main.c "$OUT"/msd_sdr_ifile.o "$OUT"/msd_fifo.o "$OUT"/m
 $CC $CF ../../tests/c/fifo_stress.c "$OUT"/msd_fifo.o -o "$OUT/fifo_stress" -lpthread
 $CC $CF ../../tests/c/host_units.c "$OUT"/msd_wire.o "$OUT"/msd_tables.o "$OUT"/msd_fields.o "$OUT"/msd_sdr_ifile.o "$OUT"/msd_fifo.o "$OUT"/msd_converter.o \
     -o "$OUT/host_units" -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
+# the aircraft table's host twin (msd_trk_impl.h) under its own main: no python, no preload
+$CC $CF -ffp-contract=off ../../tests/c/aircraft_table_units.c "$OUT"/msd_pos_host.o "$OUT"/msd_fields.o "$OUT"/msd_tables.o \
+    -o "$OUT/aircraft_table_units" -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
 echo "sanitizer build ($MODE): $(ls "$OUT" | grep -v '\.o$' | tr '\n' ' ')"
