@@ -1,6 +1,11 @@
 /*
- * msd_ctx.h -- the context of msd_capi.cpp as the receiver-group driver (msd_group.cpp) sees it: the pipeline slot, the
- * context itself, and the few steps of the stream pipeline a group call reuses.  Private to the library.
+ * msd_ctx.h -- what the files of the stream driver share, with each other and with the receiver-group driver
+ * (msd_group.cpp): the pipeline slot, the context itself, and the steps of the stream pipeline that are called across
+ * a file boundary.  The driver is cut by stage:
+ *   msd_capi.cpp     context lifetime and the exported functions
+ *   msd_batch.cpp    everything that puts a batch on the GPU (the slot's buffers, enqueue, rescans, launch)
+ *   msd_collect.cpp  everything that takes a batch off the GPU (the GPU resolve chain, the host fallback, delivery)
+ * Private to the library.
  */
 #ifndef MSD_CTX_H
 #define MSD_CTX_H
@@ -26,6 +31,8 @@ namespace msd_impl {
 
 constexpr uint64_t MIN_HIT_ARENA = 131072;      /* every position of one buffer */
 constexpr uint64_t MIN_TRY_ARENA = 131072 * 5;  /* every phase of every position of one buffer */
+constexpr int TAIL_SAMPLES = MSD_HALO_FRONT;    /* what a batch leaves for its successor's look-behind */
+constexpr uint32_t SNAP_CAP = 64;               /* filter membership versions of one batch kept on the device */
 
 /* One helper thread per context for the per-message part of finishing a batch (signal level, power
  * statistics, the copy into the caller's arrays), so that it overlaps with the calling thread queueing
@@ -185,10 +192,9 @@ struct Slot {
     uint64_t rhit_arena = 0, rtry_arena = 0, dense_hits = 0, dense_tries = 0;
     uint64_t *d_powr = nullptr; /* [buffer][MSD_RB_MSG_CAP] signal power of the accepted messages */
     uint8_t *h_ctl = nullptr; /* pinned, read by the kernels in place: ts[2n] u64 | valid[n] | snap_idx[n] | todo[n] */
-    msd_wire *d_wire = nullptr, *h_wire = nullptr; /* message records of the emit kernel and their pinned copy */
+    msd_wire *h_wire = nullptr;                    /* pinned: the message records, written there by the kernels */
     unsigned long long *h_side = nullptr;          /* per record: power sum | signal_len << 48, for the statistics */
     msd_fields *h_fields = nullptr; /* pinned: header fields next to the records (MSD_CFG_DECODE_FIELDS) */
-    msd_fields *d_fields = nullptr; /* their device copy when the records travel by DMA (records_dma) */
     hipEvent_t ev_resolve = nullptr, ev_records = nullptr, ev_power = nullptr;
     hipEvent_t ev_scanned = nullptr; /* side-stream layout: this batch's scan + gather are done (its float sums / Mode A/C kernels follow) */
     uint64_t launch_seq = 0;         /* running number of the launch that filled the slot */
@@ -284,7 +290,6 @@ struct msd_ctx {
     msd_fields_fn fsink = nullptr;  /* set while msd_collect_fields runs: messages go here with their fields */
     void *fuser = nullptr;
     std::vector<msd_fields> out_fields; /* host-resolve path */
-    bool records_dma = false; /* MSD_RECORDS_DMA=1: fetch the message records with a DMA instead of kernel stores */
     hipEvent_t ev_aux = nullptr, ev_inputs = nullptr;
     msd_pred_entry *h_pred = nullptr;
     uint32_t *h_pred_count = nullptr;
@@ -306,7 +311,6 @@ struct msd_ctx {
     uint32_t timing_interval = 1; /* msd_set_timing_interval() */
     /* experiment knobs, read from the environment once in msd_create */
     bool trace = false;      /* MSD_RESOLVE_TRACE */
-    bool repass_aux = false; /* MSD_REPASS_AUX */
     /* In-order layout without field decoding: the record kernel of a batch is not launched; the wavefronts of the
      * next scan write the records on their way in (MsdScanParams.emit).  pending_emit: resolve chain and signal
      * power queued, records not yet.  MSD_EMIT_FUSED=0 turns it off. */
@@ -362,6 +366,17 @@ inline bool ac_on(const msd_ctx *c, const Slot &s)
     return c->cfg.mode_ac || (s.group && s.group->nac);
 }
 
+/* the batch in the slot can be resolved on the GPU */
+inline bool gpu_eligible(const msd_ctx *c, const Slot &s)
+{
+    return c->gpu_resolve && s.nbuffers >= 4;
+}
+
+inline size_t bps_of(int format) /* bytes per sample */
+{
+    return (format == MSD_FMT_UC8 || format == MSD_FMT_MAG16) ? 2 : 4;
+}
+
 /* the message in c->err; returns code */
 int fail(msd_ctx *c, int code, const char *fmt, ...);
 
@@ -383,6 +398,24 @@ int ensure_host(msd_ctx *c, Slot &s, size_t nh, size_t nt);
 int ensure_ac_host(msd_ctx *c, Slot &s, size_t nac);
 /* the scan parameters of the slot's batch (a group call's look-behind, options and two-bit tables included) */
 void fill_params(const msd_ctx *c, const Slot &s, MsdScanParams &p);
+/* an overflowed batch again: in pieces for the host resolver; a lean one into bigger region slices (0: rescanned, 1: not
+ * possible); a lean batch's dense lists after all */
+int rerun_in_pieces(msd_ctx *c, Slot &s, int format);
+int grow_and_rescan(msd_ctx *c, Slot &s, int format);
+int lean_gather_now(msd_ctx *c, Slot &s);
+/* --dcfilter: the batch's IQ -> DC-blocked magnitudes and squares, in order on `stream` */
+int launch_dc_block(msd_ctx *c, const void *d_iq, uint64_t nsamples, uint16_t *d_mag, float *d_magsq, hipStream_t stream);
+/* msd_collect behind its argument checks: finish() of the oldest batch in flight */
+int collect(msd_ctx *c, msd_message_fn sink, void *user);
+/* Wait for a batch's lists, resolve in order, deliver messages. */
+int finish(msd_ctx *c, Slot &s, int format, msd_message_fn sink, void *user, const uint64_t *ts_override,
+           const double *means_override, uint64_t resolver_first_chunk);
+/* hipEventSynchronize for events that are about to fire: polls first */
+hipError_t event_wait(hipEvent_t ev);
+/* the first resolve pass of the slot's batch (and its speculative records) behind its own kernels */
+int gpu_begin(msd_ctx *c, Slot &s, int format);
+/* the records of the batch whose chain was queued last, if no scan came along to carry them */
+int flush_pending_emit(msd_ctx *c);
 
 /* the slot's control arrays of the GPU resolve stage, in pinned host memory */
 struct GpuCtl {

@@ -284,6 +284,13 @@ void msd_resolve_power(msd_resolver *r, uint32_t nbuffers, const uint32_t *valid
                        void *msgs, size_t msg_stride, const uint64_t *power_req, const uint32_t *buffer,
                        const void *power, size_t power_stride, uint64_t nmsgs);
 
+/* Signal power on the host for the mag_buf entry (msd_magbuf.c): out[i] = the sum of squares the request req[i]
+ * (position << 16 | samples, as msd_emit_fn's power_req) covers in the caller's views -- each MSD_OVERLAP samples of
+ * look-behind, then the buffer's new samples, which follow one another in the batch.  Not part of the library's interface. */
+struct msd_magbuf_view;
+__attribute__((visibility("hidden"))) void msd_magbuf_power(const struct msd_magbuf_view *views, unsigned nviews,
+                                                            const uint64_t *req, size_t n, uint64_t *out);
+
 /* header fields of a whole batch on the host (msd_fields.c); msgs[i] belongs to buffer[i] */
 struct msd_fields;
 void msd_fields_batch(const void *msgs, size_t msg_stride, const uint32_t *buffer, uint64_t n, struct msd_fields *out);

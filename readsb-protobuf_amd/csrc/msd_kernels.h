@@ -1,4 +1,4 @@
-/* msd_kernels.h -- launch interface between msd_capi.cpp and msd_kernels.hip */
+/* msd_kernels.h -- launch interface between the stream driver (msd_capi.cpp, msd_batch.cpp, msd_collect.cpp) and msd_kernels.hip */
 #ifndef MSD_KERNELS_H
 #define MSD_KERNELS_H
 

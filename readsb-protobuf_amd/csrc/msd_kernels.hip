@@ -3231,7 +3231,7 @@ __global__ void __launch_bounds__(256) msd_ac_gather_kernel(const msd_wg_counts 
 } /* namespace */
 
 /* ------------------------------------------------------------------------------------------ */
-/* launchers (C linkage, used by msd_capi.cpp)                                                */
+/* launchers (C linkage, used by msd_batch.cpp, msd_collect.cpp and msd_capi.cpp)              */
 /* ------------------------------------------------------------------------------------------ */
 
 extern "C" uint32_t msd_scan_tile(int format)

@@ -1147,7 +1147,7 @@ void msd_resolve_power(msd_resolver *r, uint32_t nbuffers, const uint32_t *valid
     }
 }
 
-/* The statistics half alone, for the GPU resolve path (msd_capi.cpp): the record kernel has already written every
+/* The statistics half alone, for the GPU resolve path (msd_collect.cpp): the record kernel has already written every
  * message's signalLevel (msd_emit_impl.h, the same double arithmetic), and the order-sensitive sums (one
  * dependent double add per message, demod_2400.c:398-408,422-427) follow from side[] = power sum | signal_len
  * << 48 (0: a Mode A/C reply) while the caller already works on the next batch. */

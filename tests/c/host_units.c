@@ -1,6 +1,6 @@
 /* The single-threaded host C under the sanitizers (scripts/sanitize.sh): wire formats, the constant tables with their
- * self-check and both CRC-repair tables, the field decoder on every DF with extreme payloads, the pacer, and the error
- * paths of the ifile handler and the converter factory on a box without a GPU. */
+ * self-check and both CRC-repair tables, the field decoder on every DF with extreme payloads, the mag_buf power sum at
+ * its buffer edges, the pacer, and the error paths of the ifile handler and the converter factory on a box without a GPU. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +19,68 @@ static uint32_t rnd(void)
     rs ^= rs >> 17;
     rs ^= rs << 5;
     return rs;
+}
+
+/* msd_magbuf_power (msd_magbuf.c) against a naive sum over one flat array: three views of the real geometry, every one
+ * allocated to its validLength exactly (a read past it is the sanitizer's), the last one short.  The flat array is the
+ * first view's look-behind and then every view's new samples; what lies past its end counts as zero. */
+static int magbuf_power_case(void)
+{
+    enum { NV = 3, LAST_NEW = 1000, LONG = 112 * 12 / 5, SHORT = 56 * 12 / 5 };
+    const size_t flat_len = MSD_OVERLAP + 2 * (size_t)MSD_CHUNK_SAMPLES + LAST_NEW;
+    uint16_t *flat = malloc(flat_len * sizeof *flat);
+    uint16_t *data[NV];
+    msd_magbuf_view views[NV];
+    for (size_t i = 0; i < flat_len; ++i)
+        flat[i] = (uint16_t)rnd(); /* 65535 * 65535 * 268 fits the sums with room to spare; the squares need 32 bits */
+    flat[MSD_OVERLAP + 5000] = 65535;
+    memset(views, 0, sizeof views);
+    for (int v = 0; v < NV; ++v) { /* view v: the MSD_OVERLAP samples in front of its new ones, then those */
+        const size_t n = MSD_OVERLAP + (v == NV - 1 ? (size_t)LAST_NEW : (size_t)MSD_CHUNK_SAMPLES);
+        data[v] = malloc(n * sizeof(uint16_t));
+        memcpy(data[v], flat + (size_t)v * MSD_CHUNK_SAMPLES, n * sizeof(uint16_t));
+        views[v].data = data[v];
+        views[v].validLength = (unsigned)n;
+        views[v].overlap = MSD_OVERLAP;
+    }
+    /* (first new sample of the sum, samples); a request's position is MSD_OVERLAP - 19 further on (demod_2400.c:386-399) */
+    const int64_t C = MSD_CHUNK_SAMPLES;
+    const int64_t cases[][2] = {
+        {5000, LONG}, {4990, SHORT},                   /* inside one buffer */
+        {C - LONG, LONG},                              /* ends exactly on a buffer's last new sample */
+        {C - LONG + 1, LONG},                          /* ... one sample later: the walk crosses into the next buffer */
+        {2 * C - 100, LONG},                           /* across the edge into the short last view */
+        {19 - (int64_t)MSD_OVERLAP, LONG}, {-207, LONG}, {-1, SHORT}, /* begins in the first view's look-behind */
+        {2 * C + LAST_NEW - LONG, LONG},               /* ends exactly on the short view's last valid sample */
+        {2 * C + LAST_NEW - LONG + 1, LONG}, {2 * C + LAST_NEW - 100, LONG}, /* runs past it: the missing samples are zero */
+        {2 * C + LAST_NEW, LONG}, {2 * C + 5000, LONG}, /* all of it past the valid samples */
+        {5000, 0}, {-207, 0},                          /* len == 0 */
+        {3 * C, LONG}, {3 * C + 50, SHORT}, {40 * C, LONG}, /* behind the last view */
+    };
+    enum { NC = sizeof cases / sizeof cases[0] };
+    uint64_t req[NC], got[NC];
+    for (int i = 0; i < NC; ++i)
+        req[i] = (uint64_t)(cases[i][0] + MSD_OVERLAP - 19) << 16 | (uint64_t)cases[i][1];
+    memset(got, 0xA5, sizeof got);
+    msd_magbuf_power(views, NV, req, NC, got);
+    int bad = 0;
+    for (int i = 0; i < NC; ++i) {
+        uint64_t want = 0;
+        for (int64_t k = 0; k < cases[i][1]; ++k) {
+            const int64_t f = cases[i][0] + (int64_t)MSD_OVERLAP + k; /* index into flat */
+            const uint64_t x = f >= 0 && (size_t)f < flat_len ? flat[f] : 0;
+            want += x * x;
+        }
+        if (got[i] != want) {
+            fprintf(stderr, "msd_magbuf_power: case %d (first %lld, %lld samples): %llu, expected %llu\n", i,
+                    (long long)cases[i][0], (long long)cases[i][1], (unsigned long long)got[i], (unsigned long long)want);
+            bad = 1;
+        }
+    }
+    for (int v = 0; v < NV; ++v)
+        free(data[v]);
+    free(flat);
+    return bad;
 }
 
 int main(void)
@@ -75,6 +137,9 @@ int main(void)
     }
     if (!total)
         return 4;
+
+    if (magbuf_power_case())
+        return 8;
 
     /* pacer: three buffers at 100 x real time */
     msd_pacer p;
