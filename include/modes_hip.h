@@ -848,7 +848,8 @@ int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, co
  * Aircraft are keyed by (receiver index, the 25 low bits of msd_fields.addr, MSD_NON_ICAO_ADDRESS included); a record's
  * receiver index also selects the receiver location and --max-range its checks use.  The other members of struct
  * aircraft, with decoded_nic / decoded_rc, are kept by a tracker made with msd_pos_create_table ("the aircraft table"
- * below).  Not built: the Mode A/C matching, the declination, the polar range, SBS and MLAT positions.
+ * below); a table tracker can also match the Mode A/C replies against its aircraft ("Mode A/C matching" below).  Not
+ * built: the declination, the polar range, SBS and MLAT positions.
  *
  * What is exact.  The coordinates: double + - * / floor fmod in the reference's order, nothing contracted; delivered
  * lat / lon are bit-identical to the reference's whenever the decisions are.
@@ -930,8 +931,8 @@ int msd_pos_get_stats(const msd_pos *p, msd_pos_stats *st);
  * :458-473).  accept_data's stale interval is 15 s for altitude_baro, squawk and airground and 60 s for the others; every
  * member expires 70 s after its update, so a member keeps `source` and `updated` only -- except altitude_geom, whose
  * validity combine_validity can make from two others and which keeps its stale and expiry times.
- * Not built: the reduce_forward half of accept_data, FATSV state, the declination (geomag_calc), the polar range,
- * Mode A/C matching (trackMatchAC, modeA_hit / modeC_hit), SBS and MLAT input.
+ * Not built: the reduce_forward half of accept_data, FATSV state, the declination (geomag_calc), the polar range, SBS
+ * and MLAT input.  modeA_hit / modeC_hit are kept beside the entry, not in it: "Mode A/C matching" below.
  *
  * Everything in a table entry is an integer the message carried or a copy of a double; no float is computed on the
  * device.  A heading is the raw value plus the kind that says which of msd_fields_to_float's expressions turns it into
@@ -1010,6 +1011,46 @@ int msd_pos_snapshot(msd_pos *p, msd_aircraft *out, size_t cap, int on_device, s
 int msd_aircraft_valid(const msd_aircraft *a, int member, uint64_t now_ms);
 /* the reference's floats of an entry, by msd_fields_to_float's expressions, on the host */
 void msd_aircraft_to_float(const msd_aircraft *a, msd_aircraft_float *out);
+
+/* ---- Mode A/C matching: trackMatchAC (track.c:1411-1485) for a table tracker -- which Mode A/C replies (msgtype 32,
+ * what --modeac delivers) belong to a Mode S aircraft the table already tracks, and which are aircraft without Mode S
+ * (DESIGN.md 4.10).  msd_pos_modeac_enable is readsb's Modes.mode_ac for the tracker.  From then on msd_pos_update /
+ * msd_pos_update_nicrc add one to count[receiver][modeAToIndex(fields.squawk)] for every record with msgtype 32
+ * (track.c:1001; SPI is ignored, the sum wraps at 2^32); such a record still gets a MSD_POS_NOT_TRIED row and creates no
+ * aircraft, and a call that is rolled back (-EINVAL, -ENOSPC) counts nothing.  The table walk applies the two resets of
+ * trackUpdateFromMessage: modeC_hit is cleared when (alt_baro + 49) / 100 changes (:1096-1102, before the plausibility
+ * gate), modeA_hit when an accepted squawk differs from the stored one (:1154-1156).
+ * Per receiver there are four arrays of 4096 words -- count, lastcount, match, age (track.c:59-62; 64 KiB) --, indexed
+ * by modeAToIndex (track.h:246-256); per slot two bytes, mode_a_hit and mode_c_hit.  msd_aircraft is what it was.  An
+ * aircraft is matched against its own receiver's arrays.  Integer work throughout.  CONTRACT: the device and the host
+ * object (msd_pos_host_modeac_*) deliver the same bytes, however a stream is cut into calls. ---- */
+typedef struct msd_modeac_code { uint32_t count, lastcount, match, age; } msd_modeac_code; /* 16 bytes */
+typedef struct msd_modeac_hit { /* 16 bytes */
+    uint32_t receiver, addr;
+    uint8_t mode_a_hit, mode_c_hit, pad[6];
+} msd_modeac_hit;
+/* -EINVAL on a tracker without a table; -ENOMEM when receivers x 64 KiB and two bytes per slot, twice, do not fit (the
+ * tracker stays as it was); a second call returns 0 and changes nothing.  msd_pos_reset zeroes the hits and the arrays
+ * and leaves the tracker enabled.  A tracker that never calls this allocates and launches what it did before the
+ * matching existed, skips Mode A/C records, and answers -EINVAL to the three calls below. */
+int msd_pos_modeac_enable(msd_pos *p);
+/* trackMatchAC(now_ms), which the reference runs once per second after trackRemoveStaleAircraft.  message_now_ms is
+ * messageNow(), which trackDataValid reads there (track.h:216-219): in readsb the time of the last message that reached
+ * the tracker; like msd_aircraft_valid, the call takes it explicitly.  Clears match; then every live aircraft with
+ * (now_ms - seen) <= 5000 -- unsigned, so not one seen after now_ms -- tries its squawk's code (squawk valid) and the
+ * codes of mode C = (alt_baro + 49) / 100, C + 1 and C - 1 (altitude valid, modeCToModeA != 0): a code with
+ * count - lastcount >= 4 sets the aircraft's hit and match[code] = match[code] ? 0xFFFFFFFF : addr.  Then every code
+ * with a count ages: not heard 4 times since the last call, ++age > 15 clears count, lastcount and age; heard,
+ * age = match ? 10 : 0; then lastcount = count. */
+int msd_pos_modeac_match(msd_pos *p, uint64_t now_ms, uint64_t message_now_ms);
+/* one receiver's 4096 entries in index order into out: device memory (on_device = 1) or host memory.  -EINVAL: not
+ * enabled, a receiver index out of range, NULL */
+int msd_pos_modeac_codes(msd_pos *p, uint32_t receiver, msd_modeac_code *out, int on_device);
+/* one entry per live aircraft in msd_pos_snapshot's order -- row j belongs to the snapshot's row j --, with its -ENOSPC /
+ * *n behaviour */
+int msd_pos_modeac_hits(msd_pos *p, msd_modeac_hit *out, size_t cap, int on_device, size_t *n);
+/* modeCToModeA (mode_ac.c:92-98): the Mode A code of a Mode C altitude in hundreds of feet, 0 if there is none; on the host */
+unsigned msd_mode_c_to_a(int mode_c);
 
 #ifdef __cplusplus
 }

@@ -240,6 +240,7 @@ EXPORTS = [
     "msd_pos_create", "msd_pos_destroy", "msd_pos_last_error", "msd_pos_reset", "msd_pos_set_receiver", "msd_pos_update",
     "msd_pos_expire", "msd_pos_get_stats",
     "msd_pos_create_table", "msd_pos_update_nicrc", "msd_pos_snapshot", "msd_aircraft_valid", "msd_aircraft_to_float",
+    "msd_pos_modeac_enable", "msd_pos_modeac_match", "msd_pos_modeac_codes", "msd_pos_modeac_hits", "msd_mode_c_to_a",
 ]
 
 _lib = None
@@ -1107,6 +1108,11 @@ AIRCRAFT_DTYPE = np.dtype(
 assert AIRCRAFT_DTYPE.itemsize == 592 and NICRC_DTYPE.itemsize == 4
 AIRCRAFT_FLOAT_DTYPE = np.dtype([(k, "<f4") for k in ("track", "mag_heading", "true_heading", "track_rate", "roll", "nav_qnh",
                                                       "nav_heading", "pad")] + [("mach", "<f8")])
+# Mode A/C matching: msd_modeac_code (one of a receiver's 4096, in modeAToIndex order) and msd_modeac_hit
+MODEAC_CODE_DTYPE = np.dtype([("count", "<u4"), ("lastcount", "<u4"), ("match", "<u4"), ("age", "<u4")])
+MODEAC_HIT_DTYPE = np.dtype([("receiver", "<u4"), ("addr", "<u4"), ("mode_a_hit", "u1"), ("mode_c_hit", "u1"), ("pad", "u1", (6,))])
+assert MODEAC_CODE_DTYPE.itemsize == 16 and MODEAC_HIT_DTYPE.itemsize == 16
+MODEAC_CODES = 4096
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmsd_host.so")
 
 
@@ -1150,7 +1156,13 @@ def _pos_lib(host):
         L = C.CDLL(HOST_LIB_PATH) if host else lib()
         pre = "msd_pos_host_" if host else "msd_pos_"
         f = {k: getattr(L, pre + k) for k in ("create", "destroy", "reset", "set_receiver", "update", "expire", "get_stats",
-                                              "create_table", "update_nicrc", "snapshot")}
+                                              "create_table", "update_nicrc", "snapshot", "modeac_enable", "modeac_match",
+                                              "modeac_codes", "modeac_hits")}
+        dev = [] if host else [C.c_int]
+        f["modeac_enable"].argtypes = [C.c_void_p]
+        f["modeac_match"].argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+        f["modeac_codes"].argtypes = [C.c_void_p, C.c_uint32, C.c_void_p] + dev
+        f["modeac_hits"].argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + dev + [C.POINTER(C.c_size_t)]
         f["create_table"].argtypes = [C.POINTER(PosConfig), C.POINTER(C.c_void_p)]
         f["update_nicrc"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + (
             [] if host else [C.c_int]) + [C.c_void_p, C.c_void_p]
@@ -1185,8 +1197,11 @@ class PositionTracker:
     """msd_pos on the GPU (host=False) or its twin on the host (host=True): the same calls, the same results on every
     stream whose min_gate_margin_m on the twin stays above 1e-3 m."""
 
-    def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False, table=False):
-        """table=True: msd_pos_create_table -- the tracker also keeps the aircraft table (update_nicrc, snapshot)."""
+    def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False, table=False,
+                 modeac=False):
+        """table=True: msd_pos_create_table -- the tracker also keeps the aircraft table (update_nicrc, snapshot).
+        modeac=True (a table tracker): msd_pos_modeac_enable -- it also counts Mode A/C replies and matches them against
+        its aircraft (modeac_match, modeac_codes, modeac_hits)."""
         self.host, self.table = host, table
         self.L, self.f = _pos_lib(host)
         receivers = receivers if receivers is not None else [None]
@@ -1198,6 +1213,47 @@ class PositionTracker:
         if rc != 0:
             self.h = None
             raise MsdError(f"msd_pos{'_host' if host else ''}_create failed: {rc} ({os.strerror(-rc)})")
+        if modeac:
+            try:
+                self.modeac_enable()
+            except MsdError:
+                self.close()
+                raise
+
+    def modeac_enable(self):
+        self._check(self.f["modeac_enable"](self.h), "msd_pos_modeac_enable")
+
+    def modeac_match(self, now_ms, message_now_ms):
+        """trackMatchAC(now_ms) with messageNow() = message_now_ms."""
+        self._check(self.f["modeac_match"](self.h, now_ms, message_now_ms), "msd_pos_modeac_match")
+
+    def modeac_codes(self, receiver=0):
+        """One receiver's counts -> MODEAC_CODE_DTYPE array of 4096 in modeAToIndex order."""
+        out = np.zeros(MODEAC_CODES, dtype=MODEAC_CODE_DTYPE)
+        self._check(self.f["modeac_codes"](self.h, receiver, out.ctypes.data, *([] if self.host else [0])), "msd_pos_modeac_codes")
+        return out
+
+    def modeac_codes_device(self, receiver, d_out):
+        """The same into device memory of 4096 entries (a pointer); GPU tracker only."""
+        assert not self.host
+        self._check(self.f["modeac_codes"](self.h, receiver, d_out, 1), "msd_pos_modeac_codes")
+
+    def modeac_hits(self, cap=None):
+        """The hits of every live aircraft, row j belonging to snapshot()'s row j -> MODEAC_HIT_DTYPE array."""
+        cap = self.live() if cap is None else cap
+        out = np.zeros(cap, dtype=MODEAC_HIT_DTYPE)
+        n = C.c_size_t(0)
+        rc = self.f["modeac_hits"](self.h, out.ctypes.data if cap else None, cap, *([] if self.host else [0]), C.byref(n))
+        self.hits_count = n.value
+        self._check(rc, "msd_pos_modeac_hits")
+        return out[:n.value]
+
+    def modeac_hits_device(self, d_out, cap):
+        """The same into device memory of cap entries (a pointer); GPU tracker only -> the number written."""
+        assert not self.host
+        n = C.c_size_t(0)
+        self._check(self.f["modeac_hits"](self.h, d_out, cap, 1, C.byref(n)), "msd_pos_modeac_hits")
+        return n.value
 
     def close(self):
         if getattr(self, "h", None):
@@ -1314,6 +1370,14 @@ def aircraft_to_float(entry):
     out = np.zeros(1, dtype=AIRCRAFT_FLOAT_DTYPE)
     L.msd_aircraft_to_float(e.ctypes.data, out.ctypes.data)
     return out[0]
+
+
+def mode_c_to_a(mode_c):
+    """msd_mode_c_to_a (modeCToModeA): the Mode A code of a Mode C altitude in hundreds of feet, 0 if there is none."""
+    L = lib()
+    L.msd_mode_c_to_a.restype = C.c_uint
+    L.msd_mode_c_to_a.argtypes = [C.c_int]
+    return int(L.msd_mode_c_to_a(int(mode_c)))
 
 
 def pos_home_slot(receiver, addr, capacity):

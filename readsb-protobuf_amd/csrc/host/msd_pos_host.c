@@ -7,7 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "msd_trk_impl.h"
+#include "msd_modeac_impl.h"
 
 struct msd_pos_host {
     uint32_t cap, nrx;
@@ -18,6 +18,10 @@ struct msd_pos_host {
     msd_pos_receiver *rx;
     uint64_t live;
     msd_pos_acc acc;
+    /* Mode A/C matching (msd_pos_host_modeac_enable), else NULL: the receivers' arrays, two hit bytes per slot, modeCToATable */
+    uint32_t *ac;
+    uint8_t *hits;
+    uint16_t *c_to_a;
 };
 
 int msd_cpr_host_airborne(int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag, double *lat, double *lon)
@@ -49,6 +53,10 @@ static void clear(msd_pos_host *p)
     p->live = 0;
     memset(&p->acc, 0, sizeof p->acc);
     p->acc.margin = INFINITY;
+    if (p->ac) {
+        memset(p->ac, 0, sizeof(uint32_t) * MSD_MODEAC_WORDS * p->nrx);
+        memset(p->hits, 0, 2u * (size_t)p->cap);
+    }
 }
 
 static int create(const msd_pos_config *cfg, msd_pos_host **out, int table)
@@ -91,6 +99,9 @@ void msd_pos_host_destroy(msd_pos_host *p)
 {
     if (!p)
         return;
+    free(p->ac);
+    free(p->hits);
+    free(p->c_to_a);
     free(p->trk);
     free(p->keys);
     free(p->st);
@@ -129,6 +140,8 @@ static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
             msd_pos_aircraft_init(&p->st[s]);
             if (p->trk)
                 msd_trk_init(&p->trk[s]);
+            if (p->hits)
+                p->hits[2u * s] = p->hits[2u * s + 1u] = 0;
             *fresh = 1;
             return s;
         }
@@ -176,6 +189,8 @@ static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fi
     p->live += nadded;
     for (size_t i = 0; i < n; ++i) {
         msd_pos_nicrc q = {0, 0, 0};
+        if (p->ac && msgs[i].msgtype == 32) /* track.c:1001 */
+            p->ac[(size_t)(receiver ? receiver[i] : 0u) * MSD_MODEAC_WORDS + MSD_MODEAC_COUNT + msd_mode_a_to_index(fields[i].squawk)]++;
         if (slot[i] == UINT32_MAX) {
             memset(&out[i], 0, sizeof out[i]);
             out[i].result = MSD_POS_NOT_TRIED;
@@ -187,7 +202,8 @@ static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fi
         msd_pos_feed(&p->st[slot[i]], &p->rx[receiver ? receiver[i] : 0u], p->fp, msgs[i].sysTimestampMsg, &fields[i],
                      &out[i], &p->acc);
         if (p->trk)
-            msd_trk_feed(&p->trk[slot[i]], msgs[i].sysTimestampMsg, &msgs[i], &fields[i], &out[i], &q);
+            msd_trk_feed(&p->trk[slot[i]], msgs[i].sysTimestampMsg, &msgs[i], &fields[i], &out[i], &q,
+                         p->hits ? &p->hits[2u * slot[i]] : NULL);
         if (want_nicrc)
             nicrc[i] = q;
     }
@@ -214,6 +230,23 @@ static int by_key(const void *a, const void *b)
     return x < y ? -1 : x > y;
 }
 
+/* the live aircraft as (key, slot) pairs in key order: keys are unique.  NULL: out of memory */
+static uint64_t *ordered_slots(const msd_pos_host *p)
+{
+    uint64_t *ks = malloc(sizeof(uint64_t) * 2 * p->live);
+    if (!ks)
+        return NULL;
+    size_t k = 0;
+    for (uint32_t s = 0; s < p->cap; ++s)
+        if (p->keys[s] != MSD_POS_EMPTY) {
+            ks[2 * k] = p->keys[s];
+            ks[2 * k + 1] = s;
+            ++k;
+        }
+    qsort(ks, k, 2 * sizeof(uint64_t), by_key);
+    return ks;
+}
+
 int msd_pos_host_snapshot(msd_pos_host *p, msd_aircraft *out, size_t cap, size_t *n)
 {
     if (!p || !p->trk || !n || (!out && cap > 0))
@@ -223,20 +256,76 @@ int msd_pos_host_snapshot(msd_pos_host *p, msd_aircraft *out, size_t cap, size_t
         return -ENOSPC;
     if (p->live == 0)
         return 0;
-    /* (key, slot) pairs in key order: keys are unique */
-    uint64_t *ks = malloc(sizeof(uint64_t) * 2 * p->live);
+    uint64_t *ks = ordered_slots(p);
     if (!ks)
         return -ENOMEM;
-    size_t k = 0;
-    for (uint32_t s = 0; s < p->cap; ++s)
-        if (p->keys[s] != MSD_POS_EMPTY) {
-            ks[2 * k] = p->keys[s];
-            ks[2 * k + 1] = s;
-            ++k;
-        }
-    qsort(ks, k, 2 * sizeof(uint64_t), by_key);
-    for (size_t j = 0; j < k; ++j)
+    for (size_t j = 0; j < p->live; ++j)
         msd_trk_export(ks[2 * j], &p->st[ks[2 * j + 1]], &p->trk[ks[2 * j + 1]], &out[j]);
+    free(ks);
+    return 0;
+}
+
+int msd_pos_host_modeac_enable(msd_pos_host *p)
+{
+    if (!p || !p->trk)
+        return -EINVAL;
+    if (p->ac)
+        return 0;
+    uint32_t *ac = calloc((size_t)p->nrx * MSD_MODEAC_WORDS, sizeof(uint32_t));
+    uint8_t *hits = calloc(p->cap, 2);
+    uint16_t *c_to_a = malloc(sizeof(uint16_t) * MSD_MODEAC_CODES);
+    if (!ac || !hits || !c_to_a) {
+        free(ac);
+        free(hits);
+        free(c_to_a);
+        return -ENOMEM;
+    }
+    msd_modeac_build_c_to_a(c_to_a);
+    p->ac = ac;
+    p->hits = hits;
+    p->c_to_a = c_to_a;
+    return 0;
+}
+
+int msd_pos_host_modeac_match(msd_pos_host *p, uint64_t now_ms, uint64_t message_now_ms)
+{
+    if (!p || !p->ac)
+        return -EINVAL;
+    for (uint32_t r = 0; r < p->nrx; ++r)
+        memset(p->ac + (size_t)r * MSD_MODEAC_WORDS + MSD_MODEAC_MATCH, 0, sizeof(uint32_t) * MSD_MODEAC_CODES);
+    for (uint32_t s = 0; s < p->cap; ++s)
+        if (p->keys[s] != MSD_POS_EMPTY)
+            msd_modeac_match_one(&p->trk[s], p->st[s].seen, (uint32_t)(p->keys[s] & 0x1FFFFFFu), now_ms, message_now_ms,
+                                 p->c_to_a, p->ac + (size_t)(p->keys[s] >> 25) * MSD_MODEAC_WORDS, &p->hits[2u * s]);
+    for (uint32_t r = 0; r < p->nrx; ++r)
+        for (unsigned i = 0; i < MSD_MODEAC_CODES; ++i)
+            msd_modeac_age_one(p->ac + (size_t)r * MSD_MODEAC_WORDS, i);
+    return 0;
+}
+
+int msd_pos_host_modeac_codes(msd_pos_host *p, uint32_t receiver, msd_modeac_code *out)
+{
+    if (!p || !p->ac || receiver >= p->nrx || !out)
+        return -EINVAL;
+    for (unsigned i = 0; i < MSD_MODEAC_CODES; ++i)
+        msd_modeac_export_code(p->ac + (size_t)receiver * MSD_MODEAC_WORDS, i, &out[i]);
+    return 0;
+}
+
+int msd_pos_host_modeac_hits(msd_pos_host *p, msd_modeac_hit *out, size_t cap, size_t *n)
+{
+    if (!p || !p->ac || !n || (!out && cap > 0))
+        return -EINVAL;
+    *n = (size_t)p->live;
+    if (p->live > cap)
+        return -ENOSPC;
+    if (p->live == 0)
+        return 0;
+    uint64_t *ks = ordered_slots(p);
+    if (!ks)
+        return -ENOMEM;
+    for (size_t j = 0; j < p->live; ++j)
+        msd_modeac_export_hit(ks[2 * j], &p->hits[2u * ks[2 * j + 1]], &out[j]);
     free(ks);
     return 0;
 }
@@ -261,12 +350,16 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
     uint64_t *keys = malloc(sizeof(uint64_t) * p->cap);
     msd_pos_aircraft *st = malloc(sizeof(msd_pos_aircraft) * p->cap);
     msd_trk_aircraft *trk = p->trk ? malloc(sizeof(msd_trk_aircraft) * p->cap) : NULL;
-    if (!keys || !st || (p->trk && !trk)) {
+    uint8_t *hits = p->hits ? malloc(2u * (size_t)p->cap) : NULL;
+    if (!keys || !st || (p->trk && !trk) || (p->hits && !hits)) {
         free(keys);
         free(st);
         free(trk);
+        free(hits);
         return -ENOMEM;
     }
+    if (hits)
+        memcpy(hits, p->hits, 2u * (size_t)p->cap);
     if (trk)
         memcpy(trk, p->trk, sizeof(msd_trk_aircraft) * p->cap);
     memcpy(keys, p->keys, sizeof(uint64_t) * p->cap);
@@ -280,11 +373,16 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
             p->st[d] = st[s];
             if (trk)
                 p->trk[d] = trk[s];
+            if (hits) { /* after find_or_insert, which starts a new slot with no hits */
+                p->hits[2u * d] = hits[2u * s];
+                p->hits[2u * d + 1u] = hits[2u * s + 1u];
+            }
         }
     p->live -= removed;
     free(keys);
     free(st);
     free(trk);
+    free(hits);
     return 0;
 }
 

@@ -24,6 +24,11 @@ int msd_pos_host_create_table(const msd_pos_config *cfg, msd_pos_host **out);
 int msd_pos_host_update_nicrc(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                               size_t n, msd_position *out, msd_pos_nicrc *nicrc);
 int msd_pos_host_snapshot(msd_pos_host *p, msd_aircraft *out, size_t cap, size_t *n);
+/* Mode A/C matching (modes_hip.h, "Mode A/C matching"): msd_pos_modeac_* on the host, from msd_modeac_impl.h; the same bytes */
+int msd_pos_host_modeac_enable(msd_pos_host *p);
+int msd_pos_host_modeac_match(msd_pos_host *p, uint64_t now_ms, uint64_t message_now_ms);
+int msd_pos_host_modeac_codes(msd_pos_host *p, uint32_t receiver, msd_modeac_code *out);
+int msd_pos_host_modeac_hits(msd_pos_host *p, msd_modeac_hit *out, size_t cap, size_t *n);
 int msd_pos_host_get_stats(const msd_pos_host *p, msd_pos_stats *st);
 /* the home slot of (receiver, addr) in a table of `capacity` slots (tests build collisions with it) */
 uint32_t msd_pos_host_home_slot(uint32_t receiver, uint32_t addr, uint32_t capacity);

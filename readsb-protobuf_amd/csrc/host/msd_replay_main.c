@@ -51,6 +51,10 @@ static void print_raw(const msd_message *mm, void *user)
 static msd_pos *g_pos;
 static uint64_t g_clock_start_ms; /* --clock-start-ms: added to sysTimestampMsg in front of the tracker ("The clock") */
 static uint64_t g_last_ms;        /* the last record's timestamp as the tracker saw it */
+/* --match-modeac: trackPeriodicUpdate's once-per-second step on the message clock (track.c:1576-1588) */
+static int g_match_modeac;
+static uint64_t g_next_update;     /* static next_update of trackPeriodicUpdate */
+static uint64_t g_last_tracked_ms; /* messageNow(): the time of the last message the tracker did not skip (track.c:1010) */
 static void print_raw_positions(const msd_message *mm, void *user)
 {
     FILE *out = user;
@@ -67,6 +71,18 @@ static void print_raw_positions(const msd_message *mm, void *user)
         fprintf(out, "%02x", mm->msg[j]);
     fputc(';', out);
     msd_decode_fields(mm, NULL, &f);
+    if (g_match_modeac && tm.sysTimestampMsg >= g_next_update) { /* trackRemoveStaleAircraft, then trackMatchAC */
+        int prc = msd_pos_expire(g_pos, tm.sysTimestampMsg);
+        if (!prc)
+            prc = msd_pos_modeac_match(g_pos, tm.sysTimestampMsg, g_last_tracked_ms);
+        if (prc) {
+            fprintf(stderr, "msd_pos_modeac_match: %s (%d)\n", msd_pos_last_error(g_pos), prc);
+            g_pos_failed = 1;
+        }
+        g_next_update = tm.sysTimestampMsg + 1000;
+    }
+    if (mm->msgtype != 32 && f.addr != 0)
+        g_last_tracked_ms = tm.sysTimestampMsg;
     const int rc = msd_pos_update(g_pos, &tm, &f, NULL, 1, 0, &p);
     if (rc) {
         fprintf(stderr, "msd_pos_update: %s (%d)\n", msd_pos_last_error(g_pos), rc);
@@ -119,6 +135,45 @@ static int print_aircraft(FILE *out)
         fputc('\n', out);
     }
     free(ac);
+    return 0;
+}
+
+/* --match-modeac: behind the aircraft lines "modeac ADDR,mode_a_hit,mode_c_hit" for every aircraft with a hit, then
+ * "modeac-code SQUAWK,count,age,match" for every code heard (count != 0), match being the one aircraft's address, ffffffff
+ * for more than one, or empty */
+static int print_modeac(FILE *out)
+{
+    size_t n = 0;
+    int rc = msd_pos_modeac_hits(g_pos, NULL, 0, 0, &n);
+    if (rc != 0 && rc != -ENOSPC) {
+        fprintf(stderr, "msd_pos_modeac_hits: %s (%d)\n", msd_pos_last_error(g_pos), rc);
+        return 1;
+    }
+    msd_modeac_hit *hits = calloc(n ? n : 1, sizeof *hits);
+    msd_modeac_code *codes = calloc(4096, sizeof *codes);
+    if (!hits || !codes || (n && (rc = msd_pos_modeac_hits(g_pos, hits, n, 0, &n)) != 0) ||
+        (rc = msd_pos_modeac_codes(g_pos, 0, codes, 0)) != 0) {
+        fprintf(stderr, "msd_pos_modeac_hits / _codes: %s (%d)\n", hits && codes ? msd_pos_last_error(g_pos) : "out of memory", rc);
+        free(hits);
+        free(codes);
+        return 1;
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (hits[i].mode_a_hit || hits[i].mode_c_hit)
+            fprintf(out, "modeac %06x,%u,%u\n", hits[i].addr, hits[i].mode_a_hit, hits[i].mode_c_hit);
+    for (unsigned i = 0; i < 4096; ++i) {
+        if (!codes[i].count)
+            continue;
+        const unsigned squawk = (i & 00007u) | ((i & 00070u) << 1) | ((i & 00700u) << 2) | ((i & 07000u) << 3); /* indexToModeA */
+        fprintf(out, "modeac-code %04x,%u,%u,", squawk, codes[i].count, codes[i].age);
+        if (codes[i].match == 0xFFFFFFFFu)
+            fputs("ffffffff", out);
+        else if (codes[i].match)
+            fprintf(out, "%06x", codes[i].match);
+        fputc('\n', out);
+    }
+    free(hits);
+    free(codes);
     return 0;
 }
 
@@ -261,7 +316,8 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--fix")) rx.nfix_crc = 1;
         else if (!strcmp(a, "--no-fix")) rx.nfix_crc = 0;
         else if (!strcmp(a, "--aggressive")) rx.nfix_crc = 2; /* readsb.c:542 */
-        else if (!strcmp(a, "--modeac")) rx.mode_ac = 1;
+        else if (!strcmp(a, "--modeac") || !strcmp(a, "--mode-ac")) rx.mode_ac = 1;
+        else if (!strcmp(a, "--match-modeac")) g_match_modeac = 1;
         else if (!strcmp(a, "--dcfilter")) rx.dc_filter = 1; /* readsb.c:486 */
         else if (!strcmp(a, "--mlat")) g_mlat = 1;
         else if (!strcmp(a, "--net-verbatim")) g_net_verbatim = 1; /* readsb.c: Modes.net_verbatim */
@@ -293,7 +349,7 @@ int main(int argc, char **argv)
         } else {
             fprintf(stderr, "usage: msd_replay --ifile F [--iformat uc8|sc16|sc16q11] [--fix|--no-fix|--aggressive] [--dcfilter] "
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
-                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft] [--clock-start-ms N]]\n"
+                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft [--match-modeac]] [--clock-start-ms N]]\n"
                             "       --positions: the --raw lines, with \"lat,lon\" behind the ';' of every message from which readsb's tracker\n"
                             "       would have decoded a position (CPR global and local, its range and speed checks; the coordinates are exact, the\n"
                             "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
@@ -302,6 +358,9 @@ int main(int argc, char **argv)
                             "       --aircraft (with --positions): after the last message one line per tracked aircraft,\n"
                             "       \"aircraft ADDR,messages,callsign,squawk,altitude_baro,gs,lat,lon\", a member empty when it is not valid at the\n"
                             "       last message's time.  --clock-start-ms: milliseconds added to every message's time in front of the tracker.\n"
+                            "       --match-modeac (with --modeac and --aircraft): readsb's once-per-second trackMatchAC on the message clock; behind\n"
+                            "       the aircraft lines \"modeac ADDR,mode_a_hit,mode_c_hit\" for every aircraft with a hit and\n"
+                            "       \"modeac-code SQUAWK,count,age,match\" for every Mode A/C code heard (match: an address, ffffffff, or empty).\n"
                             "       msd_replay --beast-in F [--beast-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
                             "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n"
                             "       msd_replay --avr-in F [--avr-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
@@ -311,6 +370,10 @@ int main(int argc, char **argv)
     }
     if (want_aircraft && !want_positions) {
         fprintf(stderr, "--aircraft goes with --positions\n");
+        return 2;
+    }
+    if (g_match_modeac && (!rx.mode_ac || !want_aircraft)) {
+        fprintf(stderr, "--match-modeac goes with --modeac and --aircraft\n");
         return 2;
     }
     if (want_positions) {
@@ -334,12 +397,17 @@ int main(int argc, char **argv)
             fprintf(stderr, "msd_pos_create failed (%d)\n", prc);
             return 1;
         }
+        if (g_match_modeac && msd_pos_modeac_enable(g_pos) != 0) {
+            fprintf(stderr, "msd_pos_modeac_enable failed: %s\n", msd_pos_last_error(g_pos));
+            msd_pos_destroy(g_pos);
+            return 1;
+        }
         rx.sink = print_raw_positions;
     }
     if (avr_in || beast_in) {
         const int rc = avr_in ? run_remote_in(avr_in, 1, avr_chunk, now_ms, &rx, want_stats)
                               : run_remote_in(beast_in, 0, beast_chunk, now_ms, &rx, want_stats);
-        if (want_aircraft && !rc && print_aircraft(stdout))
+        if (want_aircraft && !rc && (print_aircraft(stdout) || (g_match_modeac && print_modeac(stdout))))
             g_pos_failed = 1;
         msd_pos_destroy(g_pos);
         return rc ? rc : g_pos_failed;
@@ -383,7 +451,7 @@ int main(int argc, char **argv)
         }
     }
     msd_ifileClose();
-    if (want_aircraft && print_aircraft(stdout))
+    if (want_aircraft && (print_aircraft(stdout) || (g_match_modeac && print_modeac(stdout))))
         g_pos_failed = 1;
     msd_pos_destroy(g_pos);
     return g_pos_failed ? 1 : 0;

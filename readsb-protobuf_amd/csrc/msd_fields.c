@@ -3,8 +3,10 @@
 #define _DEFAULT_SOURCE /* M_PI */
 #include "msd_fields_impl.h"
 #include "msd_internal.h"
+#include "msd_modeac_impl.h"
 
 #include <math.h>
+#include <pthread.h>
 #include <string.h>
 
 void msd_decode_fields(const msd_message *mm, const msd_fields *carry, msd_fields *out)
@@ -187,4 +189,18 @@ void msd_aircraft_to_float(const msd_aircraft *a, msd_aircraft_float *o)
         o->nav_qnh = a->nav_qnh_commb ? (float)(800 + a->nav_qnh_raw * 0.1) : (float)(800.0 + (a->nav_qnh_raw - 1) * 0.8);
     if (a->updated[MSD_AC_NAV_HEADING] || a->source[MSD_AC_NAV_HEADING])
         o->nav_heading = a->nav_heading_v2 ? (float)(a->nav_heading_raw * 180.0 / 256.0) : (float)a->nav_heading_raw;
+}
+
+/* modeCToModeA (mode_ac.c:92-98) over the table msd_modeac_impl.h builds, made on the first call */
+static uint16_t mode_c_to_a_table[MSD_MODEAC_CODES];
+static pthread_once_t mode_c_to_a_once = PTHREAD_ONCE_INIT;
+static void mode_c_to_a_init(void)
+{
+    msd_modeac_build_c_to_a(mode_c_to_a_table);
+}
+
+unsigned msd_mode_c_to_a(int mode_c)
+{
+    pthread_once(&mode_c_to_a_once, mode_c_to_a_init);
+    return msd_modeac_c_to_a(mode_c_to_a_table, mode_c);
 }

@@ -36,6 +36,13 @@ struct msd_pos {
     msd_message *d_msgs = nullptr;
     msd_fields *d_fields = nullptr;
     uint32_t *d_receiver = nullptr;
+    /* Mode A/C matching (msd_pos_modeac_enable): tab[k].hits, the receivers' arrays, modeCToATable and the buffers the
+     * two read-out calls hand to the host */
+    uint32_t *d_ac = nullptr;
+    uint16_t *d_c_to_a = nullptr;
+    msd_modeac_code *d_codes = nullptr;
+    msd_modeac_hit *d_hits_out = nullptr;
+    size_t cap_hits_out = 0;
     char err[256] = "";
 };
 
@@ -62,6 +69,11 @@ int clear(msd_pos *p)
     msd_pos_launch_fill(p->stream, p->tab[p->cur].keys, p->tab[p->cur].cap);
     POS_HIP(p, hipGetLastError());
     POS_HIP(p, hipMemcpyAsync(p->d_stats, init, sizeof init, hipMemcpyHostToDevice, p->stream));
+    if (p->d_ac) {
+        POS_HIP(p, hipMemsetAsync(p->d_ac, 0, sizeof(uint32_t) * MSD_MODEAC_WORDS * p->nrx, p->stream));
+        for (int k = 0; k < 2; ++k)
+            POS_HIP(p, hipMemsetAsync(p->tab[k].hits, 0, 2u * (size_t)p->tab[k].cap, p->stream));
+    }
     POS_HIP(p, hipStreamSynchronize(p->stream));
     p->live = 0;
     return 0;
@@ -104,6 +116,27 @@ int reserve(msd_pos *p, size_t n, bool host_input)
     return 0;
 }
 
+
+/* the index and histogram buffers of the snapshot's ordering passes, made at the first use */
+int snapshot_buffers(msd_pos *p)
+{
+    if (p->s_hist)
+        return 0;
+    const size_t cap = p->tab[p->cur].cap, tiles = (cap + MSD_POS_TILE - 1) / MSD_POS_TILE;
+    POS_HIP(p, hipMalloc(&p->s_idx[0], cap * sizeof(uint32_t)));
+    POS_HIP(p, hipMalloc(&p->s_idx[1], cap * sizeof(uint32_t)));
+    POS_HIP(p, hipMalloc(&p->s_hist, 256 * tiles * sizeof(uint32_t)));
+    return 0;
+}
+
+/* the key is receiver << 25 | address: the passes above the highest receiver index's top bit have nothing to order */
+uint32_t snapshot_key_bits(const msd_pos *p)
+{
+    uint32_t key_bits = 25;
+    while (key_bits < 64 && ((uint64_t)(p->nrx - 1u) >> (key_bits - 25)) != 0)
+        ++key_bits;
+    return key_bits;
+}
 
 int create(const msd_pos_config *cfg, msd_pos **out, bool table)
 {
@@ -170,7 +203,8 @@ void msd_pos_destroy(msd_pos *p)
     if (p->stream)
         (void)hipStreamSynchronize(p->stream);
     for (int k = 0; k < 2; ++k)
-        release(p->tab[k].keys), release(p->tab[k].st), release(p->tab[k].trk);
+        release(p->tab[k].keys), release(p->tab[k].st), release(p->tab[k].trk), release(p->tab[k].hits);
+    release(p->d_ac), release(p->d_c_to_a), release(p->d_codes), release(p->d_hits_out);
     release(p->d_nicrc), release(p->s_idx[0]), release(p->s_idx[1]), release(p->s_hist), release(p->d_snap);
     release(p->d_rx), release(p->d_stats), release(p->d_ctl), release(p->d_slot), release(p->d_fresh), release(p->d_out);
     release(p->d_idx[0]), release(p->d_idx[1]), release(p->d_hist), release(p->d_msgs), release(p->d_fields),
@@ -248,6 +282,10 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
         return ctl[MSD_POS_CTL_BAD_RECEIVER] ? -EINVAL : -ENOSPC;
     }
     p->live += ctl[MSD_POS_CTL_INSERTED];
+    if (p->d_ac) { /* the call has passed its checks: its Mode A/C replies count (track.c:1001) */
+        msd_pos_launch_modeac_count(p->stream, msgs, fields, receiver, p->nrx, (uint32_t)n, p->d_ac);
+        POS_HIP(p, hipGetLastError());
+    }
     if (p->table) /* a skipped record's entry stays zero */
         POS_HIP(p, hipMemsetAsync(p->d_nicrc, 0, n * sizeof(msd_pos_nicrc), p->stream));
     for (size_t base = 0; base < n; base += MSD_POS_PIECE) {
@@ -288,27 +326,117 @@ int msd_pos_snapshot(msd_pos *p, msd_aircraft *out, size_t cap, int on_device, s
         return 0;
     POS_HIP(p, hipSetDevice(p->device));
     const msd_pos_table t = p->tab[p->cur];
-    if (!p->s_hist) {
-        const size_t tiles = (t.cap + MSD_POS_TILE - 1) / MSD_POS_TILE;
-        POS_HIP(p, hipMalloc(&p->s_idx[0], t.cap * sizeof(uint32_t)));
-        POS_HIP(p, hipMalloc(&p->s_idx[1], t.cap * sizeof(uint32_t)));
-        POS_HIP(p, hipMalloc(&p->s_hist, 256 * tiles * sizeof(uint32_t)));
-    }
+    const int rc = snapshot_buffers(p);
+    if (rc)
+        return rc;
     if (!on_device && p->live > p->cap_snap) {
         release(p->d_snap);
         p->cap_snap = 0;
         POS_HIP(p, hipMalloc(&p->d_snap, p->live * sizeof(msd_aircraft)));
         p->cap_snap = (size_t)p->live;
     }
-    /* the key is receiver << 25 | address: the passes above the highest receiver index's top bit have nothing to order */
-    uint32_t key_bits = 25;
-    while (key_bits < 64 && ((uint64_t)(p->nrx - 1u) >> (key_bits - 25)) != 0)
-        ++key_bits;
     msd_aircraft *dst = on_device ? out : p->d_snap;
-    msd_pos_launch_snapshot(p->stream, t, (uint32_t)p->live, key_bits, p->s_idx[0], p->s_idx[1], p->s_hist, dst);
+    msd_pos_launch_snapshot(p->stream, t, (uint32_t)p->live, snapshot_key_bits(p), p->s_idx[0], p->s_idx[1], p->s_hist, dst);
     POS_HIP(p, hipGetLastError());
     if (!on_device)
         POS_HIP(p, hipMemcpyAsync(out, p->d_snap, p->live * sizeof(msd_aircraft), hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int msd_pos_modeac_enable(msd_pos *p)
+{
+    if (!p || !p->table)
+        return -EINVAL;
+    if (p->d_ac)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    uint16_t c_to_a[MSD_MODEAC_CODES];
+    msd_modeac_build_c_to_a(c_to_a);
+    const size_t ac_bytes = sizeof(uint32_t) * MSD_MODEAC_WORDS * p->nrx;
+    uint32_t *ac = nullptr;
+    uint16_t *d_c_to_a = nullptr;
+    msd_modeac_code *codes = nullptr;
+    uint8_t *hits[2] = {nullptr, nullptr};
+    const auto build = [&]() -> int {
+        POS_HIP(p, hipMalloc(&ac, ac_bytes));
+        POS_HIP(p, hipMalloc(&d_c_to_a, sizeof c_to_a));
+        POS_HIP(p, hipMalloc(&codes, sizeof(msd_modeac_code) * MSD_MODEAC_CODES));
+        for (int k = 0; k < 2; ++k)
+            POS_HIP(p, hipMalloc(&hits[k], 2u * (size_t)p->tab[k].cap));
+        POS_HIP(p, hipMemsetAsync(ac, 0, ac_bytes, p->stream));
+        for (int k = 0; k < 2; ++k) /* the aircraft the table has already start without hits */
+            POS_HIP(p, hipMemsetAsync(hits[k], 0, 2u * (size_t)p->tab[k].cap, p->stream));
+        POS_HIP(p, hipMemcpyAsync(d_c_to_a, c_to_a, sizeof c_to_a, hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipStreamSynchronize(p->stream));
+        return 0;
+    };
+    const int rc = build();
+    if (rc) { /* the tracker stays as it was */
+        (void)hipGetLastError();
+        release(ac), release(d_c_to_a), release(codes), release(hits[0]), release(hits[1]);
+        return rc;
+    }
+    p->d_ac = ac;
+    p->d_c_to_a = d_c_to_a;
+    p->d_codes = codes;
+    p->tab[0].hits = hits[0];
+    p->tab[1].hits = hits[1];
+    return 0;
+}
+
+int msd_pos_modeac_match(msd_pos *p, uint64_t now_ms, uint64_t message_now_ms)
+{
+    if (!p || !p->d_ac)
+        return -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    msd_pos_launch_modeac_match(p->stream, p->tab[p->cur], p->nrx, now_ms, message_now_ms, p->d_c_to_a, p->d_ac);
+    POS_HIP(p, hipGetLastError());
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int msd_pos_modeac_codes(msd_pos *p, uint32_t receiver, msd_modeac_code *out, int on_device)
+{
+    if (!p || !p->d_ac || receiver >= p->nrx || !out)
+        return -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    msd_modeac_code *dst = on_device ? out : p->d_codes;
+    msd_pos_launch_modeac_codes(p->stream, p->d_ac + (size_t)receiver * MSD_MODEAC_WORDS, dst);
+    POS_HIP(p, hipGetLastError());
+    if (!on_device)
+        POS_HIP(p, hipMemcpyAsync(out, p->d_codes, sizeof(msd_modeac_code) * MSD_MODEAC_CODES, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int msd_pos_modeac_hits(msd_pos *p, msd_modeac_hit *out, size_t cap, int on_device, size_t *n)
+{
+    if (!p || !p->d_ac || !n || (!out && cap > 0))
+        return -EINVAL;
+    *n = (size_t)p->live;
+    if (p->live > cap) {
+        snprintf(p->err, sizeof p->err, "%llu aircraft do not fit %zu entries", (unsigned long long)p->live, cap);
+        return -ENOSPC;
+    }
+    if (p->live == 0)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    const int rc = snapshot_buffers(p);
+    if (rc)
+        return rc;
+    if (!on_device && p->live > p->cap_hits_out) {
+        release(p->d_hits_out);
+        p->cap_hits_out = 0;
+        POS_HIP(p, hipMalloc(&p->d_hits_out, p->live * sizeof(msd_modeac_hit)));
+        p->cap_hits_out = (size_t)p->live;
+    }
+    msd_modeac_hit *dst = on_device ? out : p->d_hits_out;
+    msd_pos_launch_modeac_hits(p->stream, p->tab[p->cur], (uint32_t)p->live, snapshot_key_bits(p), p->s_idx[0], p->s_idx[1],
+                               p->s_hist, dst);
+    POS_HIP(p, hipGetLastError());
+    if (!on_device)
+        POS_HIP(p, hipMemcpyAsync(out, p->d_hits_out, p->live * sizeof(msd_modeac_hit), hipMemcpyDeviceToHost, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
 }

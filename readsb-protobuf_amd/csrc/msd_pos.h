@@ -5,7 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "msd_trk_impl.h"
+#include "msd_modeac_impl.h"
 
 #define MSD_POS_TILE 256u          /* records per workgroup of a counting pass */
 #define MSD_POS_PIECE (1u << 20)   /* records grouped and walked at a time; a call of more is cut into pieces */
@@ -19,6 +19,7 @@ typedef struct msd_pos_table {
     uint64_t *keys;        /* cap entries; MSD_POS_EMPTY = free */
     msd_pos_aircraft *st;  /* cap entries */
     msd_trk_aircraft *trk; /* cap entries of a table tracker (msd_pos_create_table), else NULL */
+    uint8_t *hits;         /* 2 * cap bytes {modeA_hit, modeC_hit} of a tracker that matches Mode A/C replies, else NULL */
     uint32_t cap;          /* a power of two */
 } msd_pos_table;
 
@@ -44,5 +45,16 @@ void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_tabl
  * key_bits: no key has a bit set at or above it */
 void msd_pos_launch_snapshot(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
                              uint32_t *idx_b, uint32_t *hist, msd_aircraft *out);
+/* Mode A/C matching (msd_modeac_impl.h).  ac: the receivers' arrays, MSD_MODEAC_WORDS words each.
+ * count: one for every record with msgtype 32 of a call that has passed its checks (every receiver index below nrx) */
+void msd_pos_launch_modeac_count(hipStream_t stream, const msd_message *msgs, const msd_fields *fields,
+                                 const uint32_t *receiver, uint32_t nrx, uint32_t n, uint32_t *ac);
+/* trackMatchAC: match cleared, one lane per slot, one lane per (receiver, code) */
+void msd_pos_launch_modeac_match(hipStream_t stream, msd_pos_table t, uint32_t nrx, uint64_t now_ms, uint64_t message_now_ms,
+                                 const uint16_t *c_to_a, uint32_t *ac);
+void msd_pos_launch_modeac_codes(hipStream_t stream, const uint32_t *rx_ac, msd_modeac_code *out);
+/* the hits in the snapshot's order; buffers as msd_pos_launch_snapshot's */
+void msd_pos_launch_modeac_hits(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
+                                uint32_t *idx_b, uint32_t *hist, msd_modeac_hit *out);
 
 #endif

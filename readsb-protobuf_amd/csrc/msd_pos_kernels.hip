@@ -16,6 +16,9 @@
  * A table tracker (msd_pos_create_table) adds, per piece, 5. a second walk by the same heads over the same runs that feeds
  * the aircraft table entry (msd_trk_impl.h) from each record and from what step 3 wrote for it; and msd_pos_snapshot
  * reuses step 2's passes with the digit taken from the slots' keys to deliver the table in key order.
+ * A tracker that matches Mode A/C replies (msd_modeac_impl.h) adds 1b. a kernel that counts the call's msgtype 32 records
+ * per (receiver, code) with integer atomics, and trackMatchAC as three kernels: match cleared, one lane per slot, one
+ * lane per (receiver, code).
  * Wave64 throughout: ballots are 64 bits wide and a workgroup of 256 threads is four waves.  The walk is double
  * precision arithmetic with long dependent chains and divergent branches per aircraft; its rate comes from the number of
  * aircraft in flight, not from the vector width.
@@ -26,6 +29,9 @@ namespace {
 
 constexpr uint32_t NT = MSD_POS_TILE;
 constexpr uint64_t TOMB = MSD_POS_EMPTY - 1u; /* a slot whose aircraft expired, until the table is rebuilt */
+#ifndef MSD_MODEAC_COMBINE_ROUNDS
+#define MSD_MODEAC_COMBINE_ROUNDS 4 /* 0: every reply adds one by itself (scripts/modeac_rate.py measures both) */
+#endif
 
 __global__ void __launch_bounds__(NT) msd_pos_fill_kernel(uint64_t *keys, uint32_t cap)
 {
@@ -75,6 +81,8 @@ msd_pos_find_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
             msd_pos_aircraft_init(&t.st[s]);
             if (t.trk)
                 msd_trk_init(&t.trk[s]);
+            if (t.hits)
+                t.hits[2u * s] = t.hits[2u * s + 1u] = 0;
             atomicAdd(&ctl[MSD_POS_CTL_INSERTED], 1u);
         }
     }
@@ -231,7 +239,9 @@ msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
 
 /* step 5, table trackers: the same heads walk the same runs again and feed the table entry, in place in device memory --
  * a record touches a few members of the 592 bytes, and only those are loaded and stored.  Reads what step 3 wrote for
- * each record (out[i].result) and writes its NIC / Rc. */
+ * each record (out[i].result) and writes its NIC / Rc.  HITS: the tracker matches Mode A/C replies and the walk resets
+ * the aircraft's hit bytes; a tracker that does not runs the instantiation without them. */
+template <bool HITS>
 __global__ void __launch_bounds__(NT)
 msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, uint32_t base, uint32_t n,
                     const uint32_t *slot, const uint32_t *idx, const msd_position *out, msd_pos_nicrc *nicrc)
@@ -243,6 +253,7 @@ msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
     if (s >= t.cap || (j > 0 && slot[base + element(idx, j - 1u)] == s))
         return;
     msd_trk_aircraft *a = &t.trk[s];
+    uint8_t *const hits = HITS ? &t.hits[2u * s] : nullptr;
     for (uint32_t k = j; k < n; ++k) {
         const uint32_t i = base + element(idx, k);
         if (slot[i] != s)
@@ -251,7 +262,7 @@ msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
         const msd_fields f = fields[i];
         const msd_position o = out[i];
         msd_pos_nicrc q;
-        msd_trk_feed(a, m.sysTimestampMsg, &m, &f, &o, &q);
+        msd_trk_feed(a, m.sysTimestampMsg, &m, &f, &o, &q, hits);
         nicrc[i] = q;
     }
 }
@@ -282,6 +293,10 @@ __global__ void __launch_bounds__(NT) msd_pos_rebuild_kernel(msd_pos_table from,
     to.st[d] = from.st[s];
     if (from.trk)
         to.trk[d] = from.trk[s];
+    if (from.hits) {
+        to.hits[2u * d] = from.hits[2u * s];
+        to.hits[2u * d + 1u] = from.hits[2u * s + 1u];
+    }
 }
 
 /* snapshot: entry j of the output is the aircraft in slot idx[j] */
@@ -293,6 +308,104 @@ __global__ void __launch_bounds__(NT) msd_trk_gather_kernel(msd_pos_table t, con
     const uint32_t s = idx[j];
     if (s < t.cap)
         msd_trk_export(t.keys[s], &t.st[s], &t.trk[s], &out[j]);
+}
+
+/* ---- Mode A/C matching ---- */
+/* 1b: count[receiver][code] += 1 for every msgtype 32 record.  Replies of one aircraft hammer one word, so lanes of a wave
+ * with the same (receiver, code) are combined first: the first pending lane's word is broadcast, the lanes with the same
+ * word are counted by a ballot and leave, and the first adds their number.  That is repeated, up to COMBINE_ROUNDS times,
+ * only while it pays: a group of fewer than COMBINE_MIN lanes says the wave holds many different codes, where nothing
+ * contends, and the lanes still pending add one each.  Integer sums: the order does not matter.  The whole wave runs the
+ * loop -- no lane returns early -- and leaves it together: every condition of the loop is a ballot's. */
+constexpr int COMBINE_ROUNDS = MSD_MODEAC_COMBINE_ROUNDS;
+constexpr int COMBINE_MIN = 4;
+__global__ void __launch_bounds__(NT)
+msd_modeac_count_kernel(const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, uint32_t nrx, uint32_t n,
+                        uint32_t *ac)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    bool pending = false;
+    uint32_t word = 0;
+    if (i < n && msgs[i].msgtype == 32) {
+        const uint32_t r = receiver ? receiver[i] : 0u;
+        if (r < nrx) { /* the find step has refused a call with any other */
+            pending = true;
+            word = r * (uint32_t)MSD_MODEAC_WORDS + MSD_MODEAC_COUNT + msd_mode_a_to_index(fields[i].squawk);
+        }
+    }
+    for (int round = 0; round < COMBINE_ROUNDS; ++round) {
+        const unsigned long long left = __ballot(pending);
+        if (!left)
+            break;
+        const int first = __ffsll((long long)left) - 1;
+        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)word, first);
+        const bool same = pending && word == w;
+        const int peers = __popcll(__ballot(same));
+        if ((int)lane == first)
+            atomicAdd(&ac[w], (uint32_t)peers);
+        pending = pending && !same;
+        if (peers < COMBINE_MIN)
+            break;
+    }
+    if (pending)
+        atomicAdd(&ac[word], 1u);
+}
+
+__global__ void __launch_bounds__(NT) msd_modeac_clear_match_kernel(uint32_t *ac, uint32_t codes)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i < codes)
+        ac[(size_t)(i >> 12) * MSD_MODEAC_WORDS + MSD_MODEAC_MATCH + (i & 4095u)] = 0;
+}
+
+/* one lane per slot; the key is tested first, the 592-byte entry is read for live slots only and only in the members
+ * the rule looks at */
+__global__ void __launch_bounds__(NT)
+msd_modeac_match_kernel(msd_pos_table t, uint32_t nrx, uint64_t now, uint64_t message_now, const uint16_t *c_to_a, uint32_t *ac)
+{
+    const uint32_t s = blockIdx.x * NT + threadIdx.x;
+    if (s >= t.cap)
+        return;
+    const uint64_t key = t.keys[s];
+    if (key >= TOMB)
+        return;
+    const uint32_t r = (uint32_t)(key >> 25);
+    if (r >= nrx)
+        return;
+    msd_modeac_match_one(&t.trk[s], t.st[s].seen, (uint32_t)(key & 0x1FFFFFFu), now, message_now, c_to_a,
+                         ac + (size_t)r * MSD_MODEAC_WORDS, &t.hits[2u * s]);
+}
+
+__global__ void __launch_bounds__(NT) msd_modeac_age_kernel(uint32_t *ac, uint32_t codes)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i < codes)
+        msd_modeac_age_one(ac + (size_t)(i >> 12) * MSD_MODEAC_WORDS, i & 4095u);
+}
+
+__global__ void __launch_bounds__(NT) msd_modeac_codes_kernel(const uint32_t *rx_ac, msd_modeac_code *out)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i < MSD_MODEAC_CODES) {
+        msd_modeac_code c;
+        msd_modeac_export_code(rx_ac, i, &c);
+        out[i] = c;
+    }
+}
+
+/* entry j of the output is the hits of the aircraft in slot idx[j]: msd_trk_gather_kernel's row j */
+__global__ void __launch_bounds__(NT) msd_modeac_gather_kernel(msd_pos_table t, const uint32_t *idx, uint32_t live, msd_modeac_hit *out)
+{
+    const uint32_t j = blockIdx.x * NT + threadIdx.x;
+    if (j >= live)
+        return;
+    const uint32_t s = idx[j];
+    if (s < t.cap) {
+        msd_modeac_hit h;
+        msd_modeac_export_hit(t.keys[s], &t.hits[2u * s], &h);
+        out[j] = h;
+    }
 }
 
 /* one stable counting pass over n elements */
@@ -349,8 +462,10 @@ void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message
     }
     msd_pos_walk_kernel<<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out,
                                                   dstats);
-    if (t.trk)
-        msd_trk_walk_kernel<<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc);
+    if (t.trk && t.hits)
+        msd_trk_walk_kernel<true><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc);
+    else if (t.trk)
+        msd_trk_walk_kernel<false><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc);
 }
 
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl)
@@ -363,10 +478,11 @@ void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_tabl
     msd_pos_rebuild_kernel<<<blocks(from.cap), NT, 0, stream>>>(from, to);
 }
 
-void msd_pos_launch_snapshot(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
-                             uint32_t *idx_b, uint32_t *hist, msd_aircraft *out)
+/* the slots of the live aircraft in ascending key order: the live slots to the front, in slot order; then
+ * least-significant-digit passes over those by their keys.  -> the one of idx_a / idx_b that holds them */
+static const uint32_t *ordered_slots(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
+                                     uint32_t *idx_b, uint32_t *hist)
 {
-    /* the live slots to the front, in slot order; then least-significant-digit passes over those by their keys */
     counting_pass(stream, (const uint32_t *)nullptr, FreeDigit{t.keys}, t.cap, hist, idx_a);
     uint32_t *bufs[2] = {idx_a, idx_b};
     int w = 0;
@@ -374,5 +490,39 @@ void msd_pos_launch_snapshot(hipStream_t stream, msd_pos_table t, uint32_t live,
         counting_pass(stream, (const uint32_t *)bufs[w], KeyDigit{t.keys, shift}, live, hist, bufs[w ^ 1]);
         w ^= 1;
     }
-    msd_trk_gather_kernel<<<blocks(live), NT, 0, stream>>>(t, bufs[w], live, out);
+    return bufs[w];
+}
+
+void msd_pos_launch_snapshot(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
+                             uint32_t *idx_b, uint32_t *hist, msd_aircraft *out)
+{
+    const uint32_t *idx = ordered_slots(stream, t, live, key_bits, idx_a, idx_b, hist);
+    msd_trk_gather_kernel<<<blocks(live), NT, 0, stream>>>(t, idx, live, out);
+}
+
+void msd_pos_launch_modeac_count(hipStream_t stream, const msd_message *msgs, const msd_fields *fields,
+                                 const uint32_t *receiver, uint32_t nrx, uint32_t n, uint32_t *ac)
+{
+    msd_modeac_count_kernel<<<blocks(n), NT, 0, stream>>>(msgs, fields, receiver, nrx, n, ac);
+}
+
+void msd_pos_launch_modeac_match(hipStream_t stream, msd_pos_table t, uint32_t nrx, uint64_t now_ms, uint64_t message_now_ms,
+                                 const uint16_t *c_to_a, uint32_t *ac)
+{
+    const uint32_t codes = nrx * MSD_MODEAC_CODES; /* at most 65536 * 4096 = 2^28 */
+    msd_modeac_clear_match_kernel<<<blocks(codes), NT, 0, stream>>>(ac, codes);
+    msd_modeac_match_kernel<<<blocks(t.cap), NT, 0, stream>>>(t, nrx, now_ms, message_now_ms, c_to_a, ac);
+    msd_modeac_age_kernel<<<blocks(codes), NT, 0, stream>>>(ac, codes);
+}
+
+void msd_pos_launch_modeac_codes(hipStream_t stream, const uint32_t *rx_ac, msd_modeac_code *out)
+{
+    msd_modeac_codes_kernel<<<blocks(MSD_MODEAC_CODES), NT, 0, stream>>>(rx_ac, out);
+}
+
+void msd_pos_launch_modeac_hits(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
+                                uint32_t *idx_b, uint32_t *hist, msd_modeac_hit *out)
+{
+    const uint32_t *idx = ordered_slots(stream, t, live, key_bits, idx_a, idx_b, hist);
+    msd_modeac_gather_kernel<<<blocks(live), NT, 0, stream>>>(t, idx, live, out);
 }

@@ -8,8 +8,8 @@
  *   msd_pos_feed does (seen / messages, gs / ias / tas, the CPR halves and updatePosition), the NIC / Rc of doGlobalCPR
  *   :378-379 and doLocalCPR :458-473 with updatePosition's stores :667-674, and trackRemoveStaleAircraft's EXPIRE list
  *   :1520-1563 for these members.
- * Not here: the reduce_forward half of accept_data, FATSV state, geomag_calc, update_polar_range, trackMatchAC with
- * modeA_hit / modeC_hit, SBS and MLAT input.
+ * Not here: the reduce_forward half of accept_data, FATSV state, geomag_calc, update_polar_range, SBS and MLAT input.
+ * trackMatchAC is msd_modeac_impl.h; of modeA_hit / modeC_hit this file has the two resets (:1096-1102, :1154-1156).
  *
  * The entry is the public msd_aircraft (modes_hip.h); its head -- receiver .. pos_reliable_even -- and the validities
  * of gs, ias, tas, the CPR halves and the position belong to the position state and are filled in by msd_trk_export.
@@ -236,9 +236,10 @@ MSD_HD int msd_trk_min(int a, int b)
 }
 
 /* One record of an aircraft, after msd_pos_feed has had it: pos is what that wrote for the record.  nicrc: decoded_nic /
- * decoded_rc of the record. */
+ * decoded_rc of the record.  hits: the aircraft's {modeA_hit, modeC_hit} bytes of a tracker that matches Mode A/C
+ * replies (msd_modeac_impl.h), else NULL. */
 MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m, const msd_fields *f,
-                         const msd_position *pos, msd_pos_nicrc *nicrc)
+                         const msd_position *pos, msd_pos_nicrc *nicrc, uint8_t *hits)
 {
     const unsigned source = f->source;
     nicrc->rc = 0;
@@ -291,6 +292,9 @@ MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m
     if (f->altitude_baro_valid &&
         (source >= a->source[MSD_AC_ALTITUDE_BARO] || msd_trk_age(a, MSD_AC_ALTITUDE_BARO, now) > 15 * 1000)) {
         const int alt = msd_trk_to_feet(f->altitude_baro, f->altitude_baro_unit);
+        /* :1096-1102, before the gate: an altitude the gate refuses below clears the hit too */
+        if (hits && hits[1] && (a->alt_baro + 49) / 100 != (alt + 49) / 100)
+            hits[1] = 0;
         const int delta = alt - a->alt_baro;
         const int adelta = delta < 0 ? -delta : delta;
         int fpm = 0, max_fpm = 12500, min_fpm = -12500;
@@ -335,8 +339,11 @@ MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m
         }
     }
 
-    if (f->squawk_valid && msd_trk_accept(a, MSD_AC_SQUAWK, source, now))
+    if (f->squawk_valid && msd_trk_accept(a, MSD_AC_SQUAWK, source, now)) {
+        if (hits && f->squawk != a->squawk) /* :1154-1156 */
+            hits[0] = 0;
         a->squawk = f->squawk;
+    }
     if (f->emergency_valid && msd_trk_accept(a, MSD_AC_EMERGENCY, source, now))
         a->emergency = f->emergency;
     if (f->altitude_geom_valid && msd_trk_accept(a, MSD_AC_ALTITUDE_GEOM, source, now))

@@ -11,6 +11,7 @@
 #   OUTDIR/fifo_stress      tests/c/fifo_stress.c: producer twelve buffers ahead, consumer, a halt in mid-stream
 #   OUTDIR/aircraft_table_units  tests/c/aircraft_table_units.c: the aircraft table's host twin and msd_aircraft_to_float
 #                           under a main of their own; run it as it is
+#   OUTDIR/modeac_units     tests/c/modeac_units.c: the Mode A/C matching's host twin and msd_mode_c_to_a, the same way
 # Run the python tests against them with MSD_LIBMODES_HIP=OUTDIR/libmodes_hip.so and LD_PRELOAD=$(gcc -print-file-name=libasan.so)
 # (tests/test_sanitizers.py does).
 set -e
@@ -67,4 +68,6 @@ $CC $CF ../../tests/c/host_units.c "$OUT"/msd_wire.o "$OUT"/msd_tables.o "$OUT"/
 # the aircraft table's host twin (msd_trk_impl.h) under its own main: no python, no preload
 $CC $CF -ffp-contract=off ../../tests/c/aircraft_table_units.c "$OUT"/msd_pos_host.o "$OUT"/msd_fields.o "$OUT"/msd_tables.o \
     -o "$OUT/aircraft_table_units" -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
+$CC $CF -ffp-contract=off ../../tests/c/modeac_units.c "$OUT"/msd_pos_host.o "$OUT"/msd_fields.o "$OUT"/msd_tables.o \
+    -o "$OUT/modeac_units" -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
 echo "sanitizer build ($MODE): $(ls "$OUT" | grep -v '\.o$' | tr '\n' ' ')"
