@@ -848,7 +848,8 @@ int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, co
  * Aircraft are keyed by (receiver index, the 25 low bits of msd_fields.addr, MSD_NON_ICAO_ADDRESS included); a record's
  * receiver index also selects the receiver location and --max-range its checks use.  The other members of struct
  * aircraft, with decoded_nic / decoded_rc, are kept by a tracker made with msd_pos_create_table ("the aircraft table"
- * below); a table tracker can also match the Mode A/C replies against its aircraft ("Mode A/C matching" below).  Not
+ * below); a table tracker can also match the Mode A/C replies against its aircraft ("Mode A/C matching" below) and thin
+ * the feed to readsb's reduced Beast output ("Reduced Beast output" below).  Not
  * built: the declination, the polar range, SBS and MLAT positions.
  *
  * What is exact.  The coordinates: double + - * / floor fmod in the reference's order, nothing contracted; delivered
@@ -931,8 +932,9 @@ int msd_pos_get_stats(const msd_pos *p, msd_pos_stats *st);
  * :458-473).  accept_data's stale interval is 15 s for altitude_baro, squawk and airground and 60 s for the others; every
  * member expires 70 s after its update, so a member keeps `source` and `updated` only -- except altitude_geom, whose
  * validity combine_validity can make from two others and which keeps its stale and expiry times.
- * Not built: the reduce_forward half of accept_data, FATSV state, the declination (geomag_calc), the polar range, SBS
- * and MLAT input.  modeA_hit / modeC_hit are kept beside the entry, not in it: "Mode A/C matching" below.
+ * Not built: FATSV state, the declination (geomag_calc), the polar range, SBS and MLAT input.  modeA_hit / modeC_hit
+ * are kept beside the entry, not in it: "Mode A/C matching" below; so are the timers of accept_data's reduce_forward half:
+ * "Reduced Beast output" below.
  *
  * Everything in a table entry is an integer the message carried or a copy of a double; no float is computed on the
  * device.  A heading is the raw value plus the kind that says which of msd_fields_to_float's expressions turns it into
@@ -1051,6 +1053,47 @@ int msd_pos_modeac_codes(msd_pos *p, uint32_t receiver, msd_modeac_code *out, in
 int msd_pos_modeac_hits(msd_pos *p, msd_modeac_hit *out, size_t cap, int on_device, size_t *n);
 /* modeCToModeA (mode_ac.c:92-98): the Mode A code of a Mode C altitude in hundreds of feet, 0 if there is none; on the host */
 unsigned msd_mode_c_to_a(int mode_c);
+
+/* ---- Reduced Beast output: readsb's beast_reduce_out (--net-beast-reduce-out-port, --net-beast-reduce-interval) for a
+ * table tracker -- the Beast feed thinned to the messages that brought an aircraft something new, at most once per
+ * interval and member.  The rule is the reduce_forward half of accept_data (track.c:182-193): when a
+ * member is accepted and messageNow() > the member's next_reduce_forward (strict), the message is forwarded and the timer
+ * becomes now + interval for a DF17 or a member the reference accepts with reduce_often (position, altitude_baro,
+ * altitude_geom, geom_delta, the three headings, track_rate, roll, gs, baro_rate, geom_rate, cpr_even, cpr_odd), else
+ * now + 4 * interval; now + 7000 instead when interval > 7000 and the message carries a CPR.  A DF11 with IID 0 and
+ * correctedbits 0 is also forwarded when now > the aircraft's next_reduce_forward_DF11, which becomes now + 4 * interval
+ * (:1396-1400).  combine_validity's one-source copy (:201-208) carries altitude_baro's or geom_delta's timer into
+ * altitude_geom's.  Timers start at 0 with the aircraft, move with its slot, are never touched by msd_pos_expire's
+ * EXPIRE, and go with msd_pos_reset.  Per slot MSD_AC_N + 1 words of 64 bits beside the entry, twice; msd_aircraft and
+ * msd_position are what they were.  Integer work throughout.  CONTRACT, the table's: the device and the host object
+ * (msd_pos_host_reduce_*, msd_pos_host_update_reduce) deliver the same verdict bytes and the same stream on every stream on
+ * which they deliver the same msd_position records, however the stream is cut into calls and whichever update call fed a
+ * record.
+ * A record's verdict byte: MSD_REDUCE_FORWARD = mm->reduce_forward; MSD_REDUCE_SEEN_TWICE = the aircraft's
+ * meta.messages > 1 after the record (mode_s.c:2164-2172); 0 for Mode A/C replies and records with addr == 0.  A record
+ * reaches the stream when MSD_REDUCE_FORWARD is set, MSD_WIRE_VERBATIM or correctedbits < 2 (net_io.c:1278-1285), and
+ * MSD_WIRE_VERBATIM or MSD_REDUCE_NET_ONLY (--net-only) or MSD_REDUCE_SEEN_TWICE. ---- */
+#define MSD_REDUCE_FORWARD 1u
+#define MSD_REDUCE_SEEN_TWICE 2u
+#define MSD_REDUCE_NET_ONLY 2u /* a flag of msd_pos_reduce_wire, beside MSD_WIRE_VERBATIM */
+/* Modes.net_output_beast_reduce_interval in ms, for good.  -EINVAL: no table, an interval above 15000 (readsb's cap), a
+ * second call with another interval (with the same: 0, nothing changes); -ENOMEM leaves the tracker as it was.  The
+ * aircraft the table already has start with timers of 0.  From then on msd_pos_update and msd_pos_update_nicrc advance
+ * the timers too (and deliver no verdicts).  A tracker that never calls this allocates and launches what it did before
+ * reducing existed and answers -EINVAL to the two calls below. */
+int msd_pos_reduce_enable(msd_pos *p, uint32_t interval_ms);
+/* msd_pos_update_nicrc (nicrc may be NULL) with the verdict byte of every record in forward: n bytes of device memory
+ * (on_device = 1) or host memory.  On -EINVAL / -ENOSPC nothing changed, no timer moved and forward is not written. */
+int msd_pos_update_reduce(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                          int on_device, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward);
+/* The Beast frames of the records that reach the reduced stream, dense and in record order, compacted on the device:
+ * msd_wire_encode's out / cap / out_len / ends with MSD_WIRE_BEAST -- ends[i] (n entries, or NULL) repeats the end before
+ * it for a record that does not go out --, the bytes of msd_beast_frame_out on those records.  msgs and forward: device
+ * memory (on_device = 1) or host memory; out and ends: host arrays.  Stateless: the tracker lends its stream and buffers.
+ * -ENOSPC: cap is too small, *out_len is the size needed, nothing else was written and the call can be repeated.
+ * -EINVAL: not enabled, an unknown flag bit, n above 2^24, NULL.  n == 0: 0 and *out_len = 0. */
+int msd_pos_reduce_wire(msd_pos *p, const msd_message *msgs, const uint8_t *forward, size_t n, int on_device, uint32_t flags,
+                        uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
 
 #ifdef __cplusplus
 }

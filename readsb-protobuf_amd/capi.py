@@ -241,6 +241,7 @@ EXPORTS = [
     "msd_pos_expire", "msd_pos_get_stats",
     "msd_pos_create_table", "msd_pos_update_nicrc", "msd_pos_snapshot", "msd_aircraft_valid", "msd_aircraft_to_float",
     "msd_pos_modeac_enable", "msd_pos_modeac_match", "msd_pos_modeac_codes", "msd_pos_modeac_hits", "msd_mode_c_to_a",
+    "msd_pos_reduce_enable", "msd_pos_update_reduce", "msd_pos_reduce_wire",
 ]
 
 _lib = None
@@ -1113,6 +1114,9 @@ MODEAC_CODE_DTYPE = np.dtype([("count", "<u4"), ("lastcount", "<u4"), ("match", 
 MODEAC_HIT_DTYPE = np.dtype([("receiver", "<u4"), ("addr", "<u4"), ("mode_a_hit", "u1"), ("mode_c_hit", "u1"), ("pad", "u1", (6,))])
 assert MODEAC_CODE_DTYPE.itemsize == 16 and MODEAC_HIT_DTYPE.itemsize == 16
 MODEAC_CODES = 4096
+# reduced Beast output: a record's verdict byte, msd_pos_reduce_wire's flag beside WIRE_VERBATIM, the timers per aircraft
+REDUCE_FORWARD, REDUCE_SEEN_TWICE, REDUCE_NET_ONLY = 1, 2, 2
+REDUCE_TIMERS = len(AC_MEMBERS) + 1
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmsd_host.so")
 
 
@@ -1157,8 +1161,13 @@ def _pos_lib(host):
         pre = "msd_pos_host_" if host else "msd_pos_"
         f = {k: getattr(L, pre + k) for k in ("create", "destroy", "reset", "set_receiver", "update", "expire", "get_stats",
                                               "create_table", "update_nicrc", "snapshot", "modeac_enable", "modeac_match",
-                                              "modeac_codes", "modeac_hits")}
+                                              "modeac_codes", "modeac_hits", "reduce_enable", "update_reduce",
+                                              "reduce_wire")}
         dev = [] if host else [C.c_int]
+        f["reduce_enable"].argtypes = [C.c_void_p, C.c_uint32]
+        f["update_reduce"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [C.c_void_p] * 3
+        f["reduce_wire"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [
+            C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
         f["modeac_enable"].argtypes = [C.c_void_p]
         f["modeac_match"].argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
         f["modeac_codes"].argtypes = [C.c_void_p, C.c_uint32, C.c_void_p] + dev
@@ -1182,6 +1191,8 @@ def _pos_lib(host):
         if host:
             L.msd_pos_host_home_slot.restype = C.c_uint32
             L.msd_pos_host_home_slot.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+            L.msd_pos_host_reduce_timers.restype = C.c_int
+            L.msd_pos_host_reduce_timers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             for name, n_ref, n_int in (("airborne", 0, 5), ("surface", 2, 5), ("relative", 2, 4)):
                 fn = getattr(L, "msd_cpr_host_" + name)
                 fn.restype = C.c_int
@@ -1198,10 +1209,12 @@ class PositionTracker:
     stream whose min_gate_margin_m on the twin stays above 1e-3 m."""
 
     def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False, table=False,
-                 modeac=False):
+                 modeac=False, reduce_interval_ms=None):
         """table=True: msd_pos_create_table -- the tracker also keeps the aircraft table (update_nicrc, snapshot).
         modeac=True (a table tracker): msd_pos_modeac_enable -- it also counts Mode A/C replies and matches them against
-        its aircraft (modeac_match, modeac_codes, modeac_hits)."""
+        its aircraft (modeac_match, modeac_codes, modeac_hits).
+        reduce_interval_ms (a table tracker): msd_pos_reduce_enable -- it also keeps the timers of readsb's reduced Beast
+        output (update_reduce, reduce_wire)."""
         self.host, self.table = host, table
         self.L, self.f = _pos_lib(host)
         receivers = receivers if receivers is not None else [None]
@@ -1213,12 +1226,76 @@ class PositionTracker:
         if rc != 0:
             self.h = None
             raise MsdError(f"msd_pos{'_host' if host else ''}_create failed: {rc} ({os.strerror(-rc)})")
-        if modeac:
-            try:
+        try:
+            if modeac:
                 self.modeac_enable()
-            except MsdError:
-                self.close()
-                raise
+            if reduce_interval_ms is not None:
+                self.reduce_enable(reduce_interval_ms)
+        except MsdError:
+            self.close()
+            raise
+
+    def reduce_enable(self, interval_ms):
+        self._check(self.f["reduce_enable"](self.h, interval_ms), "msd_pos_reduce_enable")
+
+    def update_reduce(self, messages, fields, receiver=None, nicrc=True):
+        """update_nicrc() with the verdict byte of every record (REDUCE_FORWARD | REDUCE_SEEN_TWICE)
+        -> (POSITION_DTYPE array, NICRC_DTYPE array or None, uint8 array)."""
+        n = len(messages)
+        assert len(fields) == n and messages.dtype == MESSAGE_DTYPE and fields.dtype == FIELDS_DTYPE
+        messages, fields = np.ascontiguousarray(messages), np.ascontiguousarray(fields)
+        rx = None if receiver is None else np.ascontiguousarray(receiver, dtype=np.uint32)
+        out, q, fwd = np.zeros(n, dtype=POSITION_DTYPE), np.zeros(n, dtype=NICRC_DTYPE), np.zeros(n, dtype=np.uint8)
+        args = [self.h, messages.ctypes.data, fields.ctypes.data, None if rx is None else rx.ctypes.data, n]
+        self._check(self.f["update_reduce"](*args, *([] if self.host else [0]), out.ctypes.data,
+                                            q.ctypes.data if nicrc else None, fwd.ctypes.data), "msd_pos_update_reduce")
+        return out, (q if nicrc else None), fwd
+
+    def update_reduce_device(self, d_messages, d_fields, n, d_forward, d_receiver=None):
+        """The same with the records and the verdict bytes in device memory (pointers); GPU tracker only
+        -> (POSITION_DTYPE array, NICRC_DTYPE array)."""
+        assert not self.host
+        out, q = np.zeros(n, dtype=POSITION_DTYPE), np.zeros(n, dtype=NICRC_DTYPE)
+        self._check(self.f["update_reduce"](self.h, d_messages, d_fields, d_receiver, n, 1, out.ctypes.data, q.ctypes.data,
+                                            d_forward), "msd_pos_update_reduce")
+        return out, q
+
+    def reduce_wire(self, messages, forward, verbatim=False, net_only=False, cap=None, flags=None, n=None, on_device=False):
+        """The reduced Beast stream of the records -> (bytes, ends).  cap: the bytes offered (default: as many as are
+        needed, asked for first); self.reduce_needed is *out_len of the last call.  on_device: messages and forward are
+        device pointers and n the number of records."""
+        if not on_device:
+            n = len(messages)
+            assert messages.dtype == MESSAGE_DTYPE and len(forward) == n
+            messages = np.ascontiguousarray(messages)
+            forward = np.ascontiguousarray(forward, dtype=np.uint8)
+        flags = ((WIRE_VERBATIM if verbatim else 0) | (REDUCE_NET_ONLY if net_only else 0)) if flags is None else flags
+        pm, pf = (messages, forward) if on_device else (messages.ctypes.data if n else None, forward.ctypes.data if n else None)
+        dev = [] if self.host else [1 if on_device else 0]
+        need = C.c_size_t(0)
+        if cap is None:
+            rc = self.f["reduce_wire"](self.h, pm, pf, n, *dev, flags, None, 0, C.byref(need), None)
+            if rc not in (0, -errno.ENOSPC):
+                self._check(rc, "msd_pos_reduce_wire")
+            cap = need.value
+        out = np.zeros(cap, dtype=np.uint8)
+        ends = np.zeros(n, dtype=np.uint32)
+        rc = self.f["reduce_wire"](self.h, pm, pf, n, *dev, flags, out.ctypes.data if cap else None, cap, C.byref(need),
+                                   ends.ctypes.data if n else None)
+        self.reduce_needed = need.value
+        self.reduce_out = out
+        self._check(rc, "msd_pos_reduce_wire")
+        return out[:need.value].tobytes(), ends
+
+    def reduce_timers(self, receiver, addr):
+        """The twin's timers of one aircraft -> uint64 array of REDUCE_TIMERS (AC_MEMBERS order, then DF11), or None."""
+        assert self.host
+        out = np.zeros(REDUCE_TIMERS, dtype=np.uint64)
+        rc = self.L.msd_pos_host_reduce_timers(self.h, receiver, addr, out.ctypes.data)
+        if rc == -errno.ENOENT:
+            return None
+        self._check(rc, "msd_pos_host_reduce_timers")
+        return out
 
     def modeac_enable(self):
         self._check(self.f["modeac_enable"](self.h), "msd_pos_modeac_enable")

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "msd_modeac_impl.h"
+#include "msd_wire.h"
 
 struct msd_pos_host {
     uint32_t cap, nrx;
@@ -22,6 +23,9 @@ struct msd_pos_host {
     uint32_t *ac;
     uint8_t *hits;
     uint16_t *c_to_a;
+    /* reduced Beast output (msd_pos_host_reduce_enable), else NULL: MSD_REDUCE_TIMERS timers per slot */
+    uint64_t *next_reduce;
+    uint32_t reduce_interval;
 };
 
 int msd_cpr_host_airborne(int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag, double *lat, double *lon)
@@ -57,6 +61,8 @@ static void clear(msd_pos_host *p)
         memset(p->ac, 0, sizeof(uint32_t) * MSD_MODEAC_WORDS * p->nrx);
         memset(p->hits, 0, 2u * (size_t)p->cap);
     }
+    if (p->next_reduce)
+        memset(p->next_reduce, 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->cap);
 }
 
 static int create(const msd_pos_config *cfg, msd_pos_host **out, int table)
@@ -99,6 +105,7 @@ void msd_pos_host_destroy(msd_pos_host *p)
 {
     if (!p)
         return;
+    free(p->next_reduce);
     free(p->ac);
     free(p->hits);
     free(p->c_to_a);
@@ -142,6 +149,8 @@ static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
                 msd_trk_init(&p->trk[s]);
             if (p->hits)
                 p->hits[2u * s] = p->hits[2u * s + 1u] = 0;
+            if (p->next_reduce)
+                memset(&p->next_reduce[(size_t)s * MSD_REDUCE_TIMERS], 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS);
             *fresh = 1;
             return s;
         }
@@ -150,13 +159,13 @@ static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
 }
 
 static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
-                  msd_position *out, msd_pos_nicrc *nicrc, int want_nicrc)
+                  msd_position *out, msd_pos_nicrc *nicrc, int want_nicrc, uint8_t *forward, int want_forward)
 {
-    if (!p || (want_nicrc && !p->trk))
+    if (!p || (want_nicrc && !p->trk) || (want_forward && !p->next_reduce))
         return -EINVAL;
     if (n == 0)
         return 0;
-    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || n > ((size_t)1 << 24))
+    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || (want_forward && !forward) || n > ((size_t)1 << 24))
         return -EINVAL;
     if (receiver)
         for (size_t i = 0; i < n; ++i)
@@ -196,16 +205,24 @@ static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fi
             out[i].result = MSD_POS_NOT_TRIED;
             if (want_nicrc)
                 nicrc[i] = q;
+            if (want_forward)
+                forward[i] = 0;
             continue;
         }
         memset(&out[i], 0, sizeof out[i]);
+        p->acc.accepted = 0;
         msd_pos_feed(&p->st[slot[i]], &p->rx[receiver ? receiver[i] : 0u], p->fp, msgs[i].sysTimestampMsg, &fields[i],
                      &out[i], &p->acc);
+        int fwd = 0;
         if (p->trk)
-            msd_trk_feed(&p->trk[slot[i]], msgs[i].sysTimestampMsg, &msgs[i], &fields[i], &out[i], &q,
-                         p->hits ? &p->hits[2u * slot[i]] : NULL);
+            fwd = msd_trk_feed(&p->trk[slot[i]], msgs[i].sysTimestampMsg, &msgs[i], &fields[i], &out[i], &q,
+                               p->hits ? &p->hits[2u * slot[i]] : NULL,
+                               p->next_reduce ? &p->next_reduce[(size_t)slot[i] * MSD_REDUCE_TIMERS] : NULL, p->reduce_interval,
+                               p->acc.accepted);
         if (want_nicrc)
             nicrc[i] = q;
+        if (want_forward)
+            forward[i] = (uint8_t)((fwd ? MSD_REDUCE_FORWARD : 0u) | (p->st[slot[i]].messages > 1 ? MSD_REDUCE_SEEN_TWICE : 0u));
     }
     free(slot);
     free(added);
@@ -215,13 +232,80 @@ static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fi
 int msd_pos_host_update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                         size_t n, msd_position *out)
 {
-    return update(p, msgs, fields, receiver, n, out, NULL, 0);
+    return update(p, msgs, fields, receiver, n, out, NULL, 0, NULL, 0);
 }
 
 int msd_pos_host_update_nicrc(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                               size_t n, msd_position *out, msd_pos_nicrc *nicrc)
 {
-    return update(p, msgs, fields, receiver, n, out, nicrc, 1);
+    return update(p, msgs, fields, receiver, n, out, nicrc, 1, NULL, 0);
+}
+
+int msd_pos_host_update_reduce(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                               size_t n, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward)
+{
+    return update(p, msgs, fields, receiver, n, out, nicrc, nicrc != NULL, forward, 1);
+}
+
+int msd_pos_host_reduce_enable(msd_pos_host *p, uint32_t interval_ms)
+{
+    if (!p || !p->trk || interval_ms > MSD_REDUCE_MAX_INTERVAL)
+        return -EINVAL;
+    if (p->next_reduce)
+        return interval_ms == p->reduce_interval ? 0 : -EINVAL;
+    uint64_t *next = calloc((size_t)p->cap * MSD_REDUCE_TIMERS, sizeof(uint64_t));
+    if (!next)
+        return -ENOMEM;
+    p->next_reduce = next;
+    p->reduce_interval = interval_ms;
+    return 0;
+}
+
+int msd_pos_host_reduce_wire(msd_pos_host *p, const msd_message *msgs, const uint8_t *forward, size_t n, uint32_t flags,
+                             uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends)
+{
+    if (!p || !p->next_reduce || !out_len || (flags & ~(MSD_WIRE_VERBATIM | MSD_REDUCE_NET_ONLY)) || n > ((size_t)1 << 24))
+        return -EINVAL;
+    *out_len = 0;
+    if (n == 0)
+        return 0;
+    if (!msgs || !forward || (!out && cap > 0))
+        return -EINVAL;
+    const int verbatim = (flags & MSD_WIRE_VERBATIM) != 0;
+    uint8_t frame[MSD_BEAST_MAX];
+    for (int pass = 0; pass < 2; ++pass) { /* the size first: a stream that does not fit leaves out alone */
+        size_t len = 0;
+        for (size_t i = 0; i < n; ++i) {
+            /* mode_s.c:2164-2172 and net_io.c:1282; msd_beast_frame_out applies net_io.c:1278 */
+            if ((forward[i] & MSD_REDUCE_FORWARD) &&
+                ((flags & (MSD_WIRE_VERBATIM | MSD_REDUCE_NET_ONLY)) || (forward[i] & MSD_REDUCE_SEEN_TWICE))) {
+                const size_t k = msd_beast_frame_out(&msgs[i], verbatim, frame);
+                if (pass)
+                    memcpy(out + len, frame, k);
+                len += k;
+            }
+            if (pass && ends)
+                ends[i] = (uint32_t)len;
+        }
+        *out_len = len;
+        if (len > cap)
+            return -ENOSPC;
+    }
+    return 0;
+}
+
+int msd_pos_host_reduce_timers(const msd_pos_host *p, uint32_t receiver, uint32_t addr, uint64_t *out)
+{
+    if (!p || !p->next_reduce || !out)
+        return -EINVAL;
+    const uint64_t key = msd_pos_key(receiver, addr);
+    uint32_t s = msd_pos_hash(key) & (p->cap - 1u);
+    for (uint32_t probes = 0; probes < p->cap && p->keys[s] != MSD_POS_EMPTY; ++probes, s = (s + 1u) & (p->cap - 1u))
+        if (p->keys[s] == key) {
+            memcpy(out, &p->next_reduce[(size_t)s * MSD_REDUCE_TIMERS], sizeof(uint64_t) * MSD_REDUCE_TIMERS);
+            return 0;
+        }
+    return -ENOENT;
 }
 
 static int by_key(const void *a, const void *b)
@@ -351,13 +435,18 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
     msd_pos_aircraft *st = malloc(sizeof(msd_pos_aircraft) * p->cap);
     msd_trk_aircraft *trk = p->trk ? malloc(sizeof(msd_trk_aircraft) * p->cap) : NULL;
     uint8_t *hits = p->hits ? malloc(2u * (size_t)p->cap) : NULL;
-    if (!keys || !st || (p->trk && !trk) || (p->hits && !hits)) {
+    const size_t next_bytes = sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->cap;
+    uint64_t *next = p->next_reduce ? malloc(next_bytes) : NULL;
+    if (!keys || !st || (p->trk && !trk) || (p->hits && !hits) || (p->next_reduce && !next)) {
         free(keys);
         free(st);
         free(trk);
         free(hits);
+        free(next);
         return -ENOMEM;
     }
+    if (next)
+        memcpy(next, p->next_reduce, next_bytes);
     if (hits)
         memcpy(hits, p->hits, 2u * (size_t)p->cap);
     if (trk)
@@ -377,12 +466,16 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
                 p->hits[2u * d] = hits[2u * s];
                 p->hits[2u * d + 1u] = hits[2u * s + 1u];
             }
+            if (next)
+                memcpy(&p->next_reduce[(size_t)d * MSD_REDUCE_TIMERS], &next[(size_t)s * MSD_REDUCE_TIMERS],
+                       sizeof(uint64_t) * MSD_REDUCE_TIMERS);
         }
     p->live -= removed;
     free(keys);
     free(st);
     free(trk);
     free(hits);
+    free(next);
     return 0;
 }
 

@@ -29,6 +29,16 @@ int msd_pos_host_modeac_enable(msd_pos_host *p);
 int msd_pos_host_modeac_match(msd_pos_host *p, uint64_t now_ms, uint64_t message_now_ms);
 int msd_pos_host_modeac_codes(msd_pos_host *p, uint32_t receiver, msd_modeac_code *out);
 int msd_pos_host_modeac_hits(msd_pos_host *p, msd_modeac_hit *out, size_t cap, size_t *n);
+/* reduced Beast output (modes_hip.h, "Reduced Beast output"): msd_pos_reduce_enable, msd_pos_update_reduce and
+ * msd_pos_reduce_wire on the host; the rule from msd_trk_impl.h, the frames from msd_beast_frame_out; the same bytes */
+int msd_pos_host_reduce_enable(msd_pos_host *p, uint32_t interval_ms);
+int msd_pos_host_update_reduce(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                               size_t n, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward);
+int msd_pos_host_reduce_wire(msd_pos_host *p, const msd_message *msgs, const uint8_t *forward, size_t n, uint32_t flags,
+                             uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
+/* for tests: the MSD_AC_N + 1 timers of one aircraft (the members' in MSD_AC_* order, then the DF11 timer) into out;
+ * -ENOENT: no such aircraft */
+int msd_pos_host_reduce_timers(const msd_pos_host *p, uint32_t receiver, uint32_t addr, uint64_t *out);
 int msd_pos_host_get_stats(const msd_pos_host *p, msd_pos_stats *st);
 /* the home slot of (receiver, addr) in a table of `capacity` slots (tests build collisions with it) */
 uint32_t msd_pos_host_home_slot(uint32_t receiver, uint32_t addr, uint32_t capacity);

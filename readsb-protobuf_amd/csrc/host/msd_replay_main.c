@@ -17,6 +17,10 @@
  * `--avr-in F` does the same for an AVR raw text stream (the --net-ri-port input, "*hex;" lines): pieces of --avr-chunk
  * bytes (default 65536) through msd_accept_avr; --mlat also keeps the lines' timestamps (MSD_AVR_KEEP_TIMESTAMP), and
  * --stats adds the four line counters.
+ *
+ * `--positions --aircraft --beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]` writes readsb's
+ * beast_reduce_out to FILE (--net-beast-reduce-out-port, --net-beast-reduce-interval; default 0.125 s, at most 15): the
+ * Beast frames of the messages that brought their aircraft something new (msd_pos_update_reduce, msd_pos_reduce_wire).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -55,6 +59,52 @@ static uint64_t g_last_ms;        /* the last record's timestamp as the tracker 
 static int g_match_modeac;
 static uint64_t g_next_update;     /* static next_update of trackPeriodicUpdate */
 static uint64_t g_last_tracked_ms; /* messageNow(): the time of the last message the tracker did not skip (track.c:1010) */
+/* --beast-reduce-out: the records and their verdict bytes wait here until REDUCE_BATCH are together, then go through
+ * msd_pos_reduce_wire in one call */
+#define REDUCE_BATCH 4096u
+static FILE *g_reduce_out;
+static uint32_t g_reduce_flags;
+static msd_message *g_reduce_msgs;
+static uint8_t *g_reduce_forward, *g_reduce_bytes;
+static uint32_t *g_reduce_ends;
+static size_t g_reduce_n;
+static uint64_t g_reduce_forwarded, g_reduce_records, g_reduce_total_bytes;
+static void reduce_flush(void)
+{
+    size_t len = 0;
+    if (!g_reduce_n)
+        return;
+    const int rc = msd_pos_reduce_wire(g_pos, g_reduce_msgs, g_reduce_forward, g_reduce_n, 0, g_reduce_flags, g_reduce_bytes,
+                                       (size_t)REDUCE_BATCH * MSD_BEAST_MAX, &len, g_reduce_ends);
+    if (rc) {
+        fprintf(stderr, "msd_pos_reduce_wire: %s (%d)\n", msd_pos_last_error(g_pos), rc);
+        g_pos_failed = 1;
+    } else {
+        if (fwrite(g_reduce_bytes, 1, len, g_reduce_out) != len)
+            g_pos_failed = 1;
+        for (size_t i = 0; i < g_reduce_n; ++i)
+            g_reduce_forwarded += g_reduce_ends[i] != (i ? g_reduce_ends[i - 1] : 0u);
+        g_reduce_total_bytes += len;
+    }
+    g_reduce_records += g_reduce_n;
+    g_reduce_n = 0;
+}
+
+/* the rest of the records, the file closed, and with --stats "reduce forwarded,N,of,M,bytes,B" */
+static int reduce_finish(int want_stats)
+{
+    reduce_flush();
+    const int bad = fclose(g_reduce_out) != 0;
+    if (want_stats)
+        fprintf(stderr, "reduce forwarded,%" PRIu64 ",of,%" PRIu64 ",bytes,%" PRIu64 "\n", g_reduce_forwarded, g_reduce_records,
+                g_reduce_total_bytes);
+    free(g_reduce_msgs);
+    free(g_reduce_forward);
+    free(g_reduce_bytes);
+    free(g_reduce_ends);
+    return bad;
+}
+
 static void print_raw_positions(const msd_message *mm, void *user)
 {
     FILE *out = user;
@@ -83,7 +133,15 @@ static void print_raw_positions(const msd_message *mm, void *user)
     }
     if (mm->msgtype != 32 && f.addr != 0)
         g_last_tracked_ms = tm.sysTimestampMsg;
-    const int rc = msd_pos_update(g_pos, &tm, &f, NULL, 1, 0, &p);
+    uint8_t forward = 0;
+    const int rc = g_reduce_out ? msd_pos_update_reduce(g_pos, &tm, &f, NULL, 1, 0, &p, NULL, &forward)
+                                : msd_pos_update(g_pos, &tm, &f, NULL, 1, 0, &p);
+    if (g_reduce_out && !rc) {
+        g_reduce_msgs[g_reduce_n] = *mm;
+        g_reduce_forward[g_reduce_n] = forward;
+        if (++g_reduce_n == REDUCE_BATCH)
+            reduce_flush();
+    }
     if (rc) {
         fprintf(stderr, "msd_pos_update: %s (%d)\n", msd_pos_last_error(g_pos), rc);
         g_pos_failed = 1;
@@ -294,7 +352,9 @@ int main(int argc, char **argv)
     const char *beast_in = NULL, *avr_in = NULL;
     size_t beast_chunk = 65536, avr_chunk = 65536;
     uint64_t now_ms = 0;
-    int want_positions = 0, want_aircraft = 0, other_sink = 0;
+    int want_positions = 0, want_aircraft = 0, other_sink = 0, net_only = 0;
+    const char *reduce_path = NULL;
+    double reduce_interval_s = 0.125; /* readsb.c: net_output_beast_reduce_interval = 125 */
     msd_pos_receiver home; /* --lat / --lon / --max-range as readsb spells them (readsb.c: Modes.receiver, Modes.maxRange) */
     memset(&home, 0, sizeof home);
     int have_lat = 0, have_lon = 0;
@@ -324,6 +384,9 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--stats")) want_stats = 1;
         else if (!strcmp(a, "--positions")) want_positions = 1;
         else if (!strcmp(a, "--aircraft")) want_aircraft = 1;
+        else if (!strcmp(a, "--beast-reduce-out") && next) { reduce_path = next; ++i; }
+        else if (!strcmp(a, "--beast-reduce-interval") && next) { reduce_interval_s = atof(next); ++i; }
+        else if (!strcmp(a, "--net-only")) net_only = 1; /* readsb.c: Modes.net_only */
         else if (!strcmp(a, "--clock-start-ms") && next) { g_clock_start_ms = strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--lat") && next) { home.lat = atof(next); have_lat = 1; ++i; }
         else if (!strcmp(a, "--lon") && next) { home.lon = atof(next); have_lon = 1; ++i; }
@@ -349,7 +412,8 @@ int main(int argc, char **argv)
         } else {
             fprintf(stderr, "usage: msd_replay --ifile F [--iformat uc8|sc16|sc16q11] [--fix|--no-fix|--aggressive] [--dcfilter] "
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
-                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft [--match-modeac]] [--clock-start-ms N]]\n"
+                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft [--match-modeac] "
+                            "[--beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]]] [--clock-start-ms N]]\n"
                             "       --positions: the --raw lines, with \"lat,lon\" behind the ';' of every message from which readsb's tracker\n"
                             "       would have decoded a position (CPR global and local, its range and speed checks; the coordinates are exact, the\n"
                             "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
@@ -361,6 +425,9 @@ int main(int argc, char **argv)
                             "       --match-modeac (with --modeac and --aircraft): readsb's once-per-second trackMatchAC on the message clock; behind\n"
                             "       the aircraft lines \"modeac ADDR,mode_a_hit,mode_c_hit\" for every aircraft with a hit and\n"
                             "       \"modeac-code SQUAWK,count,age,match\" for every Mode A/C code heard (match: an address, ffffffff, or empty).\n"
+                            "       --beast-reduce-out FILE (with --aircraft): readsb's reduced Beast output to FILE -- the frames of the messages\n"
+                            "       that brought their aircraft something new, at most once per --beast-reduce-interval (seconds, default 0.125, at\n"
+                            "       most 15) and member; a first message only with --net-only or --net-verbatim.\n"
                             "       msd_replay --beast-in F [--beast-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
                             "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n"
                             "       msd_replay --avr-in F [--avr-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
@@ -374,6 +441,10 @@ int main(int argc, char **argv)
     }
     if (g_match_modeac && (!rx.mode_ac || !want_aircraft)) {
         fprintf(stderr, "--match-modeac goes with --modeac and --aircraft\n");
+        return 2;
+    }
+    if (reduce_path && !want_aircraft) {
+        fprintf(stderr, "--beast-reduce-out goes with --positions --aircraft\n");
         return 2;
     }
     if (want_positions) {
@@ -402,12 +473,32 @@ int main(int argc, char **argv)
             msd_pos_destroy(g_pos);
             return 1;
         }
+        if (reduce_path) {
+            if (!(reduce_interval_s >= 0))
+                reduce_interval_s = 0;
+            if (reduce_interval_s > 15) /* readsb.c caps the interval at 15 s */
+                reduce_interval_s = 15;
+            g_reduce_flags = (g_net_verbatim ? MSD_WIRE_VERBATIM : 0u) | (net_only ? MSD_REDUCE_NET_ONLY : 0u);
+            g_reduce_msgs = malloc(REDUCE_BATCH * sizeof *g_reduce_msgs);
+            g_reduce_forward = malloc(REDUCE_BATCH);
+            g_reduce_bytes = malloc((size_t)REDUCE_BATCH * MSD_BEAST_MAX);
+            g_reduce_ends = malloc(REDUCE_BATCH * sizeof *g_reduce_ends);
+            const int erc = msd_pos_reduce_enable(g_pos, (uint32_t)(reduce_interval_s * 1000.0 + 0.5));
+            if (erc || !g_reduce_msgs || !g_reduce_forward || !g_reduce_bytes || !g_reduce_ends ||
+                !(g_reduce_out = fopen(reduce_path, "wb"))) {
+                fprintf(stderr, "--beast-reduce-out %s: %s\n", reduce_path, erc ? msd_pos_last_error(g_pos) : "cannot open, or out of memory");
+                msd_pos_destroy(g_pos);
+                return 1;
+            }
+        }
         rx.sink = print_raw_positions;
     }
     if (avr_in || beast_in) {
         const int rc = avr_in ? run_remote_in(avr_in, 1, avr_chunk, now_ms, &rx, want_stats)
                               : run_remote_in(beast_in, 0, beast_chunk, now_ms, &rx, want_stats);
         if (want_aircraft && !rc && (print_aircraft(stdout) || (g_match_modeac && print_modeac(stdout))))
+            g_pos_failed = 1;
+        if (g_reduce_out && reduce_finish(want_stats))
             g_pos_failed = 1;
         msd_pos_destroy(g_pos);
         return rc ? rc : g_pos_failed;
@@ -452,6 +543,8 @@ int main(int argc, char **argv)
     }
     msd_ifileClose();
     if (want_aircraft && (print_aircraft(stdout) || (g_match_modeac && print_modeac(stdout))))
+        g_pos_failed = 1;
+    if (g_reduce_out && reduce_finish(want_stats))
         g_pos_failed = 1;
     msd_pos_destroy(g_pos);
     return g_pos_failed ? 1 : 0;

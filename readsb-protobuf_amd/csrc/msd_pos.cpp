@@ -43,6 +43,15 @@ struct msd_pos {
     msd_modeac_code *d_codes = nullptr;
     msd_modeac_hit *d_hits_out = nullptr;
     size_t cap_hits_out = 0;
+    /* reduced Beast output (msd_pos_reduce_enable): tab[k].next_reduce, the verdict byte per record of a call, and the
+     * writer's buffers -- records and verdicts that came from the host, lengths, offsets, ends, the stream */
+    bool reduce = false;
+    uint32_t reduce_interval = 0;
+    uint8_t *d_forward = nullptr;
+    size_t cap_forward = 0, cap_w = 0, cap_w_in = 0, cap_w_out = 0;
+    msd_message *d_w_msgs = nullptr;
+    uint8_t *d_w_forward = nullptr, *d_w_lens = nullptr, *d_w_out = nullptr;
+    uint32_t *d_w_block = nullptr, *d_w_ends = nullptr;
     char err[256] = "";
 };
 
@@ -74,6 +83,9 @@ int clear(msd_pos *p)
         for (int k = 0; k < 2; ++k)
             POS_HIP(p, hipMemsetAsync(p->tab[k].hits, 0, 2u * (size_t)p->tab[k].cap, p->stream));
     }
+    if (p->reduce)
+        for (int k = 0; k < 2; ++k)
+            POS_HIP(p, hipMemsetAsync(p->tab[k].next_reduce, 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->tab[k].cap, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     p->live = 0;
     return 0;
@@ -104,6 +116,12 @@ int reserve(msd_pos *p, size_t n, bool host_input)
         if (p->table)
             POS_HIP(p, hipMalloc(&p->d_nicrc, n * sizeof(msd_pos_nicrc)));
         p->cap_n = n;
+    }
+    if (p->reduce && n > p->cap_forward) {
+        release(p->d_forward);
+        p->cap_forward = 0;
+        POS_HIP(p, hipMalloc(&p->d_forward, n));
+        p->cap_forward = n;
     }
     if (host_input && n > p->cap_in) {
         release(p->d_msgs), release(p->d_fields), release(p->d_receiver);
@@ -203,7 +221,10 @@ void msd_pos_destroy(msd_pos *p)
     if (p->stream)
         (void)hipStreamSynchronize(p->stream);
     for (int k = 0; k < 2; ++k)
-        release(p->tab[k].keys), release(p->tab[k].st), release(p->tab[k].trk), release(p->tab[k].hits);
+        release(p->tab[k].keys), release(p->tab[k].st), release(p->tab[k].trk), release(p->tab[k].hits),
+            release(p->tab[k].next_reduce);
+    release(p->d_forward), release(p->d_w_msgs), release(p->d_w_forward), release(p->d_w_lens), release(p->d_w_out);
+    release(p->d_w_block), release(p->d_w_ends);
     release(p->d_ac), release(p->d_c_to_a), release(p->d_codes), release(p->d_hits_out);
     release(p->d_nicrc), release(p->s_idx[0]), release(p->s_idx[1]), release(p->s_hist), release(p->d_snap);
     release(p->d_rx), release(p->d_stats), release(p->d_ctl), release(p->d_slot), release(p->d_fresh), release(p->d_out);
@@ -241,13 +262,13 @@ int msd_pos_set_receiver(msd_pos *p, uint32_t receiver, const msd_pos_receiver *
 }
 
 static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
-                  int on_device, msd_position *out, msd_pos_nicrc *nicrc, bool want_nicrc)
+                  int on_device, msd_position *out, msd_pos_nicrc *nicrc, bool want_nicrc, uint8_t *forward, bool want_forward)
 {
-    if (!p || (want_nicrc && !p->table))
+    if (!p || (want_nicrc && !p->table) || (want_forward && !p->reduce))
         return -EINVAL;
     if (n == 0)
         return 0;
-    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || n > MSD_POS_MAX_N)
+    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || (want_forward && !forward) || n > MSD_POS_MAX_N)
         return -EINVAL;
     if (!on_device && receiver)
         for (size_t i = 0; i < n; ++i)
@@ -288,15 +309,21 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
     }
     if (p->table) /* a skipped record's entry stays zero */
         POS_HIP(p, hipMemsetAsync(p->d_nicrc, 0, n * sizeof(msd_pos_nicrc), p->stream));
+    if (p->reduce) /* and its verdict */
+        POS_HIP(p, hipMemsetAsync(p->d_forward, 0, n, p->stream));
     for (size_t base = 0; base < n; base += MSD_POS_PIECE) {
         const size_t m = n - base < MSD_POS_PIECE ? n - base : MSD_POS_PIECE;
         msd_pos_launch_piece(p->stream, t, msgs, fields, receiver, p->d_rx, p->fp, (uint32_t)base, (uint32_t)m, p->d_slot,
-                             p->d_idx[0], p->d_idx[1], p->d_hist, p->d_out, p->d_stats, p->d_nicrc);
+                             p->d_idx[0], p->d_idx[1], p->d_hist, p->d_out, p->d_stats, p->d_nicrc, p->reduce_interval,
+                             p->d_forward);
         POS_HIP(p, hipGetLastError());
     }
     POS_HIP(p, hipMemcpyAsync(out, p->d_out, n * sizeof(msd_position), hipMemcpyDeviceToHost, p->stream));
     if (want_nicrc)
         POS_HIP(p, hipMemcpyAsync(nicrc, p->d_nicrc, n * sizeof(msd_pos_nicrc), hipMemcpyDeviceToHost, p->stream));
+    if (want_forward)
+        POS_HIP(p, hipMemcpyAsync(forward, p->d_forward, n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                  p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -304,13 +331,109 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
 int msd_pos_update(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
                    int on_device, msd_position *out)
 {
-    return update(p, msgs, fields, receiver, n, on_device, out, nullptr, false);
+    return update(p, msgs, fields, receiver, n, on_device, out, nullptr, false, nullptr, false);
 }
 
 int msd_pos_update_nicrc(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
                          int on_device, msd_position *out, msd_pos_nicrc *nicrc)
 {
-    return update(p, msgs, fields, receiver, n, on_device, out, nicrc, true);
+    return update(p, msgs, fields, receiver, n, on_device, out, nicrc, true, nullptr, false);
+}
+
+int msd_pos_update_reduce(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                          int on_device, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward)
+{
+    return update(p, msgs, fields, receiver, n, on_device, out, nicrc, nicrc != nullptr, forward, true);
+}
+
+int msd_pos_reduce_enable(msd_pos *p, uint32_t interval_ms)
+{
+    if (!p || !p->table || interval_ms > MSD_REDUCE_MAX_INTERVAL)
+        return -EINVAL;
+    if (p->reduce)
+        return interval_ms == p->reduce_interval ? 0 : -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    uint64_t *next[2] = {nullptr, nullptr};
+    const auto build = [&]() -> int {
+        for (int k = 0; k < 2; ++k) { /* the aircraft the table already has start at 0, as a new one does */
+            const size_t bytes = sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->tab[k].cap;
+            POS_HIP(p, hipMalloc(&next[k], bytes));
+            POS_HIP(p, hipMemsetAsync(next[k], 0, bytes, p->stream));
+        }
+        POS_HIP(p, hipStreamSynchronize(p->stream));
+        return 0;
+    };
+    const int rc = build();
+    if (rc) { /* the tracker stays as it was */
+        (void)hipGetLastError();
+        release(next[0]), release(next[1]);
+        return rc;
+    }
+    p->tab[0].next_reduce = next[0];
+    p->tab[1].next_reduce = next[1];
+    p->reduce_interval = interval_ms;
+    p->reduce = true;
+    return 0;
+}
+
+int msd_pos_reduce_wire(msd_pos *p, const msd_message *msgs, const uint8_t *forward, size_t n, int on_device, uint32_t flags,
+                        uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends)
+{
+    if (!p || !p->reduce || !out_len || (flags & ~(MSD_WIRE_VERBATIM | MSD_REDUCE_NET_ONLY)) || n > MSD_POS_MAX_N)
+        return -EINVAL;
+    *out_len = 0;
+    if (n == 0)
+        return 0;
+    if (!msgs || !forward || (!out && cap > 0))
+        return -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    const uint32_t nblocks = (uint32_t)((n + 255u) / 256u);
+    if (n > p->cap_w) {
+        release(p->d_w_lens), release(p->d_w_block), release(p->d_w_ends);
+        p->cap_w = 0;
+        POS_HIP(p, hipMalloc(&p->d_w_lens, n));
+        POS_HIP(p, hipMalloc(&p->d_w_block, sizeof(uint32_t) * (nblocks + 1u)));
+        POS_HIP(p, hipMalloc(&p->d_w_ends, sizeof(uint32_t) * n));
+        p->cap_w = n;
+    }
+    if (!on_device) {
+        if (n > p->cap_w_in) {
+            release(p->d_w_msgs), release(p->d_w_forward);
+            p->cap_w_in = 0;
+            POS_HIP(p, hipMalloc(&p->d_w_msgs, n * sizeof(msd_message)));
+            POS_HIP(p, hipMalloc(&p->d_w_forward, n));
+            p->cap_w_in = n;
+        }
+        POS_HIP(p, hipMemcpyAsync(p->d_w_msgs, msgs, n * sizeof(msd_message), hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipMemcpyAsync(p->d_w_forward, forward, n, hipMemcpyHostToDevice, p->stream));
+        msgs = p->d_w_msgs;
+        forward = p->d_w_forward;
+    }
+    msd_reduce_launch_lengths(p->stream, msgs, forward, (uint32_t)n, flags, p->d_w_lens, p->d_w_block);
+    POS_HIP(p, hipGetLastError());
+    uint32_t need = 0; /* at most 2^24 * 44 */
+    POS_HIP(p, hipMemcpyAsync(&need, p->d_w_block + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    *out_len = need;
+    if (need > cap) {
+        snprintf(p->err, sizeof p->err, "the reduced stream takes %u bytes, %zu were offered", need, cap);
+        return -ENOSPC;
+    }
+    if (need > p->cap_w_out) {
+        release(p->d_w_out);
+        p->cap_w_out = 0;
+        POS_HIP(p, hipMalloc(&p->d_w_out, need));
+        p->cap_w_out = need;
+    }
+    /* (with need == 0 the store kernel still runs: it writes the ends and no byte of the stream) */
+    msd_reduce_launch_store(p->stream, msgs, (uint32_t)n, flags, p->d_w_lens, p->d_w_block, p->d_w_out, p->d_w_ends);
+    POS_HIP(p, hipGetLastError());
+    if (need)
+        POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
+    if (ends)
+        POS_HIP(p, hipMemcpyAsync(ends, p->d_w_ends, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
 }
 
 int msd_pos_snapshot(msd_pos *p, msd_aircraft *out, size_t cap, int on_device, size_t *n)

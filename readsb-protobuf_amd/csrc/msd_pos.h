@@ -20,6 +20,7 @@ typedef struct msd_pos_table {
     msd_pos_aircraft *st;  /* cap entries */
     msd_trk_aircraft *trk; /* cap entries of a table tracker (msd_pos_create_table), else NULL */
     uint8_t *hits;         /* 2 * cap bytes {modeA_hit, modeC_hit} of a tracker that matches Mode A/C replies, else NULL */
+    uint64_t *next_reduce; /* MSD_REDUCE_TIMERS * cap timers of a tracker that reduces (msd_trk_reduce), else NULL */
     uint32_t cap;          /* a power of two */
 } msd_pos_table;
 
@@ -32,11 +33,13 @@ void msd_pos_launch_find(hipStream_t stream, msd_pos_table t, const msd_message 
 void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t *slot, const uint8_t *fresh, uint32_t n);
 /* steps 2 to 4 for records base .. base + n (n <= MSD_POS_PIECE): idx_a / idx_b hold n words each, hist
  * 256 * ceil(n / MSD_POS_TILE) words.  With t.trk, step 5: the table walk over the same grouped order, which reads the
- * out[] of step 3 and writes nicrc[] (n entries from base) */
+ * out[] of step 3 and writes nicrc[] (n entries from base).  With t.next_reduce, the reduce instantiations of both walks:
+ * forward[] (as out[], zeroed by the caller) gets every walked record's verdict byte, reduce_interval is in ms */
 void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
                           const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
                           uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
-                          msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc);
+                          msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc, uint32_t reduce_interval,
+                          uint8_t *forward);
 /* expiry: marks and counts the aircraft to remove (ctl[MSD_POS_CTL_REMOVED]); rebuild inserts the others into `to` */
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl);
 void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_table to);
@@ -56,5 +59,12 @@ void msd_pos_launch_modeac_codes(hipStream_t stream, const uint32_t *rx_ac, msd_
 /* the hits in the snapshot's order; buffers as msd_pos_launch_snapshot's */
 void msd_pos_launch_modeac_hits(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
                                 uint32_t *idx_b, uint32_t *hist, msd_modeac_hit *out);
+/* Reduced Beast output (msd_reduce_kernels.hip): the Beast frames of the records whose verdict byte passes the delivery
+ * conditions, dense and in record order.  lengths: lens[i] and block_sums[0 .. ceil(n / 256)] -- the workgroups' offsets,
+ * then the stream's length.  store: the bytes to out (device memory, as many as block_sums' last word says) and ends[i] */
+void msd_reduce_launch_lengths(hipStream_t stream, const msd_message *msgs, const uint8_t *forward, uint32_t n, uint32_t flags,
+                               uint8_t *lens, uint32_t *block_sums);
+void msd_reduce_launch_store(hipStream_t stream, const msd_message *msgs, uint32_t n, uint32_t flags, const uint8_t *lens,
+                             const uint32_t *block_off, uint8_t *out, uint32_t *ends);
 
 #endif

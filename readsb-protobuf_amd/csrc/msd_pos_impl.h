@@ -1,7 +1,8 @@
 /* msd_pos_impl.h -- the position path of the reference's tracker, one implementation for the position kernels
  * (device) and the host twin (libmsd_host.so): the per-aircraft state and the function that feeds it one record.
  * Restated from track.c / track.h:
- *   accept_data :170-196 (without its reduce_forward half), trackDataValid track.h:217-219, trackDataAge :229-235,
+ *   accept_data :170-196 (its reduce_forward half is msd_trk_impl.h's: msd_pos_acc.accepted tells it which of the six
+ *   members a record's feed accepted), trackDataValid track.h:217-219, trackDataAge :229-235,
  *   greatcircle :260-279, speed_check :313-369, doGlobalCPR :371-446, doLocalCPR :448-542, updatePosition :551-688 up to
  *   the assignment of a->meta.lat/lon, the part of trackUpdateFromMessage that reaches them -- seen / messages
  *   :1024-1025, the per-source versions :1032-1075, the gs / ias / tas stores :1222-1235, the CPR stores :1313-1329,
@@ -52,6 +53,7 @@ typedef struct msd_pos_aircraft { /* 136 bytes: what struct aircraft (track.h) k
 typedef struct msd_pos_acc {
     uint64_t c[MSD_PC_N];
     double margin;
+    uint32_t accepted; /* bit MSD_PV_x: accept_data took member x; only ever set here, whoever reads it clears it per record */
 } msd_pos_acc;
 
 MSD_HD uint64_t msd_pos_key(uint32_t receiver, uint32_t addr)
@@ -318,6 +320,7 @@ MSD_HD int msd_pos_update_position(msd_pos_aircraft *a, const msd_pos_receiver *
         } else if (location_result == -1) {
             acc->c[MSD_PC_GLOBAL_SKIPPED]++;
         } else if (msd_pos_accept(a, MSD_PV_POSITION, source, now)) {
+            acc->accepted |= 1u << MSD_PV_POSITION;
             acc->c[MSD_PC_GLOBAL_OK]++;
             if (a->reliable_odd <= 0 || a->reliable_even <= 0) {
                 a->reliable_odd = 1;
@@ -337,6 +340,7 @@ MSD_HD int msd_pos_update_position(msd_pos_aircraft *a, const msd_pos_receiver *
     if (location_result == -1) {
         location_result = msd_pos_local(a, rx, now, source, fflag, surface, f->cpr_lat, f->cpr_lon, new_lat, new_lon, acc);
         if (location_result >= 0 && msd_pos_accept(a, MSD_PV_POSITION, source, now)) {
+            acc->accepted |= 1u << MSD_PV_POSITION;
             acc->c[MSD_PC_LOCAL_OK]++;
             if (msd_pos_valid(a, MSD_PV_GS, now))
                 a->gs_last_pos = (float)a->gs;
@@ -386,20 +390,28 @@ MSD_HD void msd_pos_feed(msd_pos_aircraft *a, const msd_pos_receiver *rx, int fi
     const int gs_valid = msd_pos_record_gs(f, &v0, &v2);
     if (gs_valid) { /* :1222-1227 */
         gs_selected = version == 2 ? v2 : v0;
-        if (msd_pos_accept(a, MSD_PV_GS, source, now))
+        if (msd_pos_accept(a, MSD_PV_GS, source, now)) {
+            acc->accepted |= 1u << MSD_PV_GS;
             a->gs = (uint32_t)gs_selected;
+        }
     }
-    if (f->ias_valid && msd_pos_accept(a, MSD_PV_IAS, source, now))
+    if (f->ias_valid && msd_pos_accept(a, MSD_PV_IAS, source, now)) {
+        acc->accepted |= 1u << MSD_PV_IAS;
         a->ias = f->ias;
-    if (f->tas_valid && msd_pos_accept(a, MSD_PV_TAS, source, now))
+    }
+    if (f->tas_valid && msd_pos_accept(a, MSD_PV_TAS, source, now)) {
+        acc->accepted |= 1u << MSD_PV_TAS;
         a->tas = f->tas;
+    }
     if (f->cpr_valid && !f->cpr_odd && msd_pos_accept(a, MSD_PV_CPR_EVEN, source, now)) { /* :1313-1320 */
+        acc->accepted |= 1u << MSD_PV_CPR_EVEN;
         a->even_type = f->cpr_type;
         a->even_lat = f->cpr_lat;
         a->even_lon = f->cpr_lon;
         cpr_new = 1;
     }
     if (f->cpr_valid && f->cpr_odd && msd_pos_accept(a, MSD_PV_CPR_ODD, source, now)) { /* :1322-1329 */
+        acc->accepted |= 1u << MSD_PV_CPR_ODD;
         a->odd_type = f->cpr_type;
         a->odd_lat = f->cpr_lat;
         a->odd_lon = f->cpr_lon;

@@ -19,6 +19,9 @@
  * A tracker that matches Mode A/C replies (msd_modeac_impl.h) adds 1b. a kernel that counts the call's msgtype 32 records
  * per (receiver, code) with integer atomics, and trackMatchAC as three kernels: match cleared, one lane per slot, one
  * lane per (receiver, code).
+ * A tracker that reduces (modes_hip.h "Reduced Beast output") runs the reduce instantiations of the two walks: step 3
+ * leaves one byte per record for step 5, which keeps the aircraft's timers and leaves the record's verdict in its place.
+ * The compacting Beast writer is msd_reduce_kernels.hip.
  * Wave64 throughout: ballots are 64 bits wide and a workgroup of 256 threads is four waves.  The walk is double
  * precision arithmetic with long dependent chains and divergent branches per aircraft; its rate comes from the number of
  * aircraft in flight, not from the vector width.
@@ -83,6 +86,9 @@ msd_pos_find_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
                 msd_trk_init(&t.trk[s]);
             if (t.hits)
                 t.hits[2u * s] = t.hits[2u * s + 1u] = 0;
+            if (t.next_reduce)
+                for (uint32_t k = 0; k < MSD_REDUCE_TIMERS; ++k)
+                    t.next_reduce[(size_t)s * MSD_REDUCE_TIMERS + k] = 0;
             atomicAdd(&ctl[MSD_POS_CTL_INSERTED], 1u);
         }
     }
@@ -204,11 +210,14 @@ msd_pos_scatter_kernel(const uint32_t *idx_in, Digit digit, uint32_t n, const ui
     }
 }
 
-/* step 3 and 4: the lane at the head of an aircraft's run walks it */
+/* step 3 and 4: the lane at the head of an aircraft's run walks it.  REDUCE: the tracker reduces, and the walk leaves in
+ * forward[i] what the table walk's rule needs of this one: the members msd_pos_feed accepted and whether the aircraft has
+ * been seen twice; a tracker that does not runs the instantiation without it. */
+template <bool REDUCE>
 __global__ void __launch_bounds__(NT)
 msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                     const msd_pos_receiver *rx, int filter_persistence, uint32_t base, uint32_t n, const uint32_t *slot,
-                    const uint32_t *idx, msd_position *out, unsigned long long *dstats)
+                    const uint32_t *idx, msd_position *out, unsigned long long *dstats, uint8_t *forward)
 {
     const uint32_t j = blockIdx.x * NT + threadIdx.x;
     if (j >= n)
@@ -226,8 +235,12 @@ msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
         const msd_fields f = fields[i];
         const msd_pos_receiver r = rx[receiver ? receiver[i] : 0u];
         msd_position o = {};
+        if (REDUCE)
+            acc.accepted = 0;
         msd_pos_feed(&a, &r, filter_persistence, msgs[i].sysTimestampMsg, &f, &o, &acc);
         out[i] = o;
+        if (REDUCE)
+            forward[i] = (uint8_t)(acc.accepted | (a.messages > 1 ? MSD_REDUCE_WALK_SEEN_TWICE : 0u));
     }
     t.st[s] = a;
     for (int c = 0; c < MSD_PC_N; ++c)
@@ -240,11 +253,14 @@ msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
 /* step 5, table trackers: the same heads walk the same runs again and feed the table entry, in place in device memory --
  * a record touches a few members of the 592 bytes, and only those are loaded and stored.  Reads what step 3 wrote for
  * each record (out[i].result) and writes its NIC / Rc.  HITS: the tracker matches Mode A/C replies and the walk resets
- * the aircraft's hit bytes; a tracker that does not runs the instantiation without them. */
-template <bool HITS>
+ * the aircraft's hit bytes; a tracker that does not runs the instantiation without them.  REDUCE: the tracker reduces;
+ * the walk applies accept_data's reduce_forward half to the aircraft's timers and turns forward[i] from what the position
+ * walk left there into the record's verdict (MSD_REDUCE_FORWARD, MSD_REDUCE_SEEN_TWICE). */
+template <bool HITS, bool REDUCE>
 __global__ void __launch_bounds__(NT)
 msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, uint32_t base, uint32_t n,
-                    const uint32_t *slot, const uint32_t *idx, const msd_position *out, msd_pos_nicrc *nicrc)
+                    const uint32_t *slot, const uint32_t *idx, const msd_position *out, msd_pos_nicrc *nicrc,
+                    uint32_t reduce_interval, uint8_t *forward)
 {
     const uint32_t j = blockIdx.x * NT + threadIdx.x;
     if (j >= n)
@@ -254,6 +270,7 @@ msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
         return;
     msd_trk_aircraft *a = &t.trk[s];
     uint8_t *const hits = HITS ? &t.hits[2u * s] : nullptr;
+    uint64_t *const next_reduce = REDUCE ? &t.next_reduce[(size_t)s * MSD_REDUCE_TIMERS] : nullptr;
     for (uint32_t k = j; k < n; ++k) {
         const uint32_t i = base + element(idx, k);
         if (slot[i] != s)
@@ -262,7 +279,13 @@ msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
         const msd_fields f = fields[i];
         const msd_position o = out[i];
         msd_pos_nicrc q;
-        msd_trk_feed(a, m.sysTimestampMsg, &m, &f, &o, &q, hits);
+        if (REDUCE) {
+            const uint32_t w = forward[i];
+            const int fwd = msd_trk_feed(a, m.sysTimestampMsg, &m, &f, &o, &q, hits, next_reduce, reduce_interval, w & 63u);
+            forward[i] = (uint8_t)((fwd ? MSD_REDUCE_FORWARD : 0u) | (w & MSD_REDUCE_WALK_SEEN_TWICE ? MSD_REDUCE_SEEN_TWICE : 0u));
+        } else {
+            (void)msd_trk_feed(a, m.sysTimestampMsg, &m, &f, &o, &q, hits, nullptr, 0u, 0u);
+        }
         nicrc[i] = q;
     }
 }
@@ -297,6 +320,9 @@ __global__ void __launch_bounds__(NT) msd_pos_rebuild_kernel(msd_pos_table from,
         to.hits[2u * d] = from.hits[2u * s];
         to.hits[2u * d + 1u] = from.hits[2u * s + 1u];
     }
+    if (from.next_reduce)
+        for (uint32_t k = 0; k < MSD_REDUCE_TIMERS; ++k)
+            to.next_reduce[(size_t)d * MSD_REDUCE_TIMERS + k] = from.next_reduce[(size_t)s * MSD_REDUCE_TIMERS + k];
 }
 
 /* snapshot: entry j of the output is the aircraft in slot idx[j] */
@@ -445,7 +471,8 @@ void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t
 void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
                           const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
                           uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
-                          msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc)
+                          msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc, uint32_t reduce_interval,
+                          uint8_t *forward)
 {
     const uint32_t tiles = blocks(n);
     /* slots run from 0 to cap inclusive (cap = skipped) */
@@ -460,12 +487,23 @@ void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message
         in = bufs[w];
         w ^= 1;
     }
-    msd_pos_walk_kernel<<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out,
-                                                  dstats);
+    if (t.next_reduce) { /* (a table tracker: msd_pos_reduce_enable refuses any other) */
+        msd_pos_walk_kernel<true><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in,
+                                                            out, dstats, forward);
+        if (t.hits)
+            msd_trk_walk_kernel<true, true><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc,
+                                                                      reduce_interval, forward);
+        else
+            msd_trk_walk_kernel<false, true><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc,
+                                                                       reduce_interval, forward);
+        return;
+    }
+    msd_pos_walk_kernel<false><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in,
+                                                         out, dstats, nullptr);
     if (t.trk && t.hits)
-        msd_trk_walk_kernel<true><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc);
+        msd_trk_walk_kernel<true, false><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc, 0u, nullptr);
     else if (t.trk)
-        msd_trk_walk_kernel<false><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc);
+        msd_trk_walk_kernel<false, false><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc, 0u, nullptr);
 }
 
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl)

@@ -1,14 +1,14 @@
 /* msd_trk_impl.h -- the rest of trackUpdateFromMessage, one implementation for the table kernels (device) and the host
  * twin (libmsd_host.so): the per-aircraft table entry and the function that feeds it one record.  Restated from
  * track.c / track.h, in the reference's order:
- *   trackCreateAircraft's defaults :83-90, accept_data :170-196 (without its reduce_forward half) with the per-member
- *   stale intervals of :108-143, combine_validity :200-215, compare_validity :217-228, trackDataValid / Fresh / Age
+ *   trackCreateAircraft's defaults :83-90, accept_data :170-196 with the per-member stale intervals of :108-143 and, for a
+ *   tracker that reduces, its reduce_forward half with the DF11 timer of :1396-1400 (msd_trk_reduce below), combine_validity :200-215, compare_validity :217-228, trackDataValid / Fresh / Age
  *   track.h:217-235, compute_nic :690-776, compute_rc :778-892, compute_v0_nacp :897-924, compute_v0_sil :929-967,
  *   compute_nic_rc_from_message :969-976, altitude_to_feet :978-987, trackUpdateFromMessage :1020-1378 minus what
  *   msd_pos_feed does (seen / messages, gs / ias / tas, the CPR halves and updatePosition), the NIC / Rc of doGlobalCPR
  *   :378-379 and doLocalCPR :458-473 with updatePosition's stores :667-674, and trackRemoveStaleAircraft's EXPIRE list
  *   :1520-1563 for these members.
- * Not here: the reduce_forward half of accept_data, FATSV state, geomag_calc, update_polar_range, SBS and MLAT input.
+ * Not here: FATSV state, geomag_calc, update_polar_range, SBS and MLAT input.
  * trackMatchAC is msd_modeac_impl.h; of modeA_hit / modeC_hit this file has the two resets (:1096-1102, :1154-1156).
  *
  * The entry is the public msd_aircraft (modes_hip.h); its head -- receiver .. pos_reliable_even -- and the validities
@@ -26,6 +26,10 @@
 typedef msd_aircraft msd_trk_aircraft;
 
 #define MSD_TRK_RELIABLE_MAX 20 /* ALTITUDE_BARO_RELIABLE_MAX, track.h:71 */
+#define MSD_REDUCE_TIMERS (MSD_AC_N + 1) /* per slot of a tracker that reduces: the members' timers, then the DF11 timer */
+#define MSD_REDUCE_MAX_INTERVAL 15000u   /* --net-beast-reduce-interval is capped at 15 s (readsb.c) */
+/* what the position walk leaves in a record's verdict byte for the table walk: msd_pos_acc.accepted in bits 0-5 and */
+#define MSD_REDUCE_WALK_SEEN_TWICE 64u   /* the aircraft's messages > 1 after the record */
 
 MSD_HD void msd_trk_init(msd_trk_aircraft *a) /* trackCreateAircraft */
 {
@@ -71,7 +75,31 @@ MSD_HD uint64_t msd_trk_age(const msd_trk_aircraft *a, int k, uint64_t now) /* t
     return now - a->updated[k];
 }
 
-MSD_HD int msd_trk_accept(msd_trk_aircraft *a, int k, unsigned source, uint64_t now) /* accept_data */
+/* The reduce_forward half of accept_data (:182-193) for one record of a tracker that reduces (modes_hip.h "Reduced Beast
+ * output"): next[k] is data_validity.next_reduce_forward of member k, next[MSD_AC_N] the aircraft's
+ * next_reduce_forward_DF11; they sit beside the entry, as the hit bytes do, start at 0 and are not touched by EXPIRE.
+ * `forward` is mm->reduce_forward.  A timer depends on its own member's accepts only, so the order in which a record's
+ * members come by does not matter.  mm->sbs_in is never set here. */
+typedef struct msd_trk_reduce {
+    uint64_t *next;
+    uint32_t interval; /* Modes.net_output_beast_reduce_interval, ms */
+    uint8_t df17;      /* mm->msgtype == 17 */
+    uint8_t cpr;       /* mm->cpr_valid */
+    uint8_t forward;
+} msd_trk_reduce;
+
+MSD_HD void msd_trk_reduce_member(msd_trk_reduce *r, int k, uint64_t now, int reduce_often)
+{
+    if (now > r->next[k]) {
+        r->next[k] = now + ((r->df17 || reduce_often) ? (uint64_t)r->interval : (uint64_t)r->interval * 4u);
+        if (r->interval > 7000u && r->cpr) /* global CPR stays possible at a long interval */
+            r->next[k] = now + 7000u;
+        r->forward = 1;
+    }
+}
+
+/* r: NULL for a tracker that does not reduce */
+MSD_HD int msd_trk_accept(msd_trk_aircraft *a, int k, unsigned source, uint64_t now, int reduce_often, msd_trk_reduce *r) /* accept_data */
 {
     if (now < a->updated[k])
         return 0;
@@ -83,6 +111,8 @@ MSD_HD int msd_trk_accept(msd_trk_aircraft *a, int k, unsigned source, uint64_t 
         a->altitude_geom_stale = now + (a->altitude_geom_stale_15s ? 15000u : 60000u);
         a->altitude_geom_expires = now + 70000u;
     }
+    if (r)
+        msd_trk_reduce_member(r, k, now, reduce_often);
     return 1;
 }
 
@@ -237,11 +267,34 @@ MSD_HD int msd_trk_min(int a, int b)
 
 /* One record of an aircraft, after msd_pos_feed has had it: pos is what that wrote for the record.  nicrc: decoded_nic /
  * decoded_rc of the record.  hits: the aircraft's {modeA_hit, modeC_hit} bytes of a tracker that matches Mode A/C
- * replies (msd_modeac_impl.h), else NULL. */
-MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m, const msd_fields *f,
-                         const msd_position *pos, msd_pos_nicrc *nicrc, uint8_t *hits)
+ * replies (msd_modeac_impl.h), else NULL.  next_reduce: the aircraft's MSD_AC_N + 1 timers of a tracker that reduces,
+ * else NULL; with them, interval is the reduce interval, pos_accepted msd_pos_acc.accepted as msd_pos_feed left it for
+ * this record, and the return value is mm->reduce_forward.  Without them it is 0. */
+MSD_HD int msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m, const msd_fields *f,
+                        const msd_position *pos, msd_pos_nicrc *nicrc, uint8_t *hits, uint64_t *next_reduce,
+                        uint32_t interval, unsigned pos_accepted)
 {
     const unsigned source = f->source;
+    msd_trk_reduce red, *const r = next_reduce ? &red : 0;
+    red.next = next_reduce;
+    red.interval = interval;
+    red.df17 = m->msgtype == 17;
+    red.cpr = f->cpr_valid != 0;
+    red.forward = 0;
+    if (r) { /* the six members msd_pos_feed accepted: gs, the CPR halves and the position are reduce_often (:617 .. :1323) */
+        if (pos_accepted & (1u << MSD_PV_GS))
+            msd_trk_reduce_member(r, MSD_AC_GS, now, 1);
+        if (pos_accepted & (1u << MSD_PV_IAS))
+            msd_trk_reduce_member(r, MSD_AC_IAS, now, 0);
+        if (pos_accepted & (1u << MSD_PV_TAS))
+            msd_trk_reduce_member(r, MSD_AC_TAS, now, 0);
+        if (pos_accepted & (1u << MSD_PV_CPR_ODD))
+            msd_trk_reduce_member(r, MSD_AC_CPR_ODD, now, 1);
+        if (pos_accepted & (1u << MSD_PV_CPR_EVEN))
+            msd_trk_reduce_member(r, MSD_AC_CPR_EVEN, now, 1);
+        if (pos_accepted & (1u << MSD_PV_POSITION))
+            msd_trk_reduce_member(r, MSD_AC_POSITION, now, 1);
+    }
     nicrc->rc = 0;
     nicrc->nic = 0;
     nicrc->set = 0;
@@ -326,7 +379,7 @@ MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m
         const int good_crc = (m->crc == 0 && source != 2) ? (MSD_TRK_RELIABLE_MAX / 2 - 1) : 0;
         if (a->altitude_baro_reliable <= 0 || adelta < 300 || (fpm < max_fpm && fpm > min_fpm) ||
             (good_crc && a->altitude_baro_reliable <= (MSD_TRK_RELIABLE_MAX / 2 + 2))) {
-            if (msd_trk_accept(a, MSD_AC_ALTITUDE_BARO, source, now)) {
+            if (msd_trk_accept(a, MSD_AC_ALTITUDE_BARO, source, now, 1, r)) {
                 a->altitude_baro_reliable = msd_trk_min(MSD_TRK_RELIABLE_MAX, a->altitude_baro_reliable + (good_crc + 1));
                 a->alt_baro = alt;
             }
@@ -339,16 +392,16 @@ MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m
         }
     }
 
-    if (f->squawk_valid && msd_trk_accept(a, MSD_AC_SQUAWK, source, now)) {
+    if (f->squawk_valid && msd_trk_accept(a, MSD_AC_SQUAWK, source, now, 0, r)) {
         if (hits && f->squawk != a->squawk) /* :1154-1156 */
             hits[0] = 0;
         a->squawk = f->squawk;
     }
-    if (f->emergency_valid && msd_trk_accept(a, MSD_AC_EMERGENCY, source, now))
+    if (f->emergency_valid && msd_trk_accept(a, MSD_AC_EMERGENCY, source, now, 0, r))
         a->emergency = f->emergency;
-    if (f->altitude_geom_valid && msd_trk_accept(a, MSD_AC_ALTITUDE_GEOM, source, now))
+    if (f->altitude_geom_valid && msd_trk_accept(a, MSD_AC_ALTITUDE_GEOM, source, now, 1, r))
         a->alt_geom = msd_trk_to_feet(f->altitude_geom, f->altitude_geom_unit);
-    if (f->geom_delta_valid && msd_trk_accept(a, MSD_AC_GEOM_DELTA, source, now))
+    if (f->geom_delta_valid && msd_trk_accept(a, MSD_AC_GEOM_DELTA, source, now, 1, r))
         a->geom_delta = f->geom_delta;
 
     /* the record's heading, valid and typed as msd_fields_to_float says (:1197-1212) */
@@ -385,55 +438,55 @@ MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m
                 a->heading_type = a->adsb_hrd;
             else if (a->heading_type == 5) /* HEADING_TRACK_OR_HEADING */
                 a->heading_type = a->adsb_tah;
-            if (a->heading_type == 1 && msd_trk_accept(a, MSD_AC_TRACK, source, now))
+            if (a->heading_type == 1 && msd_trk_accept(a, MSD_AC_TRACK, source, now, 1, r))
                 a->track = h;
-            else if (a->heading_type == 3 && msd_trk_accept(a, MSD_AC_MAG_HEADING, source, now))
+            else if (a->heading_type == 3 && msd_trk_accept(a, MSD_AC_MAG_HEADING, source, now, 1, r))
                 a->mag_heading = h;
-            else if (a->heading_type == 2 && msd_trk_accept(a, MSD_AC_TRUE_HEADING, source, now))
+            else if (a->heading_type == 2 && msd_trk_accept(a, MSD_AC_TRUE_HEADING, source, now, 1, r))
                 a->true_heading = h;
         }
     }
 
-    if ((f->commb_valid & MSD_COMMB_TRACK_RATE) && msd_trk_accept(a, MSD_AC_TRACK_RATE, source, now))
+    if ((f->commb_valid & MSD_COMMB_TRACK_RATE) && msd_trk_accept(a, MSD_AC_TRACK_RATE, source, now, 1, r))
         a->track_rate_q = f->track_rate_q;
-    if ((f->commb_valid & MSD_COMMB_ROLL) && msd_trk_accept(a, MSD_AC_ROLL, source, now))
+    if ((f->commb_valid & MSD_COMMB_ROLL) && msd_trk_accept(a, MSD_AC_ROLL, source, now, 1, r))
         a->roll_q = f->roll_q;
     /* gs, ias, tas: msd_pos_feed (:1222-1235) */
-    if ((f->commb_valid & MSD_COMMB_MACH) && msd_trk_accept(a, MSD_AC_MACH, source, now))
+    if ((f->commb_valid & MSD_COMMB_MACH) && msd_trk_accept(a, MSD_AC_MACH, source, now, 0, r))
         a->mach_raw = f->mach_raw;
-    if (f->baro_rate_valid && msd_trk_accept(a, MSD_AC_BARO_RATE, source, now))
+    if (f->baro_rate_valid && msd_trk_accept(a, MSD_AC_BARO_RATE, source, now, 1, r))
         a->baro_rate = f->baro_rate;
-    if (f->geom_rate_valid && msd_trk_accept(a, MSD_AC_GEOM_RATE, source, now))
+    if (f->geom_rate_valid && msd_trk_accept(a, MSD_AC_GEOM_RATE, source, now, 1, r))
         a->geom_rate = f->geom_rate;
 
     if (f->airground != 0) { /* :1249-1258: an uncertain state does not replace fresh certain data */
         if (f->airground != 3 || !msd_trk_fresh(a, MSD_AC_AIRGROUND, now)) {
-            if (msd_trk_accept(a, MSD_AC_AIRGROUND, source, now))
+            if (msd_trk_accept(a, MSD_AC_AIRGROUND, source, now, 0, r))
                 a->air_ground = f->airground;
         }
     }
-    if (f->callsign_valid && msd_trk_accept(a, MSD_AC_CALLSIGN, source, now))
+    if (f->callsign_valid && msd_trk_accept(a, MSD_AC_CALLSIGN, source, now, 0, r))
         for (int i = 0; i < 8; ++i)
             a->callsign[i] = f->callsign[i];
-    if ((f->nav_valid & MSD_NAV_MCP_ALTITUDE) && msd_trk_accept(a, MSD_AC_NAV_ALTITUDE_MCP, source, now))
+    if ((f->nav_valid & MSD_NAV_MCP_ALTITUDE) && msd_trk_accept(a, MSD_AC_NAV_ALTITUDE_MCP, source, now, 0, r))
         a->nav_altitude_mcp = f->nav_mcp_altitude;
-    if ((f->nav_valid & MSD_NAV_FMS_ALTITUDE) && msd_trk_accept(a, MSD_AC_NAV_ALTITUDE_FMS, source, now))
+    if ((f->nav_valid & MSD_NAV_FMS_ALTITUDE) && msd_trk_accept(a, MSD_AC_NAV_ALTITUDE_FMS, source, now, 0, r))
         a->nav_altitude_fms = f->nav_fms_altitude;
-    if (f->nav_altitude_source != 0 && msd_trk_accept(a, MSD_AC_NAV_ALTITUDE_SRC, source, now))
+    if (f->nav_altitude_source != 0 && msd_trk_accept(a, MSD_AC_NAV_ALTITUDE_SRC, source, now, 0, r))
         a->nav_altitude_src = f->nav_altitude_source;
-    if ((f->nav_valid & MSD_NAV_HEADING) && msd_trk_accept(a, MSD_AC_NAV_HEADING, source, now)) {
+    if ((f->nav_valid & MSD_NAV_HEADING) && msd_trk_accept(a, MSD_AC_NAV_HEADING, source, now, 0, r)) {
         a->nav_heading_raw = f->nav_heading_raw;
         a->nav_heading_v2 = (f->nav_valid & MSD_NAV_HEADING_V2) != 0;
     }
-    if ((f->nav_valid & MSD_NAV_MODES) && msd_trk_accept(a, MSD_AC_NAV_MODES, source, now))
+    if ((f->nav_valid & MSD_NAV_MODES) && msd_trk_accept(a, MSD_AC_NAV_MODES, source, now, 0, r))
         a->nav_modes |= f->nav_modes; /* :1281-1298 only ever set the flags */
-    if ((f->nav_valid & MSD_NAV_QNH) && msd_trk_accept(a, MSD_AC_NAV_QNH, source, now)) {
+    if ((f->nav_valid & MSD_NAV_QNH) && msd_trk_accept(a, MSD_AC_NAV_QNH, source, now, 0, r)) {
         a->nav_qnh_raw = f->nav_qnh_raw;
         a->nav_qnh_commb = (f->nav_valid & MSD_NAV_QNH_COMMB) != 0;
     }
-    if (f->alert_valid && msd_trk_accept(a, MSD_AC_ALERT, source, now))
+    if (f->alert_valid && msd_trk_accept(a, MSD_AC_ALERT, source, now, 0, r))
         a->alert = f->alert;
-    if (f->spi_valid && msd_trk_accept(a, MSD_AC_SPI, source, now))
+    if (f->spi_valid && msd_trk_accept(a, MSD_AC_SPI, source, now, 0, r))
         a->spi = f->spi;
 
     /* :1313-1329: NIC / Rc of the CPR half this record stored (msd_pos_feed accepted it: updatePosition ran) */
@@ -454,24 +507,24 @@ MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m
         }
     }
 
-    if ((f->acc_valid & MSD_ACC_SDA) && msd_trk_accept(a, MSD_AC_SDA, source, now))
+    if ((f->acc_valid & MSD_ACC_SDA) && msd_trk_accept(a, MSD_AC_SDA, source, now, 0, r))
         a->sda = f->sda;
-    if ((f->acc_valid & MSD_ACC_NIC_A) && msd_trk_accept(a, MSD_AC_NIC_A, source, now))
+    if ((f->acc_valid & MSD_ACC_NIC_A) && msd_trk_accept(a, MSD_AC_NIC_A, source, now, 0, r))
         a->nic_a = f->nic_a & 1u;
-    if ((f->acc_valid & MSD_ACC_NIC_C) && msd_trk_accept(a, MSD_AC_NIC_C, source, now))
+    if ((f->acc_valid & MSD_ACC_NIC_C) && msd_trk_accept(a, MSD_AC_NIC_C, source, now, 0, r))
         a->nic_c = f->nic_c & 1u;
-    if ((f->acc_valid & MSD_ACC_NIC_BARO) && msd_trk_accept(a, MSD_AC_NIC_BARO, source, now))
+    if ((f->acc_valid & MSD_ACC_NIC_BARO) && msd_trk_accept(a, MSD_AC_NIC_BARO, source, now, 0, r))
         a->nic_baro = f->nic_baro;
-    if (nac_p_valid && msd_trk_accept(a, MSD_AC_NAC_P, source, now))
+    if (nac_p_valid && msd_trk_accept(a, MSD_AC_NAC_P, source, now, 0, r))
         a->nac_p = (uint8_t)nac_p;
-    if (f->nac_v_valid && msd_trk_accept(a, MSD_AC_NAC_V, source, now))
+    if (f->nac_v_valid && msd_trk_accept(a, MSD_AC_NAC_V, source, now, 0, r))
         a->nac_v = f->nac_v;
-    if (sil_type != 0 && msd_trk_accept(a, MSD_AC_SIL, source, now)) { /* :1355-1360 */
+    if (sil_type != 0 && msd_trk_accept(a, MSD_AC_SIL, source, now, 0, r)) { /* :1355-1360 */
         a->sil = (uint8_t)sil;
         if (a->sil_type == 0 || sil_type != 1)
             a->sil_type = (uint8_t)sil_type;
     }
-    if ((f->acc_valid & MSD_ACC_GVA) && msd_trk_accept(a, MSD_AC_GVA, source, now))
+    if ((f->acc_valid & MSD_ACC_GVA) && msd_trk_accept(a, MSD_AC_GVA, source, now, 0, r))
         a->gva = f->gva;
     /* :1366 accepts sda a second time: the same stores again */
 
@@ -489,6 +542,8 @@ MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m
             a->altitude_geom_stale = st;
             a->altitude_geom_expires = ex;
             a->altitude_geom_stale_15s = from == b; /* `*to = *from` copies the stale interval too */
+            if (r) /* and next_reduce_forward; the two-source branch leaves it alone */
+                r->next[g] = r->next[from];
         } else {
             const uint64_t sb = msd_trk_stale(a, b), sd = msd_trk_stale(a, d);
             const uint64_t eb = msd_trk_expires(a, b), ed = msd_trk_expires(a, d);
@@ -521,6 +576,12 @@ MSD_HD void msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m
         nicrc->rc = (uint16_t)rc;
         nicrc->set = 1;
     }
+
+    if (r && m->msgtype == 11 && m->iid == 0 && m->correctedbits == 0 && now > r->next[MSD_AC_N]) { /* :1396-1400 */
+        r->next[MSD_AC_N] = now + (uint64_t)interval * 4u;
+        r->forward = 1;
+    }
+    return r ? red.forward : 0;
 }
 
 /* trackRemoveStaleAircraft's EXPIRE list for an aircraft that stays (:1520-1563).  No line for nac_v, emergency, alert
