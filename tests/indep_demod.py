@@ -50,6 +50,9 @@ def convert(fmt, raw, dc=False, sample_rate=2.4e6):
         b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 2)
         mag = uc8_table()[b[:, 1], b[:, 0]]  # uc8_lookup[le16 of the pair]: high byte = second byte
         return mag, mag.astype(np.uint64), mag.astype(np.uint64) * mag.astype(np.uint64), False
+    if fmt == "mag16":  # magnitudes in, as a mag_buf holds them: the same integer level and power terms
+        mag = np.frombuffer(raw, dtype="<u2")
+        return mag, mag.astype(np.uint64), mag.astype(np.uint64) * mag.astype(np.uint64), False
     if fmt == "uc8":  # convert_uc8_generic, convert.c:113-162
         s = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 2).astype(np.float32)
         f = ((s - np.float32(127.5)) / np.float32(127.5)).astype(np.float32)
@@ -550,7 +553,7 @@ class Receiver:
 
     # ---- sdr_ifile.c:164-237 (lossless, i.e. throttled, feed) + fifo.c:168-188 + readsb.c:820-855,331
     def replay(self, raw):
-        bps = 2 if self.fmt == "uc8" else 4
+        bps = 2 if self.fmt in ("uc8", "mag16") else 4
         raw = bytes(raw)
         nsamples = len(raw) // bps
         whole = convert(self.fmt, raw[: nsamples * bps], True) if self.dc_filter else None  # the filter runs through the stream
@@ -583,7 +586,7 @@ class Receiver:
     # drops[i]: samples lost in front of segment i.  The last segment ends like a file.
     def live_feed(self, segments, drops):
         assert not self.dc_filter
-        bps = 2 if self.fmt == "uc8" else 4
+        bps = 2 if self.fmt in ("uc8", "mag16") else 4
         tail = np.zeros(OVERLAP, dtype=np.uint16)
         counter = 0
         for si, (seg, drop) in enumerate(zip(segments, drops)):
