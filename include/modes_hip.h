@@ -849,8 +849,8 @@ int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, co
  * receiver index also selects the receiver location and --max-range its checks use.  The other members of struct
  * aircraft, with decoded_nic / decoded_rc, are kept by a tracker made with msd_pos_create_table ("the aircraft table"
  * below); a table tracker can also match the Mode A/C replies against its aircraft ("Mode A/C matching" below) and thin
- * the feed to readsb's reduced Beast output ("Reduced Beast output" below).  Not
- * built: the declination, the polar range, SBS and MLAT positions.
+ * the feed to readsb's reduced Beast output ("Reduced Beast output" below) and write the SBS output ("SBS output" below).
+ * Not built: the declination, the polar range, SBS input and MLAT positions.
  *
  * What is exact.  The coordinates: double + - * / floor fmod in the reference's order, nothing contracted; delivered
  * lat / lon are bit-identical to the reference's whenever the decisions are.
@@ -932,7 +932,8 @@ int msd_pos_get_stats(const msd_pos *p, msd_pos_stats *st);
  * :458-473).  accept_data's stale interval is 15 s for altitude_baro, squawk and airground and 60 s for the others; every
  * member expires 70 s after its update, so a member keeps `source` and `updated` only -- except altitude_geom, whose
  * validity combine_validity can make from two others and which keeps its stale and expiry times.
- * Not built: FATSV state, the declination (geomag_calc), the polar range, SBS and MLAT input.  modeA_hit / modeC_hit
+ * Not built: FATSV state, the declination (geomag_calc), the polar range, SBS and MLAT input (SBS output: "SBS output"
+ * below).  modeA_hit / modeC_hit
  * are kept beside the entry, not in it: "Mode A/C matching" below; so are the timers of accept_data's reduce_forward half:
  * "Reduced Beast output" below.
  *
@@ -1094,6 +1095,81 @@ int msd_pos_update_reduce(msd_pos *p, const msd_message *msgs, const msd_fields 
  * -EINVAL: not enabled, an unknown flag bit, n above 2^24, NULL.  n == 0: 0 and *out_len = 0. */
 int msd_pos_reduce_wire(msd_pos *p, const msd_message *msgs, const uint8_t *forward, size_t n, int on_device, uint32_t flags,
                         uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
+
+/* ---- SBS output: readsb's BaseStation feed (port 30003, modesSendSBSOutput net_io.c:1038-1241) for a table tracker --
+ * one `MSG,3,1,1,4840D6,1,...` text line of 22 fields per message, with the delivery conditions around it
+ * (net_io.c:1266-1270, mode_s.c:2164-2172).  SBS is the one output that needs the tracker's state per
+ * message; msd_pos_update_sbs hands it over in a row per record, msd_pos_sbs_wire writes the text on the device.
+ *
+ * A record's row: MSD_SBS_TRACKED says trackUpdateFromMessage returned an aircraft (0, with an all-zero row, for Mode A/C
+ * replies and records with addr == 0); gs_selected is mm->gs.selected after track.c:1223 (gs.v2 when the version of the
+ * message's source is 2, else gs.v0), lat / lon the record's msd_position, geom_delta and its validity the aircraft's
+ * after the record.  The rows are no state: a call other than msd_pos_update_sbs delivers none and changes nothing for
+ * the next.
+ *
+ * A record writes a line when MSD_SBS_TRACKED is set, correctedbits < 2 (with MSD_WIRE_VERBATIM too, net_io.c:1266),
+ * fields.addr has no MSD_NON_ICAO_ADDRESS, one of MSD_WIRE_VERBATIM, MSD_SBS_NET_ONLY, MSD_SBS_SEEN_TWICE is present, and
+ * the message has an SBS type: DF4 / 20 -> 5, DF5 / 21 -> 6, DF0 / 16 -> 7, DF11 -> 8, DF17 / 18 with metype 1-4 -> 1,
+ * 5-8 -> 2, 9-18 -> 3, 19 -> 4; nothing for any other DF or metype.
+ * The line, ending in \r\n: MSG,type,1,1,%06X of the address,1 | reception date, time | now's date, time
+ * (%04d/%02d/%02d,%02d:%02d:%02d.%03u) | callsign (%s of the 8 characters) | altitude (%d, with H where geometric under
+ * MSD_SBS_GNSS; altitude_baro + geom_delta / altitude_geom - geom_delta in int32_t, wrapping) | ground speed (%.0f of
+ * gs_selected) | track (%.0f; only a heading of type HEADING_GROUND_TRACK: the ES type 19 velocity of subtypes 1 / 2 with
+ * gs_selected > 0 and the BDS 5,0 track) | latitude, longitude (%1.5f) | vertical rate (%d; geometric first and with H
+ * under MSD_SBS_GNSS) | squawk (%04x) | alert, emergency (squawk 7500 / 7600 / 7700), SPI, ground: -1 / 0 / empty.
+ * Times: the reference calls localtime_r; here the caller states the zone.  A time is sysTimestampMsg + utc_offset_ms, or
+ * now_ms + utc_offset_ms, read as POSIX time (proleptic Gregorian, no leap seconds); a caller in a zone with daylight
+ * saving passes the offset in force.  A record's own time is device data and cannot be refused: the year is printed
+ * modulo 10000, a sum that is negative as an int64_t as 0.
+ * Numbers: the bytes are glibc printf's.  %1.5f is the exactly rounded decimal of the double (128-bit integer arithmetic,
+ * ties to even, the sign kept: -0.00000), %.0f of a float is rintf, the velocity's ground track
+ * float(atan2(ew, ns) * 180 / pi) (+ 360 when negative) comes out of a table that msd_pos_sbs_enable computes with the
+ * host's libm for every (sign, magnitude) pair a message can carry -- the device evaluates no atan2.
+ * What no decoder delivers is printed as an empty field, so that a line is never longer than MSD_SBS_MAX whatever the
+ * arrays hold: a gs_selected outside [0, 100000) or NaN, a latitude or longitude that is not finite or beyond +-360, a
+ * velocity whose components are not what subtype 1 / 2 can carry (|component| <= 1022, times 4 for subtype 2); of the
+ * address the 24 low bits are printed, of heading_raw the bits its message carries (11, 10 or 7).
+ * CONTRACT, the table's: the device and the host object (msd_pos_host_sbs_enable, msd_pos_host_update_sbs,
+ * msd_pos_host_sbs_wire -- snprintf with the reference's format strings, gmtime_r, the libm's atan2) deliver the same rows
+ * and the same stream on every stream on which they deliver the same msd_position records, however the stream is cut into
+ * calls.  Not built: sockets, the heartbeat, SBS input. ---- */
+#define MSD_SBS_TRACKED 1u          /* trackUpdateFromMessage returned an aircraft: not Mode A/C, fields.addr != 0 */
+#define MSD_SBS_SEEN_TWICE 2u       /* a->meta.messages > 1 after the record (mode_s.c:2168) */
+#define MSD_SBS_GS_VALID 4u
+#define MSD_SBS_GEOM_DELTA_VALID 8u /* trackDataValid(&a->geom_delta_valid) at messageNow(), after the record's update */
+#define MSD_SBS_CPR_DECODED 16u
+typedef struct msd_sbs_track { /* 32 bytes, no implicit padding */
+    double lat, lon;      /* decoded_lat / decoded_lon, as msd_position; 0 unless MSD_SBS_CPR_DECODED */
+    float gs_selected;    /* mm->gs.selected after track.c:1223: gs.v2 for a message version of 2, else gs.v0 */
+    int32_t geom_delta;   /* a->geom_delta after the record */
+    uint8_t flags, pad[7];
+} msd_sbs_track;
+/* -EINVAL on a tracker without a table; a second call returns 0 and changes nothing; -ENOMEM leaves the tracker as it was.
+ * Builds the ground-track table (4 x 1023 x 1023 entries of 16 bits, 8 MiB) on the host and uploads it; msd_pos_reset
+ * leaves the tracker enabled.  A tracker that never calls this allocates and launches what it did before SBS existed and
+ * answers -EINVAL to the two calls below. */
+int msd_pos_sbs_enable(msd_pos *p);
+/* msd_pos_update_reduce (nicrc may be NULL; forward may be NULL, and where it is not the tracker must reduce, else
+ * -EINVAL) with the row of every record in trk: n entries of device memory (on_device = 1) or host memory.  On -EINVAL /
+ * -ENOSPC nothing changed and trk is not written. */
+int msd_pos_update_sbs(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                       int on_device, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward, msd_sbs_track *trk);
+#define MSD_SBS_NET_ONLY 2u        /* --net-only; MSD_WIRE_VERBATIM (1u) is --net-verbatim */
+#define MSD_SBS_GNSS 4u            /* --gnss, Modes.use_gnss */
+#define MSD_SBS_NOW_IS_RECEIVED 8u /* fields 9-10 repeat the record's own reception time (replays have no wall clock) */
+typedef struct msd_sbs_options { uint64_t now_ms; int64_t utc_offset_ms; uint32_t flags, reserved; } msd_sbs_options;
+/* the longest line: 19 `MSG,1,1,1,FFFFFF,1,` + 24 `YYYY/MM/DD,HH:MM:SS.mmm,` + 23 the same without the last comma
+ * + 9 `,` callsign + 13 `,-2147483648H` + 6 `,65535` + 4 `,360` + 22 `,-180.00000,-180.00000` + 8 `,-32768H` + 5 `,7700`
+ * + 4 x 3 `,-1` + 2 `\r\n` = 147 (prepareWrite asks for 200) */
+#define MSD_SBS_MAX 147
+/* The lines of the records that reach the SBS output, dense and in record order, compacted on the device:
+ * msd_pos_reduce_wire's out / cap / out_len / ends.  msgs, fields and trk: device memory (on_device = 1) or host memory;
+ * out and ends: host arrays.  Stateless: the tracker lends its stream, its buffers and the ground-track table.
+ * -ENOSPC: cap is too small, *out_len is the size needed, nothing else was written and the call can be repeated.
+ * -EINVAL: not enabled, an unknown flag bit, reserved != 0, n above 2^24, NULL, a now_ms + utc_offset_ms that is negative
+ * or at or beyond 253402300800000 (year 10000; checked with MSD_SBS_NOW_IS_RECEIVED too).  n == 0: 0 and *out_len = 0. */
+int msd_pos_sbs_wire(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk, size_t n,
+                     int on_device, const msd_sbs_options *opt, uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
 
 #ifdef __cplusplus
 }

@@ -242,6 +242,7 @@ EXPORTS = [
     "msd_pos_create_table", "msd_pos_update_nicrc", "msd_pos_snapshot", "msd_aircraft_valid", "msd_aircraft_to_float",
     "msd_pos_modeac_enable", "msd_pos_modeac_match", "msd_pos_modeac_codes", "msd_pos_modeac_hits", "msd_mode_c_to_a",
     "msd_pos_reduce_enable", "msd_pos_update_reduce", "msd_pos_reduce_wire",
+    "msd_pos_sbs_enable", "msd_pos_update_sbs", "msd_pos_sbs_wire",
 ]
 
 _lib = None
@@ -1117,7 +1118,18 @@ MODEAC_CODES = 4096
 # reduced Beast output: a record's verdict byte, msd_pos_reduce_wire's flag beside WIRE_VERBATIM, the timers per aircraft
 REDUCE_FORWARD, REDUCE_SEEN_TWICE, REDUCE_NET_ONLY = 1, 2, 2
 REDUCE_TIMERS = len(AC_MEMBERS) + 1
+# SBS output: a record's row (msd_sbs_track), its flags, msd_pos_sbs_wire's flags beside WIRE_VERBATIM, the longest line
+SBS_TRACK_DTYPE = np.dtype([("lat", "<f8"), ("lon", "<f8"), ("gs_selected", "<f4"), ("geom_delta", "<i4"), ("flags", "u1"),
+                            ("pad", "u1", (7,))])
+assert SBS_TRACK_DTYPE.itemsize == 32
+SBS_TRACKED, SBS_SEEN_TWICE, SBS_GS_VALID, SBS_GEOM_DELTA_VALID, SBS_CPR_DECODED = 1, 2, 4, 8, 16
+SBS_NET_ONLY, SBS_GNSS, SBS_NOW_IS_RECEIVED = 2, 4, 8
+SBS_MAX = 147
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmsd_host.so")
+
+
+class SbsOptions(C.Structure):
+    _fields_ = [("now_ms", C.c_uint64), ("utc_offset_ms", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PosReceiver(C.Structure):
@@ -1162,8 +1174,12 @@ def _pos_lib(host):
         f = {k: getattr(L, pre + k) for k in ("create", "destroy", "reset", "set_receiver", "update", "expire", "get_stats",
                                               "create_table", "update_nicrc", "snapshot", "modeac_enable", "modeac_match",
                                               "modeac_codes", "modeac_hits", "reduce_enable", "update_reduce",
-                                              "reduce_wire")}
+                                              "reduce_wire", "sbs_enable", "update_sbs", "sbs_wire")}
         dev = [] if host else [C.c_int]
+        f["sbs_enable"].argtypes = [C.c_void_p]
+        f["update_sbs"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [C.c_void_p] * 4
+        f["sbs_wire"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [
+            C.POINTER(SbsOptions), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
         f["reduce_enable"].argtypes = [C.c_void_p, C.c_uint32]
         f["update_reduce"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [C.c_void_p] * 3
         f["reduce_wire"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [
@@ -1209,12 +1225,14 @@ class PositionTracker:
     stream whose min_gate_margin_m on the twin stays above 1e-3 m."""
 
     def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False, table=False,
-                 modeac=False, reduce_interval_ms=None):
+                 modeac=False, reduce_interval_ms=None, sbs=False):
         """table=True: msd_pos_create_table -- the tracker also keeps the aircraft table (update_nicrc, snapshot).
         modeac=True (a table tracker): msd_pos_modeac_enable -- it also counts Mode A/C replies and matches them against
         its aircraft (modeac_match, modeac_codes, modeac_hits).
         reduce_interval_ms (a table tracker): msd_pos_reduce_enable -- it also keeps the timers of readsb's reduced Beast
-        output (update_reduce, reduce_wire)."""
+        output (update_reduce, reduce_wire).
+        sbs=True (a table tracker): msd_pos_sbs_enable -- update_sbs hands over a row per record and sbs_wire writes
+        readsb's SBS (BaseStation) lines from them."""
         self.host, self.table = host, table
         self.L, self.f = _pos_lib(host)
         receivers = receivers if receivers is not None else [None]
@@ -1231,6 +1249,8 @@ class PositionTracker:
                 self.modeac_enable()
             if reduce_interval_ms is not None:
                 self.reduce_enable(reduce_interval_ms)
+            if sbs:
+                self.sbs_enable()
         except MsdError:
             self.close()
             raise
@@ -1285,6 +1305,63 @@ class PositionTracker:
         self.reduce_needed = need.value
         self.reduce_out = out
         self._check(rc, "msd_pos_reduce_wire")
+        return out[:need.value].tobytes(), ends
+
+    def sbs_enable(self):
+        self._check(self.f["sbs_enable"](self.h), "msd_pos_sbs_enable")
+
+    def update_sbs(self, messages, fields, receiver=None, nicrc=True, forward=False):
+        """update_nicrc() with the SBS row of every record, and the verdict bytes of a tracker that reduces (forward=True)
+        -> (POSITION_DTYPE array, NICRC_DTYPE array or None, uint8 array or None, SBS_TRACK_DTYPE array)."""
+        n = len(messages)
+        assert len(fields) == n and messages.dtype == MESSAGE_DTYPE and fields.dtype == FIELDS_DTYPE
+        messages, fields = np.ascontiguousarray(messages), np.ascontiguousarray(fields)
+        rx = None if receiver is None else np.ascontiguousarray(receiver, dtype=np.uint32)
+        out, q, fwd = np.zeros(n, dtype=POSITION_DTYPE), np.zeros(n, dtype=NICRC_DTYPE), np.zeros(n, dtype=np.uint8)
+        trk = np.zeros(n, dtype=SBS_TRACK_DTYPE)
+        args = [self.h, messages.ctypes.data, fields.ctypes.data, None if rx is None else rx.ctypes.data, n]
+        self._check(self.f["update_sbs"](*args, *([] if self.host else [0]), out.ctypes.data, q.ctypes.data if nicrc else None,
+                                         fwd.ctypes.data if forward else None, trk.ctypes.data), "msd_pos_update_sbs")
+        return out, (q if nicrc else None), (fwd if forward else None), trk
+
+    def update_sbs_device(self, d_messages, d_fields, n, d_trk, d_receiver=None, d_forward=None):
+        """The same with the records, the rows (and the verdict bytes) in device memory (pointers); GPU tracker only
+        -> (POSITION_DTYPE array, NICRC_DTYPE array)."""
+        assert not self.host
+        out, q = np.zeros(n, dtype=POSITION_DTYPE), np.zeros(n, dtype=NICRC_DTYPE)
+        self._check(self.f["update_sbs"](self.h, d_messages, d_fields, d_receiver, n, 1, out.ctypes.data, q.ctypes.data,
+                                         d_forward, d_trk), "msd_pos_update_sbs")
+        return out, q
+
+    def sbs_wire(self, messages, fields, trk, verbatim=False, net_only=False, gnss=False, now_ms=0, utc_offset_ms=0,
+                 now_is_received=False, cap=None, flags=None, n=None, on_device=False, reserved=0):
+        """The SBS lines of the records -> (bytes, ends).  cap: the bytes offered (default: as many as are needed, asked
+        for first); self.sbs_needed is *out_len of the last call.  on_device: messages, fields and trk are device
+        pointers and n the number of records."""
+        if not on_device:
+            n = len(messages)
+            assert messages.dtype == MESSAGE_DTYPE and fields.dtype == FIELDS_DTYPE and trk.dtype == SBS_TRACK_DTYPE
+            assert len(fields) == n and len(trk) == n
+            messages, fields, trk = np.ascontiguousarray(messages), np.ascontiguousarray(fields), np.ascontiguousarray(trk)
+        if flags is None:
+            flags = ((WIRE_VERBATIM if verbatim else 0) | (SBS_NET_ONLY if net_only else 0) | (SBS_GNSS if gnss else 0) |
+                     (SBS_NOW_IS_RECEIVED if now_is_received else 0))
+        opt = SbsOptions(now_ms=now_ms, utc_offset_ms=utc_offset_ms, flags=flags, reserved=reserved)
+        ptrs = (messages, fields, trk) if on_device else tuple(a.ctypes.data if n else None for a in (messages, fields, trk))
+        dev = [] if self.host else [1 if on_device else 0]
+        need = C.c_size_t(0)
+        if cap is None:
+            rc = self.f["sbs_wire"](self.h, *ptrs, n, *dev, C.byref(opt), None, 0, C.byref(need), None)
+            if rc not in (0, -errno.ENOSPC):
+                self._check(rc, "msd_pos_sbs_wire")
+            cap = need.value
+        out = np.zeros(cap, dtype=np.uint8)
+        ends = np.zeros(n, dtype=np.uint32)
+        rc = self.f["sbs_wire"](self.h, *ptrs, n, *dev, C.byref(opt), out.ctypes.data if cap else None, cap, C.byref(need),
+                                ends.ctypes.data if n else None)
+        self.sbs_needed = need.value
+        self.sbs_out = out
+        self._check(rc, "msd_pos_sbs_wire")
         return out[:need.value].tobytes(), ends
 
     def reduce_timers(self, receiver, addr):

@@ -1,11 +1,14 @@
 /* msd_pos_host.c -- the host twin of the position tracker: msd_cpr_impl.h and msd_pos_impl.h compiled for the host,
  * the same open-addressing table in host memory, records fed one after the other. */
+#define _POSIX_C_SOURCE 200809L /* gmtime_r */
 #include "msd_pos_host.h"
 
 #include <errno.h>
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 #include "msd_modeac_impl.h"
 #include "msd_wire.h"
@@ -26,6 +29,7 @@ struct msd_pos_host {
     /* reduced Beast output (msd_pos_host_reduce_enable), else NULL: MSD_REDUCE_TIMERS timers per slot */
     uint64_t *next_reduce;
     uint32_t reduce_interval;
+    int sbs; /* SBS output (msd_pos_host_sbs_enable): the twin keeps nothing for it */
 };
 
 int msd_cpr_host_airborne(int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag, double *lat, double *lon)
@@ -159,13 +163,15 @@ static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
 }
 
 static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
-                  msd_position *out, msd_pos_nicrc *nicrc, int want_nicrc, uint8_t *forward, int want_forward)
+                  msd_position *out, msd_pos_nicrc *nicrc, int want_nicrc, uint8_t *forward, int want_forward,
+                  msd_sbs_track *sbs, int want_sbs)
 {
-    if (!p || (want_nicrc && !p->trk) || (want_forward && !p->next_reduce))
+    if (!p || (want_nicrc && !p->trk) || (want_forward && !p->next_reduce) || (want_sbs && !p->sbs))
         return -EINVAL;
     if (n == 0)
         return 0;
-    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || (want_forward && !forward) || n > ((size_t)1 << 24))
+    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || (want_forward && !forward) || (want_sbs && !sbs) ||
+        n > ((size_t)1 << 24))
         return -EINVAL;
     if (receiver)
         for (size_t i = 0; i < n; ++i)
@@ -207,18 +213,24 @@ static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fi
                 nicrc[i] = q;
             if (want_forward)
                 forward[i] = 0;
+            if (want_sbs)
+                memset(&sbs[i], 0, sizeof sbs[i]);
             continue;
         }
         memset(&out[i], 0, sizeof out[i]);
         p->acc.accepted = 0;
         msd_pos_feed(&p->st[slot[i]], &p->rx[receiver ? receiver[i] : 0u], p->fp, msgs[i].sysTimestampMsg, &fields[i],
                      &out[i], &p->acc);
+        if (want_sbs)
+            msd_pos_sbs(&out[i], &p->acc, p->st[slot[i]].messages, &sbs[i]);
         int fwd = 0;
         if (p->trk)
             fwd = msd_trk_feed(&p->trk[slot[i]], msgs[i].sysTimestampMsg, &msgs[i], &fields[i], &out[i], &q,
                                p->hits ? &p->hits[2u * slot[i]] : NULL,
                                p->next_reduce ? &p->next_reduce[(size_t)slot[i] * MSD_REDUCE_TIMERS] : NULL, p->reduce_interval,
                                p->acc.accepted);
+        if (want_sbs) /* (a table tracker: msd_pos_host_sbs_enable refuses any other) */
+            msd_trk_sbs(&p->trk[slot[i]], msgs[i].sysTimestampMsg, &sbs[i]);
         if (want_nicrc)
             nicrc[i] = q;
         if (want_forward)
@@ -232,19 +244,19 @@ static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fi
 int msd_pos_host_update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                         size_t n, msd_position *out)
 {
-    return update(p, msgs, fields, receiver, n, out, NULL, 0, NULL, 0);
+    return update(p, msgs, fields, receiver, n, out, NULL, 0, NULL, 0, NULL, 0);
 }
 
 int msd_pos_host_update_nicrc(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                               size_t n, msd_position *out, msd_pos_nicrc *nicrc)
 {
-    return update(p, msgs, fields, receiver, n, out, nicrc, 1, NULL, 0);
+    return update(p, msgs, fields, receiver, n, out, nicrc, 1, NULL, 0, NULL, 0);
 }
 
 int msd_pos_host_update_reduce(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                                size_t n, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward)
 {
-    return update(p, msgs, fields, receiver, n, out, nicrc, nicrc != NULL, forward, 1);
+    return update(p, msgs, fields, receiver, n, out, nicrc, nicrc != NULL, forward, 1, NULL, 0);
 }
 
 int msd_pos_host_reduce_enable(msd_pos_host *p, uint32_t interval_ms)
@@ -284,6 +296,240 @@ int msd_pos_host_reduce_wire(msd_pos_host *p, const msd_message *msgs, const uin
                     memcpy(out + len, frame, k);
                 len += k;
             }
+            if (pass && ends)
+                ends[i] = (uint32_t)len;
+        }
+        *out_len = len;
+        if (len > cap)
+            return -ENOSPC;
+    }
+    return 0;
+}
+
+int msd_pos_host_sbs_enable(msd_pos_host *p)
+{
+    if (!p || !p->trk)
+        return -EINVAL;
+    p->sbs = 1;
+    return 0;
+}
+
+int msd_pos_host_update_sbs(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                            size_t n, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward, msd_sbs_track *trk)
+{
+    return update(p, msgs, fields, receiver, n, out, nicrc, nicrc != NULL, forward, forward != NULL, trk, 1);
+}
+
+/* ---- the SBS writer: modesSendSBSOutput (net_io.c:1038-1241) with its own format strings, snprintf, gmtime_r and the
+ * libm.  The yardstick of the device's writer (msd_sbs_impl.h), which has no printf: nothing of that file's number or date
+ * code is used here. ---- */
+#define SBS_YEAR_10000_MS 253402300800000ll
+
+static int sbs_options_ok(const msd_sbs_options *opt)
+{
+    if (!opt || opt->reserved != 0 ||
+        (opt->flags & ~(MSD_WIRE_VERBATIM | MSD_SBS_NET_ONLY | MSD_SBS_GNSS | MSD_SBS_NOW_IS_RECEIVED)))
+        return 0;
+    if (opt->now_ms >= (uint64_t)SBS_YEAR_10000_MS * 2u || opt->utc_offset_ms <= -SBS_YEAR_10000_MS * 2 ||
+        opt->utc_offset_ms >= SBS_YEAR_10000_MS * 2) /* beyond this the sum is out of range whatever the other is */
+        return 0;
+    const int64_t now = (int64_t)opt->now_ms + opt->utc_offset_ms;
+    return now >= 0 && now < SBS_YEAR_10000_MS;
+}
+
+/* date and time of ms + offset; localtime_r's part is played by the offset (modes_hip.h) */
+static char *sbs_time(char *q, uint64_t ms, int64_t utc_offset_ms, int comma)
+{
+    int64_t s = (int64_t)(ms + (uint64_t)utc_offset_ms);
+    if (s < 0)
+        s = 0;
+    const time_t sec = (time_t)(s / 1000);
+    struct tm tm;
+    memset(&tm, 0, sizeof tm);
+    gmtime_r(&sec, &tm);
+    q += sprintf(q, "%04d/%02d/%02d,", (int)(((long long)tm.tm_year + 1900) % 10000), (tm.tm_mon + 1), tm.tm_mday);
+    q += sprintf(q, comma ? "%02d:%02d:%02d.%03u," : "%02d:%02d:%02d.%03u", tm.tm_hour, tm.tm_min, tm.tm_sec, (unsigned)(s % 1000));
+    return q;
+}
+
+/* the line of one record into buf (256 bytes) -> its length, 0: the record writes nothing */
+static size_t sbs_line(const msd_message *mm, const msd_fields *f, const msd_sbs_track *a, const msd_sbs_options *opt, char *buf)
+{
+    char *q = buf;
+    int msgType;
+    const int use_gnss = (opt->flags & MSD_SBS_GNSS) != 0;
+    const int delta_valid = (a->flags & MSD_SBS_GEOM_DELTA_VALID) != 0;
+    /* mode_s.c:2164-2172, net_io.c:1266 */
+    if (!(a->flags & MSD_SBS_TRACKED) || mm->correctedbits >= 2)
+        return 0;
+    if (!(opt->flags & (MSD_WIRE_VERBATIM | MSD_SBS_NET_ONLY)) && !(a->flags & MSD_SBS_SEEN_TWICE))
+        return 0;
+    if (f->addr & MSD_NON_ICAO_ADDRESS)
+        return 0;
+    switch (mm->msgtype) {
+    case 4:
+    case 20:
+        msgType = 5;
+        break;
+    case 5:
+    case 21:
+        msgType = 6;
+        break;
+    case 0:
+    case 16:
+        msgType = 7;
+        break;
+    case 11:
+        msgType = 8;
+        break;
+    case 17:
+    case 18:
+        if (f->metype >= 1 && f->metype <= 4)
+            msgType = 1;
+        else if (f->metype >= 5 && f->metype <= 8)
+            msgType = 2;
+        else if (f->metype >= 9 && f->metype <= 18)
+            msgType = 3;
+        else if (f->metype == 19)
+            msgType = 4;
+        else
+            return 0;
+        break;
+    default:
+        return 0;
+    }
+    q += sprintf(q, "MSG,%d,1,1,%06X,1,", msgType, (unsigned)(f->addr & 0xFFFFFFu));
+    q = sbs_time(q, mm->sysTimestampMsg, opt->utc_offset_ms, 1);
+    q = sbs_time(q, (opt->flags & MSD_SBS_NOW_IS_RECEIVED) ? mm->sysTimestampMsg : opt->now_ms, opt->utc_offset_ms, 0);
+    if (f->callsign_valid) {
+        char callsign[9];
+        memcpy(callsign, f->callsign, 8);
+        callsign[8] = 0;
+        q += sprintf(q, ",%s", callsign);
+    } else {
+        q += sprintf(q, ",");
+    }
+    if (use_gnss) {
+        if (f->altitude_geom_valid)
+            q += sprintf(q, ",%dH", (int)f->altitude_geom);
+        else if (f->altitude_baro_valid && delta_valid)
+            q += sprintf(q, ",%dH", (int)(int32_t)((uint32_t)f->altitude_baro + (uint32_t)a->geom_delta));
+        else if (f->altitude_baro_valid)
+            q += sprintf(q, ",%d", (int)f->altitude_baro);
+        else
+            q += sprintf(q, ",");
+    } else {
+        if (f->altitude_baro_valid)
+            q += sprintf(q, ",%d", (int)f->altitude_baro);
+        else if (f->altitude_geom_valid && delta_valid)
+            q += sprintf(q, ",%d", (int)(int32_t)((uint32_t)f->altitude_geom - (uint32_t)a->geom_delta));
+        else
+            q += sprintf(q, ",");
+    }
+    /* what no decoder delivers stays empty (modes_hip.h): a ground speed that is negative, NaN or 100000 and more */
+    if ((a->flags & MSD_SBS_GS_VALID) && !signbit(a->gs_selected) && a->gs_selected < 100000.0f)
+        q += sprintf(q, ",%.0f", a->gs_selected);
+    else
+        q += sprintf(q, ",");
+    { /* mm->heading as decodeModesMessage / decodeCommB leave it, in msd_fields_to_float's order */
+        int heading_valid = f->heading_valid, carried = 1;
+        unsigned heading_type = f->heading_type;
+        float heading = 0;
+        if (f->velocity_valid && a->gs_selected > 0) {
+            const int ew_vel = f->ew_vel, ns_vel = f->ns_vel, scale = f->mesub == 2 ? 4 : 1;
+            /* (ew_raw - 1) and (ns_raw - 1) are 0 .. 1022, times 4 for subtype 2 (mode_s.c:823-828) */
+            carried = ew_vel % scale == 0 && ns_vel % scale == 0 && abs(ew_vel) / scale <= 1022 && abs(ns_vel) / scale <= 1022;
+            float ground_track = (float)(atan2(ew_vel, ns_vel) * 180.0 / MSD_POS_PI);
+            if (ground_track < 0)
+                ground_track += 360;
+            heading = ground_track;
+            heading_type = 1; /* HEADING_GROUND_TRACK */
+            heading_valid = 1;
+        }
+        if (carried && f->heading_valid) {
+            if (f->commb_format == 8 || f->commb_format == 9) {
+                heading = (float)((f->heading_raw & 1023u) * 90.0 / 512.0);
+                if (f->heading_raw & 1024u)
+                    heading = (float)(heading + 180.0);
+            } else if (f->metype == 19) {
+                heading = (float)((f->heading_raw & 1023u) * 360.0 / 1024.0); /* the bits the message carries */
+            } else {
+                heading = (float)((f->heading_raw & 127u) * 360.0 / 128.0);
+            }
+        }
+        if (carried && heading_valid && heading_type == 1)
+            q += sprintf(q, ",%.0f", heading);
+        else
+            q += sprintf(q, ",");
+    }
+    if ((a->flags & MSD_SBS_CPR_DECODED) && fabs(a->lat) <= 360.0 && fabs(a->lon) <= 360.0)
+        q += sprintf(q, ",%1.5f,%1.5f", a->lat, a->lon);
+    else
+        q += sprintf(q, ",,");
+    if (use_gnss) {
+        if (f->geom_rate_valid)
+            q += sprintf(q, ",%dH", (int)f->geom_rate);
+        else if (f->baro_rate_valid)
+            q += sprintf(q, ",%d", (int)f->baro_rate);
+        else
+            q += sprintf(q, ",");
+    } else {
+        if (f->baro_rate_valid)
+            q += sprintf(q, ",%d", (int)f->baro_rate);
+        else if (f->geom_rate_valid)
+            q += sprintf(q, ",%d", (int)f->geom_rate);
+        else
+            q += sprintf(q, ",");
+    }
+    if (f->squawk_valid)
+        q += sprintf(q, ",%04x", (unsigned)f->squawk);
+    else
+        q += sprintf(q, ",");
+    if (f->alert_valid)
+        q += sprintf(q, f->alert ? ",-1" : ",0");
+    else
+        q += sprintf(q, ",");
+    if (f->squawk_valid)
+        q += sprintf(q, (f->squawk == 0x7500 || f->squawk == 0x7600 || f->squawk == 0x7700) ? ",-1" : ",0");
+    else
+        q += sprintf(q, ",");
+    if (f->spi_valid)
+        q += sprintf(q, f->spi ? ",-1" : ",0");
+    else
+        q += sprintf(q, ",");
+    switch (f->airground) {
+    case 1: /* AG_GROUND */
+        q += sprintf(q, ",-1");
+        break;
+    case 2: /* AG_AIRBORNE */
+        q += sprintf(q, ",0");
+        break;
+    default:
+        q += sprintf(q, ",");
+        break;
+    }
+    q += sprintf(q, "\r\n");
+    return (size_t)(q - buf);
+}
+
+int msd_pos_host_sbs_wire(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk, size_t n,
+                          const msd_sbs_options *opt, uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends)
+{
+    if (!p || !p->sbs || !out_len || !sbs_options_ok(opt) || n > ((size_t)1 << 24))
+        return -EINVAL;
+    *out_len = 0;
+    if (n == 0)
+        return 0;
+    if (!msgs || !fields || !trk || (!out && cap > 0))
+        return -EINVAL;
+    char line[256];
+    for (int pass = 0; pass < 2; ++pass) { /* the size first: a stream that does not fit leaves out alone */
+        size_t len = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t k = sbs_line(&msgs[i], &fields[i], &trk[i], opt, line);
+            if (pass)
+                memcpy(out + len, line, k);
+            len += k;
             if (pass && ends)
                 ends[i] = (uint32_t)len;
         }

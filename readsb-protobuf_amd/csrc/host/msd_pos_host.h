@@ -36,6 +36,13 @@ int msd_pos_host_update_reduce(msd_pos_host *p, const msd_message *msgs, const m
                                size_t n, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward);
 int msd_pos_host_reduce_wire(msd_pos_host *p, const msd_message *msgs, const uint8_t *forward, size_t n, uint32_t flags,
                              uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
+/* SBS output (modes_hip.h, "SBS output"): msd_pos_sbs_enable, msd_pos_update_sbs and msd_pos_sbs_wire on the host; the
+ * rows from the same walk, the text from snprintf, gmtime_r and the libm -- the yardstick of the device's writer */
+int msd_pos_host_sbs_enable(msd_pos_host *p);
+int msd_pos_host_update_sbs(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
+                            size_t n, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward, msd_sbs_track *trk);
+int msd_pos_host_sbs_wire(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk, size_t n,
+                          const msd_sbs_options *opt, uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
 /* for tests: the MSD_AC_N + 1 timers of one aircraft (the members' in MSD_AC_* order, then the DF11 timer) into out;
  * -ENOENT: no such aircraft */
 int msd_pos_host_reduce_timers(const msd_pos_host *p, uint32_t receiver, uint32_t addr, uint64_t *out);

@@ -21,6 +21,11 @@
  * `--positions --aircraft --beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]` writes readsb's
  * beast_reduce_out to FILE (--net-beast-reduce-out-port, --net-beast-reduce-interval; default 0.125 s, at most 15): the
  * Beast frames of the messages that brought their aircraft something new (msd_pos_update_reduce, msd_pos_reduce_wire).
+ *
+ * `--positions --aircraft --sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]` writes readsb's SBS (BaseStation,
+ * port 30003) output to FILE (msd_pos_update_sbs, msd_pos_sbs_wire): one MSG line per message the tracker knows the
+ * aircraft of.  A replay has no wall clock: fields 9-10 repeat the message's own time (MSD_SBS_NOW_IS_RECEIVED), so the
+ * file is the same on every run.  Works beside --beast-reduce-out.
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -105,6 +110,53 @@ static int reduce_finish(int want_stats)
     return bad;
 }
 
+/* --sbs-out: the records, their fields and their rows wait here until REDUCE_BATCH are together, then go through
+ * msd_pos_sbs_wire in one call */
+static FILE *g_sbs_out;
+static msd_sbs_options g_sbs_opt;
+static msd_message *g_sbs_msgs;
+static msd_fields *g_sbs_fields;
+static msd_sbs_track *g_sbs_rows;
+static uint8_t *g_sbs_bytes;
+static uint32_t *g_sbs_ends;
+static size_t g_sbs_n;
+static uint64_t g_sbs_lines, g_sbs_records, g_sbs_total_bytes;
+static void sbs_flush(void)
+{
+    size_t len = 0;
+    if (!g_sbs_n)
+        return;
+    const int rc = msd_pos_sbs_wire(g_pos, g_sbs_msgs, g_sbs_fields, g_sbs_rows, g_sbs_n, 0, &g_sbs_opt, g_sbs_bytes,
+                                    (size_t)REDUCE_BATCH * MSD_SBS_MAX, &len, g_sbs_ends);
+    if (rc) {
+        fprintf(stderr, "msd_pos_sbs_wire: %s (%d)\n", msd_pos_last_error(g_pos), rc);
+        g_pos_failed = 1;
+    } else {
+        if (fwrite(g_sbs_bytes, 1, len, g_sbs_out) != len)
+            g_pos_failed = 1;
+        for (size_t i = 0; i < g_sbs_n; ++i)
+            g_sbs_lines += g_sbs_ends[i] != (i ? g_sbs_ends[i - 1] : 0u);
+        g_sbs_total_bytes += len;
+    }
+    g_sbs_records += g_sbs_n;
+    g_sbs_n = 0;
+}
+
+/* the rest of the records, the file closed, and with --stats "sbs lines,N,of,M,bytes,B" */
+static int sbs_finish(int want_stats)
+{
+    sbs_flush();
+    const int bad = fclose(g_sbs_out) != 0;
+    if (want_stats)
+        fprintf(stderr, "sbs lines,%" PRIu64 ",of,%" PRIu64 ",bytes,%" PRIu64 "\n", g_sbs_lines, g_sbs_records, g_sbs_total_bytes);
+    free(g_sbs_msgs);
+    free(g_sbs_fields);
+    free(g_sbs_rows);
+    free(g_sbs_bytes);
+    free(g_sbs_ends);
+    return bad;
+}
+
 static void print_raw_positions(const msd_message *mm, void *user)
 {
     FILE *out = user;
@@ -134,8 +186,17 @@ static void print_raw_positions(const msd_message *mm, void *user)
     if (mm->msgtype != 32 && f.addr != 0)
         g_last_tracked_ms = tm.sysTimestampMsg;
     uint8_t forward = 0;
-    const int rc = g_reduce_out ? msd_pos_update_reduce(g_pos, &tm, &f, NULL, 1, 0, &p, NULL, &forward)
-                                : msd_pos_update(g_pos, &tm, &f, NULL, 1, 0, &p);
+    msd_sbs_track row;
+    const int rc = g_sbs_out      ? msd_pos_update_sbs(g_pos, &tm, &f, NULL, 1, 0, &p, NULL, g_reduce_out ? &forward : NULL, &row)
+                   : g_reduce_out ? msd_pos_update_reduce(g_pos, &tm, &f, NULL, 1, 0, &p, NULL, &forward)
+                                  : msd_pos_update(g_pos, &tm, &f, NULL, 1, 0, &p);
+    if (g_sbs_out && !rc) { /* the line carries the time the tracker saw */
+        g_sbs_msgs[g_sbs_n] = tm;
+        g_sbs_fields[g_sbs_n] = f;
+        g_sbs_rows[g_sbs_n] = row;
+        if (++g_sbs_n == REDUCE_BATCH)
+            sbs_flush();
+    }
     if (g_reduce_out && !rc) {
         g_reduce_msgs[g_reduce_n] = *mm;
         g_reduce_forward[g_reduce_n] = forward;
@@ -353,7 +414,9 @@ int main(int argc, char **argv)
     size_t beast_chunk = 65536, avr_chunk = 65536;
     uint64_t now_ms = 0;
     int want_positions = 0, want_aircraft = 0, other_sink = 0, net_only = 0;
-    const char *reduce_path = NULL;
+    const char *reduce_path = NULL, *sbs_path = NULL;
+    int gnss = 0;
+    double utc_offset_s = 0;
     double reduce_interval_s = 0.125; /* readsb.c: net_output_beast_reduce_interval = 125 */
     msd_pos_receiver home; /* --lat / --lon / --max-range as readsb spells them (readsb.c: Modes.receiver, Modes.maxRange) */
     memset(&home, 0, sizeof home);
@@ -387,6 +450,9 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--beast-reduce-out") && next) { reduce_path = next; ++i; }
         else if (!strcmp(a, "--beast-reduce-interval") && next) { reduce_interval_s = atof(next); ++i; }
         else if (!strcmp(a, "--net-only")) net_only = 1; /* readsb.c: Modes.net_only */
+        else if (!strcmp(a, "--sbs-out") && next) { sbs_path = next; ++i; }
+        else if (!strcmp(a, "--gnss")) gnss = 1; /* readsb.c: Modes.use_gnss */
+        else if (!strcmp(a, "--utc-offset") && next) { utc_offset_s = atof(next); ++i; }
         else if (!strcmp(a, "--clock-start-ms") && next) { g_clock_start_ms = strtoull(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--lat") && next) { home.lat = atof(next); have_lat = 1; ++i; }
         else if (!strcmp(a, "--lon") && next) { home.lon = atof(next); have_lon = 1; ++i; }
@@ -413,7 +479,8 @@ int main(int argc, char **argv)
             fprintf(stderr, "usage: msd_replay --ifile F [--iformat uc8|sc16|sc16q11] [--fix|--no-fix|--aggressive] [--dcfilter] "
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
                             "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft [--match-modeac] "
-                            "[--beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]]] [--clock-start-ms N]]\n"
+                            "[--beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]] "
+                            "[--sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]]] [--clock-start-ms N]]\n"
                             "       --positions: the --raw lines, with \"lat,lon\" behind the ';' of every message from which readsb's tracker\n"
                             "       would have decoded a position (CPR global and local, its range and speed checks; the coordinates are exact, the\n"
                             "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
@@ -428,6 +495,9 @@ int main(int argc, char **argv)
                             "       --beast-reduce-out FILE (with --aircraft): readsb's reduced Beast output to FILE -- the frames of the messages\n"
                             "       that brought their aircraft something new, at most once per --beast-reduce-interval (seconds, default 0.125, at\n"
                             "       most 15) and member; a first message only with --net-only or --net-verbatim.\n"
+                            "       --sbs-out FILE (with --aircraft): readsb's SBS (BaseStation) output to FILE, one MSG line per message of a\n"
+                            "       tracked aircraft; --gnss: geometric altitudes and rates first, marked H; --utc-offset: the zone the dates\n"
+                            "       are written in, seconds east of UTC (default 0, at most a day); the \"now\" of fields 9-10 is the message's own time.\n"
                             "       msd_replay --beast-in F [--beast-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
                             "[--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--device N]\n"
                             "       msd_replay --avr-in F [--avr-chunk BYTES] [--now-ms N] [--fix|--no-fix|--aggressive] [--modeac] [--mlat] "
@@ -445,6 +515,14 @@ int main(int argc, char **argv)
     }
     if (reduce_path && !want_aircraft) {
         fprintf(stderr, "--beast-reduce-out goes with --positions --aircraft\n");
+        return 2;
+    }
+    if (sbs_path && !want_aircraft) {
+        fprintf(stderr, "--sbs-out goes with --positions --aircraft\n");
+        return 2;
+    }
+    if (!(utc_offset_s >= -86400.0 && utc_offset_s <= 86400.0)) {
+        fprintf(stderr, "--utc-offset is at most a day either way\n");
         return 2;
     }
     if (want_positions) {
@@ -491,6 +569,24 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        if (sbs_path) {
+            g_sbs_opt.utc_offset_ms = (int64_t)(utc_offset_s * 1000.0 + (utc_offset_s < 0 ? -0.5 : 0.5));
+            /* fields 9-10 repeat the message's time; now_ms is not printed and only has to be in range with the offset */
+            g_sbs_opt.now_ms = g_sbs_opt.utc_offset_ms < 0 ? (uint64_t)-g_sbs_opt.utc_offset_ms : 0u;
+            g_sbs_opt.flags = MSD_SBS_NOW_IS_RECEIVED | (g_net_verbatim ? MSD_WIRE_VERBATIM : 0u) | (net_only ? MSD_SBS_NET_ONLY : 0u) |
+                              (gnss ? MSD_SBS_GNSS : 0u);
+            g_sbs_msgs = malloc(REDUCE_BATCH * sizeof *g_sbs_msgs);
+            g_sbs_fields = malloc(REDUCE_BATCH * sizeof *g_sbs_fields);
+            g_sbs_rows = malloc(REDUCE_BATCH * sizeof *g_sbs_rows);
+            g_sbs_bytes = malloc((size_t)REDUCE_BATCH * MSD_SBS_MAX);
+            g_sbs_ends = malloc(REDUCE_BATCH * sizeof *g_sbs_ends);
+            const int erc = msd_pos_sbs_enable(g_pos);
+            if (erc || !g_sbs_msgs || !g_sbs_fields || !g_sbs_rows || !g_sbs_bytes || !g_sbs_ends || !(g_sbs_out = fopen(sbs_path, "wb"))) {
+                fprintf(stderr, "--sbs-out %s: %s\n", sbs_path, erc ? msd_pos_last_error(g_pos) : "cannot open, or out of memory");
+                msd_pos_destroy(g_pos);
+                return 1;
+            }
+        }
         rx.sink = print_raw_positions;
     }
     if (avr_in || beast_in) {
@@ -499,6 +595,8 @@ int main(int argc, char **argv)
         if (want_aircraft && !rc && (print_aircraft(stdout) || (g_match_modeac && print_modeac(stdout))))
             g_pos_failed = 1;
         if (g_reduce_out && reduce_finish(want_stats))
+            g_pos_failed = 1;
+        if (g_sbs_out && sbs_finish(want_stats))
             g_pos_failed = 1;
         msd_pos_destroy(g_pos);
         return rc ? rc : g_pos_failed;
@@ -545,6 +643,8 @@ int main(int argc, char **argv)
     if (want_aircraft && (print_aircraft(stdout) || (g_match_modeac && print_modeac(stdout))))
         g_pos_failed = 1;
     if (g_reduce_out && reduce_finish(want_stats))
+        g_pos_failed = 1;
+    if (g_sbs_out && sbs_finish(want_stats))
         g_pos_failed = 1;
     msd_pos_destroy(g_pos);
     return g_pos_failed ? 1 : 0;

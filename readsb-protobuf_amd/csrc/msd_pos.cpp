@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "msd_pos.h"
+#include "msd_sbs_impl.h"
 
 struct msd_pos {
     int device = 0;
@@ -52,6 +53,13 @@ struct msd_pos {
     msd_message *d_w_msgs = nullptr;
     uint8_t *d_w_forward = nullptr, *d_w_lens = nullptr, *d_w_out = nullptr;
     uint32_t *d_w_block = nullptr, *d_w_ends = nullptr;
+    /* SBS output (msd_pos_sbs_enable): the ground-track table, the row per record of a call, and the writer's buffers --
+     * records, fields and rows that came from the host; lengths, offsets, ends and the stream are the reduced writer's */
+    uint16_t *d_track_table = nullptr;
+    msd_sbs_track *d_sbs = nullptr, *d_s_trk = nullptr;
+    size_t cap_sbs = 0, cap_s_in = 0;
+    msd_message *d_s_msgs = nullptr;
+    msd_fields *d_s_fields = nullptr;
     char err[256] = "";
 };
 
@@ -99,7 +107,7 @@ template <typename T> void release(T *&ptr)
 }
 
 /* room for a call of n records (and for its inputs, when they come from the host) */
-int reserve(msd_pos *p, size_t n, bool host_input)
+int reserve(msd_pos *p, size_t n, bool host_input, bool want_sbs)
 {
     if (n > p->cap_n) {
         release(p->d_slot), release(p->d_fresh), release(p->d_out), release(p->d_idx[0]), release(p->d_idx[1]), release(p->d_hist);
@@ -122,6 +130,12 @@ int reserve(msd_pos *p, size_t n, bool host_input)
         p->cap_forward = 0;
         POS_HIP(p, hipMalloc(&p->d_forward, n));
         p->cap_forward = n;
+    }
+    if (want_sbs && n > p->cap_sbs) {
+        release(p->d_sbs);
+        p->cap_sbs = 0;
+        POS_HIP(p, hipMalloc(&p->d_sbs, n * sizeof(msd_sbs_track)));
+        p->cap_sbs = n;
     }
     if (host_input && n > p->cap_in) {
         release(p->d_msgs), release(p->d_fields), release(p->d_receiver);
@@ -225,6 +239,7 @@ void msd_pos_destroy(msd_pos *p)
             release(p->tab[k].next_reduce);
     release(p->d_forward), release(p->d_w_msgs), release(p->d_w_forward), release(p->d_w_lens), release(p->d_w_out);
     release(p->d_w_block), release(p->d_w_ends);
+    release(p->d_track_table), release(p->d_sbs), release(p->d_s_trk), release(p->d_s_msgs), release(p->d_s_fields);
     release(p->d_ac), release(p->d_c_to_a), release(p->d_codes), release(p->d_hits_out);
     release(p->d_nicrc), release(p->s_idx[0]), release(p->s_idx[1]), release(p->s_hist), release(p->d_snap);
     release(p->d_rx), release(p->d_stats), release(p->d_ctl), release(p->d_slot), release(p->d_fresh), release(p->d_out);
@@ -262,20 +277,22 @@ int msd_pos_set_receiver(msd_pos *p, uint32_t receiver, const msd_pos_receiver *
 }
 
 static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
-                  int on_device, msd_position *out, msd_pos_nicrc *nicrc, bool want_nicrc, uint8_t *forward, bool want_forward)
+                  int on_device, msd_position *out, msd_pos_nicrc *nicrc, bool want_nicrc, uint8_t *forward, bool want_forward,
+                  msd_sbs_track *trk = nullptr, bool want_sbs = false)
 {
-    if (!p || (want_nicrc && !p->table) || (want_forward && !p->reduce))
+    if (!p || (want_nicrc && !p->table) || (want_forward && !p->reduce) || (want_sbs && !p->d_track_table))
         return -EINVAL;
     if (n == 0)
         return 0;
-    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || (want_forward && !forward) || n > MSD_POS_MAX_N)
+    if (!msgs || !fields || !out || (want_nicrc && !nicrc) || (want_forward && !forward) || (want_sbs && !trk) ||
+        n > MSD_POS_MAX_N)
         return -EINVAL;
     if (!on_device && receiver)
         for (size_t i = 0; i < n; ++i)
             if (receiver[i] >= p->nrx)
                 return -EINVAL;
     POS_HIP(p, hipSetDevice(p->device));
-    const int rc = reserve(p, n, !on_device);
+    const int rc = reserve(p, n, !on_device, want_sbs);
     if (rc)
         return rc;
     if (!on_device) {
@@ -311,11 +328,13 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
         POS_HIP(p, hipMemsetAsync(p->d_nicrc, 0, n * sizeof(msd_pos_nicrc), p->stream));
     if (p->reduce) /* and its verdict */
         POS_HIP(p, hipMemsetAsync(p->d_forward, 0, n, p->stream));
+    if (want_sbs) /* and its row; no other call makes rows */
+        POS_HIP(p, hipMemsetAsync(p->d_sbs, 0, n * sizeof(msd_sbs_track), p->stream));
     for (size_t base = 0; base < n; base += MSD_POS_PIECE) {
         const size_t m = n - base < MSD_POS_PIECE ? n - base : MSD_POS_PIECE;
         msd_pos_launch_piece(p->stream, t, msgs, fields, receiver, p->d_rx, p->fp, (uint32_t)base, (uint32_t)m, p->d_slot,
                              p->d_idx[0], p->d_idx[1], p->d_hist, p->d_out, p->d_stats, p->d_nicrc, p->reduce_interval,
-                             p->d_forward);
+                             p->d_forward, want_sbs ? p->d_sbs : nullptr);
         POS_HIP(p, hipGetLastError());
     }
     POS_HIP(p, hipMemcpyAsync(out, p->d_out, n * sizeof(msd_position), hipMemcpyDeviceToHost, p->stream));
@@ -324,6 +343,9 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
     if (want_forward)
         POS_HIP(p, hipMemcpyAsync(forward, p->d_forward, n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                                   p->stream));
+    if (want_sbs)
+        POS_HIP(p, hipMemcpyAsync(trk, p->d_sbs, n * sizeof(msd_sbs_track),
+                                  on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -344,6 +366,107 @@ int msd_pos_update_reduce(msd_pos *p, const msd_message *msgs, const msd_fields 
                           int on_device, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward)
 {
     return update(p, msgs, fields, receiver, n, on_device, out, nicrc, nicrc != nullptr, forward, true);
+}
+
+int msd_pos_update_sbs(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
+                       int on_device, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward, msd_sbs_track *trk)
+{
+    return update(p, msgs, fields, receiver, n, on_device, out, nicrc, nicrc != nullptr, forward, forward != nullptr, trk, true);
+}
+
+int msd_pos_sbs_enable(msd_pos *p)
+{
+    if (!p || !p->table)
+        return -EINVAL;
+    if (p->d_track_table)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    std::vector<uint16_t> table;
+    try {
+        table.resize(MSD_SBS_TRACK_ENTRIES);
+    } catch (const std::bad_alloc &) {
+        return -ENOMEM;
+    }
+    msd_sbs_build_track_table(table.data());
+    uint16_t *d_table = nullptr;
+    const auto build = [&]() -> int {
+        POS_HIP(p, hipMalloc(&d_table, sizeof(uint16_t) * MSD_SBS_TRACK_ENTRIES));
+        POS_HIP(p, hipMemcpyAsync(d_table, table.data(), sizeof(uint16_t) * MSD_SBS_TRACK_ENTRIES, hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipStreamSynchronize(p->stream));
+        return 0;
+    };
+    const int rc = build();
+    if (rc) { /* the tracker stays as it was */
+        (void)hipGetLastError();
+        release(d_table);
+        return rc;
+    }
+    p->d_track_table = d_table; /* the rows' buffer grows with the calls, as the verdicts' does */
+    return 0;
+}
+
+int msd_pos_sbs_wire(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk, size_t n,
+                     int on_device, const msd_sbs_options *opt, uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends)
+{
+    if (!p || !p->d_track_table || !out_len || !msd_sbs_options_ok(opt) || n > MSD_POS_MAX_N)
+        return -EINVAL;
+    *out_len = 0;
+    if (n == 0)
+        return 0;
+    if (!msgs || !fields || !trk || (!out && cap > 0))
+        return -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    const uint32_t nblocks = (uint32_t)((n + 255u) / 256u);
+    if (n > p->cap_w) {
+        release(p->d_w_lens), release(p->d_w_block), release(p->d_w_ends);
+        p->cap_w = 0;
+        POS_HIP(p, hipMalloc(&p->d_w_lens, n));
+        POS_HIP(p, hipMalloc(&p->d_w_block, sizeof(uint32_t) * (nblocks + 1u)));
+        POS_HIP(p, hipMalloc(&p->d_w_ends, sizeof(uint32_t) * n));
+        p->cap_w = n;
+    }
+    if (!on_device) {
+        if (n > p->cap_s_in) {
+            release(p->d_s_msgs), release(p->d_s_fields), release(p->d_s_trk);
+            p->cap_s_in = 0;
+            POS_HIP(p, hipMalloc(&p->d_s_msgs, n * sizeof(msd_message)));
+            POS_HIP(p, hipMalloc(&p->d_s_fields, n * sizeof(msd_fields)));
+            POS_HIP(p, hipMalloc(&p->d_s_trk, n * sizeof(msd_sbs_track)));
+            p->cap_s_in = n;
+        }
+        POS_HIP(p, hipMemcpyAsync(p->d_s_msgs, msgs, n * sizeof(msd_message), hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipMemcpyAsync(p->d_s_fields, fields, n * sizeof(msd_fields), hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipMemcpyAsync(p->d_s_trk, trk, n * sizeof(msd_sbs_track), hipMemcpyHostToDevice, p->stream));
+        msgs = p->d_s_msgs;
+        fields = p->d_s_fields;
+        trk = p->d_s_trk;
+    }
+    msd_sbs_launch_lengths(p->stream, msgs, fields, trk, (uint32_t)n, *opt, p->d_track_table, p->d_w_lens, p->d_w_block);
+    POS_HIP(p, hipGetLastError());
+    uint32_t need = 0; /* at most 2^24 * 147 */
+    POS_HIP(p, hipMemcpyAsync(&need, p->d_w_block + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    *out_len = need;
+    if (need > cap) {
+        snprintf(p->err, sizeof p->err, "the SBS stream takes %u bytes, %zu were offered", need, cap);
+        return -ENOSPC;
+    }
+    if (need > p->cap_w_out) {
+        release(p->d_w_out);
+        p->cap_w_out = 0;
+        POS_HIP(p, hipMalloc(&p->d_w_out, need));
+        p->cap_w_out = need;
+    }
+    /* (with need == 0 the store kernel still runs: it writes the ends and no byte of the stream) */
+    msd_sbs_launch_store(p->stream, msgs, fields, trk, (uint32_t)n, *opt, p->d_track_table, p->d_w_lens, p->d_w_block, p->d_w_out,
+                         p->d_w_ends);
+    POS_HIP(p, hipGetLastError());
+    if (need)
+        POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
+    if (ends)
+        POS_HIP(p, hipMemcpyAsync(ends, p->d_w_ends, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
 }
 
 int msd_pos_reduce_enable(msd_pos *p, uint32_t interval_ms)

@@ -34,12 +34,13 @@ void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t
 /* steps 2 to 4 for records base .. base + n (n <= MSD_POS_PIECE): idx_a / idx_b hold n words each, hist
  * 256 * ceil(n / MSD_POS_TILE) words.  With t.trk, step 5: the table walk over the same grouped order, which reads the
  * out[] of step 3 and writes nicrc[] (n entries from base).  With t.next_reduce, the reduce instantiations of both walks:
- * forward[] (as out[], zeroed by the caller) gets every walked record's verdict byte, reduce_interval is in ms */
+ * forward[] (as out[], zeroed by the caller) gets every walked record's verdict byte, reduce_interval is in ms.  With sbs
+ * (as out[], zeroed by the caller; a table tracker), the SBS instantiations: every walked record's row */
 void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
                           const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
                           uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
                           msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc, uint32_t reduce_interval,
-                          uint8_t *forward);
+                          uint8_t *forward, msd_sbs_track *sbs);
 /* expiry: marks and counts the aircraft to remove (ctl[MSD_POS_CTL_REMOVED]); rebuild inserts the others into `to` */
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl);
 void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_table to);
@@ -66,5 +67,12 @@ void msd_reduce_launch_lengths(hipStream_t stream, const msd_message *msgs, cons
                                uint8_t *lens, uint32_t *block_sums);
 void msd_reduce_launch_store(hipStream_t stream, const msd_message *msgs, uint32_t n, uint32_t flags, const uint8_t *lens,
                              const uint32_t *block_off, uint8_t *out, uint32_t *ends);
+/* SBS output (msd_sbs_kernels.hip): the lines of the records that pass the delivery conditions, dense and in record
+ * order; lengths and store as the reduced output's.  track_table: msd_sbs_build_track_table's entries in device memory */
+void msd_sbs_launch_lengths(hipStream_t stream, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk,
+                            uint32_t n, msd_sbs_options opt, const uint16_t *track_table, uint8_t *lens, uint32_t *block_sums);
+void msd_sbs_launch_store(hipStream_t stream, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk,
+                          uint32_t n, msd_sbs_options opt, const uint16_t *track_table, const uint8_t *lens,
+                          const uint32_t *block_off, uint8_t *out, uint32_t *ends);
 
 #endif

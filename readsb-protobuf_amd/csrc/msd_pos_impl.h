@@ -7,7 +7,7 @@
  *   the assignment of a->meta.lat/lon, the part of trackUpdateFromMessage that reaches them -- seen / messages
  *   :1024-1025, the per-source versions :1032-1075, the gs / ias / tas stores :1222-1235, the CPR stores :1313-1329,
  *   :1381-1383 -- and the part of trackRemoveStaleAircraft :1494-1570 that concerns these members.
- * Not here: geomag_calc, update_polar_range, SBS and MLAT input.  NIC / Rc and the other members of struct aircraft are
+ * Not here: geomag_calc, update_polar_range, SBS and MLAT input (the SBS output's text is msd_sbs_impl.h).  NIC / Rc and the other members of struct aircraft are
  * msd_trk_impl.h's, for a tracker with the aircraft table.
  *
  * Every validity of the six kept members has stale_interval 60 s and expire_interval 70 s (track.c:113-115,132-134), so
@@ -54,6 +54,8 @@ typedef struct msd_pos_acc {
     uint64_t c[MSD_PC_N];
     double margin;
     uint32_t accepted; /* bit MSD_PV_x: accept_data took member x; only ever set here, whoever reads it clears it per record */
+    uint32_t gs_valid; /* of the record fed last: mm->gs_valid and mm->gs.selected as :1223 leaves it (0 when not valid), */
+    float gs_selected; /* for the SBS row (modes_hip.h "SBS output"); nobody else reads them */
 } msd_pos_acc;
 
 MSD_HD uint64_t msd_pos_key(uint32_t receiver, uint32_t addr)
@@ -375,6 +377,8 @@ MSD_HD void msd_pos_feed(msd_pos_aircraft *a, const msd_pos_receiver *rx, int fi
     out->result = MSD_POS_NOT_TRIED;
     a->seen = now;
     a->messages++;
+    acc->gs_valid = 0;
+    acc->gs_selected = 0;
 
     /* the version of this message's source (:1032-1075); -1 for everything that is not ADS-B, TIS-B or ADS-R */
     const int vi = source == 7 ? 0 : source == 5 ? 1 : source == 6 ? 2 : -1;
@@ -390,6 +394,8 @@ MSD_HD void msd_pos_feed(msd_pos_aircraft *a, const msd_pos_receiver *rx, int fi
     const int gs_valid = msd_pos_record_gs(f, &v0, &v2);
     if (gs_valid) { /* :1222-1227 */
         gs_selected = version == 2 ? v2 : v0;
+        acc->gs_selected = gs_selected;
+        acc->gs_valid = 1;
         if (msd_pos_accept(a, MSD_PV_GS, source, now)) {
             acc->accepted |= 1u << MSD_PV_GS;
             a->gs = (uint32_t)gs_selected;

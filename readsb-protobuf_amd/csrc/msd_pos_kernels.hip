@@ -22,6 +22,9 @@
  * A tracker that reduces (modes_hip.h "Reduced Beast output") runs the reduce instantiations of the two walks: step 3
  * leaves one byte per record for step 5, which keeps the aircraft's timers and leaves the record's verdict in its place.
  * The compacting Beast writer is msd_reduce_kernels.hip.
+ * msd_pos_update_sbs (modes_hip.h "SBS output") runs the SBS instantiations of the two walks, which leave one row per
+ * record: step 3 everything it knows, step 5 the aircraft's geometric delta.  No other call runs them.  The text writer
+ * is msd_sbs_kernels.hip.
  * Wave64 throughout: ballots are 64 bits wide and a workgroup of 256 threads is four waves.  The walk is double
  * precision arithmetic with long dependent chains and divergent branches per aircraft; its rate comes from the number of
  * aircraft in flight, not from the vector width.
@@ -212,12 +215,14 @@ msd_pos_scatter_kernel(const uint32_t *idx_in, Digit digit, uint32_t n, const ui
 
 /* step 3 and 4: the lane at the head of an aircraft's run walks it.  REDUCE: the tracker reduces, and the walk leaves in
  * forward[i] what the table walk's rule needs of this one: the members msd_pos_feed accepted and whether the aircraft has
- * been seen twice; a tracker that does not runs the instantiation without it. */
-template <bool REDUCE>
+ * been seen twice; a tracker that does not runs the instantiation without it.  SBS: the call is msd_pos_update_sbs, and
+ * the walk leaves the record's row in sbs[i] -- all of it but the geometric delta, which the table walk adds; every other
+ * call runs the instantiation without it. */
+template <bool REDUCE, bool SBS>
 __global__ void __launch_bounds__(NT)
 msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                     const msd_pos_receiver *rx, int filter_persistence, uint32_t base, uint32_t n, const uint32_t *slot,
-                    const uint32_t *idx, msd_position *out, unsigned long long *dstats, uint8_t *forward)
+                    const uint32_t *idx, msd_position *out, unsigned long long *dstats, uint8_t *forward, msd_sbs_track *sbs)
 {
     const uint32_t j = blockIdx.x * NT + threadIdx.x;
     if (j >= n)
@@ -241,6 +246,11 @@ msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
         out[i] = o;
         if (REDUCE)
             forward[i] = (uint8_t)(acc.accepted | (a.messages > 1 ? MSD_REDUCE_WALK_SEEN_TWICE : 0u));
+        if (SBS) {
+            msd_sbs_track row;
+            msd_pos_sbs(&o, &acc, a.messages, &row);
+            sbs[i] = row;
+        }
     }
     t.st[s] = a;
     for (int c = 0; c < MSD_PC_N; ++c)
@@ -256,11 +266,11 @@ msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
  * the aircraft's hit bytes; a tracker that does not runs the instantiation without them.  REDUCE: the tracker reduces;
  * the walk applies accept_data's reduce_forward half to the aircraft's timers and turns forward[i] from what the position
  * walk left there into the record's verdict (MSD_REDUCE_FORWARD, MSD_REDUCE_SEEN_TWICE). */
-template <bool HITS, bool REDUCE>
+template <bool HITS, bool REDUCE, bool SBS>
 __global__ void __launch_bounds__(NT)
 msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, uint32_t base, uint32_t n,
                     const uint32_t *slot, const uint32_t *idx, const msd_position *out, msd_pos_nicrc *nicrc,
-                    uint32_t reduce_interval, uint8_t *forward)
+                    uint32_t reduce_interval, uint8_t *forward, msd_sbs_track *sbs)
 {
     const uint32_t j = blockIdx.x * NT + threadIdx.x;
     if (j >= n)
@@ -287,6 +297,11 @@ msd_trk_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
             (void)msd_trk_feed(a, m.sysTimestampMsg, &m, &f, &o, &q, hits, nullptr, 0u, 0u);
         }
         nicrc[i] = q;
+        if (SBS) { /* the row the position walk left: the aircraft's geometric delta after this record */
+            msd_sbs_track row = sbs[i];
+            msd_trk_sbs(a, m.sysTimestampMsg, &row);
+            sbs[i] = row;
+        }
     }
 }
 
@@ -468,11 +483,39 @@ void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t
     msd_pos_rollback_kernel<<<blocks(n), NT, 0, stream>>>(t, slot, fresh, n);
 }
 
+/* steps 3 to 5 over the grouped order `in` */
+template <bool SBS>
+static void walks(hipStream_t stream, uint32_t tiles, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
+                  const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base, uint32_t n,
+                  const uint32_t *slot, const uint32_t *in, msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc,
+                  uint32_t reduce_interval, uint8_t *forward, msd_sbs_track *sbs)
+{
+    if (t.next_reduce) { /* (a table tracker: msd_pos_reduce_enable refuses any other) */
+        msd_pos_walk_kernel<true, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot,
+                                                                 in, out, dstats, forward, sbs);
+        if (t.hits)
+            msd_trk_walk_kernel<true, true, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc,
+                                                                           reduce_interval, forward, sbs);
+        else
+            msd_trk_walk_kernel<false, true, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc,
+                                                                            reduce_interval, forward, sbs);
+        return;
+    }
+    msd_pos_walk_kernel<false, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in,
+                                                              out, dstats, nullptr, sbs);
+    if (t.trk && t.hits)
+        msd_trk_walk_kernel<true, false, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc, 0u, nullptr,
+                                                                        sbs);
+    else if (t.trk)
+        msd_trk_walk_kernel<false, false, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc, 0u,
+                                                                         nullptr, sbs);
+}
+
 void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
                           const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
                           uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
                           msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc, uint32_t reduce_interval,
-                          uint8_t *forward)
+                          uint8_t *forward, msd_sbs_track *sbs)
 {
     const uint32_t tiles = blocks(n);
     /* slots run from 0 to cap inclusive (cap = skipped) */
@@ -487,23 +530,12 @@ void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message
         in = bufs[w];
         w ^= 1;
     }
-    if (t.next_reduce) { /* (a table tracker: msd_pos_reduce_enable refuses any other) */
-        msd_pos_walk_kernel<true><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in,
-                                                            out, dstats, forward);
-        if (t.hits)
-            msd_trk_walk_kernel<true, true><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc,
-                                                                      reduce_interval, forward);
-        else
-            msd_trk_walk_kernel<false, true><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc,
-                                                                       reduce_interval, forward);
-        return;
-    }
-    msd_pos_walk_kernel<false><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in,
-                                                         out, dstats, nullptr);
-    if (t.trk && t.hits)
-        msd_trk_walk_kernel<true, false><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc, 0u, nullptr);
-    else if (t.trk)
-        msd_trk_walk_kernel<false, false><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc, 0u, nullptr);
+    if (sbs) /* msd_pos_update_sbs: the instantiations that leave the rows (a table tracker: msd_pos_sbs_enable refuses any other) */
+        walks<true>(stream, tiles, t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out, dstats, nicrc,
+                    reduce_interval, forward, sbs);
+    else
+        walks<false>(stream, tiles, t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out, dstats, nicrc,
+                     reduce_interval, forward, nullptr);
 }
 
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl)

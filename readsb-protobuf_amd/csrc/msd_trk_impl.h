@@ -8,7 +8,8 @@
  *   msd_pos_feed does (seen / messages, gs / ias / tas, the CPR halves and updatePosition), the NIC / Rc of doGlobalCPR
  *   :378-379 and doLocalCPR :458-473 with updatePosition's stores :667-674, and trackRemoveStaleAircraft's EXPIRE list
  *   :1520-1563 for these members.
- * Not here: FATSV state, geomag_calc, update_polar_range, SBS and MLAT input.
+ * Not here: FATSV state, geomag_calc, update_polar_range, SBS and MLAT input.  The SBS output takes the aircraft's
+ * geom_delta and its validity from the entry after a record's feed (msd_trk_sbs below); its text is msd_sbs_impl.h.
  * trackMatchAC is msd_modeac_impl.h; of modeA_hit / modeC_hit this file has the two resets (:1096-1102, :1154-1156).
  *
  * The entry is the public msd_aircraft (modes_hip.h); its head -- receiver .. pos_reliable_even -- and the validities
@@ -582,6 +583,27 @@ MSD_HD int msd_trk_feed(msd_trk_aircraft *a, uint64_t now, const msd_message *m,
         r->forward = 1;
     }
     return r ? red.forward : 0;
+}
+
+/* The SBS row of a record (modes_hip.h "SBS output"), in two halves as the record is fed in two: what the position feed
+ * knows -- acc is msd_pos_feed's after this record, messages the aircraft's -- and what the table entry holds after
+ * msd_trk_feed. */
+MSD_HD void msd_pos_sbs(const msd_position *pos, const msd_pos_acc *acc, uint64_t messages, msd_sbs_track *row)
+{
+    const msd_sbs_track z = {0};
+    *row = z;
+    row->flags = (uint8_t)(MSD_SBS_TRACKED | (messages > 1 ? MSD_SBS_SEEN_TWICE : 0u) | (acc->gs_valid ? MSD_SBS_GS_VALID : 0u) |
+                           (pos->decoded ? MSD_SBS_CPR_DECODED : 0u));
+    row->lat = pos->lat;
+    row->lon = pos->lon;
+    row->gs_selected = acc->gs_selected;
+}
+
+MSD_HD void msd_trk_sbs(const msd_trk_aircraft *a, uint64_t now, msd_sbs_track *row)
+{
+    row->geom_delta = a->geom_delta;
+    if (msd_trk_valid(a, MSD_AC_GEOM_DELTA, now))
+        row->flags |= MSD_SBS_GEOM_DELTA_VALID;
 }
 
 /* trackRemoveStaleAircraft's EXPIRE list for an aircraft that stays (:1520-1563).  No line for nac_v, emergency, alert
