@@ -849,7 +849,8 @@ int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, co
  * receiver index also selects the receiver location and --max-range its checks use.  The other members of struct
  * aircraft, with decoded_nic / decoded_rc, are kept by a tracker made with msd_pos_create_table ("the aircraft table"
  * below); a table tracker can also match the Mode A/C replies against its aircraft ("Mode A/C matching" below) and thin
- * the feed to readsb's reduced Beast output ("Reduced Beast output" below) and write the SBS output ("SBS output" below).
+ * the feed to readsb's reduced Beast output ("Reduced Beast output" below), write the SBS output ("SBS output" below) and
+ * write aircraft.pb, the AircraftsUpdate protobuf, from the table ("aircraft.pb" below).
  * Not built: the declination, the polar range, SBS input and MLAT positions.
  *
  * What is exact.  The coordinates: double + - * / floor fmod in the reference's order, nothing contracted; delivered
@@ -1170,6 +1171,83 @@ typedef struct msd_sbs_options { uint64_t now_ms; int64_t utc_offset_ms; uint32_
  * or at or beyond 253402300800000 (year 10000; checked with MSD_SBS_NOW_IS_RECEIVED too).  n == 0: 0 and *out_len = 0. */
 int msd_pos_sbs_wire(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk, size_t n,
                      int on_device, const msd_sbs_options *opt, uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
+
+/* ---- aircraft.pb: the file readsb-protobuf is named after -- the AircraftsUpdate message of readsb.proto that
+ * generateAircraftProtoBuf (net_io.c:1977-2080) packs from the aircraft list once per second -- for a table tracker, one
+ * file per receiver index, written on the device from the table.  The one output that is per table, not
+ * per message.
+ *
+ * A file.  Content and order are protobuf-c 1.3's aircrafts_update__pack: fields in ascending field number; a scalar is
+ * omitted when zero (a float or double when 0 == value: -0.0 is omitted, NaN is written), a string when empty, a
+ * sub-message when its pointer is NULL; a sub-message whose pointer is set is written even when empty (tag, length 0);
+ * int32 and enums are sign-extended to 10-byte varints when negative.  `now` (1) = now_ms / 1000, `messages` (2), then
+ * one `aircraft` (15) entry -- tag 0x7A, a varint length, the AircraftMeta body -- per selected aircraft; `history` (14)
+ * is empty in this file.  With now_ms < 1000 and messages 0 a file without aircraft is zero bytes.
+ * Selection (net_io.c:2011): an aircraft is written unless messages < 2 or now_ms > seen + 90000, in integers; one seen
+ * after now_ms is written.
+ * Order: ascending address within a receiver, msd_pos_snapshot's.  The reference walks its hash buckets; the order of a
+ * repeated field means nothing to a reader.  This is the one deliberate difference in layout.
+ * The body.  Integers are the entry's stored values whether or not their validity has expired (the reference never clears
+ * meta): addr, squawk, category, alt_baro, ias, lat / lon, messages, seen, air_ground, alt_geom, baro_rate, geom_rate, gs,
+ * tas, nav_altitude_mcp / fms, nic, rc, nic_baro, nac_p, nac_v, sil, alert, spi, gva, sda, addr_type, emergency, sil_type;
+ * version = adsb_version when >= 0, else 0.  mag_heading, true_heading, track and nav_heading are the C conversion to
+ * int32_t of msd_aircraft_to_float's floats; the ground track of a velocity comes out of a table that msd_pos_pb_enable
+ * computes with the host's libm for every pair a message can carry (a pair none can carry writes 0).  mach, track_rate,
+ * roll and nav_qnh are msd_aircraft_to_float's expressions, IEEE operations the device evaluates identically.
+ * rssi = (float)(10 * log10((signal_level[0] + ... + [7] + 1e-5) / 8)), summed in that order in double (net_io.c:2052):
+ * the one libm call, the device library's on the device.  The host object reports the smallest distance, over every
+ * aircraft it wrote, between the double 10 * log10(...) and the nearest midpoint of two adjacent floats, in ulps of that
+ * double (msd_pos_host_aircraft_pb's min_rssi_margin_ulps; +infinity when nothing was written).
+ * valid_source (151) is always present: generateValidSourceMessage's 32 members from `source`, lat / lon / nic / rc
+ * repeating MSD_AC_POSITION and sil_type MSD_AC_SIL; an aircraft with nothing valid writes BA 09 00.
+ * The written state, per slot.  The reference attaches flight and nav_modes to meta only while their validity holds at a
+ * write, never detaches them, and sets seen_pos only while the position is valid.  So a slot keeps "flight attached",
+ * "nav_modes attached" and the last seen_pos.  A write at which msd_aircraft_valid holds for MSD_AC_CALLSIGN /
+ * MSD_AC_NAV_MODES sets the bit; with a valid position seen_pos = (now_ms - updated[MSD_AC_POSITION]) / 1000, the wrapped
+ * 64-bit difference in integer division, saturated at 2^32 - 1.  Then flight (2) = the stored callsign up to its first
+ * NUL, at most 8 bytes, if attached; nav_modes (150) with its six bools if attached (all false: B2 09 00); seen_pos (41)
+ * if non-zero.  The state starts at 0 with the aircraft, moves with its slot, goes with removal and msd_pos_reset, is not
+ * touched for an aircraft that is not selected, and is committed only by a call that returns 0.
+ * Not written: distance (13), declination (46), wind_speed / wind_direction (47 / 48) and valid_source.wind (132).  They
+ * need update_polar_range and geomag_calc, which are not built; a wind against a declination of 0 would be wrong.
+ * CONTRACT, the table's: the device and the host object (msd_pos_host_pb_enable, msd_pos_host_aircraft_pb -- a plain
+ * sequential encoder that shares no code with the device's) deliver the same stream, the same rows and the same written
+ * state on every table on which they hold the same msd_aircraft bytes and min_rssi_margin_ulps is at least
+ * MSD_PB_RSSI_MARGIN_ULPS (derived in DESIGN.md 4.10), whichever slots the aircraft occupy. ---- */
+typedef struct msd_pb_options { /* 24 bytes */
+    uint64_t now_ms;                /* mstime() of the write */
+    const uint64_t *messages_total; /* host array, one per receiver: stats_current + stats_alltime messages_total, which
+                                       the tracker does not count; NULL: all 0 */
+    uint32_t flags, reserved;       /* 0 */
+} msd_pb_options;
+typedef struct msd_pb_receiver { /* 24 bytes */
+    uint64_t end;            /* the end offset of this receiver's file in the stream; it begins at the end before it */
+    uint32_t aircraft;       /* aircraft written */
+    uint32_t with_positions; /* of those, with a valid position (net_io.c:2035) */
+    uint32_t tisb_positions; /* of those, from TIS-B (net_io.c:2038) */
+    uint32_t reserved;       /* 0 */
+} msd_pb_receiver;
+#define MSD_PB_RSSI_MARGIN_ULPS 8.0
+/* the longest `aircraft` entry, every field present and every negative int32 at 10 bytes.  Body: 5 addr (25 bits) + 10
+ * flight + 4 squawk + 3 category + 11 alt_baro + 4 mag_heading (at most 65535 x 360 / 128) + 6 ias + 9 lat + 9 lon
+ * + 11 messages + 11 seen + 5 rssi + 3 air_ground + 3 x 12 alt_geom, baro_rate, geom_rate + 7 gs + 7 tas + 6 mach
+ * + 5 true_heading + 5 track + 3 x 6 track_rate, roll, nav_qnh + 2 x 12 nav_altitude_mcp / fms + 5 nav_heading + 4 nic
+ * + 5 rc + 3 version + 4 x 4 nic_baro, nac_p, nac_v, sil + 7 seen_pos + 3 alert + 3 spi + 4 gva + 4 sda + 3 x 4 addr_type,
+ * emergency, sil_type + 15 nav_modes + 132 valid_source (2 + 2 + 32 x 4) = 412; with the tag and a two-byte length 415 */
+#define MSD_PB_AIRCRAFT_MAX 415
+/* -EINVAL on a tracker without a table; a second call returns 0 and changes nothing; -ENOMEM leaves the tracker as it was.
+ * Allocates the written state (8 bytes per slot, twice; the aircraft the table already has start at 0) and builds on the
+ * host and uploads a second ground-track table (4 x 1023 x 1023 entries of 16 bits, 8 MiB): the SBS table's shape with
+ * the conversion to int32_t in place of rintf; the SBS table stays as it is.  msd_pos_reset zeroes the state and leaves
+ * the tracker enabled.  A tracker that never calls this allocates and launches what it did before and answers -EINVAL to
+ * msd_pos_aircraft_pb. */
+int msd_pos_pb_enable(msd_pos *p);
+/* The aircraft.pb of every receiver index 0 .. receivers-1 in ascending order as one dense stream in the host array out;
+ * rx: a host array of `receivers` rows, or NULL.  An empty file repeats the end before it.
+ * -ENOSPC: cap is too small, *out_len is the size needed, nothing was written and no written state moved: the call can be
+ * repeated and gives the bytes the first call would have given.  -EINVAL: not enabled, NULL, an unknown flag,
+ * reserved != 0.  -E2BIG: the table could hold more than 2^32 - 1 bytes of stream (above some 10 million aircraft). */
+int msd_pos_aircraft_pb(msd_pos *p, const msd_pb_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_pb_receiver *rx);
 
 #ifdef __cplusplus
 }

@@ -242,7 +242,7 @@ EXPORTS = [
     "msd_pos_create_table", "msd_pos_update_nicrc", "msd_pos_snapshot", "msd_aircraft_valid", "msd_aircraft_to_float",
     "msd_pos_modeac_enable", "msd_pos_modeac_match", "msd_pos_modeac_codes", "msd_pos_modeac_hits", "msd_mode_c_to_a",
     "msd_pos_reduce_enable", "msd_pos_update_reduce", "msd_pos_reduce_wire",
-    "msd_pos_sbs_enable", "msd_pos_update_sbs", "msd_pos_sbs_wire",
+    "msd_pos_sbs_enable", "msd_pos_update_sbs", "msd_pos_sbs_wire", "msd_pos_pb_enable", "msd_pos_aircraft_pb",
 ]
 
 _lib = None
@@ -1125,11 +1125,22 @@ assert SBS_TRACK_DTYPE.itemsize == 32
 SBS_TRACKED, SBS_SEEN_TWICE, SBS_GS_VALID, SBS_GEOM_DELTA_VALID, SBS_CPR_DECODED = 1, 2, 4, 8, 16
 SBS_NET_ONLY, SBS_GNSS, SBS_NOW_IS_RECEIVED = 2, 4, 8
 SBS_MAX = 147
+# aircraft.pb: a receiver's row of msd_pos_aircraft_pb (msd_pb_receiver), the longest `aircraft` entry, and the smallest
+# rssi margin on the host object under which the device and the host object may differ (MSD_PB_RSSI_MARGIN_ULPS)
+PB_RECEIVER_DTYPE = np.dtype([("end", "<u8"), ("aircraft", "<u4"), ("with_positions", "<u4"), ("tisb_positions", "<u4"),
+                              ("reserved", "<u4")])
+assert PB_RECEIVER_DTYPE.itemsize == 24
+PB_AIRCRAFT_MAX = 415
+PB_RSSI_MARGIN_ULPS = 8.0
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmsd_host.so")
 
 
 class SbsOptions(C.Structure):
     _fields_ = [("now_ms", C.c_uint64), ("utc_offset_ms", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PbOptions(C.Structure):
+    _fields_ = [("now_ms", C.c_uint64), ("messages_total", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PosReceiver(C.Structure):
@@ -1174,8 +1185,11 @@ def _pos_lib(host):
         f = {k: getattr(L, pre + k) for k in ("create", "destroy", "reset", "set_receiver", "update", "expire", "get_stats",
                                               "create_table", "update_nicrc", "snapshot", "modeac_enable", "modeac_match",
                                               "modeac_codes", "modeac_hits", "reduce_enable", "update_reduce",
-                                              "reduce_wire", "sbs_enable", "update_sbs", "sbs_wire")}
+                                              "reduce_wire", "sbs_enable", "update_sbs", "sbs_wire", "pb_enable", "aircraft_pb")}
         dev = [] if host else [C.c_int]
+        f["pb_enable"].argtypes = [C.c_void_p]
+        f["aircraft_pb"].argtypes = [C.c_void_p, C.POINTER(PbOptions), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                     C.c_void_p] + ([C.POINTER(C.c_double)] if host else [])
         f["sbs_enable"].argtypes = [C.c_void_p]
         f["update_sbs"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [C.c_void_p] * 4
         f["sbs_wire"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [
@@ -1225,15 +1239,17 @@ class PositionTracker:
     stream whose min_gate_margin_m on the twin stays above 1e-3 m."""
 
     def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False, table=False,
-                 modeac=False, reduce_interval_ms=None, sbs=False):
+                 modeac=False, reduce_interval_ms=None, sbs=False, pb=False):
         """table=True: msd_pos_create_table -- the tracker also keeps the aircraft table (update_nicrc, snapshot).
         modeac=True (a table tracker): msd_pos_modeac_enable -- it also counts Mode A/C replies and matches them against
         its aircraft (modeac_match, modeac_codes, modeac_hits).
         reduce_interval_ms (a table tracker): msd_pos_reduce_enable -- it also keeps the timers of readsb's reduced Beast
         output (update_reduce, reduce_wire).
         sbs=True (a table tracker): msd_pos_sbs_enable -- update_sbs hands over a row per record and sbs_wire writes
-        readsb's SBS (BaseStation) lines from them."""
+        readsb's SBS (BaseStation) lines from them.
+        pb=True (a table tracker): msd_pos_pb_enable -- aircraft_pb writes every receiver's aircraft.pb from the table."""
         self.host, self.table = host, table
+        self.nrx = len(receivers) if receivers is not None else 1
         self.L, self.f = _pos_lib(host)
         receivers = receivers if receivers is not None else [None]
         self._rx = _pos_receivers(receivers)
@@ -1251,6 +1267,8 @@ class PositionTracker:
                 self.reduce_enable(reduce_interval_ms)
             if sbs:
                 self.sbs_enable()
+            if pb:
+                self.pb_enable()
         except MsdError:
             self.close()
             raise
@@ -1363,6 +1381,37 @@ class PositionTracker:
         self.sbs_out = out
         self._check(rc, "msd_pos_sbs_wire")
         return out[:need.value].tobytes(), ends
+
+    def pb_enable(self):
+        self._check(self.f["pb_enable"](self.h), "msd_pos_pb_enable")
+
+    def aircraft_pb_stream(self, now_ms, messages_total=None, cap=None, flags=0, reserved=0):
+        """msd_pos_aircraft_pb -> (the stream of every receiver's aircraft.pb, PB_RECEIVER_DTYPE array).  cap: the bytes
+        offered (default: as many as are needed, asked for first); self.pb_needed is *out_len of the last call, and on
+        the host object self.pb_margin the smallest rssi margin in ulps over the aircraft written."""
+        mt = None if messages_total is None else np.ascontiguousarray(messages_total, dtype=np.uint64)
+        assert mt is None or len(mt) == self.nrx
+        opt = PbOptions(now_ms=now_ms, messages_total=None if mt is None else mt.ctypes.data, flags=flags, reserved=reserved)
+        need, margin = C.c_size_t(0), C.c_double(float("inf"))
+        tail = [C.byref(margin)] if self.host else []
+        if cap is None:
+            rc = self.f["aircraft_pb"](self.h, C.byref(opt), None, 0, C.byref(need), None, *([None] if self.host else []))
+            if rc not in (0, -errno.ENOSPC):
+                self._check(rc, "msd_pos_aircraft_pb")
+            cap = need.value
+        out = np.zeros(cap, dtype=np.uint8)
+        rx = np.zeros(self.nrx, dtype=PB_RECEIVER_DTYPE)
+        rc = self.f["aircraft_pb"](self.h, C.byref(opt), out.ctypes.data if cap else None, cap, C.byref(need), rx.ctypes.data, *tail)
+        self.pb_needed = need.value
+        self.pb_margin = margin.value
+        self._check(rc, "msd_pos_aircraft_pb")
+        return out[:need.value].tobytes(), rx
+
+    def aircraft_pb(self, now_ms, messages_total=None):
+        """Every receiver's aircraft.pb at now_ms -> a list of bytes, one file per receiver index."""
+        stream, rx = self.aircraft_pb_stream(now_ms, messages_total)
+        ends = [0] + [int(e) for e in rx["end"]]
+        return [stream[a:b] for a, b in zip(ends[:-1], ends[1:])]
 
     def reduce_timers(self, receiver, addr):
         """The twin's timers of one aircraft -> uint64 array of REDUCE_TIMERS (AC_MEMBERS order, then DF11), or None."""

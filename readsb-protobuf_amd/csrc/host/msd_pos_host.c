@@ -30,6 +30,7 @@ struct msd_pos_host {
     uint64_t *next_reduce;
     uint32_t reduce_interval;
     int sbs; /* SBS output (msd_pos_host_sbs_enable): the twin keeps nothing for it */
+    uint64_t *pb_state; /* aircraft.pb (msd_pos_host_pb_enable), else NULL: the written state per slot */
 };
 
 int msd_cpr_host_airborne(int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag, double *lat, double *lon)
@@ -67,6 +68,8 @@ static void clear(msd_pos_host *p)
     }
     if (p->next_reduce)
         memset(p->next_reduce, 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->cap);
+    if (p->pb_state)
+        memset(p->pb_state, 0, sizeof(uint64_t) * p->cap);
 }
 
 static int create(const msd_pos_config *cfg, msd_pos_host **out, int table)
@@ -109,6 +112,7 @@ void msd_pos_host_destroy(msd_pos_host *p)
 {
     if (!p)
         return;
+    free(p->pb_state);
     free(p->next_reduce);
     free(p->ac);
     free(p->hits);
@@ -155,6 +159,8 @@ static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
                 p->hits[2u * s] = p->hits[2u * s + 1u] = 0;
             if (p->next_reduce)
                 memset(&p->next_reduce[(size_t)s * MSD_REDUCE_TIMERS], 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS);
+            if (p->pb_state)
+                p->pb_state[s] = 0;
             *fresh = 1;
             return s;
         }
@@ -540,6 +546,277 @@ int msd_pos_host_sbs_wire(msd_pos_host *p, const msd_message *msgs, const msd_fi
     return 0;
 }
 
+/* ---- the aircraft.pb writer: generateAircraftProtoBuf (net_io.c:1977-2080) and protobuf-c 1.3's pack as a plain
+ * sequential encoder over the exported entries, with msd_aircraft_to_float and the libm.  The yardstick of the device's
+ * writer (msd_pb_impl.h): nothing of that file is used here. ---- */
+#define PB_FLIGHT 1u
+#define PB_NAV_MODES 2u
+
+static uint64_t *ordered_slots(const msd_pos_host *p); /* below, with the snapshot */
+
+int msd_pos_host_pb_enable(msd_pos_host *p)
+{
+    if (!p || !p->trk)
+        return -EINVAL;
+    if (p->pb_state)
+        return 0;
+    uint64_t *state = calloc(p->cap, sizeof(uint64_t)); /* low word: seen_pos; bits 32 / 33: PB_FLIGHT / PB_NAV_MODES */
+    if (!state)
+        return -ENOMEM;
+    p->pb_state = state;
+    return 0;
+}
+
+typedef struct pb_buf {
+    uint8_t *at; /* NULL: the size alone */
+    size_t n;
+} pb_buf;
+
+static void pb_put(pb_buf *b, const void *bytes, size_t k)
+{
+    if (b->at)
+        memcpy(b->at + b->n, bytes, k);
+    b->n += k;
+}
+
+static void pb_put_varint(pb_buf *b, uint64_t v)
+{
+    uint8_t tmp[10];
+    size_t k = 0;
+    do {
+        tmp[k] = (uint8_t)(v & 0x7f);
+        v >>= 7;
+        if (v)
+            tmp[k] |= 0x80;
+        ++k;
+    } while (v);
+    pb_put(b, tmp, k);
+}
+
+static void pb_put_key(pb_buf *b, unsigned field, unsigned wire_type)
+{
+    pb_put_varint(b, ((uint64_t)field << 3) | wire_type);
+}
+
+static void pb_put_u64(pb_buf *b, unsigned field, uint64_t v)
+{
+    if (v == 0)
+        return;
+    pb_put_key(b, field, 0);
+    pb_put_varint(b, v);
+}
+
+static void pb_put_i32(pb_buf *b, unsigned field, int32_t v)
+{
+    if (v == 0)
+        return;
+    pb_put_key(b, field, 0);
+    pb_put_varint(b, v < 0 ? (uint64_t)(int64_t)v : (uint64_t)v);
+}
+
+static void pb_put_float(pb_buf *b, unsigned field, float v)
+{
+    if (0 == v)
+        return;
+    uint32_t u;
+    uint8_t le[4];
+    memcpy(&u, &v, 4);
+    for (int i = 0; i < 4; ++i)
+        le[i] = (uint8_t)(u >> (8 * i));
+    pb_put_key(b, field, 5);
+    pb_put(b, le, 4);
+}
+
+static void pb_put_double(pb_buf *b, unsigned field, double v)
+{
+    if (0 == v)
+        return;
+    uint64_t u;
+    uint8_t le[8];
+    memcpy(&u, &v, 8);
+    for (int i = 0; i < 8; ++i)
+        le[i] = (uint8_t)(u >> (8 * i));
+    pb_put_key(b, field, 1);
+    pb_put(b, le, 8);
+}
+
+static void pb_put_bytes(pb_buf *b, unsigned field, const pb_buf *body, const uint8_t *bytes)
+{
+    pb_put_key(b, field, 2);
+    pb_put_varint(b, body->n);
+    pb_put(b, bytes, body->n);
+}
+
+/* a velocity whose components a subtype 1 / 2 message can carry: (raw - 1) is 0 .. 1022, times 4 for subtype 2 */
+static int pb_velocity_carried(const msd_aircraft_heading *h)
+{
+    const int a = abs(h->ew), b = abs(h->ns);
+    if (a <= 1022 && b <= 1022)
+        return 1;
+    return a % 4 == 0 && b % 4 == 0 && a / 4 <= 1022 && b / 4 <= 1022;
+}
+
+static int32_t pb_heading(const msd_aircraft_heading *h, float degrees)
+{
+    if (h->kind == MSD_HDG_VELOCITY && !pb_velocity_carried(h))
+        return 0;
+    return (int32_t)degrees;
+}
+
+/* the distance of d to the nearest midpoint of two adjacent floats, in ulps of d */
+static double pb_float_margin(double d)
+{
+    const float f = (float)d;
+    const double below = ((double)f + (double)nextafterf(f, -INFINITY)) / 2, above = ((double)f + (double)nextafterf(f, INFINITY)) / 2;
+    const double dist = fmin(fabs(d - below), fabs(d - above));
+    const double ulp = nextafter(fabs(d), INFINITY) - fabs(d);
+    return dist / ulp;
+}
+
+/* AircraftMeta of one exported entry with its written state after this write -> body (at most 512 bytes) */
+static void pb_meta(const msd_aircraft *e, uint64_t state, pb_buf *b, double *margin)
+{
+    msd_aircraft_float fl;
+    msd_aircraft_to_float(e, &fl);
+    pb_put_u64(b, 1, e->addr);
+    if (state >> 32 & PB_FLIGHT) {
+        const size_t k = strnlen(e->callsign, 8);
+        if (k) {
+            pb_put_key(b, 2, 2);
+            pb_put_varint(b, k);
+            pb_put(b, e->callsign, k);
+        }
+    }
+    pb_put_u64(b, 3, e->squawk);
+    pb_put_u64(b, 4, e->category);
+    pb_put_i32(b, 5, e->alt_baro);
+    pb_put_i32(b, 6, pb_heading(&e->mag_heading, fl.mag_heading));
+    pb_put_u64(b, 7, e->ias);
+    pb_put_double(b, 8, e->lat);
+    pb_put_double(b, 9, e->lon);
+    pb_put_u64(b, 10, e->messages);
+    pb_put_u64(b, 11, e->seen);
+    {
+        const double d = 10 * log10((e->signal_level[0] + e->signal_level[1] + e->signal_level[2] + e->signal_level[3] +
+                                     e->signal_level[4] + e->signal_level[5] + e->signal_level[6] + e->signal_level[7] + 1e-5) / 8);
+        const double m = pb_float_margin(d);
+        if (margin && !(m >= *margin))
+            *margin = m;
+        pb_put_float(b, 12, (float)d);
+    }
+    pb_put_i32(b, 15, e->air_ground);
+    pb_put_i32(b, 20, e->alt_geom);
+    pb_put_i32(b, 21, e->baro_rate);
+    pb_put_i32(b, 22, e->geom_rate);
+    pb_put_u64(b, 23, e->gs);
+    pb_put_u64(b, 24, e->tas);
+    pb_put_float(b, 25, (float)fl.mach);
+    pb_put_i32(b, 26, pb_heading(&e->true_heading, fl.true_heading));
+    pb_put_i32(b, 27, pb_heading(&e->track, fl.track));
+    pb_put_float(b, 28, fl.track_rate);
+    pb_put_float(b, 29, fl.roll);
+    pb_put_float(b, 30, fl.nav_qnh);
+    pb_put_i32(b, 31, e->nav_altitude_mcp);
+    pb_put_i32(b, 32, e->nav_altitude_fms);
+    pb_put_i32(b, 33, (int32_t)fl.nav_heading);
+    pb_put_u64(b, 34, e->nic);
+    pb_put_u64(b, 35, e->rc);
+    pb_put_i32(b, 36, e->adsb_version >= 0 ? e->adsb_version : 0);
+    pb_put_u64(b, 37, e->nic_baro);
+    pb_put_u64(b, 38, e->nac_p);
+    pb_put_u64(b, 39, e->nac_v);
+    pb_put_u64(b, 40, e->sil);
+    pb_put_u64(b, 41, (uint32_t)state);
+    pb_put_u64(b, 42, e->alert ? 1 : 0);
+    pb_put_u64(b, 43, e->spi ? 1 : 0);
+    pb_put_u64(b, 44, e->gva);
+    pb_put_u64(b, 45, e->sda);
+    pb_put_i32(b, 100, e->addr_type);
+    pb_put_i32(b, 101, e->emergency);
+    pb_put_i32(b, 102, e->sil_type);
+    if (state >> 32 & PB_NAV_MODES) {
+        uint8_t sub[16];
+        pb_buf m = {sub, 0};
+        for (unsigned bit = 0; bit < 6; ++bit)
+            pb_put_u64(&m, bit + 1, (e->nav_modes >> bit) & 1u);
+        pb_put_bytes(b, 150, &m, sub);
+    }
+    {
+        /* generateValidSourceMessage's members in field order, 100 .. 131 */
+        static const uint8_t member[32] = {
+            MSD_AC_CALLSIGN, MSD_AC_ALTITUDE_BARO, MSD_AC_ALTITUDE_GEOM, MSD_AC_GS, MSD_AC_IAS, MSD_AC_TAS, MSD_AC_MACH,
+            MSD_AC_TRACK, MSD_AC_TRACK_RATE, MSD_AC_ROLL, MSD_AC_MAG_HEADING, MSD_AC_TRUE_HEADING, MSD_AC_BARO_RATE,
+            MSD_AC_GEOM_RATE, MSD_AC_SQUAWK, MSD_AC_EMERGENCY, MSD_AC_NAV_QNH, MSD_AC_NAV_ALTITUDE_MCP,
+            MSD_AC_NAV_ALTITUDE_FMS, MSD_AC_NAV_HEADING, MSD_AC_NAV_MODES, MSD_AC_POSITION, MSD_AC_POSITION, MSD_AC_POSITION,
+            MSD_AC_POSITION, MSD_AC_NIC_BARO, MSD_AC_NAC_P, MSD_AC_NAC_V, MSD_AC_SIL, MSD_AC_SIL, MSD_AC_GVA, MSD_AC_SDA};
+        uint8_t sub[160];
+        pb_buf v = {sub, 0};
+        for (unsigned k = 0; k < 32; ++k)
+            pb_put_u64(&v, 100 + k, e->source[member[k]]);
+        pb_put_bytes(b, 151, &v, sub);
+    }
+}
+
+int msd_pos_host_aircraft_pb(msd_pos_host *p, const msd_pb_options *opt, uint8_t *out, size_t cap, size_t *out_len,
+                             msd_pb_receiver *rx, double *min_rssi_margin_ulps)
+{
+    if (!p || !p->pb_state || !out_len || !opt || opt->flags != 0 || opt->reserved != 0 || (!out && cap > 0))
+        return -EINVAL;
+    *out_len = 0;
+    uint64_t *ks = NULL;
+    if (p->live && !(ks = ordered_slots(p)))
+        return -ENOMEM;
+    const uint64_t now = opt->now_ms;
+    double margin = INFINITY;
+    for (int pass = 0; pass < 2; ++pass) { /* the size first: a stream that does not fit leaves out and the state alone */
+        pb_buf file = {pass ? out : NULL, 0};
+        size_t j = 0;
+        for (uint32_t r = 0; r < p->nrx; ++r) {
+            msd_pb_receiver row = {0, 0, 0, 0, 0};
+            pb_put_u64(&file, 1, now / 1000);
+            pb_put_u64(&file, 2, opt->messages_total ? opt->messages_total[r] : 0);
+            for (; j < p->live && (ks[2 * j] >> 25) == r; ++j) {
+                const uint64_t s = ks[2 * j + 1];
+                msd_aircraft e;
+                msd_trk_export(ks[2 * j], &p->st[s], &p->trk[s], &e);
+                if (e.messages < 2 || (now > e.seen && now - e.seen > 90000)) /* net_io.c:2011 */
+                    continue;
+                uint64_t state = p->pb_state[s];
+                if (msd_trk_valid(&e, MSD_AC_CALLSIGN, now))
+                    state |= (uint64_t)PB_FLIGHT << 32;
+                if (msd_trk_valid(&e, MSD_AC_NAV_MODES, now))
+                    state |= (uint64_t)PB_NAV_MODES << 32;
+                if (msd_trk_valid(&e, MSD_AC_POSITION, now)) {
+                    const uint64_t age = (now - e.updated[MSD_AC_POSITION]) / 1000;
+                    state = (state >> 32 << 32) | (age > UINT32_MAX ? UINT32_MAX : age);
+                    row.with_positions++;
+                    if (e.source[MSD_AC_POSITION] == 5) /* SOURCE_TISB */
+                        row.tisb_positions++;
+                }
+                uint8_t body[512];
+                pb_buf b = {body, 0};
+                pb_meta(&e, state, &b, &margin);
+                pb_put_bytes(&file, 15, &b, body);
+                row.aircraft++;
+                if (pass)
+                    p->pb_state[s] = state;
+            }
+            row.end = file.n;
+            if (pass && rx)
+                rx[r] = row;
+        }
+        *out_len = file.n;
+        if (file.n > cap) {
+            free(ks);
+            return -ENOSPC;
+        }
+    }
+    free(ks);
+    if (min_rssi_margin_ulps)
+        *min_rssi_margin_ulps = margin;
+    return 0;
+}
+
 int msd_pos_host_reduce_timers(const msd_pos_host *p, uint32_t receiver, uint32_t addr, uint64_t *out)
 {
     if (!p || !p->next_reduce || !out)
@@ -683,7 +960,9 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
     uint8_t *hits = p->hits ? malloc(2u * (size_t)p->cap) : NULL;
     const size_t next_bytes = sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->cap;
     uint64_t *next = p->next_reduce ? malloc(next_bytes) : NULL;
-    if (!keys || !st || (p->trk && !trk) || (p->hits && !hits) || (p->next_reduce && !next)) {
+    uint64_t *pb = p->pb_state ? malloc(sizeof(uint64_t) * p->cap) : NULL;
+    if (!keys || !st || (p->trk && !trk) || (p->hits && !hits) || (p->next_reduce && !next) || (p->pb_state && !pb)) {
+        free(pb);
         free(keys);
         free(st);
         free(trk);
@@ -693,6 +972,8 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
     }
     if (next)
         memcpy(next, p->next_reduce, next_bytes);
+    if (pb)
+        memcpy(pb, p->pb_state, sizeof(uint64_t) * p->cap);
     if (hits)
         memcpy(hits, p->hits, 2u * (size_t)p->cap);
     if (trk)
@@ -715,8 +996,11 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
             if (next)
                 memcpy(&p->next_reduce[(size_t)d * MSD_REDUCE_TIMERS], &next[(size_t)s * MSD_REDUCE_TIMERS],
                        sizeof(uint64_t) * MSD_REDUCE_TIMERS);
+            if (pb)
+                p->pb_state[d] = pb[s];
         }
     p->live -= removed;
+    free(pb);
     free(keys);
     free(st);
     free(trk);

@@ -43,6 +43,13 @@ int msd_pos_host_update_sbs(msd_pos_host *p, const msd_message *msgs, const msd_
                             size_t n, msd_position *out, msd_pos_nicrc *nicrc, uint8_t *forward, msd_sbs_track *trk);
 int msd_pos_host_sbs_wire(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk, size_t n,
                           const msd_sbs_options *opt, uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends);
+/* aircraft.pb (modes_hip.h, "aircraft.pb"): msd_pos_pb_enable and msd_pos_aircraft_pb on the host -- a plain sequential
+ * encoder over msd_pos_host_snapshot's entries with msd_aircraft_to_float and the libm's log10, the yardstick of the
+ * device's writer.  min_rssi_margin_ulps (or NULL): the smallest distance, over every aircraft the call wrote, between the
+ * double 10 * log10(...) and the nearest midpoint of two adjacent floats, in ulps of that double; +infinity without one */
+int msd_pos_host_pb_enable(msd_pos_host *p);
+int msd_pos_host_aircraft_pb(msd_pos_host *p, const msd_pb_options *opt, uint8_t *out, size_t cap, size_t *out_len,
+                             msd_pb_receiver *rx, double *min_rssi_margin_ulps);
 /* for tests: the MSD_AC_N + 1 timers of one aircraft (the members' in MSD_AC_* order, then the DF11 timer) into out;
  * -ENOENT: no such aircraft */
 int msd_pos_host_reduce_timers(const msd_pos_host *p, uint32_t receiver, uint32_t addr, uint64_t *out);

@@ -22,6 +22,9 @@
  * beast_reduce_out to FILE (--net-beast-reduce-out-port, --net-beast-reduce-interval; default 0.125 s, at most 15): the
  * Beast frames of the messages that brought their aircraft something new (msd_pos_update_reduce, msd_pos_reduce_wire).
  *
+ * `--positions --aircraft --aircraft-pb FILE` writes receiver 0's aircraft.pb (readsb's AircraftsUpdate protobuf,
+ * msd_pos_aircraft_pb) to FILE once, after the last message, with now = that message's time and `messages` = the messages
+ * this run delivered.
  * `--positions --aircraft --sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]` writes readsb's SBS (BaseStation,
  * port 30003) output to FILE (msd_pos_update_sbs, msd_pos_sbs_wire): one MSG line per message the tracker knows the
  * aircraft of.  A replay has no wall clock: fields 9-10 repeat the message's own time (MSD_SBS_NOW_IS_RECEIVED), so the
@@ -154,6 +157,38 @@ static int sbs_finish(int want_stats)
     free(g_sbs_rows);
     free(g_sbs_bytes);
     free(g_sbs_ends);
+    return bad;
+}
+
+/* --aircraft-pb: after the last message, receiver 0's aircraft.pb at now_ms = the last message's time, with `messages` =
+ * the messages this run delivered (msd_pos_aircraft_pb: the size first, then the bytes) */
+static const char *g_pb_path;
+static int write_aircraft_pb(int want_stats)
+{
+    const uint64_t total = g_count;
+    msd_pb_options opt;
+    memset(&opt, 0, sizeof opt);
+    opt.now_ms = g_last_ms;
+    opt.messages_total = &total;
+    msd_pb_receiver row;
+    size_t len = 0;
+    int rc = msd_pos_aircraft_pb(g_pos, &opt, NULL, 0, &len, NULL);
+    uint8_t *bytes = rc == -ENOSPC ? malloc(len) : NULL;
+    if (rc == -ENOSPC && bytes)
+        rc = msd_pos_aircraft_pb(g_pos, &opt, bytes, len, &len, &row);
+    else if (rc == 0)
+        rc = msd_pos_aircraft_pb(g_pos, &opt, NULL, 0, &len, &row); /* an empty file */
+    FILE *out = rc ? NULL : fopen(g_pb_path, "wb");
+    int bad = !out;
+    if (out) {
+        bad = fwrite(bytes, 1, len, out) != len;
+        bad |= fclose(out) != 0;
+    }
+    if (bad)
+        fprintf(stderr, "--aircraft-pb %s: %s (%d)\n", g_pb_path, rc ? msd_pos_last_error(g_pos) : "cannot write", rc);
+    else if (want_stats)
+        fprintf(stderr, "aircraft.pb aircraft,%u,with_positions,%u,bytes,%zu\n", row.aircraft, row.with_positions, len);
+    free(bytes);
     return bad;
 }
 
@@ -451,6 +486,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--beast-reduce-interval") && next) { reduce_interval_s = atof(next); ++i; }
         else if (!strcmp(a, "--net-only")) net_only = 1; /* readsb.c: Modes.net_only */
         else if (!strcmp(a, "--sbs-out") && next) { sbs_path = next; ++i; }
+        else if (!strcmp(a, "--aircraft-pb") && next) { g_pb_path = next; ++i; }
         else if (!strcmp(a, "--gnss")) gnss = 1; /* readsb.c: Modes.use_gnss */
         else if (!strcmp(a, "--utc-offset") && next) { utc_offset_s = atof(next); ++i; }
         else if (!strcmp(a, "--clock-start-ms") && next) { g_clock_start_ms = strtoull(next, NULL, 10); ++i; }
@@ -480,7 +516,7 @@ int main(int argc, char **argv)
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
                             "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft [--match-modeac] "
                             "[--beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]] "
-                            "[--sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]]] [--clock-start-ms N]]\n"
+                            "[--sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]] [--aircraft-pb FILE]] [--clock-start-ms N]]\n"
                             "       --positions: the --raw lines, with \"lat,lon\" behind the ';' of every message from which readsb's tracker\n"
                             "       would have decoded a position (CPR global and local, its range and speed checks; the coordinates are exact, the\n"
                             "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
@@ -495,6 +531,8 @@ int main(int argc, char **argv)
                             "       --beast-reduce-out FILE (with --aircraft): readsb's reduced Beast output to FILE -- the frames of the messages\n"
                             "       that brought their aircraft something new, at most once per --beast-reduce-interval (seconds, default 0.125, at\n"
                             "       most 15) and member; a first message only with --net-only or --net-verbatim.\n"
+                            "       --aircraft-pb FILE (with --aircraft): after the last message, readsb's aircraft.pb (the AircraftsUpdate\n"
+                            "       protobuf) of the table, written on the GPU; now = the last message's time, messages = this run's count.\n"
                             "       --sbs-out FILE (with --aircraft): readsb's SBS (BaseStation) output to FILE, one MSG line per message of a\n"
                             "       tracked aircraft; --gnss: geometric altitudes and rates first, marked H; --utc-offset: the zone the dates\n"
                             "       are written in, seconds east of UTC (default 0, at most a day); the \"now\" of fields 9-10 is the message's own time.\n"
@@ -515,6 +553,10 @@ int main(int argc, char **argv)
     }
     if (reduce_path && !want_aircraft) {
         fprintf(stderr, "--beast-reduce-out goes with --positions --aircraft\n");
+        return 2;
+    }
+    if (g_pb_path && !want_aircraft) {
+        fprintf(stderr, "--aircraft-pb goes with --positions --aircraft\n");
         return 2;
     }
     if (sbs_path && !want_aircraft) {
@@ -587,6 +629,11 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        if (g_pb_path && msd_pos_pb_enable(g_pos) != 0) {
+            fprintf(stderr, "--aircraft-pb %s: %s\n", g_pb_path, msd_pos_last_error(g_pos));
+            msd_pos_destroy(g_pos);
+            return 1;
+        }
         rx.sink = print_raw_positions;
     }
     if (avr_in || beast_in) {
@@ -597,6 +644,8 @@ int main(int argc, char **argv)
         if (g_reduce_out && reduce_finish(want_stats))
             g_pos_failed = 1;
         if (g_sbs_out && sbs_finish(want_stats))
+            g_pos_failed = 1;
+        if (g_pb_path && !rc && write_aircraft_pb(want_stats))
             g_pos_failed = 1;
         msd_pos_destroy(g_pos);
         return rc ? rc : g_pos_failed;
@@ -645,6 +694,8 @@ int main(int argc, char **argv)
     if (g_reduce_out && reduce_finish(want_stats))
         g_pos_failed = 1;
     if (g_sbs_out && sbs_finish(want_stats))
+        g_pos_failed = 1;
+    if (g_pb_path && write_aircraft_pb(want_stats))
         g_pos_failed = 1;
     msd_pos_destroy(g_pos);
     return g_pos_failed ? 1 : 0;

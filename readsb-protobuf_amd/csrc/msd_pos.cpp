@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "msd_pos.h"
+#include "msd_pb_impl.h"
 #include "msd_sbs_impl.h"
 
 struct msd_pos {
@@ -60,6 +61,18 @@ struct msd_pos {
     size_t cap_sbs = 0, cap_s_in = 0;
     msd_message *d_s_msgs = nullptr;
     msd_fields *d_s_fields = nullptr;
+    /* aircraft.pb (msd_pos_pb_enable): the written state beside tab[k], the truncating ground-track table, and the
+     * writer's buffers -- per receiver (made with the state), per item (grown to the largest call seen); the stream is the
+     * reduced writer's */
+    uint64_t *pb_state[2] = {nullptr, nullptr};
+    uint16_t *d_pb_table = nullptr;
+    uint32_t *d_pb_first = nullptr;
+    uint64_t *d_pb_total = nullptr;
+    msd_pb_receiver *d_pb_rx = nullptr;
+    size_t cap_pb = 0;
+    uint32_t *d_pb_items = nullptr, *d_pb_within = nullptr, *d_pb_cwithin = nullptr, *d_pb_block = nullptr;
+    uint64_t *d_pb_shadow = nullptr;
+    uint16_t *d_pb_lens = nullptr;
     char err[256] = "";
 };
 
@@ -94,6 +107,9 @@ int clear(msd_pos *p)
     if (p->reduce)
         for (int k = 0; k < 2; ++k)
             POS_HIP(p, hipMemsetAsync(p->tab[k].next_reduce, 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->tab[k].cap, p->stream));
+    if (p->d_pb_table)
+        for (int k = 0; k < 2; ++k)
+            POS_HIP(p, hipMemsetAsync(p->pb_state[k], 0, sizeof(uint64_t) * p->tab[k].cap, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     p->live = 0;
     return 0;
@@ -240,6 +256,9 @@ void msd_pos_destroy(msd_pos *p)
     release(p->d_forward), release(p->d_w_msgs), release(p->d_w_forward), release(p->d_w_lens), release(p->d_w_out);
     release(p->d_w_block), release(p->d_w_ends);
     release(p->d_track_table), release(p->d_sbs), release(p->d_s_trk), release(p->d_s_msgs), release(p->d_s_fields);
+    release(p->pb_state[0]), release(p->pb_state[1]), release(p->d_pb_table), release(p->d_pb_first), release(p->d_pb_total);
+    release(p->d_pb_rx), release(p->d_pb_items), release(p->d_pb_within), release(p->d_pb_cwithin), release(p->d_pb_block);
+    release(p->d_pb_shadow), release(p->d_pb_lens);
     release(p->d_ac), release(p->d_c_to_a), release(p->d_codes), release(p->d_hits_out);
     release(p->d_nicrc), release(p->s_idx[0]), release(p->s_idx[1]), release(p->s_hist), release(p->d_snap);
     release(p->d_rx), release(p->d_stats), release(p->d_ctl), release(p->d_slot), release(p->d_fresh), release(p->d_out);
@@ -320,6 +339,10 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
         return ctl[MSD_POS_CTL_BAD_RECEIVER] ? -EINVAL : -ENOSPC;
     }
     p->live += ctl[MSD_POS_CTL_INSERTED];
+    if (p->d_pb_table && ctl[MSD_POS_CTL_INSERTED]) { /* the new aircraft have been written nowhere yet */
+        msd_pb_launch_fresh(p->stream, p->d_slot, p->d_fresh, (uint32_t)n, t.cap, p->pb_state[p->cur]);
+        POS_HIP(p, hipGetLastError());
+    }
     if (p->d_ac) { /* the call has passed its checks: its Mode A/C replies count (track.c:1001) */
         msd_pos_launch_modeac_count(p->stream, msgs, fields, receiver, p->nrx, (uint32_t)n, p->d_ac);
         POS_HIP(p, hipGetLastError());
@@ -465,6 +488,116 @@ int msd_pos_sbs_wire(msd_pos *p, const msd_message *msgs, const msd_fields *fiel
         POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
     if (ends)
         POS_HIP(p, hipMemcpyAsync(ends, p->d_w_ends, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int msd_pos_pb_enable(msd_pos *p)
+{
+    if (!p || !p->table)
+        return -EINVAL;
+    if (p->d_pb_table)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    std::vector<uint16_t> table;
+    try {
+        table.resize(MSD_PB_TRACK_ENTRIES);
+    } catch (const std::bad_alloc &) {
+        return -ENOMEM;
+    }
+    msd_pb_build_track_table(table.data());
+    uint16_t *d_table = nullptr;
+    uint64_t *state[2] = {nullptr, nullptr}, *total = nullptr;
+    uint32_t *first = nullptr;
+    msd_pb_receiver *rx = nullptr;
+    const auto build = [&]() -> int {
+        for (int k = 0; k < 2; ++k) { /* the aircraft the table already has have been written nowhere yet */
+            POS_HIP(p, hipMalloc(&state[k], sizeof(uint64_t) * p->tab[k].cap));
+            POS_HIP(p, hipMemsetAsync(state[k], 0, sizeof(uint64_t) * p->tab[k].cap, p->stream));
+        }
+        POS_HIP(p, hipMalloc(&first, sizeof(uint32_t) * ((size_t)p->nrx + 1u)));
+        POS_HIP(p, hipMalloc(&total, sizeof(uint64_t) * p->nrx));
+        POS_HIP(p, hipMalloc(&rx, sizeof(msd_pb_receiver) * p->nrx));
+        POS_HIP(p, hipMalloc(&d_table, sizeof(uint16_t) * MSD_PB_TRACK_ENTRIES));
+        POS_HIP(p, hipMemcpyAsync(d_table, table.data(), sizeof(uint16_t) * MSD_PB_TRACK_ENTRIES, hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipStreamSynchronize(p->stream));
+        return snapshot_buffers(p);
+    };
+    const int rc = build();
+    if (rc) { /* the tracker stays as it was (the snapshot's buffers, if they were made, are the snapshot's) */
+        (void)hipGetLastError();
+        release(state[0]), release(state[1]), release(first), release(total), release(rx), release(d_table);
+        return rc;
+    }
+    p->pb_state[0] = state[0];
+    p->pb_state[1] = state[1];
+    p->d_pb_first = first;
+    p->d_pb_total = total;
+    p->d_pb_rx = rx;
+    p->d_pb_table = d_table;
+    return 0;
+}
+
+int msd_pos_aircraft_pb(msd_pos *p, const msd_pb_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_pb_receiver *rx)
+{
+    if (!p || !p->d_pb_table || !out_len || !msd_pb_options_ok(opt) || (!out && cap > 0))
+        return -EINVAL;
+    *out_len = 0;
+    if (p->live * MSD_PB_AIRCRAFT_MAX + (uint64_t)p->nrx * MSD_PB_HEADER_MAX > 0xFFFFFFFFull) {
+        snprintf(p->err, sizeof p->err, "%llu aircraft could take more than 2^32 - 1 bytes", (unsigned long long)p->live);
+        return -E2BIG;
+    }
+    POS_HIP(p, hipSetDevice(p->device));
+    const msd_pos_table t = p->tab[p->cur];
+    const uint32_t live = (uint32_t)p->live;
+    const size_t nitems = (size_t)live + p->nrx;
+    const uint32_t nblocks = (uint32_t)((nitems + 255u) / 256u);
+    if (nitems > p->cap_pb) {
+        release(p->d_pb_items), release(p->d_pb_within), release(p->d_pb_cwithin), release(p->d_pb_block);
+        release(p->d_pb_shadow), release(p->d_pb_lens);
+        p->cap_pb = 0;
+        POS_HIP(p, hipMalloc(&p->d_pb_items, sizeof(uint32_t) * nitems));
+        POS_HIP(p, hipMalloc(&p->d_pb_within, sizeof(uint32_t) * nitems));
+        POS_HIP(p, hipMalloc(&p->d_pb_cwithin, sizeof(uint32_t) * nitems));
+        POS_HIP(p, hipMalloc(&p->d_pb_block, sizeof(uint32_t) * 4u * ((size_t)nblocks + 1u)));
+        POS_HIP(p, hipMalloc(&p->d_pb_shadow, sizeof(uint64_t) * nitems));
+        POS_HIP(p, hipMalloc(&p->d_pb_lens, sizeof(uint16_t) * nitems));
+        p->cap_pb = nitems;
+    }
+    const uint64_t *d_total = nullptr;
+    if (opt->messages_total) {
+        POS_HIP(p, hipMemcpyAsync(p->d_pb_total, opt->messages_total, sizeof(uint64_t) * p->nrx, hipMemcpyHostToDevice, p->stream));
+        d_total = p->d_pb_total;
+    }
+    const uint32_t *idx = p->s_idx[0]; /* (not read without aircraft) */
+    if (live)
+        idx = msd_pos_launch_ordered_slots(p->stream, t, live, snapshot_key_bits(p), p->s_idx[0], p->s_idx[1], p->s_hist);
+    msd_pb_launch_lengths(p->stream, t, p->pb_state[p->cur], idx, live, p->nrx, opt->now_ms, d_total, p->d_pb_table,
+                          p->d_pb_first, p->d_pb_items, p->d_pb_shadow, p->d_pb_lens, p->d_pb_within, p->d_pb_cwithin,
+                          p->d_pb_block, p->d_pb_rx);
+    POS_HIP(p, hipGetLastError());
+    uint32_t need = 0;
+    POS_HIP(p, hipMemcpyAsync(&need, p->d_pb_block + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    *out_len = need;
+    if (need > cap) { /* no written state has moved: only the store kernel commits the shadow copy */
+        snprintf(p->err, sizeof p->err, "the aircraft.pb stream takes %u bytes, %zu were offered", need, cap);
+        return -ENOSPC;
+    }
+    if (need > p->cap_w_out) {
+        release(p->d_w_out);
+        p->cap_w_out = 0;
+        POS_HIP(p, hipMalloc(&p->d_w_out, need));
+        p->cap_w_out = need;
+    }
+    if (need) { /* (no byte: no aircraft was written, so no state moves either) */
+        msd_pb_launch_store(p->stream, t, p->pb_state[p->cur], idx, live, p->nrx, opt->now_ms, d_total, p->d_pb_table,
+                            p->d_pb_items, p->d_pb_shadow, p->d_pb_lens, p->d_pb_block, p->d_w_out);
+        POS_HIP(p, hipGetLastError());
+        POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
+    }
+    if (rx)
+        POS_HIP(p, hipMemcpyAsync(rx, p->d_pb_rx, sizeof(msd_pb_receiver) * p->nrx, hipMemcpyDeviceToHost, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -710,6 +843,10 @@ int msd_pos_expire(msd_pos *p, uint64_t now_ms)
     msd_pos_launch_fill(p->stream, p->tab[other].keys, p->tab[other].cap);
     msd_pos_launch_rebuild(p->stream, p->tab[p->cur], p->tab[other]);
     POS_HIP(p, hipGetLastError());
+    if (p->d_pb_table) {
+        msd_pb_launch_move(p->stream, p->tab[p->cur], p->pb_state[p->cur], p->tab[other], p->pb_state[other]);
+        POS_HIP(p, hipGetLastError());
+    }
     POS_HIP(p, hipStreamSynchronize(p->stream));
     p->cur = other;
     p->live -= ctl[MSD_POS_CTL_REMOVED];

@@ -74,5 +74,29 @@ void msd_sbs_launch_lengths(hipStream_t stream, const msd_message *msgs, const m
 void msd_sbs_launch_store(hipStream_t stream, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk,
                           uint32_t n, msd_sbs_options opt, const uint16_t *track_table, const uint8_t *lens,
                           const uint32_t *block_off, uint8_t *out, uint32_t *ends);
+/* the snapshot's ordering passes alone: the slots of the `live` aircraft in ascending key order -> the one of idx_a /
+ * idx_b that holds them (buffers as msd_pos_launch_snapshot's; live > 0) */
+const uint32_t *msd_pos_launch_ordered_slots(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits,
+                                             uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist);
+/* aircraft.pb (msd_pb_kernels.hip).  state: the written state, 8 bytes per slot beside the table (msd_pb_impl.h).
+ * fresh: a call's new aircraft start at 0 (slot / fresh as msd_pos_launch_find left them).  move: after
+ * msd_pos_launch_rebuild(from, to), every survivor's state follows it */
+#define MSD_PB_TILE 128u /* items per LDS image of the store kernel; tests/test_gpu_aircraft_pb.py sizes its receivers
+                            around this value (its TILE): change both together */
+void msd_pb_launch_fresh(hipStream_t stream, const uint32_t *slot, const uint8_t *fresh, uint32_t n, uint32_t cap, uint64_t *state);
+void msd_pb_launch_move(hipStream_t stream, msd_pos_table from, const uint64_t *from_state, msd_pos_table to, uint64_t *to_state);
+/* The items of a call are the nrx file heads and the live aircraft in stream order (live + nrx of them; idx: the ordered
+ * slots).  lengths: first[0 .. nrx], items[], and per item shadow (the next written state), lens, within / cwithin (the
+ * exclusive prefixes inside its workgroup of 256: bytes; the three counts, packed); block_sums: four arrays of
+ * ceil(items / 256) + 1 words -- bytes, written, with position, TIS-B --, the workgroups' offsets and then the total; rx:
+ * nrx rows.  store: the bytes to out (device memory, as many as block_sums' first total says), and every written
+ * aircraft's shadow into state */
+void msd_pb_launch_lengths(hipStream_t stream, msd_pos_table t, const uint64_t *state, const uint32_t *idx, uint32_t live,
+                           uint32_t nrx, uint64_t now_ms, const uint64_t *messages_total, const uint16_t *track_table,
+                           uint32_t *first, uint32_t *items, uint64_t *shadow, uint16_t *lens, uint32_t *within,
+                           uint32_t *cwithin, uint32_t *block_sums, msd_pb_receiver *rx);
+void msd_pb_launch_store(hipStream_t stream, msd_pos_table t, uint64_t *state, const uint32_t *idx, uint32_t live, uint32_t nrx,
+                         uint64_t now_ms, const uint64_t *messages_total, const uint16_t *track_table, const uint32_t *items,
+                         const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off, uint8_t *out);
 
 #endif

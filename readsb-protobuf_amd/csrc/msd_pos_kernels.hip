@@ -570,6 +570,12 @@ void msd_pos_launch_snapshot(hipStream_t stream, msd_pos_table t, uint32_t live,
     msd_trk_gather_kernel<<<blocks(live), NT, 0, stream>>>(t, idx, live, out);
 }
 
+const uint32_t *msd_pos_launch_ordered_slots(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits,
+                                             uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist)
+{
+    return ordered_slots(stream, t, live, key_bits, idx_a, idx_b, hist);
+}
+
 void msd_pos_launch_modeac_count(hipStream_t stream, const msd_message *msgs, const msd_fields *fields,
                                  const uint32_t *receiver, uint32_t nrx, uint32_t n, uint32_t *ac)
 {
