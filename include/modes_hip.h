@@ -1238,7 +1238,8 @@ typedef struct msd_pb_receiver { /* 24 bytes */
 /* -EINVAL on a tracker without a table; a second call returns 0 and changes nothing; -ENOMEM leaves the tracker as it was.
  * Allocates the written state (8 bytes per slot, twice; the aircraft the table already has start at 0) and builds on the
  * host and uploads a second ground-track table (4 x 1023 x 1023 entries of 16 bits, 8 MiB): the SBS table's shape with
- * the conversion to int32_t in place of rintf; the SBS table stays as it is.  msd_pos_reset zeroes the state and leaves
+ * the conversion to int32_t in place of rintf; the SBS table stays as it is; msd_pos_vrs_enable ("VRS output" below) uses
+ * the same table, and whichever of the two calls comes first builds it, once.  msd_pos_reset zeroes the state and leaves
  * the tracker enabled.  A tracker that never calls this allocates and launches what it did before and answers -EINVAL to
  * msd_pos_aircraft_pb. */
 int msd_pos_pb_enable(msd_pos *p);
@@ -1248,6 +1249,84 @@ int msd_pos_pb_enable(msd_pos *p);
  * repeated and gives the bytes the first call would have given.  -EINVAL: not enabled, NULL, an unknown flag,
  * reserved != 0.  -E2BIG: the table could hold more than 2^32 - 1 bytes of stream (above some 10 million aircraft). */
 int msd_pos_aircraft_pb(msd_pos *p, const msd_pb_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_pb_receiver *rx);
+
+/* ---- VRS output: readsb's Virtual Radar Server feed (--net-vrs-port, vrs_out in --net-connector) -- the JSON aircraft
+ * list generateVRS(part, n_parts) builds (net_io.c:3230-3377) and modesNetPeriodicWork sends one eighth of every 125 ms
+ * (:3175-3183) -- for a table tracker, one document per receiver index, written on the device from the table
+ * (DESIGN.md 4.10).  No state beyond the table: a call reads the table and changes nothing.
+ *
+ * A document (:3243, :3372) is `{"acList":[` + the aircraft objects separated by `,` + `]}\n`; a receiver with nothing
+ * selected writes the 14 bytes `{"acList":[]}\n`.
+ * Part (:3238-3246).  The reference walks buckets part * (2048 / n_parts) up to the next part's start, and an aircraft
+ * lives in bucket addr % 2048 (track.c:1016): it belongs to part (addr & 2047) >> (11 - log2(n_parts)).  One call writes
+ * one part of every receiver -- the reference's cadence is one part per 125 ms.
+ * Selection (:3248-3256), in integers: an aircraft is written when it is in the part, messages >= 2, addr has no
+ * MSD_NON_ICAO_ADDRESS, and the unsigned 64-bit difference now_ms - seen is <= 5000 (the reference compares that
+ * difference as a double against 5E3: the same).  An aircraft seen after now_ms is therefore NOT written -- the opposite
+ * of aircraft.pb, which writes it.
+ * Order: ascending address within a receiver, msd_pos_snapshot's.  The reference walks its buckets, newest first within
+ * one; the order of a JSON array means nothing to VRS.  This is the one deliberate difference, as in aircraft.pb.
+ * Keys, in order; "valid" is msd_aircraft_valid(a, member, now_ms) (generateVRS sets _messageNow = now, :3241):
+ *   "Sig":%.0f of the double 255 * ((signal_level[0] + ... + [7] + 1e-5) / 8), summed in that order (:3265)
+ *   ,"Icao":"%06X" of the 24 low bits (:3269)
+ *   ,"Alt":%d if altitude_baro is valid and altitude_baro_reliable >= 3 (:3271)
+ *   ,"GAlt":%d if altitude_geom is valid -- by its own stale and expiry members (:3273)
+ *   ,"InHg":%.2f of (double)nav_qnh * 0.02952998307, nav_qnh msd_aircraft_to_float's float, if nav_qnh is valid (:3277)
+ *   ,"TAlt":%d from nav_altitude_mcp if valid, else nav_altitude_fms if valid (:3282)
+ *   ,"Call":"<escaped>" if the callsign is valid (:3288)
+ *   ,"Lat":%f,"Long":%f,"PosTime":%llu of updated[MSD_AC_POSITION] if the position is valid (:3293)
+ *   ,"Mlat":true|false -- true when source[MSD_AC_POSITION] == 2 -- and ,"Tisb":true|false -- == 5; both read the source
+ *     alone, whether or not the position has expired (:3298-3305)
+ *   ,"Spd":..,"SpdTyp":.. from the first valid of gs (%d, 0), ias (%u, 2), tas (%u, 3) (:3308)
+ *   ,"Trak":%d,"TrkH":false|true from the first valid of track (false), mag_heading (true), true_heading (true): the
+ *     int32_t conversion aircraft.pb writes, a velocity's ground track out of msd_pos_pb_enable's table (:3319)
+ *   ,"TTrk":%d if nav_heading is valid (:3330);  ,"Sqk":"%04x" if the squawk is valid (:3333)
+ *   ,"Vsi":%d,"VsiT":1 from geom_rate if valid, else ,"Vsi":%d,"VsiT":0 from baro_rate if valid (:3336)
+ *   ,"Gnd":true only when airground is valid, its source is >= 4 and air_ground is 1 (ground), else ,"Gnd":false (:3345)
+ *   ,"Trt":%d of adsb_version + 3 when adsb_version >= 0, else 1 (:3350);  ,"Cmsgs":%llu of messages, then `}` (:3356)
+ * Escaping (jsonEscapeString :1786-1805) of the stored callsign up to its first NUL, at most 8 bytes: `"` and `\` get a
+ * backslash in front, a byte below 32 or above 127 becomes \u%04x of the unsigned byte, byte 127 goes out as it is.
+ * Numbers: the bytes are glibc printf's.  %f and %.2f are the exactly rounded decimal of the double (128-bit integer
+ * arithmetic, ties to even on the exact binary value, the sign kept: -0.000000), for |x| < 2^43; %.0f of the double is
+ * rint under the default rounding mode.  The builds use -ffp-contract=off: the double expressions are the same IEEE
+ * operations on both sides, and the device evaluates no libm function.
+ * What no decoder delivers -- a record's signalLevel is the caller's own double --: a Sig operand whose sign bit is set
+ * (-0.0 too), that is NaN, or at or above 2^32 is written as 0; a position whose latitude or longitude is not finite or
+ * beyond +-360 leaves Lat, Long and PosTime out.  So no object is longer than MSD_VRS_AIRCRAFT_MAX whatever the table
+ * holds.  The host object applies the same two rules: the contract has no exception.
+ * CONTRACT, the table's: the device and the host object (msd_pos_host_vrs_enable, msd_pos_host_vrs -- a plain sequential
+ * writer, snprintf with the reference's format strings, that shares no code with the device's) deliver the same stream
+ * and the same rows on every table on which they hold the same msd_aircraft bytes, whichever slots the aircraft occupy,
+ * with no margin.  Not built: sockets and writeJsonToNet's chunking. ---- */
+typedef struct msd_vrs_options { /* 24 bytes */
+    uint64_t now_ms;          /* mstime() of the write */
+    uint32_t part, n_parts;   /* n_parts: a power of two in 1 .. 2048 (readsb sends 8); part < n_parts */
+    uint32_t flags, reserved; /* 0 */
+} msd_vrs_options;
+typedef struct msd_vrs_receiver { /* 16 bytes, no implicit padding */
+    uint64_t end;      /* the end offset of this receiver's document in the stream; it begins at the end before it */
+    uint32_t aircraft; /* aircraft written */
+    uint32_t reserved; /* 0 */
+} msd_vrs_receiver;
+/* the longest aircraft object with its leading comma: 1 `,` + 17 `{"Sig":4294967296` + 16 `,"Icao":"FFFFFF"`
+ * + 18 `,"Alt":-2147483648` + 19 `,"GAlt":-2147483648` + 15 `,"InHg":1571.80` (nav_qnh_raw 65535: 53227.2 hPa)
+ * + 19 `,"TAlt":-2147483648` + 58 `,"Call":"` eight times the six of a byte above 127, `"` + 18 `,"Lat":-360.000000` + 19 `,"Long":-360.000000`
+ * + 31 `,"PosTime":18446744073709551615` + 13 `,"Mlat":false` + 13 `,"Tisb":false` + 18 `,"Spd":-2147483648` (%d of a gs
+ * above 2^31 - 1) + 11 `,"SpdTyp":0` + 14 `,"Trak":184317` (65535 x 360 / 128) + 13 `,"TrkH":false` + 13 `,"TTrk":65535`
+ * + 13 `,"Sqk":"ffff"` + 18 `,"Vsi":-2147483648` + 9 `,"VsiT":1` + 12 `,"Gnd":false` + 10 `,"Trt":130` (version 127)
+ * + 29 `,"Cmsgs":18446744073709551615` + 1 `}` = 418 */
+#define MSD_VRS_AIRCRAFT_MAX 418
+/* -EINVAL on a tracker without a table; a second call returns 0 and changes nothing; -ENOMEM leaves the tracker as it was.
+ * Makes sure msd_pos_pb_enable's truncating ground-track table is on the device: the two calls share one table, in either
+ * order, and it is never built twice.  msd_pos_reset leaves the tracker enabled.  A tracker that never calls this
+ * allocates and launches what it did before and answers -EINVAL to msd_pos_vrs. */
+int msd_pos_vrs_enable(msd_pos *p);
+/* Part opt->part of every receiver index 0 .. receivers-1 in ascending order, one JSON document each, as one dense stream
+ * in the host array out; rx: a host array of `receivers` rows, or NULL.
+ * -ENOSPC: cap is too small, *out_len is the size needed, nothing was written: the call can be repeated.  -EINVAL: not
+ * enabled, NULL, an unknown flag, reserved != 0, n_parts not a power of two in 1 .. 2048, part >= n_parts.  -E2BIG: the
+ * table could hold more than 2^32 - 1 bytes of stream (above some 10 million aircraft). */
+int msd_pos_vrs(msd_pos *p, const msd_vrs_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_vrs_receiver *rx);
 
 #ifdef __cplusplus
 }

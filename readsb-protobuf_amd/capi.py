@@ -243,6 +243,7 @@ EXPORTS = [
     "msd_pos_modeac_enable", "msd_pos_modeac_match", "msd_pos_modeac_codes", "msd_pos_modeac_hits", "msd_mode_c_to_a",
     "msd_pos_reduce_enable", "msd_pos_update_reduce", "msd_pos_reduce_wire",
     "msd_pos_sbs_enable", "msd_pos_update_sbs", "msd_pos_sbs_wire", "msd_pos_pb_enable", "msd_pos_aircraft_pb",
+    "msd_pos_vrs_enable", "msd_pos_vrs",
 ]
 
 _lib = None
@@ -1132,6 +1133,10 @@ PB_RECEIVER_DTYPE = np.dtype([("end", "<u8"), ("aircraft", "<u4"), ("with_positi
 assert PB_RECEIVER_DTYPE.itemsize == 24
 PB_AIRCRAFT_MAX = 415
 PB_RSSI_MARGIN_ULPS = 8.0
+# VRS output: a receiver's row of msd_pos_vrs (msd_vrs_receiver) and the longest aircraft object with its comma
+VRS_RECEIVER_DTYPE = np.dtype([("end", "<u8"), ("aircraft", "<u4"), ("reserved", "<u4")])
+assert VRS_RECEIVER_DTYPE.itemsize == 16
+VRS_AIRCRAFT_MAX = 418
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmsd_host.so")
 
 
@@ -1141,6 +1146,11 @@ class SbsOptions(C.Structure):
 
 class PbOptions(C.Structure):
     _fields_ = [("now_ms", C.c_uint64), ("messages_total", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class VrsOptions(C.Structure):
+    _fields_ = [("now_ms", C.c_uint64), ("part", C.c_uint32), ("n_parts", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class PosReceiver(C.Structure):
@@ -1185,11 +1195,14 @@ def _pos_lib(host):
         f = {k: getattr(L, pre + k) for k in ("create", "destroy", "reset", "set_receiver", "update", "expire", "get_stats",
                                               "create_table", "update_nicrc", "snapshot", "modeac_enable", "modeac_match",
                                               "modeac_codes", "modeac_hits", "reduce_enable", "update_reduce",
-                                              "reduce_wire", "sbs_enable", "update_sbs", "sbs_wire", "pb_enable", "aircraft_pb")}
+                                              "reduce_wire", "sbs_enable", "update_sbs", "sbs_wire", "pb_enable", "aircraft_pb",
+                                              "vrs_enable", "vrs")}
         dev = [] if host else [C.c_int]
         f["pb_enable"].argtypes = [C.c_void_p]
         f["aircraft_pb"].argtypes = [C.c_void_p, C.POINTER(PbOptions), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                      C.c_void_p] + ([C.POINTER(C.c_double)] if host else [])
+        f["vrs_enable"].argtypes = [C.c_void_p]
+        f["vrs"].argtypes = [C.c_void_p, C.POINTER(VrsOptions), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
         f["sbs_enable"].argtypes = [C.c_void_p]
         f["update_sbs"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [C.c_void_p] * 4
         f["sbs_wire"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [
@@ -1221,6 +1234,8 @@ def _pos_lib(host):
         if host:
             L.msd_pos_host_home_slot.restype = C.c_uint32
             L.msd_pos_host_home_slot.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+            L.msd_pos_host_vrs_object.restype = C.c_size_t
+            L.msd_pos_host_vrs_object.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
             L.msd_pos_host_reduce_timers.restype = C.c_int
             L.msd_pos_host_reduce_timers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             for name, n_ref, n_int in (("airborne", 0, 5), ("surface", 2, 5), ("relative", 2, 4)):
@@ -1239,7 +1254,7 @@ class PositionTracker:
     stream whose min_gate_margin_m on the twin stays above 1e-3 m."""
 
     def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False, table=False,
-                 modeac=False, reduce_interval_ms=None, sbs=False, pb=False):
+                 modeac=False, reduce_interval_ms=None, sbs=False, pb=False, vrs=False):
         """table=True: msd_pos_create_table -- the tracker also keeps the aircraft table (update_nicrc, snapshot).
         modeac=True (a table tracker): msd_pos_modeac_enable -- it also counts Mode A/C replies and matches them against
         its aircraft (modeac_match, modeac_codes, modeac_hits).
@@ -1247,7 +1262,9 @@ class PositionTracker:
         output (update_reduce, reduce_wire).
         sbs=True (a table tracker): msd_pos_sbs_enable -- update_sbs hands over a row per record and sbs_wire writes
         readsb's SBS (BaseStation) lines from them.
-        pb=True (a table tracker): msd_pos_pb_enable -- aircraft_pb writes every receiver's aircraft.pb from the table."""
+        pb=True (a table tracker): msd_pos_pb_enable -- aircraft_pb writes every receiver's aircraft.pb from the table.
+        vrs=True (a table tracker): msd_pos_vrs_enable -- vrs writes a part of every receiver's VRS JSON aircraft list
+        from the table."""
         self.host, self.table = host, table
         self.nrx = len(receivers) if receivers is not None else 1
         self.L, self.f = _pos_lib(host)
@@ -1269,6 +1286,8 @@ class PositionTracker:
                 self.sbs_enable()
             if pb:
                 self.pb_enable()
+            if vrs:
+                self.vrs_enable()
         except MsdError:
             self.close()
             raise
@@ -1410,6 +1429,32 @@ class PositionTracker:
     def aircraft_pb(self, now_ms, messages_total=None):
         """Every receiver's aircraft.pb at now_ms -> a list of bytes, one file per receiver index."""
         stream, rx = self.aircraft_pb_stream(now_ms, messages_total)
+        ends = [0] + [int(e) for e in rx["end"]]
+        return [stream[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
+    def vrs_enable(self):
+        self._check(self.f["vrs_enable"](self.h), "msd_pos_vrs_enable")
+
+    def vrs_stream(self, now_ms, part=0, n_parts=1, cap=None, flags=0, reserved=0):
+        """msd_pos_vrs -> (the stream of every receiver's document for this part, VRS_RECEIVER_DTYPE array).  cap: the
+        bytes offered (default: as many as are needed, asked for first); self.vrs_needed is *out_len of the last call."""
+        opt = VrsOptions(now_ms=now_ms, part=part, n_parts=n_parts, flags=flags, reserved=reserved)
+        need = C.c_size_t(0)
+        if cap is None:
+            rc = self.f["vrs"](self.h, C.byref(opt), None, 0, C.byref(need), None)
+            if rc not in (0, -errno.ENOSPC):
+                self._check(rc, "msd_pos_vrs")
+            cap = need.value
+        out = np.zeros(cap, dtype=np.uint8)
+        rx = np.zeros(self.nrx, dtype=VRS_RECEIVER_DTYPE)
+        rc = self.f["vrs"](self.h, C.byref(opt), out.ctypes.data if cap else None, cap, C.byref(need), rx.ctypes.data)
+        self.vrs_needed = need.value
+        self._check(rc, "msd_pos_vrs")
+        return out[:need.value].tobytes(), rx
+
+    def vrs(self, now_ms, part=0, n_parts=1):
+        """Part `part` of every receiver's VRS aircraft list at now_ms -> a list of bytes, one document per receiver index."""
+        stream, rx = self.vrs_stream(now_ms, part, n_parts)
         ends = [0] + [int(e) for e in rx["end"]]
         return [stream[a:b] for a, b in zip(ends[:-1], ends[1:])]
 

@@ -31,6 +31,7 @@ struct msd_pos_host {
     uint32_t reduce_interval;
     int sbs; /* SBS output (msd_pos_host_sbs_enable): the twin keeps nothing for it */
     uint64_t *pb_state; /* aircraft.pb (msd_pos_host_pb_enable), else NULL: the written state per slot */
+    int vrs; /* VRS output (msd_pos_host_vrs_enable): the twin keeps nothing for it */
 };
 
 int msd_cpr_host_airborne(int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag, double *lat, double *lon)
@@ -814,6 +815,181 @@ int msd_pos_host_aircraft_pb(msd_pos_host *p, const msd_pb_options *opt, uint8_t
     free(ks);
     if (min_rssi_margin_ulps)
         *min_rssi_margin_ulps = margin;
+    return 0;
+}
+
+/* ---- the VRS writer: generateVRS (net_io.c:3230-3377) and jsonEscapeString (:1786-1805) as a plain sequential writer
+ * over the exported entries, snprintf with the reference's own format strings, msd_aircraft_valid and
+ * msd_aircraft_to_float.  The yardstick of the device's writer (msd_vrs_impl.h): nothing of that file is used here. ---- */
+int msd_pos_host_vrs_enable(msd_pos_host *p)
+{
+    if (!p || !p->trk)
+        return -EINVAL;
+    p->vrs = 1; /* the twin keeps nothing for it */
+    return 0;
+}
+
+static const char *vrs_escape(const char *str, char *buf) /* jsonEscapeString over at most 8 bytes; buf: 8 x 6 + 1 */
+{
+    char *out = buf;
+    for (int i = 0; i < 8 && str[i]; ++i) {
+        const unsigned char ch = (unsigned char)str[i];
+        if (ch == '"' || ch == '\\') {
+            *out++ = '\\';
+            *out++ = (char)ch;
+        } else if (ch < 32 || ch > 127) {
+            out += snprintf(out, 7, "\\u%04x", ch);
+        } else {
+            *out++ = (char)ch;
+        }
+    }
+    *out = 0;
+    return buf;
+}
+
+size_t msd_pos_host_vrs_object(const msd_aircraft *a, uint64_t now, int comma, char *out)
+{
+    char *p = out, *const end = out + MSD_VRS_AIRCRAFT_MAX + 1;
+    char esc[49];
+    msd_aircraft_float fl;
+    msd_aircraft_to_float(a, &fl);
+#define VRS_PRINT(...) (p += snprintf(p, (size_t)(end - p), __VA_ARGS__))
+    if (comma)
+        *p++ = ',';
+    {
+        double sig = 255 * ((a->signal_level[0] + a->signal_level[1] + a->signal_level[2] + a->signal_level[3] +
+                             a->signal_level[4] + a->signal_level[5] + a->signal_level[6] + a->signal_level[7] + 1e-5) / 8);
+        if (signbit(sig) || !(sig < 4294967296.0)) /* modes_hip.h: what no decoder delivers is written as 0 */
+            sig = 0;
+        VRS_PRINT("{\"Sig\":%.0f", sig);
+    }
+    VRS_PRINT(",\"Icao\":\"%s%06X\"", "", a->addr & 0xFFFFFF); /* (non-ICAO addresses are not selected) */
+    if (msd_aircraft_valid(a, MSD_AC_ALTITUDE_BARO, now) && a->altitude_baro_reliable >= 3)
+        VRS_PRINT(",\"Alt\":%d", a->alt_baro);
+    if (msd_aircraft_valid(a, MSD_AC_ALTITUDE_GEOM, now))
+        VRS_PRINT(",\"GAlt\":%d", a->alt_geom);
+    if (msd_aircraft_valid(a, MSD_AC_NAV_QNH, now))
+        VRS_PRINT(",\"InHg\":%.2f", fl.nav_qnh * 0.02952998307);
+    if (msd_aircraft_valid(a, MSD_AC_NAV_ALTITUDE_MCP, now))
+        VRS_PRINT(",\"TAlt\":%d", a->nav_altitude_mcp);
+    else if (msd_aircraft_valid(a, MSD_AC_NAV_ALTITUDE_FMS, now))
+        VRS_PRINT(",\"TAlt\":%d", a->nav_altitude_fms);
+    if (msd_aircraft_valid(a, MSD_AC_CALLSIGN, now))
+        VRS_PRINT(",\"Call\":\"%s\"", vrs_escape(a->callsign, esc));
+    if (msd_aircraft_valid(a, MSD_AC_POSITION, now) && fabs(a->lat) <= 360.0 && fabs(a->lon) <= 360.0) { /* modes_hip.h */
+        VRS_PRINT(",\"Lat\":%f,\"Long\":%f", a->lat, a->lon);
+        VRS_PRINT(",\"PosTime\":%llu", (unsigned long long)a->updated[MSD_AC_POSITION]);
+    }
+    if (a->source[MSD_AC_POSITION] == 2) /* SOURCE_MLAT */
+        VRS_PRINT(",\"Mlat\":true");
+    else
+        VRS_PRINT(",\"Mlat\":false");
+    if (a->source[MSD_AC_POSITION] == 5) /* SOURCE_TISB */
+        VRS_PRINT(",\"Tisb\":true");
+    else
+        VRS_PRINT(",\"Tisb\":false");
+    if (msd_aircraft_valid(a, MSD_AC_GS, now)) {
+        VRS_PRINT(",\"Spd\":%d", (int)a->gs);
+        VRS_PRINT(",\"SpdTyp\":0");
+    } else if (msd_aircraft_valid(a, MSD_AC_IAS, now)) {
+        VRS_PRINT(",\"Spd\":%u", a->ias);
+        VRS_PRINT(",\"SpdTyp\":2");
+    } else if (msd_aircraft_valid(a, MSD_AC_TAS, now)) {
+        VRS_PRINT(",\"Spd\":%u", a->tas);
+        VRS_PRINT(",\"SpdTyp\":3");
+    }
+    if (msd_aircraft_valid(a, MSD_AC_TRACK, now)) {
+        VRS_PRINT(",\"Trak\":%d", pb_heading(&a->track, fl.track));
+        VRS_PRINT(",\"TrkH\":false");
+    } else if (msd_aircraft_valid(a, MSD_AC_MAG_HEADING, now)) {
+        VRS_PRINT(",\"Trak\":%d", pb_heading(&a->mag_heading, fl.mag_heading));
+        VRS_PRINT(",\"TrkH\":true");
+    } else if (msd_aircraft_valid(a, MSD_AC_TRUE_HEADING, now)) {
+        VRS_PRINT(",\"Trak\":%d", pb_heading(&a->true_heading, fl.true_heading));
+        VRS_PRINT(",\"TrkH\":true");
+    }
+    if (msd_aircraft_valid(a, MSD_AC_NAV_HEADING, now))
+        VRS_PRINT(",\"TTrk\":%d", (int32_t)fl.nav_heading);
+    if (msd_aircraft_valid(a, MSD_AC_SQUAWK, now))
+        VRS_PRINT(",\"Sqk\":\"%04x\"", a->squawk);
+    if (msd_aircraft_valid(a, MSD_AC_GEOM_RATE, now)) {
+        VRS_PRINT(",\"Vsi\":%d", a->geom_rate);
+        VRS_PRINT(",\"VsiT\":1");
+    } else if (msd_aircraft_valid(a, MSD_AC_BARO_RATE, now)) {
+        VRS_PRINT(",\"Vsi\":%d", a->baro_rate);
+        VRS_PRINT(",\"VsiT\":0");
+    }
+    if (msd_aircraft_valid(a, MSD_AC_AIRGROUND, now) && a->source[MSD_AC_AIRGROUND] >= 4 /* SOURCE_MODE_S_CHECKED */ &&
+        a->air_ground == 1 /* AG_GROUND */)
+        VRS_PRINT(",\"Gnd\":true");
+    else
+        VRS_PRINT(",\"Gnd\":false");
+    if (a->adsb_version >= 0)
+        VRS_PRINT(",\"Trt\":%d", a->adsb_version + 3);
+    else
+        VRS_PRINT(",\"Trt\":%d", 1);
+    VRS_PRINT(",\"Cmsgs\":%llu", (unsigned long long)a->messages);
+    VRS_PRINT("}");
+#undef VRS_PRINT
+    return (size_t)(p - out);
+}
+
+int msd_pos_host_vrs(msd_pos_host *p, const msd_vrs_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_vrs_receiver *rx)
+{
+    if (!p || !p->vrs || !out_len || !opt || opt->flags != 0 || opt->reserved != 0 || (!out && cap > 0))
+        return -EINVAL;
+    const uint32_t n_parts = opt->n_parts;
+    if (n_parts < 1 || n_parts > 2048 || (n_parts & (n_parts - 1)) != 0 || opt->part >= n_parts)
+        return -EINVAL;
+    *out_len = 0;
+    uint64_t *ks = NULL;
+    if (p->live && !(ks = ordered_slots(p)))
+        return -ENOMEM;
+    const uint64_t now = opt->now_ms;
+    const uint32_t part_len = 2048 / n_parts, part_start = opt->part * part_len; /* AIRCRAFTS_BUCKETS / n_parts */
+    for (int pass = 0; pass < 2; ++pass) { /* the size first: a stream that does not fit leaves out alone */
+        size_t n = 0, j = 0;
+        for (uint32_t r = 0; r < p->nrx; ++r) {
+            msd_vrs_receiver row = {0, 0, 0};
+            int first = 1;
+            if (pass)
+                memcpy(out + n, "{\"acList\":[", 11);
+            n += 11;
+            for (; j < p->live && (ks[2 * j] >> 25) == r; ++j) {
+                const uint64_t s = ks[2 * j + 1];
+                msd_aircraft e;
+                msd_trk_export(ks[2 * j], &p->st[s], &p->trk[s], &e);
+                const uint32_t bucket = e.addr % 2048; /* track.c:1016 */
+                if (bucket < part_start || bucket >= part_start + part_len)
+                    continue;
+                if (e.messages < 2)
+                    continue;
+                if ((double)(now - e.seen) > 5E3)
+                    continue;
+                if (e.addr & MSD_NON_ICAO_ADDRESS)
+                    continue;
+                char obj[MSD_VRS_AIRCRAFT_MAX + 2];
+                const size_t k = msd_pos_host_vrs_object(&e, now, !first, obj);
+                first = 0;
+                if (pass)
+                    memcpy(out + n, obj, k);
+                n += k;
+                row.aircraft++;
+            }
+            if (pass)
+                memcpy(out + n, "]}\n", 3);
+            n += 3;
+            row.end = n;
+            if (pass && rx)
+                rx[r] = row;
+        }
+        *out_len = n;
+        if (n > cap) {
+            free(ks);
+            return -ENOSPC;
+        }
+    }
+    free(ks);
     return 0;
 }
 

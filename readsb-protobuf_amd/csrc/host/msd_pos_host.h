@@ -50,6 +50,13 @@ int msd_pos_host_sbs_wire(msd_pos_host *p, const msd_message *msgs, const msd_fi
 int msd_pos_host_pb_enable(msd_pos_host *p);
 int msd_pos_host_aircraft_pb(msd_pos_host *p, const msd_pb_options *opt, uint8_t *out, size_t cap, size_t *out_len,
                              msd_pb_receiver *rx, double *min_rssi_margin_ulps);
+/* VRS output (modes_hip.h, "VRS output"): msd_pos_vrs_enable and msd_pos_vrs on the host -- a plain sequential writer
+ * over msd_pos_host_snapshot's entries, snprintf with the reference's format strings, the yardstick of the device's
+ * writer.  msd_pos_host_vrs_object: one entry's object at now_ms, with a comma in front when `comma`, into out
+ * (MSD_VRS_AIRCRAFT_MAX + 1 bytes at least; NUL-terminated) -> its length; it does not look at selection */
+int msd_pos_host_vrs_enable(msd_pos_host *p);
+int msd_pos_host_vrs(msd_pos_host *p, const msd_vrs_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_vrs_receiver *rx);
+size_t msd_pos_host_vrs_object(const msd_aircraft *a, uint64_t now_ms, int comma, char *out);
 /* for tests: the MSD_AC_N + 1 timers of one aircraft (the members' in MSD_AC_* order, then the DF11 timer) into out;
  * -ENOENT: no such aircraft */
 int msd_pos_host_reduce_timers(const msd_pos_host *p, uint32_t receiver, uint32_t addr, uint64_t *out);

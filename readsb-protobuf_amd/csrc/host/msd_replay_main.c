@@ -22,6 +22,8 @@
  * beast_reduce_out to FILE (--net-beast-reduce-out-port, --net-beast-reduce-interval; default 0.125 s, at most 15): the
  * Beast frames of the messages that brought their aircraft something new (msd_pos_update_reduce, msd_pos_reduce_wire).
  *
+ * `--positions --aircraft --vrs-out FILE [--vrs-parts N]` writes receiver 0's VRS JSON aircraft list (msd_pos_vrs) to FILE
+ * once, after the last message, with now = that message's time: the documents of parts 0 .. N-1 one after the other.
  * `--positions --aircraft --aircraft-pb FILE` writes receiver 0's aircraft.pb (readsb's AircraftsUpdate protobuf,
  * msd_pos_aircraft_pb) to FILE once, after the last message, with now = that message's time and `messages` = the messages
  * this run delivered.
@@ -189,6 +191,44 @@ static int write_aircraft_pb(int want_stats)
     else if (want_stats)
         fprintf(stderr, "aircraft.pb aircraft,%u,with_positions,%u,bytes,%zu\n", row.aircraft, row.with_positions, len);
     free(bytes);
+    return bad;
+}
+
+/* --vrs-out: after the last message, receiver 0's VRS documents for parts 0 .. g_vrs_parts - 1, one after the other, at
+ * now_ms = the last message's time (msd_pos_vrs: the size first, then the bytes) */
+static const char *g_vrs_path;
+static uint32_t g_vrs_parts = 8; /* readsb's: one eighth of the list every 125 ms (net_io.c:3175-3183) */
+static int write_vrs(int want_stats)
+{
+    FILE *out = fopen(g_vrs_path, "wb");
+    int rc = 0, bad = !out;
+    size_t bytes_written = 0;
+    uint32_t aircraft = 0;
+    for (uint32_t part = 0; out && !bad && part < g_vrs_parts; ++part) {
+        msd_vrs_options opt;
+        memset(&opt, 0, sizeof opt);
+        opt.now_ms = g_last_ms;
+        opt.part = part;
+        opt.n_parts = g_vrs_parts;
+        msd_vrs_receiver row;
+        size_t len = 0;
+        rc = msd_pos_vrs(g_pos, &opt, NULL, 0, &len, NULL);
+        uint8_t *bytes = rc == -ENOSPC ? malloc(len) : NULL;
+        if (rc == -ENOSPC && bytes)
+            rc = msd_pos_vrs(g_pos, &opt, bytes, len, &len, &row);
+        bad = rc != 0 || fwrite(bytes, 1, len, out) != len;
+        if (!bad) {
+            bytes_written += len;
+            aircraft += row.aircraft;
+        }
+        free(bytes);
+    }
+    if (out)
+        bad |= fclose(out) != 0;
+    if (bad)
+        fprintf(stderr, "--vrs-out %s: %s (%d)\n", g_vrs_path, rc ? msd_pos_last_error(g_pos) : "cannot write", rc);
+    else if (want_stats)
+        fprintf(stderr, "vrs parts,%u,aircraft,%u,bytes,%zu\n", g_vrs_parts, aircraft, bytes_written);
     return bad;
 }
 
@@ -487,6 +527,8 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--net-only")) net_only = 1; /* readsb.c: Modes.net_only */
         else if (!strcmp(a, "--sbs-out") && next) { sbs_path = next; ++i; }
         else if (!strcmp(a, "--aircraft-pb") && next) { g_pb_path = next; ++i; }
+        else if (!strcmp(a, "--vrs-out") && next) { g_vrs_path = next; ++i; }
+        else if (!strcmp(a, "--vrs-parts") && next) { g_vrs_parts = (uint32_t)strtoul(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--gnss")) gnss = 1; /* readsb.c: Modes.use_gnss */
         else if (!strcmp(a, "--utc-offset") && next) { utc_offset_s = atof(next); ++i; }
         else if (!strcmp(a, "--clock-start-ms") && next) { g_clock_start_ms = strtoull(next, NULL, 10); ++i; }
@@ -516,7 +558,8 @@ int main(int argc, char **argv)
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
                             "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft [--match-modeac] "
                             "[--beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]] "
-                            "[--sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]] [--aircraft-pb FILE]] [--clock-start-ms N]]\n"
+                            "[--sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]] [--aircraft-pb FILE] "
+                            "[--vrs-out FILE [--vrs-parts N]]] [--clock-start-ms N]]\n"
                             "       --positions: the --raw lines, with \"lat,lon\" behind the ';' of every message from which readsb's tracker\n"
                             "       would have decoded a position (CPR global and local, its range and speed checks; the coordinates are exact, the\n"
                             "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
@@ -533,6 +576,9 @@ int main(int argc, char **argv)
                             "       most 15) and member; a first message only with --net-only or --net-verbatim.\n"
                             "       --aircraft-pb FILE (with --aircraft): after the last message, readsb's aircraft.pb (the AircraftsUpdate\n"
                             "       protobuf) of the table, written on the GPU; now = the last message's time, messages = this run's count.\n"
+                            "       --vrs-out FILE (with --aircraft): after the last message, readsb's VRS JSON aircraft list of the table,\n"
+                            "       written on the GPU: the documents of parts 0 .. N-1 one after the other (--vrs-parts N, a power of two up to\n"
+                            "       2048, default 8 as readsb sends them); now = the last message's time.\n"
                             "       --sbs-out FILE (with --aircraft): readsb's SBS (BaseStation) output to FILE, one MSG line per message of a\n"
                             "       tracked aircraft; --gnss: geometric altitudes and rates first, marked H; --utc-offset: the zone the dates\n"
                             "       are written in, seconds east of UTC (default 0, at most a day); the \"now\" of fields 9-10 is the message's own time.\n"
@@ -557,6 +603,14 @@ int main(int argc, char **argv)
     }
     if (g_pb_path && !want_aircraft) {
         fprintf(stderr, "--aircraft-pb goes with --positions --aircraft\n");
+        return 2;
+    }
+    if (g_vrs_path && !want_aircraft) {
+        fprintf(stderr, "--vrs-out goes with --positions --aircraft\n");
+        return 2;
+    }
+    if (g_vrs_parts == 0 || g_vrs_parts > 2048 || (g_vrs_parts & (g_vrs_parts - 1)) != 0) {
+        fprintf(stderr, "--vrs-parts is a power of two from 1 to 2048\n");
         return 2;
     }
     if (sbs_path && !want_aircraft) {
@@ -634,6 +688,11 @@ int main(int argc, char **argv)
             msd_pos_destroy(g_pos);
             return 1;
         }
+        if (g_vrs_path && msd_pos_vrs_enable(g_pos) != 0) {
+            fprintf(stderr, "--vrs-out %s: %s\n", g_vrs_path, msd_pos_last_error(g_pos));
+            msd_pos_destroy(g_pos);
+            return 1;
+        }
         rx.sink = print_raw_positions;
     }
     if (avr_in || beast_in) {
@@ -646,6 +705,8 @@ int main(int argc, char **argv)
         if (g_sbs_out && sbs_finish(want_stats))
             g_pos_failed = 1;
         if (g_pb_path && !rc && write_aircraft_pb(want_stats))
+            g_pos_failed = 1;
+        if (g_vrs_path && !rc && write_vrs(want_stats))
             g_pos_failed = 1;
         msd_pos_destroy(g_pos);
         return rc ? rc : g_pos_failed;
@@ -696,6 +757,8 @@ int main(int argc, char **argv)
     if (g_sbs_out && sbs_finish(want_stats))
         g_pos_failed = 1;
     if (g_pb_path && write_aircraft_pb(want_stats))
+        g_pos_failed = 1;
+    if (g_vrs_path && write_vrs(want_stats))
         g_pos_failed = 1;
     msd_pos_destroy(g_pos);
     return g_pos_failed ? 1 : 0;

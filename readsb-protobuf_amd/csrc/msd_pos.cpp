@@ -10,6 +10,7 @@
 
 #include "msd_pos.h"
 #include "msd_pb_impl.h"
+#include "msd_vrs_impl.h"
 #include "msd_sbs_impl.h"
 
 struct msd_pos {
@@ -73,6 +74,17 @@ struct msd_pos {
     uint32_t *d_pb_items = nullptr, *d_pb_within = nullptr, *d_pb_cwithin = nullptr, *d_pb_block = nullptr;
     uint64_t *d_pb_shadow = nullptr;
     uint16_t *d_pb_lens = nullptr;
+    /* the truncating ground-track table aircraft.pb and the VRS output share: built by whichever of msd_pos_pb_enable and
+     * msd_pos_vrs_enable comes first, owned here; d_pb_table is the same pointer once pb is enabled */
+    uint16_t *d_trunc_table = nullptr;
+    /* VRS output (msd_pos_vrs_enable): the writer's buffers -- per receiver (made at the enable), per item (grown to the
+     * largest call seen); the stream is the reduced writer's */
+    bool vrs = false;
+    uint32_t *d_vrs_first = nullptr;
+    msd_vrs_receiver *d_vrs_rx = nullptr;
+    size_t cap_vrs = 0;
+    uint32_t *d_vrs_items = nullptr, *d_vrs_within = nullptr, *d_vrs_sel = nullptr, *d_vrs_block = nullptr;
+    uint16_t *d_vrs_lens = nullptr, *d_vrs_swithin = nullptr;
     char err[256] = "";
 };
 
@@ -256,9 +268,11 @@ void msd_pos_destroy(msd_pos *p)
     release(p->d_forward), release(p->d_w_msgs), release(p->d_w_forward), release(p->d_w_lens), release(p->d_w_out);
     release(p->d_w_block), release(p->d_w_ends);
     release(p->d_track_table), release(p->d_sbs), release(p->d_s_trk), release(p->d_s_msgs), release(p->d_s_fields);
-    release(p->pb_state[0]), release(p->pb_state[1]), release(p->d_pb_table), release(p->d_pb_first), release(p->d_pb_total);
+    release(p->pb_state[0]), release(p->pb_state[1]), release(p->d_trunc_table), release(p->d_pb_first), release(p->d_pb_total);
     release(p->d_pb_rx), release(p->d_pb_items), release(p->d_pb_within), release(p->d_pb_cwithin), release(p->d_pb_block);
     release(p->d_pb_shadow), release(p->d_pb_lens);
+    release(p->d_vrs_first), release(p->d_vrs_rx), release(p->d_vrs_items), release(p->d_vrs_within), release(p->d_vrs_sel);
+    release(p->d_vrs_block), release(p->d_vrs_lens), release(p->d_vrs_swithin);
     release(p->d_ac), release(p->d_c_to_a), release(p->d_codes), release(p->d_hits_out);
     release(p->d_nicrc), release(p->s_idx[0]), release(p->s_idx[1]), release(p->s_hist), release(p->d_snap);
     release(p->d_rx), release(p->d_stats), release(p->d_ctl), release(p->d_slot), release(p->d_fresh), release(p->d_out);
@@ -492,13 +506,13 @@ int msd_pos_sbs_wire(msd_pos *p, const msd_message *msgs, const msd_fields *fiel
     return 0;
 }
 
-int msd_pos_pb_enable(msd_pos *p)
+namespace {
+
+/* the truncating ground-track table on the device, built once for aircraft.pb and the VRS output */
+int trunc_table(msd_pos *p)
 {
-    if (!p || !p->table)
-        return -EINVAL;
-    if (p->d_pb_table)
+    if (p->d_trunc_table)
         return 0;
-    POS_HIP(p, hipSetDevice(p->device));
     std::vector<uint16_t> table;
     try {
         table.resize(MSD_PB_TRACK_ENTRIES);
@@ -507,6 +521,35 @@ int msd_pos_pb_enable(msd_pos *p)
     }
     msd_pb_build_track_table(table.data());
     uint16_t *d_table = nullptr;
+    const auto build = [&]() -> int {
+        POS_HIP(p, hipMalloc(&d_table, sizeof(uint16_t) * MSD_PB_TRACK_ENTRIES));
+        POS_HIP(p, hipMemcpyAsync(d_table, table.data(), sizeof(uint16_t) * MSD_PB_TRACK_ENTRIES, hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipStreamSynchronize(p->stream));
+        return 0;
+    };
+    const int rc = build();
+    if (rc) {
+        (void)hipGetLastError();
+        release(d_table);
+        return rc;
+    }
+    p->d_trunc_table = d_table;
+    return 0;
+}
+
+} // namespace
+
+int msd_pos_pb_enable(msd_pos *p)
+{
+    if (!p || !p->table)
+        return -EINVAL;
+    if (p->d_pb_table)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    const bool had_table = p->d_trunc_table != nullptr;
+    const int made = trunc_table(p);
+    if (made)
+        return made;
     uint64_t *state[2] = {nullptr, nullptr}, *total = nullptr;
     uint32_t *first = nullptr;
     msd_pb_receiver *rx = nullptr;
@@ -518,15 +561,15 @@ int msd_pos_pb_enable(msd_pos *p)
         POS_HIP(p, hipMalloc(&first, sizeof(uint32_t) * ((size_t)p->nrx + 1u)));
         POS_HIP(p, hipMalloc(&total, sizeof(uint64_t) * p->nrx));
         POS_HIP(p, hipMalloc(&rx, sizeof(msd_pb_receiver) * p->nrx));
-        POS_HIP(p, hipMalloc(&d_table, sizeof(uint16_t) * MSD_PB_TRACK_ENTRIES));
-        POS_HIP(p, hipMemcpyAsync(d_table, table.data(), sizeof(uint16_t) * MSD_PB_TRACK_ENTRIES, hipMemcpyHostToDevice, p->stream));
         POS_HIP(p, hipStreamSynchronize(p->stream));
         return snapshot_buffers(p);
     };
     const int rc = build();
     if (rc) { /* the tracker stays as it was (the snapshot's buffers, if they were made, are the snapshot's) */
         (void)hipGetLastError();
-        release(state[0]), release(state[1]), release(first), release(total), release(rx), release(d_table);
+        release(state[0]), release(state[1]), release(first), release(total), release(rx);
+        if (!had_table)
+            release(p->d_trunc_table);
         return rc;
     }
     p->pb_state[0] = state[0];
@@ -534,7 +577,97 @@ int msd_pos_pb_enable(msd_pos *p)
     p->d_pb_first = first;
     p->d_pb_total = total;
     p->d_pb_rx = rx;
-    p->d_pb_table = d_table;
+    p->d_pb_table = p->d_trunc_table;
+    return 0;
+}
+
+int msd_pos_vrs_enable(msd_pos *p)
+{
+    if (!p || !p->table)
+        return -EINVAL;
+    if (p->vrs)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    const bool had_table = p->d_trunc_table != nullptr;
+    const int made = trunc_table(p);
+    if (made)
+        return made;
+    uint32_t *first = nullptr;
+    msd_vrs_receiver *rx = nullptr;
+    const auto build = [&]() -> int {
+        POS_HIP(p, hipMalloc(&first, sizeof(uint32_t) * ((size_t)p->nrx + 1u)));
+        POS_HIP(p, hipMalloc(&rx, sizeof(msd_vrs_receiver) * p->nrx));
+        return snapshot_buffers(p);
+    };
+    const int rc = build();
+    if (rc) { /* the tracker stays as it was (the snapshot's buffers, if they were made, are the snapshot's) */
+        (void)hipGetLastError();
+        release(first), release(rx);
+        if (!had_table)
+            release(p->d_trunc_table);
+        return rc;
+    }
+    p->d_vrs_first = first;
+    p->d_vrs_rx = rx;
+    p->vrs = true;
+    return 0;
+}
+
+int msd_pos_vrs(msd_pos *p, const msd_vrs_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_vrs_receiver *rx)
+{
+    const int shift = msd_vrs_part_shift(opt);
+    if (!p || !p->vrs || !out_len || shift < 0 || (!out && cap > 0))
+        return -EINVAL;
+    *out_len = 0;
+    if (p->live * MSD_VRS_AIRCRAFT_MAX + (uint64_t)p->nrx * (MSD_VRS_HEAD_LEN + MSD_VRS_TAIL_LEN) > 0xFFFFFFFFull) {
+        snprintf(p->err, sizeof p->err, "%llu aircraft could take more than 2^32 - 1 bytes", (unsigned long long)p->live);
+        return -E2BIG;
+    }
+    POS_HIP(p, hipSetDevice(p->device));
+    const msd_pos_table t = p->tab[p->cur];
+    const uint32_t live = (uint32_t)p->live;
+    const size_t nitems = (size_t)live + 2u * (size_t)p->nrx;
+    const uint32_t nblocks = (uint32_t)((nitems + 255u) / 256u);
+    if (nitems > p->cap_vrs) {
+        release(p->d_vrs_items), release(p->d_vrs_within), release(p->d_vrs_sel), release(p->d_vrs_block);
+        release(p->d_vrs_lens), release(p->d_vrs_swithin);
+        p->cap_vrs = 0;
+        POS_HIP(p, hipMalloc(&p->d_vrs_items, sizeof(uint32_t) * nitems));
+        POS_HIP(p, hipMalloc(&p->d_vrs_within, sizeof(uint32_t) * nitems));
+        POS_HIP(p, hipMalloc(&p->d_vrs_sel, sizeof(uint32_t) * ((size_t)nblocks + 1u)));
+        POS_HIP(p, hipMalloc(&p->d_vrs_block, sizeof(uint32_t) * ((size_t)nblocks + 1u)));
+        POS_HIP(p, hipMalloc(&p->d_vrs_lens, sizeof(uint16_t) * nitems));
+        POS_HIP(p, hipMalloc(&p->d_vrs_swithin, sizeof(uint16_t) * nitems));
+        p->cap_vrs = nitems;
+    }
+    const uint32_t *idx = p->s_idx[0]; /* (not read without aircraft) */
+    if (live)
+        idx = msd_pos_launch_ordered_slots(p->stream, t, live, snapshot_key_bits(p), p->s_idx[0], p->s_idx[1], p->s_hist);
+    const msd_vrs_call c = {t, idx, p->d_vrs_items, p->d_vrs_first, p->d_trunc_table, opt->now_ms, (uint32_t)nitems, p->nrx,
+                            opt->part, (uint32_t)shift};
+    msd_vrs_launch_lengths(p->stream, c, live, p->d_vrs_first, p->d_vrs_items, p->d_vrs_lens, p->d_vrs_swithin, p->d_vrs_within,
+                           p->d_vrs_sel, p->d_vrs_block, p->d_vrs_rx);
+    POS_HIP(p, hipGetLastError());
+    uint32_t need = 0;
+    POS_HIP(p, hipMemcpyAsync(&need, p->d_vrs_block + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    *out_len = need;
+    if (need > cap) {
+        snprintf(p->err, sizeof p->err, "the VRS stream takes %u bytes, %zu were offered", need, cap);
+        return -ENOSPC;
+    }
+    if (need > p->cap_w_out) {
+        release(p->d_w_out);
+        p->cap_w_out = 0;
+        POS_HIP(p, hipMalloc(&p->d_w_out, need));
+        p->cap_w_out = need;
+    }
+    msd_vrs_launch_store(p->stream, c, p->d_vrs_lens, p->d_vrs_block, p->d_w_out); /* (need >= 14: a receiver's frame) */
+    POS_HIP(p, hipGetLastError());
+    POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
+    if (rx)
+        POS_HIP(p, hipMemcpyAsync(rx, p->d_vrs_rx, sizeof(msd_vrs_receiver) * p->nrx, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
 }
 

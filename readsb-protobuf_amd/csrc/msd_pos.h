@@ -98,5 +98,23 @@ void msd_pb_launch_lengths(hipStream_t stream, msd_pos_table t, const uint64_t *
 void msd_pb_launch_store(hipStream_t stream, msd_pos_table t, uint64_t *state, const uint32_t *idx, uint32_t live, uint32_t nrx,
                          uint64_t now_ms, const uint64_t *messages_total, const uint16_t *track_table, const uint32_t *items,
                          const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off, uint8_t *out);
+/* VRS output (msd_vrs_kernels.hip).  The items of a call are, per receiver, a head, its live aircraft and a tail, in
+ * stream order (live + 2 * nrx of them; idx: the ordered slots).  select: first[0 .. nrx], items[], and per item lens
+ * (an aircraft's without its comma; 0: not selected) and swithin (the selected aircraft before it inside its workgroup of
+ * 256); sel_sums: ceil(items / 256) + 1 words, the workgroups' offsets and then the total.  lengths: the comma goes into
+ * lens, within (the bytes before the item inside its workgroup) and byte_sums follow, rx: nrx rows.  store: the bytes to
+ * out (device memory, as many as byte_sums' total says) */
+#define MSD_VRS_TILE 128u /* items per LDS image of the store kernel; tests/vrs_streams.py sizes its receivers around
+                             this value (its TILE): change both together */
+typedef struct msd_vrs_call {
+    msd_pos_table t;
+    const uint32_t *idx, *items, *first;
+    const uint16_t *track_table;
+    uint64_t now_ms;
+    uint32_t nitems, nrx, part, part_shift;
+} msd_vrs_call;
+void msd_vrs_launch_lengths(hipStream_t stream, msd_vrs_call c, uint32_t live, uint32_t *first, uint32_t *items, uint16_t *lens,
+                            uint16_t *swithin, uint32_t *within, uint32_t *sel_sums, uint32_t *byte_sums, msd_vrs_receiver *rx);
+void msd_vrs_launch_store(hipStream_t stream, msd_vrs_call c, const uint16_t *lens, const uint32_t *block_off, uint8_t *out);
 
 #endif
