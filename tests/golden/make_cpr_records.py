@@ -16,6 +16,18 @@ Cases (kind 0 airborne, 1 surface, 2 relative):
   poles, wrap   latitudes at and next to +-90, longitudes at and next to +-180
   quadrants     surface pairs around a reference in each of the four longitude quadrants and both hemispheres, and
                 the encodes-to-zero latitudes (cpr.c:264-280)
+
+A second file, tests/golden/cpr/cpr_chained.npz, holds the chained family (chained() below): an airborne pair encoded at a
+place, decodeCPRairborne's answer P for it, and decodeCPRrelative's answer for a third half -- either parity, airborne
+or surface -- encoded at the place plus an offset and decoded against exactly P.  It is what the position tracker can be
+given for its aircraft-relative decode (tests/cpr_sweep.py).
+  places        every NL transition latitude +-1e-6 and +-3e-3 in both hemispheres at longitudes 0.3 and +-179.9995; +-89.99,
+                +-87, 0 and +-1e-7 against +-180, +-179.99999, 0 and 90; 150 random places.  A place at or 1e-6 from a
+                transition whose halves round to different sides of it has no P: it is moved away from the transition
+                (from +-87 towards the equator) by up to 1e-4 degrees until its pair decodes.
+  offsets       CHAIN_OFFSETS: nothing, either side of the surface half cell of 0.75 degrees, either side of the 100 NM
+                limit, just inside the airborne half cell
+A run leaves a file whose recorded arrays have not changed as it is, byte for byte, and refuses to change cpr_reference.npz.
 """
 import os
 import pathlib
@@ -105,29 +117,140 @@ def cases():
     return out
 
 
+CHAIN_OFFSETS = ((0.0, 0.0), (0.01, -0.01), (-0.3, 0.4), (0.74, 0.0), (-0.76, 0.2), (1.4, -1.0), (-1.6, 0.9), (0.0, 1.6),
+                 (2.9, 0.0))
+CHAIN_LIMIT_M = 1852.0 * 100
+CHAIN_RANDOM_PLACES = 150
+
+
+def chained_places():
+    """-> (lat, lon, the offsets this place gets, the direction away from its transition latitude).  All edge places with
+    all nine offsets would be 57 000 cases, so every edge place gets (0, 0) and three of the other eight offsets in
+    rotation: the twelve places around one transition latitude see each offset at least four times.  The random places,
+    which are the ones thinned to the size cap, get all nine."""
+    rng = np.random.default_rng(1091)
+    edges = []
+    for t in ip.NL_TABLE:
+        for sign in (1, -1):
+            for eps in (1e-6, -1e-6, 3e-3, -3e-3):
+                for lon in (0.3, 179.9995, -179.9995):
+                    edges.append((sign * (t + eps), lon, sign * eps))
+    for lat in (89.99, -89.99, 87.0, -87.0, 0.0, 1e-7, -1e-7):
+        for lon in (180.0, -180.0, 179.99999, -179.99999, 0.0, 90.0):
+            edges.append((lat, lon, -1e-6 * np.sign(lat) if abs(lat) == 87.0 else 0.0))  # 87 is a transition itself
+    out = [(lat, lon, (0,) + tuple(1 + (3 * k + i) % 8 for i in range(3)), away) for k, (lat, lon, away) in enumerate(edges)]
+    for _ in range(CHAIN_RANDOM_PLACES):
+        out.append((float(rng.uniform(-89.0, 89.0)), float(rng.uniform(-180.0, 180.0)), tuple(range(len(CHAIN_OFFSETS))), 0.0))
+    return out
+
+
+CHAIN_STEPS = (0, 10, 25, 50, 100)  # x 1e-6 degrees: a CPR latitude cell is 4.6e-5 degrees, so the last cannot straddle
+
+
+def ask(exe, cs):
+    """cases (kind, a, b, c, d, fflag, surface, reflat, reflon) -> result, lat bits, lon bits as the driver answers"""
+    text = "".join("%d %d %d %d %d %d %d %r %r\n" % c for c in cs)
+    res = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split()
+    assert len(res) == 3 * len(cs)
+    return (np.array(res[0::3], dtype=np.int32), np.array([int(x) for x in res[1::3]], dtype=np.uint64),
+            np.array([int(x) for x in res[2::3]], dtype=np.uint64))
+
+
+def chained(exe):
+    """The chained family -> the arrays of cpr/cpr_chained.npz.
+      pairs     (places, 4) int32: even lat, even lon, odd lat, odd lon of an airborne pair encoded at the place
+      p_lat_bits, p_lon_bits    decodeCPRairborne(pair, fflag = 1): P.  Places whose pair does not decode (the halves
+                round to different sides of a transition latitude) have no P and are left out.
+      third     (cases, 5) int32: place index, cprlat, cprlon, fflag, surface of a third half encoded at place + offset
+      result, lat_bits, lon_bits    decodeCPRrelative(P.lat, P.lon, third half)
+    A case whose answer lies within 1 m of the tracker's 100 NM limit from P is left out here, not in the tests."""
+    places = chained_places()
+
+    def pairs_of(places):
+        out = []
+        for lat, lon, _, _ in places:
+            e, o = ip.cpr_encode(lat, lon, 0, False), ip.cpr_encode(lat, lon, 1, False)
+            out.append((0, e[0], e[1], o[0], o[1], 1, 0, 0.0, 0.0))
+        return out
+
+    # a place 1e-6 from a transition whose halves round to different sides of it is moved away from the transition, in
+    # the steps of CHAIN_STEPS, until its pair decodes
+    tries = [pairs_of([(lat + np.sign(away) * step * 1e-6, lon, o, away) for lat, lon, o, away in places]) for step in CHAIN_STEPS]
+    answers = [ask(exe, t)[0] for t in tries]
+    for k, (lat, lon, o, away) in enumerate(places):
+        if abs(away) == 1e-6:
+            step = [s for s, a in zip(CHAIN_STEPS, answers) if a[k] == 0][0]
+            places[k] = (lat + np.sign(away) * step * 1e-6, lon, o, away)
+    pairs = pairs_of(places)
+    pres, plat, plon = ask(exe, pairs)
+    keep = np.flatnonzero(pres == 0)
+    cs, near = [], 0
+    for new, k in enumerate(keep):
+        lat, lon, offsets, _ = places[k]
+        reflat, reflon = float(plat[k:k + 1].view(np.float64)[0]), float(plon[k:k + 1].view(np.float64)[0])
+        for o in offsets:
+            tlat = max(-90.0, min(90.0, lat + CHAIN_OFFSETS[o][0]))
+            tlon = ((lon + CHAIN_OFFSETS[o][1] + 180.0) % 360.0) - 180.0
+            for fflag in (0, 1):
+                for surface in (0, 1):
+                    y, x = ip.cpr_encode(tlat, tlon, fflag, bool(surface))
+                    cs.append((new, (2, y, x, 0, 0, fflag, surface, reflat, reflon)))
+    res, lat, lon = ask(exe, [c for _, c in cs])
+    ok = np.ones(len(cs), dtype=bool)
+    for i, (_, c) in enumerate(cs):
+        if res[i] == 0:
+            d = ip.greatcircle(c[7], c[8], float(lat[i:i + 1].view(np.float64)[0]), float(lon[i:i + 1].view(np.float64)[0]))
+            if abs(d - CHAIN_LIMIT_M) < 1.0:
+                ok[i], near = False, near + 1
+    third = np.array([(new, c[1], c[2], c[5], c[6]) for new, c in cs], dtype=np.int32)[ok]
+    print("chained:", len(places), "places,", len(keep), "with a pair that decodes;", len(third), "cases,", near,
+          "left out within 1 m of the range limit;", {int(k): int((res[ok] == k).sum()) for k in np.unique(res[ok])})
+    return dict(pairs=np.array([pairs[k][1:5] for k in keep], dtype=np.int32), p_lat_bits=plat[keep], p_lon_bits=plon[keep],
+                third=third, result=res[ok], lat_bits=lat[ok], lon_bits=lon[ok])
+
+
+def same_arrays(path, arrays):
+    if not os.path.exists(path):
+        return False
+    old = np.load(path)
+    return sorted(old.files) == sorted(arrays) and all(
+        old[k].dtype == arrays[k].dtype and old[k].shape == arrays[k].shape and old[k].tobytes() == arrays[k].tobytes()
+        for k in arrays)
+
+
+def write(name, arrays, must_be_unchanged=False):
+    """A file whose arrays are what is recorded already is left as it is, byte for byte (a zip archive carries the time
+    it was written)."""
+    path = os.path.join(HERE, "cpr", name)
+    if same_arrays(path, arrays):
+        print("cpr/" + name, "holds these answers already: left unchanged")
+        return
+    assert not (must_be_unchanged and os.path.exists(path)), "cpr/" + name + " would change"
+    np.savez_compressed(path, **arrays)
+    print("cpr/" + name, "written:", os.path.getsize(path), "bytes")
+
+
 def main():
     O = g.load_oracle()
     if not os.path.isdir(O.REF_DIR):
         raise SystemExit("the reference tree is not there: nothing to record")
     cs = cases()
+    os.makedirs(os.path.join(HERE, "cpr"), exist_ok=True)
     with tempfile.TemporaryDirectory() as tmp:
         tmp = pathlib.Path(tmp)
         (tmp / "driver.c").write_text(DRIVER)
         exe = str(tmp / "driver")
         subprocess.check_call(["gcc", "-O2", "-I" + O.REF_DIR, str(tmp / "driver.c"), os.path.join(O.REF_DIR, "cpr.c"),
                                "-o", exe, "-lm"])
-        text = "".join("%d %d %d %d %d %d %d %r %r\n" % c for c in cs)
-        res = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split()
-    assert len(res) == 3 * len(cs)
+        result, lat, lon = ask(exe, cs)
+        chain = chained(exe)
     ints = np.array([c[:7] for c in cs], dtype=np.int32)
     refs = np.array([c[7:] for c in cs], dtype=np.float64)
-    result = np.array(res[0::3], dtype=np.int32)
-    lat = np.array([int(x) for x in res[1::3]], dtype=np.uint64)
-    lon = np.array([int(x) for x in res[2::3]], dtype=np.uint64)
-    os.makedirs(os.path.join(HERE, "cpr"), exist_ok=True)
-    np.savez_compressed(os.path.join(HERE, "cpr", "cpr_reference.npz"), ints=ints, refs=refs, result=result, lat_bits=lat,
-                        lon_bits=lon)
-    print("cpr/cpr_reference.npz written:", len(cs), "cases;", {int(k): int((result == k).sum()) for k in np.unique(result)})
+    print("reference:", len(cs), "cases;", {int(k): int((result == k).sum()) for k in np.unique(result)})
+    write("cpr_reference.npz", dict(ints=ints, refs=refs, result=result, lat_bits=lat, lon_bits=lon), must_be_unchanged=True)
+    assert len(chain["third"]) <= 30000
+    write("cpr_chained.npz", chain)
+    assert os.path.getsize(os.path.join(HERE, "cpr", "cpr_chained.npz")) <= os.path.getsize(os.path.join(HERE, "cpr", "cpr_reference.npz"))
 
 
 if __name__ == "__main__":
