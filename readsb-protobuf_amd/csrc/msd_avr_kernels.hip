@@ -13,7 +13,7 @@
  *                           its white space and whether all its payload digits are hex with a few word operations on
  *                           the masks; only the prefix character and the ';' are looked at as bytes.  Leaves the records
  *                           per workgroup and adds the piece's counters.
- *   msd_avr_offsets_kernel  the counts to offsets, one workgroup (as msd_wire_scan_kernel).
+ *   msd_avr_offsets_kernel  the counts to offsets, one workgroup (as the wire writers' scan_kernel).
  *   msd_avr_store_kernel    the same classification again; every line that yields a record is parsed from LDS and
  *                           written at its rank.
  */

@@ -10,7 +10,7 @@
  * the first synchronisation.  Every kernel is launched on the bound and guards with the count.
  *
  *   fields: msd_gro_fields_kernel, one thread per record, msd_fields_impl.h; fields[k] belongs to out[k].
- *   wire:   msd_gro_len_kernel leaves a length per record and a sum per workgroup of 256, msd_gro_scan_kernel turns the
+ *   wire:   msd_gro_len_kernel leaves a length per record and a sum per workgroup of 256, scan_kernel turns the
  *           sums into offsets (one workgroup), msd_gro_store_kernel encodes and stores one dense stream in record
  *           order, coalesced through LDS (msd_wire_store_impl.h) because the stream is page-locked host memory, and
  *           leaves every record's start; msd_gro_ranges_kernel gives every entry its bytes of the stream -- an entry
@@ -32,7 +32,7 @@
 
 namespace {
 
-using namespace msd_wire_store; /* WT, IMAGE_WORDS, block_scan, block_sums_scan, image_at, wire_store_run */
+using namespace msd_wire_store; /* WT, IMAGE_WORDS, block_scan, scan_kernel, image_at, wire_store_run */
 
 constexpr uint32_t CW = MSD_FR_CTR_WORDS;
 static_assert(MSD_GRO_WIRE_MAX == MSD_WIRE_MAX, "the host sizes the stream by MSD_GRO_WIRE_MAX");
@@ -75,12 +75,6 @@ __global__ void __launch_bounds__(WT) msd_gro_len_kernel(const msd_message *out,
     (void)block_scan(len, part, total);
     if (threadIdx.x == 0)
         block_sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(WT) msd_gro_scan_kernel(uint32_t *block_sums, uint32_t nblocks)
-{
-    __shared__ uint32_t part[4];
-    block_sums_scan(block_sums, nblocks, part);
 }
 
 /* record i's bytes to stream + starts[i]; the stream holds at least MSD_WIRE_MAX * bound bytes */
@@ -148,7 +142,7 @@ extern "C" int msd_gro_launch_wire(const msd_message *out, const uint32_t *count
     const uint32_t nblocks = (bound + WT - 1) / WT;
     hipLaunchKernelGGL(msd_gro_len_kernel, dim3(nblocks), dim3(WT), 0, st, out, count, bound, format, errbits, lens,
                        block_sums);
-    hipLaunchKernelGGL(msd_gro_scan_kernel, dim3(1), dim3(WT), 0, st, block_sums, nblocks);
+    hipLaunchKernelGGL(scan_kernel<>, dim3(1), dim3(WT), 0, st, block_sums, nblocks);
     hipLaunchKernelGGL(msd_gro_store_kernel, dim3(nblocks), dim3(WT), 0, st, out, count, bound, format, errbits, lens,
                        block_sums, bytes, starts);
     hipLaunchKernelGGL(msd_gro_ranges_kernel, dim3((n + WT - 1) / WT), dim3(WT), 0, st, ctr, n, count, bound, starts,

@@ -5,81 +5,44 @@
  * msd_pos_aircraft_pb (msd_pos.cpp) orders the live slots by (receiver, address) with the snapshot's passes and then runs
  * the SBS writer's three steps over ITEMS instead of records.  The items of a call are every receiver's file head and
  * every live aircraft, in stream order: receiver r's head is item first[r] + r, the aircraft at place j of the ordered
- * list, of receiver r, is item j + r + 1, where first[r] is the place of r's first aircraft (msd_pb_items_kernel: a binary
- * search per receiver, a scatter per aircraft).  So an empty receiver still has its head, and every place in the stream
+ * list, of receiver r, is item j + r + 1, where first[r] is the place of r's first aircraft (items_kernel<1>,
+ * msd_items_impl.h: a binary search per receiver, a scatter per aircraft).  So an empty receiver still has its head, and every place in the stream
  * is a prefix sum over items -- none is handed out by an atomic, the stream is the same on every run.
  *   msd_pb_len_kernel    one lane per item.  An aircraft's lane reads its entry once, where it lies -- the position state
  *                        and the 592-byte table entry are picked over member by member, not copied --, decides selection,
  *                        leaves the next written state in the call's shadow copy and a 16-bit length (0: not written);
  *                        per item the exclusive prefix inside its workgroup of the bytes and of the three counts (written,
  *                        with position, TIS-B; packed, at most 256 each), per workgroup their sums.
- *   msd_pb_scan_kernel   the four sums into offsets (one workgroup).
+ *   scan_kernel<4>       the four sums into offsets (one workgroup; msd_wire_store_impl.h).
  *   msd_pb_rx_kernel     one lane per receiver: its row from the prefixes at its head's item and at the next head's.
- *   msd_pb_store_kernel  lanes encode into an LDS image, wire_store_run stores it as whole-wavefront runs of aligned
- *                        dwords; an aircraft's lane then commits its shadow state to the slot.  Only a call that fits
+ *   msd_pb_store_kernel  lanes encode into an LDS image, tiled_store (msd_items_impl.h) stores it as whole-wavefront runs
+ *                        of aligned dwords; an aircraft's lane then commits its shadow state to the slot.  Only a call that fits
  *                        its buffer launches it, so a refused call moves no state.
  * Both encoding kernels run msd_pb_aircraft / msd_pb_header (msd_pb_impl.h), the length kernel with no destination: a
  * length is by construction what the store kernel writes.
  * The image.  An entry is at most MSD_PB_AIRCRAFT_MAX = 415 bytes; 256 of them are 106 KB, one workgroup per CU of 160 KB.
  * The image therefore holds PB_TILE = 128 items, 53.6 KB: three workgroups, twelve wavefronts, per CU.  A workgroup keeps
- * the writers' 256 threads (block_scan and wire_store_run are built on them) and fills and stores the image twice, lanes
- * 0-127 then lanes 128-255; all 256 threads store both times.  64 items would allow six workgroups, but the encoder's
+ * the writers' 256 threads (block_scan and wire_store_run are built on them) and fills and stores the image twice
+ * (tiled_store).  64 items would allow six workgroups, but the encoder's
  * dependent byte stores into LDS, not the wavefront count, bound the kernel, and four rounds cost two more barriers each.
  * The written state lies beside the table, not in msd_pos_table: the position kernels are what they were.
  * msd_pb_fresh_kernel starts the state of a call's new aircraft at 0, msd_pb_move_kernel carries it into the rebuilt table.
  */
 #include "msd_pos.h"
 #include "msd_pb_impl.h"
-#include "msd_wire_store_impl.h"
+#include "msd_items_impl.h"
 
 namespace {
 
-using namespace msd_wire_store; /* WT, block_scan, block_sums_scan, image_at, wire_store_run */
+using namespace msd_items; /* HEAD, items_kernel, tiled_store; of msd_wire_store: WT, block_scan, scan_kernel */
 
 constexpr uint32_t PB_TILE = MSD_PB_TILE;
-constexpr uint32_t PB_HEAD = 0x80000000u; /* an item that is a receiver's file head; the low bits are the receiver */
-static_assert(WT == 2u * PB_TILE, "a workgroup fills the image twice");
 static_assert(MSD_PB_HEADER_MAX <= MSD_PB_AIRCRAFT_MAX, "an item is at most an aircraft entry");
 /* the image starts at the destination's offset in its dword; behind the tile's longest items there is room for one more */
 constexpr uint32_t PB_IMAGE_WORDS = (PB_TILE * MSD_PB_AIRCRAFT_MAX + MSD_PB_AIRCRAFT_MAX + 3u) / 4u + 2u;
 
 __global__ void __launch_bounds__(WT)
-msd_pb_items_kernel(const uint64_t *keys, const uint32_t *idx, uint32_t live, uint32_t nrx, uint32_t *first, uint32_t *items)
-{
-    const uint32_t g = blockIdx.x * WT + threadIdx.x;
-    if (g <= nrx) { /* the first place whose receiver is g or above; first[nrx] = live */
-        uint32_t lo = 0, hi = live;
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2u;
-            if ((keys[idx[mid]] >> 25) < g)
-                lo = mid + 1u;
-            else
-                hi = mid;
-        }
-        first[g] = lo;
-        if (g < nrx)
-            items[lo + g] = PB_HEAD | g;
-    }
-    if (g < live) {
-        const uint64_t r = keys[idx[g]] >> 25;
-        if (r < nrx) /* (every key's receiver is: msd_pos_update refuses any other) */
-            items[g + (uint32_t)r + 1u] = g;
-    }
-}
-
-struct pb_call {
-    msd_pos_table t;
-    const uint64_t *state;   /* the written state, per slot */
-    const uint32_t *idx;     /* the ordered slots */
-    const uint32_t *items;
-    const uint64_t *messages_total; /* per receiver, or NULL */
-    const uint16_t *track_table;
-    uint64_t now_ms;
-    uint32_t nitems;
-};
-
-__global__ void __launch_bounds__(WT)
-msd_pb_len_kernel(pb_call c, uint64_t *shadow, uint16_t *lens, uint32_t *within, uint32_t *cwithin, uint32_t *block_sums,
+msd_pb_len_kernel(msd_pb_call c, uint64_t *shadow, uint16_t *lens, uint32_t *within, uint32_t *cwithin, uint32_t *block_sums,
                   uint32_t nblocks)
 {
     __shared__ uint32_t part[4];
@@ -87,8 +50,8 @@ msd_pb_len_kernel(pb_call c, uint64_t *shadow, uint16_t *lens, uint32_t *within,
     uint32_t len = 0, counts = 0;
     if (i < c.nitems) {
         const uint32_t item = c.items[i];
-        if (item & PB_HEAD) {
-            const uint32_t r = item & ~PB_HEAD;
+        if (item & HEAD) {
+            const uint32_t r = item & ~HEAD;
             len = msd_pb_header(c.now_ms, c.messages_total ? c.messages_total[r] : 0u, nullptr);
         } else {
             const uint32_t s = c.idx[item];
@@ -123,14 +86,6 @@ msd_pb_len_kernel(pb_call c, uint64_t *shadow, uint16_t *lens, uint32_t *within,
     }
 }
 
-/* each of the four arrays block_sums[q][0 .. nblocks) -> its exclusive prefix in place, [q][nblocks] = its sum */
-__global__ void __launch_bounds__(WT) msd_pb_scan_kernel(uint32_t *block_sums, uint32_t nblocks)
-{
-    __shared__ uint32_t part[4];
-    for (uint32_t q = 0; q < 4u; ++q)
-        block_sums_scan(block_sums + q * (nblocks + 1u), nblocks, part);
-}
-
 __device__ __forceinline__ uint32_t pb_prefix(uint32_t q, uint32_t i, uint32_t nitems, const uint32_t *within,
                                                const uint32_t *cwithin, const uint32_t *block_sums, uint32_t nblocks)
 {
@@ -162,43 +117,27 @@ msd_pb_rx_kernel(const uint32_t *first, uint32_t nrx, uint32_t nitems, const uin
 }
 
 __global__ void __launch_bounds__(WT)
-msd_pb_store_kernel(pb_call c, const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off, uint64_t *state,
-                    uint8_t *out)
+msd_pb_store_kernel(msd_pb_call c, const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off, uint8_t *out)
 {
     __shared__ uint32_t part[4];
-    __shared__ uint32_t half; /* the bytes of the workgroup's first PB_TILE items */
+    __shared__ uint32_t half;
     __shared__ uint32_t image[PB_IMAGE_WORDS];
-    const uint32_t i = blockIdx.x * WT + threadIdx.x;
-    const uint32_t len = i < c.nitems ? lens[i] : 0u;
-    uint32_t total;
-    const uint32_t off = block_scan(len, part, total);
-    if (threadIdx.x == PB_TILE)
-        half = off;
-    __syncthreads();
-    const uint32_t first_bytes = half;
-    uint8_t *const dst0 = out + block_off[blockIdx.x];
-    for (uint32_t round = 0; round < 2u; ++round) {
-        uint8_t *const dst = round ? dst0 + first_bytes : dst0;
-        const uint32_t run = round ? total - first_bytes : first_bytes;
-        if (threadIdx.x / PB_TILE == round && len) { /* (a length above 0: a head with something to say, a selected aircraft) */
-            uint8_t *at = image_at(image, dst, round ? off - first_bytes : off);
-            const uint32_t item = c.items[i];
-            if (item & PB_HEAD) {
-                const uint32_t r = item & ~PB_HEAD;
-                (void)msd_pb_header(c.now_ms, c.messages_total ? c.messages_total[r] : 0u, at);
-            } else {
-                const uint32_t s = c.idx[item];
-                const uint64_t st = shadow[i];
-                msd_pb_head h;
-                msd_pb_head_of_state(c.t.keys[s], &c.t.st[s], &h);
-                (void)msd_pb_aircraft(&h, &c.t.trk[s], st, c.track_table, at);
-                state[s] = st;
-            }
+    const uint32_t me = blockIdx.x * WT + threadIdx.x;
+    /* (a length above 0: a head with something to say, a selected aircraft) */
+    tiled_store<PB_TILE>(me < c.nitems ? lens[me] : 0u, out, block_off, part, half, image, [&](uint32_t i, uint8_t *at) {
+        const uint32_t item = c.items[i];
+        if (item & HEAD) {
+            const uint32_t r = item & ~HEAD;
+            (void)msd_pb_header(c.now_ms, c.messages_total ? c.messages_total[r] : 0u, at);
+        } else {
+            const uint32_t s = c.idx[item];
+            const uint64_t st = shadow[i];
+            msd_pb_head h;
+            msd_pb_head_of_state(c.t.keys[s], &c.t.st[s], &h);
+            (void)msd_pb_aircraft(&h, &c.t.trk[s], st, c.track_table, at);
+            c.state[s] = st;
         }
-        __syncthreads();
-        wire_store_run(dst, image, run);
-        __syncthreads();
-    }
+    });
 }
 
 __global__ void __launch_bounds__(WT)
@@ -243,25 +182,19 @@ void msd_pb_launch_move(hipStream_t stream, msd_pos_table from, const uint64_t *
     msd_pb_move_kernel<<<(from.cap + WT - 1u) / WT, WT, 0, stream>>>(from.keys, from_state, to.keys, to_state, from.cap);
 }
 
-void msd_pb_launch_lengths(hipStream_t stream, msd_pos_table t, const uint64_t *state, const uint32_t *idx, uint32_t live,
-                           uint32_t nrx, uint64_t now_ms, const uint64_t *messages_total, const uint16_t *track_table,
-                           uint32_t *first, uint32_t *items, uint64_t *shadow, uint16_t *lens, uint32_t *within,
-                           uint32_t *cwithin, uint32_t *block_sums, msd_pb_receiver *rx)
+void msd_pb_launch_lengths(hipStream_t stream, msd_pb_call c, uint32_t live, uint32_t *first, uint32_t *items, uint64_t *shadow,
+                           uint16_t *lens, uint32_t *within, uint32_t *cwithin, uint32_t *block_sums, msd_pb_receiver *rx)
 {
-    const uint32_t nitems = live + nrx, nblocks = (nitems + WT - 1u) / WT;
-    const uint32_t most = live > nrx + 1u ? live : nrx + 1u;
-    const pb_call c = {t, state, idx, items, messages_total, track_table, now_ms, nitems};
-    msd_pb_items_kernel<<<(most + WT - 1u) / WT, WT, 0, stream>>>(t.keys, idx, live, nrx, first, items);
+    const uint32_t nblocks = (c.nitems + WT - 1u) / WT;
+    const uint32_t most = live > c.nrx + 1u ? live : c.nrx + 1u;
+    items_kernel<1><<<(most + WT - 1u) / WT, WT, 0, stream>>>(c.t.keys, c.idx, live, c.nrx, first, items);
     msd_pb_len_kernel<<<nblocks, WT, 0, stream>>>(c, shadow, lens, within, cwithin, block_sums, nblocks);
-    msd_pb_scan_kernel<<<1, WT, 0, stream>>>(block_sums, nblocks);
-    msd_pb_rx_kernel<<<(nrx + WT - 1u) / WT, WT, 0, stream>>>(first, nrx, nitems, within, cwithin, block_sums, nblocks, rx);
+    scan_kernel<4><<<1, WT, 0, stream>>>(block_sums, nblocks);
+    msd_pb_rx_kernel<<<(c.nrx + WT - 1u) / WT, WT, 0, stream>>>(first, c.nrx, c.nitems, within, cwithin, block_sums, nblocks, rx);
 }
 
-void msd_pb_launch_store(hipStream_t stream, msd_pos_table t, uint64_t *state, const uint32_t *idx, uint32_t live, uint32_t nrx,
-                         uint64_t now_ms, const uint64_t *messages_total, const uint16_t *track_table, const uint32_t *items,
-                         const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off, uint8_t *out)
+void msd_pb_launch_store(hipStream_t stream, msd_pb_call c, const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off,
+                         uint8_t *out)
 {
-    const uint32_t nitems = live + nrx, nblocks = (nitems + WT - 1u) / WT;
-    const pb_call c = {t, state, idx, items, messages_total, track_table, now_ms, nitems};
-    msd_pb_store_kernel<<<nblocks, WT, 0, stream>>>(c, shadow, lens, block_off, state, out);
+    msd_pb_store_kernel<<<(c.nitems + WT - 1u) / WT, WT, 0, stream>>>(c, shadow, lens, block_off, out);
 }

@@ -1,90 +1,95 @@
-/* msd_pos.cpp -- C-ABI of the position tracker (modes_hip.h "positions"): the object, its device memory and the order
- * in which a call queues the kernels of msd_pos_kernels.hip. */
+/* msd_pos.cpp -- C-ABI of the position tracker (modes_hip.h "positions"): the object, its device memory (msd_devbuf.h:
+ * every buffer is an owning array, freed with the object) and the order in which a call queues the kernels of
+ * msd_pos_kernels.hip and of the four writers.  The writers share emit(), host input is staged by stage(), the two
+ * read-outs of the table share read_out(). */
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "msd_pos.h"
+#include "msd_devbuf.h"
 #include "msd_pb_impl.h"
 #include "msd_vrs_impl.h"
 #include "msd_sbs_impl.h"
 
+template <typename T> using dev = msd_devbuf<T>;
+
 struct msd_pos {
     int device = 0;
     hipStream_t stream = nullptr;
-    msd_pos_table tab[2] = {}; /* tab[cur] is live; expiry rebuilds into the other */
+    /* tab[cur] is live; expiry rebuilds into the other.  The kernels take a table by value, so it is raw pointers:
+     * point_tables() fills them from the arrays below */
+    msd_pos_table tab[2] = {};
+    dev<uint64_t> keys[2];
+    dev<msd_pos_aircraft> st[2];
     int cur = 0;
     uint32_t nrx = 0;
     int fp = 8;
     uint64_t live = 0;
-    msd_pos_receiver *d_rx = nullptr;
-    unsigned long long *d_stats = nullptr;
-    uint32_t *d_ctl = nullptr;
+    dev<msd_pos_receiver> d_rx;
+    dev<unsigned long long> d_stats;
+    dev<uint32_t> d_ctl;
     /* per-call buffers, grown to the largest call seen */
-    size_t cap_n = 0, cap_in = 0;
-    uint32_t *d_slot = nullptr;
-    uint8_t *d_fresh = nullptr;
-    msd_position *d_out = nullptr;
+    dev<uint32_t> d_slot;
+    dev<uint8_t> d_fresh;
+    dev<msd_position> d_out;
     /* a table tracker (msd_pos_create_table): tab[k].trk, the per-record NIC / Rc and the snapshot's buffers */
     bool table = false;
-    msd_pos_nicrc *d_nicrc = nullptr;
-    uint32_t *s_idx[2] = {nullptr, nullptr}, *s_hist = nullptr;
-    msd_aircraft *d_snap = nullptr;
-    size_t cap_snap = 0;
-    uint32_t *d_idx[2] = {nullptr, nullptr}, *d_hist = nullptr;
-    msd_message *d_msgs = nullptr;
-    msd_fields *d_fields = nullptr;
-    uint32_t *d_receiver = nullptr;
+    dev<msd_trk_aircraft> trk[2];
+    dev<msd_pos_nicrc> d_nicrc;
+    dev<uint32_t> s_idx[2], s_hist;
+    dev<msd_aircraft> d_snap;
+    dev<uint32_t> d_idx[2], d_hist;
+    dev<msd_message> d_msgs;
+    dev<msd_fields> d_fields;
+    dev<uint32_t> d_receiver;
     /* Mode A/C matching (msd_pos_modeac_enable): tab[k].hits, the receivers' arrays, modeCToATable and the buffers the
      * two read-out calls hand to the host */
-    uint32_t *d_ac = nullptr;
-    uint16_t *d_c_to_a = nullptr;
-    msd_modeac_code *d_codes = nullptr;
-    msd_modeac_hit *d_hits_out = nullptr;
-    size_t cap_hits_out = 0;
+    dev<uint8_t> hits[2];
+    dev<uint32_t> d_ac;
+    dev<uint16_t> d_c_to_a;
+    dev<msd_modeac_code> d_codes;
+    dev<msd_modeac_hit> d_hits_out;
     /* reduced Beast output (msd_pos_reduce_enable): tab[k].next_reduce, the verdict byte per record of a call, and the
      * writer's buffers -- records and verdicts that came from the host, lengths, offsets, ends, the stream */
     bool reduce = false;
     uint32_t reduce_interval = 0;
-    uint8_t *d_forward = nullptr;
-    size_t cap_forward = 0, cap_w = 0, cap_w_in = 0, cap_w_out = 0;
-    msd_message *d_w_msgs = nullptr;
-    uint8_t *d_w_forward = nullptr, *d_w_lens = nullptr, *d_w_out = nullptr;
-    uint32_t *d_w_block = nullptr, *d_w_ends = nullptr;
+    dev<uint64_t> next_reduce[2];
+    dev<uint8_t> d_forward;
+    dev<msd_message> d_w_msgs;
+    dev<uint8_t> d_w_forward, d_w_lens, d_w_out;
+    dev<uint32_t> d_w_block, d_w_ends;
     /* SBS output (msd_pos_sbs_enable): the ground-track table, the row per record of a call, and the writer's buffers --
      * records, fields and rows that came from the host; lengths, offsets, ends and the stream are the reduced writer's */
-    uint16_t *d_track_table = nullptr;
-    msd_sbs_track *d_sbs = nullptr, *d_s_trk = nullptr;
-    size_t cap_sbs = 0, cap_s_in = 0;
-    msd_message *d_s_msgs = nullptr;
-    msd_fields *d_s_fields = nullptr;
-    /* aircraft.pb (msd_pos_pb_enable): the written state beside tab[k], the truncating ground-track table, and the
-     * writer's buffers -- per receiver (made with the state), per item (grown to the largest call seen); the stream is the
-     * reduced writer's */
-    uint64_t *pb_state[2] = {nullptr, nullptr};
-    uint16_t *d_pb_table = nullptr;
-    uint32_t *d_pb_first = nullptr;
-    uint64_t *d_pb_total = nullptr;
-    msd_pb_receiver *d_pb_rx = nullptr;
-    size_t cap_pb = 0;
-    uint32_t *d_pb_items = nullptr, *d_pb_within = nullptr, *d_pb_cwithin = nullptr, *d_pb_block = nullptr;
-    uint64_t *d_pb_shadow = nullptr;
-    uint16_t *d_pb_lens = nullptr;
+    dev<uint16_t> d_track_table;
+    dev<msd_sbs_track> d_sbs, d_s_trk;
+    dev<msd_message> d_s_msgs;
+    dev<msd_fields> d_s_fields;
+    /* aircraft.pb (msd_pos_pb_enable): the written state beside tab[k], and the writer's buffers -- per receiver (made
+     * with the state), per item (grown to the largest call seen); the stream is the reduced writer's */
+    bool pb = false;
+    dev<uint64_t> pb_state[2];
+    dev<uint32_t> d_pb_first;
+    dev<uint64_t> d_pb_total;
+    dev<msd_pb_receiver> d_pb_rx;
+    dev<uint32_t> d_pb_items, d_pb_within, d_pb_cwithin, d_pb_block;
+    dev<uint64_t> d_pb_shadow;
+    dev<uint16_t> d_pb_lens;
     /* the truncating ground-track table aircraft.pb and the VRS output share: built by whichever of msd_pos_pb_enable and
-     * msd_pos_vrs_enable comes first, owned here; d_pb_table is the same pointer once pb is enabled */
-    uint16_t *d_trunc_table = nullptr;
+     * msd_pos_vrs_enable comes first */
+    dev<uint16_t> d_trunc_table;
     /* VRS output (msd_pos_vrs_enable): the writer's buffers -- per receiver (made at the enable), per item (grown to the
      * largest call seen); the stream is the reduced writer's */
     bool vrs = false;
-    uint32_t *d_vrs_first = nullptr;
-    msd_vrs_receiver *d_vrs_rx = nullptr;
-    size_t cap_vrs = 0;
-    uint32_t *d_vrs_items = nullptr, *d_vrs_within = nullptr, *d_vrs_sel = nullptr, *d_vrs_block = nullptr;
-    uint16_t *d_vrs_lens = nullptr, *d_vrs_swithin = nullptr;
+    dev<uint32_t> d_vrs_first;
+    dev<msd_vrs_receiver> d_vrs_rx;
+    dev<uint32_t> d_vrs_items, d_vrs_within, d_vrs_sel, d_vrs_block;
+    dev<uint16_t> d_vrs_lens, d_vrs_swithin;
     char err[256] = "";
 };
 
@@ -103,6 +108,18 @@ int fail(msd_pos *p, int code, const char *what, hipError_t e)
             return fail(p, e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO, #call, e_);                                    \
     } while (0)
 
+/* the one place where the tables learn where their arrays are: after the create and after every enable that adds one */
+void point_tables(msd_pos *p)
+{
+    for (int k = 0; k < 2; ++k) {
+        p->tab[k].keys = p->keys[k].get();
+        p->tab[k].st = p->st[k].get();
+        p->tab[k].trk = p->trk[k].get();
+        p->tab[k].hits = p->hits[k].get();
+        p->tab[k].next_reduce = p->next_reduce[k].get();
+    }
+}
+
 int clear(msd_pos *p)
 {
     unsigned long long init[MSD_POS_DSTATS] = {};
@@ -110,82 +127,99 @@ int clear(msd_pos *p)
     memcpy(&init[MSD_PC_N], &inf, sizeof inf);
     msd_pos_launch_fill(p->stream, p->tab[p->cur].keys, p->tab[p->cur].cap);
     POS_HIP(p, hipGetLastError());
-    POS_HIP(p, hipMemcpyAsync(p->d_stats, init, sizeof init, hipMemcpyHostToDevice, p->stream));
-    if (p->d_ac) {
-        POS_HIP(p, hipMemsetAsync(p->d_ac, 0, sizeof(uint32_t) * MSD_MODEAC_WORDS * p->nrx, p->stream));
+    POS_HIP(p, hipMemcpyAsync(p->d_stats.get(), init, sizeof init, hipMemcpyHostToDevice, p->stream));
+    if (p->d_ac.get()) {
+        POS_HIP(p, hipMemsetAsync(p->d_ac.get(), 0, sizeof(uint32_t) * MSD_MODEAC_WORDS * p->nrx, p->stream));
         for (int k = 0; k < 2; ++k)
             POS_HIP(p, hipMemsetAsync(p->tab[k].hits, 0, 2u * (size_t)p->tab[k].cap, p->stream));
     }
     if (p->reduce)
         for (int k = 0; k < 2; ++k)
             POS_HIP(p, hipMemsetAsync(p->tab[k].next_reduce, 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->tab[k].cap, p->stream));
-    if (p->d_pb_table)
+    if (p->pb)
         for (int k = 0; k < 2; ++k)
-            POS_HIP(p, hipMemsetAsync(p->pb_state[k], 0, sizeof(uint64_t) * p->tab[k].cap, p->stream));
+            POS_HIP(p, hipMemsetAsync(p->pb_state[k].get(), 0, sizeof(uint64_t) * p->tab[k].cap, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     p->live = 0;
     return 0;
 }
 
-template <typename T> void release(T *&ptr)
+/* room for a call of n records (its inputs, when they come from the host, are stage()'s) */
+int reserve(msd_pos *p, size_t n, bool want_sbs)
 {
-    if (ptr)
-        (void)hipFree(ptr);
-    ptr = nullptr;
+    const size_t piece = n < MSD_POS_PIECE ? n : MSD_POS_PIECE;
+    const size_t tiles = (piece + MSD_POS_TILE - 1) / MSD_POS_TILE;
+    POS_HIP(p, p->d_slot.reserve(n));
+    POS_HIP(p, p->d_fresh.reserve(n));
+    POS_HIP(p, p->d_out.reserve(n));
+    POS_HIP(p, p->d_idx[0].reserve(piece));
+    POS_HIP(p, p->d_idx[1].reserve(piece));
+    POS_HIP(p, p->d_hist.reserve(256 * tiles));
+    if (p->table)
+        POS_HIP(p, p->d_nicrc.reserve(n));
+    if (p->reduce)
+        POS_HIP(p, p->d_forward.reserve(n));
+    if (want_sbs)
+        POS_HIP(p, p->d_sbs.reserve(n));
+    return 0;
 }
 
-/* room for a call of n records (and for its inputs, when they come from the host) */
-int reserve(msd_pos *p, size_t n, bool host_input, bool want_sbs)
+/* Host input of a call onto the device: n elements of src into buf, and src points at the copy.  An array the caller
+ * left out keeps its room and stays left out. */
+template <typename T> int stage(msd_pos *p, dev<T> &buf, const T *&src, size_t n)
 {
-    if (n > p->cap_n) {
-        release(p->d_slot), release(p->d_fresh), release(p->d_out), release(p->d_idx[0]), release(p->d_idx[1]), release(p->d_hist);
-        release(p->d_nicrc);
-        p->cap_n = 0;
-        const size_t piece = n < MSD_POS_PIECE ? n : MSD_POS_PIECE;
-        const size_t tiles = (piece + MSD_POS_TILE - 1) / MSD_POS_TILE;
-        POS_HIP(p, hipMalloc(&p->d_slot, n * sizeof(uint32_t)));
-        POS_HIP(p, hipMalloc(&p->d_fresh, n));
-        POS_HIP(p, hipMalloc(&p->d_out, n * sizeof(msd_position)));
-        POS_HIP(p, hipMalloc(&p->d_idx[0], piece * sizeof(uint32_t)));
-        POS_HIP(p, hipMalloc(&p->d_idx[1], piece * sizeof(uint32_t)));
-        POS_HIP(p, hipMalloc(&p->d_hist, 256 * tiles * sizeof(uint32_t)));
-        if (p->table)
-            POS_HIP(p, hipMalloc(&p->d_nicrc, n * sizeof(msd_pos_nicrc)));
-        p->cap_n = n;
-    }
-    if (p->reduce && n > p->cap_forward) {
-        release(p->d_forward);
-        p->cap_forward = 0;
-        POS_HIP(p, hipMalloc(&p->d_forward, n));
-        p->cap_forward = n;
-    }
-    if (want_sbs && n > p->cap_sbs) {
-        release(p->d_sbs);
-        p->cap_sbs = 0;
-        POS_HIP(p, hipMalloc(&p->d_sbs, n * sizeof(msd_sbs_track)));
-        p->cap_sbs = n;
-    }
-    if (host_input && n > p->cap_in) {
-        release(p->d_msgs), release(p->d_fields), release(p->d_receiver);
-        p->cap_in = 0;
-        POS_HIP(p, hipMalloc(&p->d_msgs, n * sizeof(msd_message)));
-        POS_HIP(p, hipMalloc(&p->d_fields, n * sizeof(msd_fields)));
-        POS_HIP(p, hipMalloc(&p->d_receiver, n * sizeof(uint32_t)));
-        p->cap_in = n;
+    POS_HIP(p, buf.reserve(n));
+    if (src) {
+        POS_HIP(p, hipMemcpyAsync(buf.get(), src, n * sizeof(T), hipMemcpyHostToDevice, p->stream));
+        src = buf.get();
     }
     return 0;
 }
 
+/* the lengths, the workgroups' offsets and the ends of a call of n records: the reduced writer's and the SBS writer's */
+int record_writer_buffers(msd_pos *p, size_t n, uint32_t nblocks)
+{
+    POS_HIP(p, p->d_w_lens.reserve(n));
+    POS_HIP(p, p->d_w_block.reserve(nblocks + 1u));
+    POS_HIP(p, p->d_w_ends.reserve(n));
+    return 0;
+}
+
+/* What every writer does once its lengths are queued: the stream's length (block_sums[nblocks]) comes back and is
+ * *out_len from then on, also where the call is refused; a stream that does not fit cap is -ENOSPC and moves nothing;
+ * otherwise d_w_out grows to it, store(need) queues the writer's store kernel -- or not: what a writer does with no byte
+ * to write is its own and stays at its call --, the bytes go to out and the writer's side array (side_bytes from
+ * side_src, where the caller asked for it) to side_dst. */
+template <typename Store>
+int emit(msd_pos *p, const uint32_t *block_sums, uint32_t nblocks, const char *noun, uint8_t *out, size_t cap, size_t *out_len,
+         void *side_dst, const void *side_src, size_t side_bytes, Store store)
+{
+    uint32_t need = 0;
+    POS_HIP(p, hipMemcpyAsync(&need, block_sums + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    *out_len = need;
+    if (need > cap) {
+        snprintf(p->err, sizeof p->err, "the %s stream takes %u bytes, %zu were offered", noun, need, cap);
+        return -ENOSPC;
+    }
+    POS_HIP(p, p->d_w_out.reserve(need));
+    store(need);
+    POS_HIP(p, hipGetLastError());
+    if (need)
+        POS_HIP(p, hipMemcpyAsync(out, p->d_w_out.get(), need, hipMemcpyDeviceToHost, p->stream));
+    if (side_dst)
+        POS_HIP(p, hipMemcpyAsync(side_dst, side_src, side_bytes, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
 
 /* the index and histogram buffers of the snapshot's ordering passes, made at the first use */
 int snapshot_buffers(msd_pos *p)
 {
-    if (p->s_hist)
-        return 0;
     const size_t cap = p->tab[p->cur].cap, tiles = (cap + MSD_POS_TILE - 1) / MSD_POS_TILE;
-    POS_HIP(p, hipMalloc(&p->s_idx[0], cap * sizeof(uint32_t)));
-    POS_HIP(p, hipMalloc(&p->s_idx[1], cap * sizeof(uint32_t)));
-    POS_HIP(p, hipMalloc(&p->s_hist, 256 * tiles * sizeof(uint32_t)));
+    POS_HIP(p, p->s_idx[0].reserve(cap));
+    POS_HIP(p, p->s_idx[1].reserve(cap));
+    POS_HIP(p, p->s_hist.reserve(256 * tiles));
     return 0;
 }
 
@@ -196,6 +230,90 @@ uint32_t snapshot_key_bits(const msd_pos *p)
     while (key_bits < 64 && ((uint64_t)(p->nrx - 1u) >> (key_bits - 25)) != 0)
         ++key_bits;
     return key_bits;
+}
+
+/* the live slots in the snapshot's order, for a writer over items (idx is not read without aircraft) */
+const uint32_t *ordered_slots(msd_pos *p, uint32_t live)
+{
+    if (!live)
+        return p->s_idx[0].get();
+    return msd_pos_launch_ordered_slots(p->stream, p->tab[p->cur], live, snapshot_key_bits(p), p->s_idx[0].get(),
+                                        p->s_idx[1].get(), p->s_hist.get());
+}
+
+/* A read-out of one entry per live aircraft in the snapshot's order: *n is their number, also where they do not fit cap
+ * entries; launch(idx_a, idx_b, hist, dst) queues the ordered gather, into out itself where that is device memory and
+ * else into the staging array, which is copied out. */
+template <typename T, typename Launch>
+int read_out(msd_pos *p, dev<T> &staging, T *out, size_t cap, int on_device, size_t *n, Launch launch)
+{
+    *n = (size_t)p->live;
+    if (p->live > cap) {
+        snprintf(p->err, sizeof p->err, "%llu aircraft do not fit %zu entries", (unsigned long long)p->live, cap);
+        return -ENOSPC;
+    }
+    if (p->live == 0)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    const int rc = snapshot_buffers(p);
+    if (rc)
+        return rc;
+    if (!on_device)
+        POS_HIP(p, staging.reserve((size_t)p->live));
+    launch(p->s_idx[0].get(), p->s_idx[1].get(), p->s_hist.get(), on_device ? out : staging.get());
+    POS_HIP(p, hipGetLastError());
+    if (!on_device)
+        POS_HIP(p, hipMemcpyAsync(out, staging.get(), p->live * sizeof(T), hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+/* A ground-track table on the device, built once: build's `entries` entries into dst.  On an error dst stays empty. */
+int track_table(msd_pos *p, dev<uint16_t> &dst, void (*build)(uint16_t *), size_t entries)
+{
+    if (dst.get())
+        return 0;
+    std::vector<uint16_t> table;
+    try {
+        table.resize(entries);
+    } catch (const std::bad_alloc &) {
+        return -ENOMEM;
+    }
+    build(table.data());
+    dev<uint16_t> d_table;
+    const auto upload = [&]() -> int {
+        POS_HIP(p, d_table.reserve(entries));
+        POS_HIP(p, hipMemcpyAsync(d_table.get(), table.data(), sizeof(uint16_t) * entries, hipMemcpyHostToDevice, p->stream));
+        POS_HIP(p, hipStreamSynchronize(p->stream));
+        return 0;
+    };
+    const int rc = upload();
+    if (rc) { /* the tracker stays as it was */
+        (void)hipGetLastError();
+        return rc;
+    }
+    dst = std::move(d_table);
+    return 0;
+}
+
+/* What the two enables over the truncating ground-track table have in common: the table, the snapshot's buffers and
+ * `mine`, the enable's own arrays.  On an error the tracker stays as it was: the table goes again if this very call made
+ * it (the snapshot's buffers, if they were made, are the snapshot's). */
+template <typename Mine> int items_writer_enable(msd_pos *p, Mine mine)
+{
+    const bool had_table = p->d_trunc_table.get() != nullptr;
+    const int made = track_table(p, p->d_trunc_table, msd_pb_build_track_table, MSD_PB_TRACK_ENTRIES);
+    if (made)
+        return made;
+    int rc = mine();
+    if (!rc)
+        rc = snapshot_buffers(p);
+    if (rc) {
+        (void)hipGetLastError();
+        if (!had_table)
+            p->d_trunc_table = dev<uint16_t>();
+    }
+    return rc;
 }
 
 int create(const msd_pos_config *cfg, msd_pos **out, bool table)
@@ -221,15 +339,16 @@ int create(const msd_pos_config *cfg, msd_pos **out, bool table)
         POS_HIP(p, hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
         for (int k = 0; k < 2; ++k) {
             p->tab[k].cap = cfg->capacity;
-            POS_HIP(p, hipMalloc(&p->tab[k].keys, sizeof(uint64_t) * cfg->capacity));
-            POS_HIP(p, hipMalloc(&p->tab[k].st, sizeof(msd_pos_aircraft) * cfg->capacity));
+            POS_HIP(p, p->keys[k].reserve(cfg->capacity));
+            POS_HIP(p, p->st[k].reserve(cfg->capacity));
             if (table)
-                POS_HIP(p, hipMalloc(&p->tab[k].trk, sizeof(msd_trk_aircraft) * cfg->capacity));
+                POS_HIP(p, p->trk[k].reserve(cfg->capacity));
         }
-        POS_HIP(p, hipMalloc(&p->d_rx, sizeof(msd_pos_receiver) * p->nrx));
-        POS_HIP(p, hipMalloc(&p->d_stats, sizeof(unsigned long long) * MSD_POS_DSTATS));
-        POS_HIP(p, hipMalloc(&p->d_ctl, sizeof(uint32_t) * MSD_POS_CTL_N));
-        POS_HIP(p, hipMemcpy(p->d_rx, rx.data(), sizeof(msd_pos_receiver) * p->nrx, hipMemcpyHostToDevice));
+        point_tables(p);
+        POS_HIP(p, p->d_rx.reserve(p->nrx));
+        POS_HIP(p, p->d_stats.reserve(MSD_POS_DSTATS));
+        POS_HIP(p, p->d_ctl.reserve(MSD_POS_CTL_N));
+        POS_HIP(p, hipMemcpy(p->d_rx.get(), rx.data(), sizeof(msd_pos_receiver) * p->nrx, hipMemcpyHostToDevice));
         return clear(p);
     };
     const int rc = build();
@@ -260,27 +379,12 @@ void msd_pos_destroy(msd_pos *p)
     if (!p)
         return;
     (void)hipSetDevice(p->device);
-    if (p->stream)
-        (void)hipStreamSynchronize(p->stream);
-    for (int k = 0; k < 2; ++k)
-        release(p->tab[k].keys), release(p->tab[k].st), release(p->tab[k].trk), release(p->tab[k].hits),
-            release(p->tab[k].next_reduce);
-    release(p->d_forward), release(p->d_w_msgs), release(p->d_w_forward), release(p->d_w_lens), release(p->d_w_out);
-    release(p->d_w_block), release(p->d_w_ends);
-    release(p->d_track_table), release(p->d_sbs), release(p->d_s_trk), release(p->d_s_msgs), release(p->d_s_fields);
-    release(p->pb_state[0]), release(p->pb_state[1]), release(p->d_trunc_table), release(p->d_pb_first), release(p->d_pb_total);
-    release(p->d_pb_rx), release(p->d_pb_items), release(p->d_pb_within), release(p->d_pb_cwithin), release(p->d_pb_block);
-    release(p->d_pb_shadow), release(p->d_pb_lens);
-    release(p->d_vrs_first), release(p->d_vrs_rx), release(p->d_vrs_items), release(p->d_vrs_within), release(p->d_vrs_sel);
-    release(p->d_vrs_block), release(p->d_vrs_lens), release(p->d_vrs_swithin);
-    release(p->d_ac), release(p->d_c_to_a), release(p->d_codes), release(p->d_hits_out);
-    release(p->d_nicrc), release(p->s_idx[0]), release(p->s_idx[1]), release(p->s_hist), release(p->d_snap);
-    release(p->d_rx), release(p->d_stats), release(p->d_ctl), release(p->d_slot), release(p->d_fresh), release(p->d_out);
-    release(p->d_idx[0]), release(p->d_idx[1]), release(p->d_hist), release(p->d_msgs), release(p->d_fields),
-        release(p->d_receiver);
-    if (p->stream)
-        (void)hipStreamDestroy(p->stream);
-    delete p;
+    const hipStream_t stream = p->stream;
+    if (stream)
+        (void)hipStreamSynchronize(stream);
+    delete p; /* every buffer, behind the stream's last work and before the stream goes */
+    if (stream)
+        (void)hipStreamDestroy(stream);
 }
 
 const char *msd_pos_last_error(const msd_pos *p)
@@ -305,7 +409,7 @@ int msd_pos_set_receiver(msd_pos *p, uint32_t receiver, const msd_pos_receiver *
     if (rx)
         r = *rx;
     POS_HIP(p, hipSetDevice(p->device));
-    POS_HIP(p, hipMemcpy(p->d_rx + receiver, &r, sizeof r, hipMemcpyHostToDevice));
+    POS_HIP(p, hipMemcpy(p->d_rx.get() + receiver, &r, sizeof r, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -313,7 +417,7 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
                   int on_device, msd_position *out, msd_pos_nicrc *nicrc, bool want_nicrc, uint8_t *forward, bool want_forward,
                   msd_sbs_track *trk = nullptr, bool want_sbs = false)
 {
-    if (!p || (want_nicrc && !p->table) || (want_forward && !p->reduce) || (want_sbs && !p->d_track_table))
+    if (!p || (want_nicrc && !p->table) || (want_forward && !p->reduce) || (want_sbs && !p->d_track_table.get()))
         return -EINVAL;
     if (n == 0)
         return 0;
@@ -325,27 +429,26 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
             if (receiver[i] >= p->nrx)
                 return -EINVAL;
     POS_HIP(p, hipSetDevice(p->device));
-    const int rc = reserve(p, n, !on_device, want_sbs);
+    int rc = reserve(p, n, want_sbs);
     if (rc)
         return rc;
-    if (!on_device) {
-        POS_HIP(p, hipMemcpyAsync(p->d_msgs, msgs, n * sizeof(msd_message), hipMemcpyHostToDevice, p->stream));
-        POS_HIP(p, hipMemcpyAsync(p->d_fields, fields, n * sizeof(msd_fields), hipMemcpyHostToDevice, p->stream));
-        if (receiver)
-            POS_HIP(p, hipMemcpyAsync(p->d_receiver, receiver, n * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
-        msgs = p->d_msgs;
-        fields = p->d_fields;
-        receiver = receiver ? p->d_receiver : nullptr;
-    }
+    if (!on_device && ((rc = stage(p, p->d_msgs, msgs, n)) || (rc = stage(p, p->d_fields, fields, n)) ||
+                       (rc = stage(p, p->d_receiver, receiver, n))))
+        return rc;
     const msd_pos_table t = p->tab[p->cur];
+    uint32_t *const d_ctl = p->d_ctl.get(), *const d_slot = p->d_slot.get();
+    uint8_t *const d_fresh = p->d_fresh.get(), *const d_forward = p->d_forward.get();
+    msd_position *const d_out = p->d_out.get();
+    msd_pos_nicrc *const d_nicrc = p->d_nicrc.get();
+    msd_sbs_track *const d_sbs = p->d_sbs.get();
     uint32_t ctl[MSD_POS_CTL_N] = {};
-    POS_HIP(p, hipMemsetAsync(p->d_ctl, 0, sizeof ctl, p->stream));
-    msd_pos_launch_find(p->stream, t, msgs, fields, receiver, p->nrx, (uint32_t)n, p->d_slot, p->d_fresh, p->d_out, p->d_ctl);
+    POS_HIP(p, hipMemsetAsync(d_ctl, 0, sizeof ctl, p->stream));
+    msd_pos_launch_find(p->stream, t, msgs, fields, receiver, p->nrx, (uint32_t)n, d_slot, d_fresh, d_out, d_ctl);
     POS_HIP(p, hipGetLastError());
-    POS_HIP(p, hipMemcpyAsync(ctl, p->d_ctl, sizeof ctl, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     if (ctl[MSD_POS_CTL_FULL] || ctl[MSD_POS_CTL_BAD_RECEIVER]) { /* nothing changes: this call's aircraft leave again */
-        msd_pos_launch_rollback(p->stream, t, p->d_slot, p->d_fresh, (uint32_t)n);
+        msd_pos_launch_rollback(p->stream, t, d_slot, d_fresh, (uint32_t)n);
         POS_HIP(p, hipGetLastError());
         POS_HIP(p, hipStreamSynchronize(p->stream));
         snprintf(p->err, sizeof p->err, "%s", ctl[MSD_POS_CTL_BAD_RECEIVER] ? "a receiver index is out of range"
@@ -353,35 +456,35 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
         return ctl[MSD_POS_CTL_BAD_RECEIVER] ? -EINVAL : -ENOSPC;
     }
     p->live += ctl[MSD_POS_CTL_INSERTED];
-    if (p->d_pb_table && ctl[MSD_POS_CTL_INSERTED]) { /* the new aircraft have been written nowhere yet */
-        msd_pb_launch_fresh(p->stream, p->d_slot, p->d_fresh, (uint32_t)n, t.cap, p->pb_state[p->cur]);
+    if (p->pb && ctl[MSD_POS_CTL_INSERTED]) { /* the new aircraft have been written nowhere yet */
+        msd_pb_launch_fresh(p->stream, d_slot, d_fresh, (uint32_t)n, t.cap, p->pb_state[p->cur].get());
         POS_HIP(p, hipGetLastError());
     }
-    if (p->d_ac) { /* the call has passed its checks: its Mode A/C replies count (track.c:1001) */
-        msd_pos_launch_modeac_count(p->stream, msgs, fields, receiver, p->nrx, (uint32_t)n, p->d_ac);
+    if (p->d_ac.get()) { /* the call has passed its checks: its Mode A/C replies count (track.c:1001) */
+        msd_pos_launch_modeac_count(p->stream, msgs, fields, receiver, p->nrx, (uint32_t)n, p->d_ac.get());
         POS_HIP(p, hipGetLastError());
     }
     if (p->table) /* a skipped record's entry stays zero */
-        POS_HIP(p, hipMemsetAsync(p->d_nicrc, 0, n * sizeof(msd_pos_nicrc), p->stream));
+        POS_HIP(p, hipMemsetAsync(d_nicrc, 0, n * sizeof(msd_pos_nicrc), p->stream));
     if (p->reduce) /* and its verdict */
-        POS_HIP(p, hipMemsetAsync(p->d_forward, 0, n, p->stream));
+        POS_HIP(p, hipMemsetAsync(d_forward, 0, n, p->stream));
     if (want_sbs) /* and its row; no other call makes rows */
-        POS_HIP(p, hipMemsetAsync(p->d_sbs, 0, n * sizeof(msd_sbs_track), p->stream));
+        POS_HIP(p, hipMemsetAsync(d_sbs, 0, n * sizeof(msd_sbs_track), p->stream));
     for (size_t base = 0; base < n; base += MSD_POS_PIECE) {
         const size_t m = n - base < MSD_POS_PIECE ? n - base : MSD_POS_PIECE;
-        msd_pos_launch_piece(p->stream, t, msgs, fields, receiver, p->d_rx, p->fp, (uint32_t)base, (uint32_t)m, p->d_slot,
-                             p->d_idx[0], p->d_idx[1], p->d_hist, p->d_out, p->d_stats, p->d_nicrc, p->reduce_interval,
-                             p->d_forward, want_sbs ? p->d_sbs : nullptr);
+        msd_pos_launch_piece(p->stream, t, msgs, fields, receiver, p->d_rx.get(), p->fp, (uint32_t)base, (uint32_t)m, d_slot,
+                             p->d_idx[0].get(), p->d_idx[1].get(), p->d_hist.get(), d_out, p->d_stats.get(), d_nicrc,
+                             p->reduce_interval, d_forward, want_sbs ? d_sbs : nullptr);
         POS_HIP(p, hipGetLastError());
     }
-    POS_HIP(p, hipMemcpyAsync(out, p->d_out, n * sizeof(msd_position), hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipMemcpyAsync(out, d_out, n * sizeof(msd_position), hipMemcpyDeviceToHost, p->stream));
     if (want_nicrc)
-        POS_HIP(p, hipMemcpyAsync(nicrc, p->d_nicrc, n * sizeof(msd_pos_nicrc), hipMemcpyDeviceToHost, p->stream));
+        POS_HIP(p, hipMemcpyAsync(nicrc, d_nicrc, n * sizeof(msd_pos_nicrc), hipMemcpyDeviceToHost, p->stream));
     if (want_forward)
-        POS_HIP(p, hipMemcpyAsync(forward, p->d_forward, n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+        POS_HIP(p, hipMemcpyAsync(forward, d_forward, n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                                   p->stream));
     if (want_sbs)
-        POS_HIP(p, hipMemcpyAsync(trk, p->d_sbs, n * sizeof(msd_sbs_track),
+        POS_HIP(p, hipMemcpyAsync(trk, d_sbs, n * sizeof(msd_sbs_track),
                                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
@@ -415,37 +518,17 @@ int msd_pos_sbs_enable(msd_pos *p)
 {
     if (!p || !p->table)
         return -EINVAL;
-    if (p->d_track_table)
+    if (p->d_track_table.get())
         return 0;
     POS_HIP(p, hipSetDevice(p->device));
-    std::vector<uint16_t> table;
-    try {
-        table.resize(MSD_SBS_TRACK_ENTRIES);
-    } catch (const std::bad_alloc &) {
-        return -ENOMEM;
-    }
-    msd_sbs_build_track_table(table.data());
-    uint16_t *d_table = nullptr;
-    const auto build = [&]() -> int {
-        POS_HIP(p, hipMalloc(&d_table, sizeof(uint16_t) * MSD_SBS_TRACK_ENTRIES));
-        POS_HIP(p, hipMemcpyAsync(d_table, table.data(), sizeof(uint16_t) * MSD_SBS_TRACK_ENTRIES, hipMemcpyHostToDevice, p->stream));
-        POS_HIP(p, hipStreamSynchronize(p->stream));
-        return 0;
-    };
-    const int rc = build();
-    if (rc) { /* the tracker stays as it was */
-        (void)hipGetLastError();
-        release(d_table);
-        return rc;
-    }
-    p->d_track_table = d_table; /* the rows' buffer grows with the calls, as the verdicts' does */
-    return 0;
+    /* (the rows' buffer grows with the calls, as the verdicts' does) */
+    return track_table(p, p->d_track_table, msd_sbs_build_track_table, MSD_SBS_TRACK_ENTRIES);
 }
 
 int msd_pos_sbs_wire(msd_pos *p, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk, size_t n,
                      int on_device, const msd_sbs_options *opt, uint8_t *out, size_t cap, size_t *out_len, uint32_t *ends)
 {
-    if (!p || !p->d_track_table || !out_len || !msd_sbs_options_ok(opt) || n > MSD_POS_MAX_N)
+    if (!p || !p->d_track_table.get() || !out_len || !msd_sbs_options_ok(opt) || n > MSD_POS_MAX_N)
         return -EINVAL;
     *out_len = 0;
     if (n == 0)
@@ -454,130 +537,53 @@ int msd_pos_sbs_wire(msd_pos *p, const msd_message *msgs, const msd_fields *fiel
         return -EINVAL;
     POS_HIP(p, hipSetDevice(p->device));
     const uint32_t nblocks = (uint32_t)((n + 255u) / 256u);
-    if (n > p->cap_w) {
-        release(p->d_w_lens), release(p->d_w_block), release(p->d_w_ends);
-        p->cap_w = 0;
-        POS_HIP(p, hipMalloc(&p->d_w_lens, n));
-        POS_HIP(p, hipMalloc(&p->d_w_block, sizeof(uint32_t) * (nblocks + 1u)));
-        POS_HIP(p, hipMalloc(&p->d_w_ends, sizeof(uint32_t) * n));
-        p->cap_w = n;
-    }
-    if (!on_device) {
-        if (n > p->cap_s_in) {
-            release(p->d_s_msgs), release(p->d_s_fields), release(p->d_s_trk);
-            p->cap_s_in = 0;
-            POS_HIP(p, hipMalloc(&p->d_s_msgs, n * sizeof(msd_message)));
-            POS_HIP(p, hipMalloc(&p->d_s_fields, n * sizeof(msd_fields)));
-            POS_HIP(p, hipMalloc(&p->d_s_trk, n * sizeof(msd_sbs_track)));
-            p->cap_s_in = n;
-        }
-        POS_HIP(p, hipMemcpyAsync(p->d_s_msgs, msgs, n * sizeof(msd_message), hipMemcpyHostToDevice, p->stream));
-        POS_HIP(p, hipMemcpyAsync(p->d_s_fields, fields, n * sizeof(msd_fields), hipMemcpyHostToDevice, p->stream));
-        POS_HIP(p, hipMemcpyAsync(p->d_s_trk, trk, n * sizeof(msd_sbs_track), hipMemcpyHostToDevice, p->stream));
-        msgs = p->d_s_msgs;
-        fields = p->d_s_fields;
-        trk = p->d_s_trk;
-    }
-    msd_sbs_launch_lengths(p->stream, msgs, fields, trk, (uint32_t)n, *opt, p->d_track_table, p->d_w_lens, p->d_w_block);
-    POS_HIP(p, hipGetLastError());
-    uint32_t need = 0; /* at most 2^24 * 147 */
-    POS_HIP(p, hipMemcpyAsync(&need, p->d_w_block + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    *out_len = need;
-    if (need > cap) {
-        snprintf(p->err, sizeof p->err, "the SBS stream takes %u bytes, %zu were offered", need, cap);
-        return -ENOSPC;
-    }
-    if (need > p->cap_w_out) {
-        release(p->d_w_out);
-        p->cap_w_out = 0;
-        POS_HIP(p, hipMalloc(&p->d_w_out, need));
-        p->cap_w_out = need;
-    }
-    /* (with need == 0 the store kernel still runs: it writes the ends and no byte of the stream) */
-    msd_sbs_launch_store(p->stream, msgs, fields, trk, (uint32_t)n, *opt, p->d_track_table, p->d_w_lens, p->d_w_block, p->d_w_out,
-                         p->d_w_ends);
-    POS_HIP(p, hipGetLastError());
-    if (need)
-        POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
-    if (ends)
-        POS_HIP(p, hipMemcpyAsync(ends, p->d_w_ends, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    return 0;
-}
-
-namespace {
-
-/* the truncating ground-track table on the device, built once for aircraft.pb and the VRS output */
-int trunc_table(msd_pos *p)
-{
-    if (p->d_trunc_table)
-        return 0;
-    std::vector<uint16_t> table;
-    try {
-        table.resize(MSD_PB_TRACK_ENTRIES);
-    } catch (const std::bad_alloc &) {
-        return -ENOMEM;
-    }
-    msd_pb_build_track_table(table.data());
-    uint16_t *d_table = nullptr;
-    const auto build = [&]() -> int {
-        POS_HIP(p, hipMalloc(&d_table, sizeof(uint16_t) * MSD_PB_TRACK_ENTRIES));
-        POS_HIP(p, hipMemcpyAsync(d_table, table.data(), sizeof(uint16_t) * MSD_PB_TRACK_ENTRIES, hipMemcpyHostToDevice, p->stream));
-        POS_HIP(p, hipStreamSynchronize(p->stream));
-        return 0;
-    };
-    const int rc = build();
-    if (rc) {
-        (void)hipGetLastError();
-        release(d_table);
+    int rc = record_writer_buffers(p, n, nblocks);
+    if (rc)
         return rc;
-    }
-    p->d_trunc_table = d_table;
-    return 0;
+    if (!on_device && ((rc = stage(p, p->d_s_msgs, msgs, n)) || (rc = stage(p, p->d_s_fields, fields, n)) ||
+                       (rc = stage(p, p->d_s_trk, trk, n))))
+        return rc;
+    const uint16_t *const table = p->d_track_table.get();
+    msd_sbs_launch_lengths(p->stream, msgs, fields, trk, (uint32_t)n, *opt, table, p->d_w_lens.get(), p->d_w_block.get());
+    POS_HIP(p, hipGetLastError());
+    /* the stream takes at most 2^24 * 147 bytes.  (With none the store kernel still runs: it writes the ends and no byte
+     * of the stream) */
+    return emit(p, p->d_w_block.get(), nblocks, "SBS", out, cap, out_len, ends, p->d_w_ends.get(), sizeof(uint32_t) * n,
+                [&](uint32_t) {
+                    msd_sbs_launch_store(p->stream, msgs, fields, trk, (uint32_t)n, *opt, table, p->d_w_lens.get(),
+                                         p->d_w_block.get(), p->d_w_out.get(), p->d_w_ends.get());
+                });
 }
-
-} // namespace
 
 int msd_pos_pb_enable(msd_pos *p)
 {
     if (!p || !p->table)
         return -EINVAL;
-    if (p->d_pb_table)
+    if (p->pb)
         return 0;
     POS_HIP(p, hipSetDevice(p->device));
-    const bool had_table = p->d_trunc_table != nullptr;
-    const int made = trunc_table(p);
-    if (made)
-        return made;
-    uint64_t *state[2] = {nullptr, nullptr}, *total = nullptr;
-    uint32_t *first = nullptr;
-    msd_pb_receiver *rx = nullptr;
-    const auto build = [&]() -> int {
+    dev<uint64_t> state[2], total;
+    dev<uint32_t> first;
+    dev<msd_pb_receiver> rx;
+    const int rc = items_writer_enable(p, [&]() -> int {
         for (int k = 0; k < 2; ++k) { /* the aircraft the table already has have been written nowhere yet */
-            POS_HIP(p, hipMalloc(&state[k], sizeof(uint64_t) * p->tab[k].cap));
-            POS_HIP(p, hipMemsetAsync(state[k], 0, sizeof(uint64_t) * p->tab[k].cap, p->stream));
+            POS_HIP(p, state[k].reserve(p->tab[k].cap));
+            POS_HIP(p, hipMemsetAsync(state[k].get(), 0, sizeof(uint64_t) * p->tab[k].cap, p->stream));
         }
-        POS_HIP(p, hipMalloc(&first, sizeof(uint32_t) * ((size_t)p->nrx + 1u)));
-        POS_HIP(p, hipMalloc(&total, sizeof(uint64_t) * p->nrx));
-        POS_HIP(p, hipMalloc(&rx, sizeof(msd_pb_receiver) * p->nrx));
+        POS_HIP(p, first.reserve((size_t)p->nrx + 1u));
+        POS_HIP(p, total.reserve(p->nrx));
+        POS_HIP(p, rx.reserve(p->nrx));
         POS_HIP(p, hipStreamSynchronize(p->stream));
-        return snapshot_buffers(p);
-    };
-    const int rc = build();
-    if (rc) { /* the tracker stays as it was (the snapshot's buffers, if they were made, are the snapshot's) */
-        (void)hipGetLastError();
-        release(state[0]), release(state[1]), release(first), release(total), release(rx);
-        if (!had_table)
-            release(p->d_trunc_table);
+        return 0;
+    });
+    if (rc)
         return rc;
-    }
-    p->pb_state[0] = state[0];
-    p->pb_state[1] = state[1];
-    p->d_pb_first = first;
-    p->d_pb_total = total;
-    p->d_pb_rx = rx;
-    p->d_pb_table = p->d_trunc_table;
+    p->pb_state[0] = std::move(state[0]);
+    p->pb_state[1] = std::move(state[1]);
+    p->d_pb_first = std::move(first);
+    p->d_pb_total = std::move(total);
+    p->d_pb_rx = std::move(rx);
+    p->pb = true;
     return 0;
 }
 
@@ -588,27 +594,17 @@ int msd_pos_vrs_enable(msd_pos *p)
     if (p->vrs)
         return 0;
     POS_HIP(p, hipSetDevice(p->device));
-    const bool had_table = p->d_trunc_table != nullptr;
-    const int made = trunc_table(p);
-    if (made)
-        return made;
-    uint32_t *first = nullptr;
-    msd_vrs_receiver *rx = nullptr;
-    const auto build = [&]() -> int {
-        POS_HIP(p, hipMalloc(&first, sizeof(uint32_t) * ((size_t)p->nrx + 1u)));
-        POS_HIP(p, hipMalloc(&rx, sizeof(msd_vrs_receiver) * p->nrx));
-        return snapshot_buffers(p);
-    };
-    const int rc = build();
-    if (rc) { /* the tracker stays as it was (the snapshot's buffers, if they were made, are the snapshot's) */
-        (void)hipGetLastError();
-        release(first), release(rx);
-        if (!had_table)
-            release(p->d_trunc_table);
+    dev<uint32_t> first;
+    dev<msd_vrs_receiver> rx;
+    const int rc = items_writer_enable(p, [&]() -> int {
+        POS_HIP(p, first.reserve((size_t)p->nrx + 1u));
+        POS_HIP(p, rx.reserve(p->nrx));
+        return 0;
+    });
+    if (rc)
         return rc;
-    }
-    p->d_vrs_first = first;
-    p->d_vrs_rx = rx;
+    p->d_vrs_first = std::move(first);
+    p->d_vrs_rx = std::move(rx);
     p->vrs = true;
     return 0;
 }
@@ -624,56 +620,31 @@ int msd_pos_vrs(msd_pos *p, const msd_vrs_options *opt, uint8_t *out, size_t cap
         return -E2BIG;
     }
     POS_HIP(p, hipSetDevice(p->device));
-    const msd_pos_table t = p->tab[p->cur];
     const uint32_t live = (uint32_t)p->live;
     const size_t nitems = (size_t)live + 2u * (size_t)p->nrx;
     const uint32_t nblocks = (uint32_t)((nitems + 255u) / 256u);
-    if (nitems > p->cap_vrs) {
-        release(p->d_vrs_items), release(p->d_vrs_within), release(p->d_vrs_sel), release(p->d_vrs_block);
-        release(p->d_vrs_lens), release(p->d_vrs_swithin);
-        p->cap_vrs = 0;
-        POS_HIP(p, hipMalloc(&p->d_vrs_items, sizeof(uint32_t) * nitems));
-        POS_HIP(p, hipMalloc(&p->d_vrs_within, sizeof(uint32_t) * nitems));
-        POS_HIP(p, hipMalloc(&p->d_vrs_sel, sizeof(uint32_t) * ((size_t)nblocks + 1u)));
-        POS_HIP(p, hipMalloc(&p->d_vrs_block, sizeof(uint32_t) * ((size_t)nblocks + 1u)));
-        POS_HIP(p, hipMalloc(&p->d_vrs_lens, sizeof(uint16_t) * nitems));
-        POS_HIP(p, hipMalloc(&p->d_vrs_swithin, sizeof(uint16_t) * nitems));
-        p->cap_vrs = nitems;
-    }
-    const uint32_t *idx = p->s_idx[0]; /* (not read without aircraft) */
-    if (live)
-        idx = msd_pos_launch_ordered_slots(p->stream, t, live, snapshot_key_bits(p), p->s_idx[0], p->s_idx[1], p->s_hist);
-    const msd_vrs_call c = {t, idx, p->d_vrs_items, p->d_vrs_first, p->d_trunc_table, opt->now_ms, (uint32_t)nitems, p->nrx,
-                            opt->part, (uint32_t)shift};
-    msd_vrs_launch_lengths(p->stream, c, live, p->d_vrs_first, p->d_vrs_items, p->d_vrs_lens, p->d_vrs_swithin, p->d_vrs_within,
-                           p->d_vrs_sel, p->d_vrs_block, p->d_vrs_rx);
+    POS_HIP(p, p->d_vrs_items.reserve(nitems));
+    POS_HIP(p, p->d_vrs_within.reserve(nitems));
+    POS_HIP(p, p->d_vrs_sel.reserve((size_t)nblocks + 1u));
+    POS_HIP(p, p->d_vrs_block.reserve((size_t)nblocks + 1u));
+    POS_HIP(p, p->d_vrs_lens.reserve(nitems));
+    POS_HIP(p, p->d_vrs_swithin.reserve(nitems));
+    const msd_vrs_call c = {p->tab[p->cur], ordered_slots(p, live), p->d_vrs_items.get(), p->d_vrs_first.get(),
+                            p->d_trunc_table.get(), opt->now_ms, (uint32_t)nitems, p->nrx, opt->part, (uint32_t)shift};
+    msd_vrs_launch_lengths(p->stream, c, live, p->d_vrs_first.get(), p->d_vrs_items.get(), p->d_vrs_lens.get(),
+                           p->d_vrs_swithin.get(), p->d_vrs_within.get(), p->d_vrs_sel.get(), p->d_vrs_block.get(),
+                           p->d_vrs_rx.get());
     POS_HIP(p, hipGetLastError());
-    uint32_t need = 0;
-    POS_HIP(p, hipMemcpyAsync(&need, p->d_vrs_block + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    *out_len = need;
-    if (need > cap) {
-        snprintf(p->err, sizeof p->err, "the VRS stream takes %u bytes, %zu were offered", need, cap);
-        return -ENOSPC;
-    }
-    if (need > p->cap_w_out) {
-        release(p->d_w_out);
-        p->cap_w_out = 0;
-        POS_HIP(p, hipMalloc(&p->d_w_out, need));
-        p->cap_w_out = need;
-    }
-    msd_vrs_launch_store(p->stream, c, p->d_vrs_lens, p->d_vrs_block, p->d_w_out); /* (need >= 14: a receiver's frame) */
-    POS_HIP(p, hipGetLastError());
-    POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
-    if (rx)
-        POS_HIP(p, hipMemcpyAsync(rx, p->d_vrs_rx, sizeof(msd_vrs_receiver) * p->nrx, hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    return 0;
+    /* the store kernel always runs (need >= 14: a receiver's frame) */
+    return emit(p, p->d_vrs_block.get(), nblocks, "VRS", out, cap, out_len, rx, p->d_vrs_rx.get(),
+                sizeof(msd_vrs_receiver) * p->nrx, [&](uint32_t) {
+                    msd_vrs_launch_store(p->stream, c, p->d_vrs_lens.get(), p->d_vrs_block.get(), p->d_w_out.get());
+                });
 }
 
 int msd_pos_aircraft_pb(msd_pos *p, const msd_pb_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_pb_receiver *rx)
 {
-    if (!p || !p->d_pb_table || !out_len || !msd_pb_options_ok(opt) || (!out && cap > 0))
+    if (!p || !p->pb || !out_len || !msd_pb_options_ok(opt) || (!out && cap > 0))
         return -EINVAL;
     *out_len = 0;
     if (p->live * MSD_PB_AIRCRAFT_MAX + (uint64_t)p->nrx * MSD_PB_HEADER_MAX > 0xFFFFFFFFull) {
@@ -681,58 +652,33 @@ int msd_pos_aircraft_pb(msd_pos *p, const msd_pb_options *opt, uint8_t *out, siz
         return -E2BIG;
     }
     POS_HIP(p, hipSetDevice(p->device));
-    const msd_pos_table t = p->tab[p->cur];
     const uint32_t live = (uint32_t)p->live;
     const size_t nitems = (size_t)live + p->nrx;
     const uint32_t nblocks = (uint32_t)((nitems + 255u) / 256u);
-    if (nitems > p->cap_pb) {
-        release(p->d_pb_items), release(p->d_pb_within), release(p->d_pb_cwithin), release(p->d_pb_block);
-        release(p->d_pb_shadow), release(p->d_pb_lens);
-        p->cap_pb = 0;
-        POS_HIP(p, hipMalloc(&p->d_pb_items, sizeof(uint32_t) * nitems));
-        POS_HIP(p, hipMalloc(&p->d_pb_within, sizeof(uint32_t) * nitems));
-        POS_HIP(p, hipMalloc(&p->d_pb_cwithin, sizeof(uint32_t) * nitems));
-        POS_HIP(p, hipMalloc(&p->d_pb_block, sizeof(uint32_t) * 4u * ((size_t)nblocks + 1u)));
-        POS_HIP(p, hipMalloc(&p->d_pb_shadow, sizeof(uint64_t) * nitems));
-        POS_HIP(p, hipMalloc(&p->d_pb_lens, sizeof(uint16_t) * nitems));
-        p->cap_pb = nitems;
-    }
+    POS_HIP(p, p->d_pb_items.reserve(nitems));
+    POS_HIP(p, p->d_pb_within.reserve(nitems));
+    POS_HIP(p, p->d_pb_cwithin.reserve(nitems));
+    POS_HIP(p, p->d_pb_block.reserve(4u * ((size_t)nblocks + 1u)));
+    POS_HIP(p, p->d_pb_shadow.reserve(nitems));
+    POS_HIP(p, p->d_pb_lens.reserve(nitems));
     const uint64_t *d_total = nullptr;
     if (opt->messages_total) {
-        POS_HIP(p, hipMemcpyAsync(p->d_pb_total, opt->messages_total, sizeof(uint64_t) * p->nrx, hipMemcpyHostToDevice, p->stream));
-        d_total = p->d_pb_total;
+        POS_HIP(p, hipMemcpyAsync(p->d_pb_total.get(), opt->messages_total, sizeof(uint64_t) * p->nrx, hipMemcpyHostToDevice,
+                                  p->stream));
+        d_total = p->d_pb_total.get();
     }
-    const uint32_t *idx = p->s_idx[0]; /* (not read without aircraft) */
-    if (live)
-        idx = msd_pos_launch_ordered_slots(p->stream, t, live, snapshot_key_bits(p), p->s_idx[0], p->s_idx[1], p->s_hist);
-    msd_pb_launch_lengths(p->stream, t, p->pb_state[p->cur], idx, live, p->nrx, opt->now_ms, d_total, p->d_pb_table,
-                          p->d_pb_first, p->d_pb_items, p->d_pb_shadow, p->d_pb_lens, p->d_pb_within, p->d_pb_cwithin,
-                          p->d_pb_block, p->d_pb_rx);
+    const msd_pb_call c = {p->tab[p->cur], p->pb_state[p->cur].get(), ordered_slots(p, live), p->d_pb_items.get(), d_total,
+                           p->d_trunc_table.get(), opt->now_ms, (uint32_t)nitems, p->nrx};
+    msd_pb_launch_lengths(p->stream, c, live, p->d_pb_first.get(), p->d_pb_items.get(), p->d_pb_shadow.get(), p->d_pb_lens.get(),
+                          p->d_pb_within.get(), p->d_pb_cwithin.get(), p->d_pb_block.get(), p->d_pb_rx.get());
     POS_HIP(p, hipGetLastError());
-    uint32_t need = 0;
-    POS_HIP(p, hipMemcpyAsync(&need, p->d_pb_block + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    *out_len = need;
-    if (need > cap) { /* no written state has moved: only the store kernel commits the shadow copy */
-        snprintf(p->err, sizeof p->err, "the aircraft.pb stream takes %u bytes, %zu were offered", need, cap);
-        return -ENOSPC;
-    }
-    if (need > p->cap_w_out) {
-        release(p->d_w_out);
-        p->cap_w_out = 0;
-        POS_HIP(p, hipMalloc(&p->d_w_out, need));
-        p->cap_w_out = need;
-    }
-    if (need) { /* (no byte: no aircraft was written, so no state moves either) */
-        msd_pb_launch_store(p->stream, t, p->pb_state[p->cur], idx, live, p->nrx, opt->now_ms, d_total, p->d_pb_table,
-                            p->d_pb_items, p->d_pb_shadow, p->d_pb_lens, p->d_pb_block, p->d_w_out);
-        POS_HIP(p, hipGetLastError());
-        POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
-    }
-    if (rx)
-        POS_HIP(p, hipMemcpyAsync(rx, p->d_pb_rx, sizeof(msd_pb_receiver) * p->nrx, hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    return 0;
+    /* a refused call has moved no written state: only the store kernel commits the shadow copy */
+    return emit(p, p->d_pb_block.get(), nblocks, "aircraft.pb", out, cap, out_len, rx, p->d_pb_rx.get(),
+                sizeof(msd_pb_receiver) * p->nrx, [&](uint32_t need) {
+                    if (need) /* (no byte: no aircraft was written, so no state moves either) */
+                        msd_pb_launch_store(p->stream, c, p->d_pb_shadow.get(), p->d_pb_lens.get(), p->d_pb_block.get(),
+                                            p->d_w_out.get());
+                });
 }
 
 int msd_pos_reduce_enable(msd_pos *p, uint32_t interval_ms)
@@ -742,12 +688,12 @@ int msd_pos_reduce_enable(msd_pos *p, uint32_t interval_ms)
     if (p->reduce)
         return interval_ms == p->reduce_interval ? 0 : -EINVAL;
     POS_HIP(p, hipSetDevice(p->device));
-    uint64_t *next[2] = {nullptr, nullptr};
+    dev<uint64_t> next[2];
     const auto build = [&]() -> int {
         for (int k = 0; k < 2; ++k) { /* the aircraft the table already has start at 0, as a new one does */
-            const size_t bytes = sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->tab[k].cap;
-            POS_HIP(p, hipMalloc(&next[k], bytes));
-            POS_HIP(p, hipMemsetAsync(next[k], 0, bytes, p->stream));
+            const size_t timers = (size_t)MSD_REDUCE_TIMERS * p->tab[k].cap;
+            POS_HIP(p, next[k].reserve(timers));
+            POS_HIP(p, hipMemsetAsync(next[k].get(), 0, sizeof(uint64_t) * timers, p->stream));
         }
         POS_HIP(p, hipStreamSynchronize(p->stream));
         return 0;
@@ -755,11 +701,11 @@ int msd_pos_reduce_enable(msd_pos *p, uint32_t interval_ms)
     const int rc = build();
     if (rc) { /* the tracker stays as it was */
         (void)hipGetLastError();
-        release(next[0]), release(next[1]);
         return rc;
     }
-    p->tab[0].next_reduce = next[0];
-    p->tab[1].next_reduce = next[1];
+    p->next_reduce[0] = std::move(next[0]);
+    p->next_reduce[1] = std::move(next[1]);
+    point_tables(p);
     p->reduce_interval = interval_ms;
     p->reduce = true;
     return 0;
@@ -777,132 +723,78 @@ int msd_pos_reduce_wire(msd_pos *p, const msd_message *msgs, const uint8_t *forw
         return -EINVAL;
     POS_HIP(p, hipSetDevice(p->device));
     const uint32_t nblocks = (uint32_t)((n + 255u) / 256u);
-    if (n > p->cap_w) {
-        release(p->d_w_lens), release(p->d_w_block), release(p->d_w_ends);
-        p->cap_w = 0;
-        POS_HIP(p, hipMalloc(&p->d_w_lens, n));
-        POS_HIP(p, hipMalloc(&p->d_w_block, sizeof(uint32_t) * (nblocks + 1u)));
-        POS_HIP(p, hipMalloc(&p->d_w_ends, sizeof(uint32_t) * n));
-        p->cap_w = n;
-    }
-    if (!on_device) {
-        if (n > p->cap_w_in) {
-            release(p->d_w_msgs), release(p->d_w_forward);
-            p->cap_w_in = 0;
-            POS_HIP(p, hipMalloc(&p->d_w_msgs, n * sizeof(msd_message)));
-            POS_HIP(p, hipMalloc(&p->d_w_forward, n));
-            p->cap_w_in = n;
-        }
-        POS_HIP(p, hipMemcpyAsync(p->d_w_msgs, msgs, n * sizeof(msd_message), hipMemcpyHostToDevice, p->stream));
-        POS_HIP(p, hipMemcpyAsync(p->d_w_forward, forward, n, hipMemcpyHostToDevice, p->stream));
-        msgs = p->d_w_msgs;
-        forward = p->d_w_forward;
-    }
-    msd_reduce_launch_lengths(p->stream, msgs, forward, (uint32_t)n, flags, p->d_w_lens, p->d_w_block);
+    int rc = record_writer_buffers(p, n, nblocks);
+    if (rc)
+        return rc;
+    if (!on_device && ((rc = stage(p, p->d_w_msgs, msgs, n)) || (rc = stage(p, p->d_w_forward, forward, n))))
+        return rc;
+    msd_reduce_launch_lengths(p->stream, msgs, forward, (uint32_t)n, flags, p->d_w_lens.get(), p->d_w_block.get());
     POS_HIP(p, hipGetLastError());
-    uint32_t need = 0; /* at most 2^24 * 44 */
-    POS_HIP(p, hipMemcpyAsync(&need, p->d_w_block + nblocks, sizeof need, hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    *out_len = need;
-    if (need > cap) {
-        snprintf(p->err, sizeof p->err, "the reduced stream takes %u bytes, %zu were offered", need, cap);
-        return -ENOSPC;
-    }
-    if (need > p->cap_w_out) {
-        release(p->d_w_out);
-        p->cap_w_out = 0;
-        POS_HIP(p, hipMalloc(&p->d_w_out, need));
-        p->cap_w_out = need;
-    }
-    /* (with need == 0 the store kernel still runs: it writes the ends and no byte of the stream) */
-    msd_reduce_launch_store(p->stream, msgs, (uint32_t)n, flags, p->d_w_lens, p->d_w_block, p->d_w_out, p->d_w_ends);
-    POS_HIP(p, hipGetLastError());
-    if (need)
-        POS_HIP(p, hipMemcpyAsync(out, p->d_w_out, need, hipMemcpyDeviceToHost, p->stream));
-    if (ends)
-        POS_HIP(p, hipMemcpyAsync(ends, p->d_w_ends, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    return 0;
+    /* the stream takes at most 2^24 * 44 bytes.  (With none the store kernel still runs: it writes the ends and no byte
+     * of the stream) */
+    return emit(p, p->d_w_block.get(), nblocks, "reduced", out, cap, out_len, ends, p->d_w_ends.get(), sizeof(uint32_t) * n,
+                [&](uint32_t) {
+                    msd_reduce_launch_store(p->stream, msgs, (uint32_t)n, flags, p->d_w_lens.get(), p->d_w_block.get(),
+                                            p->d_w_out.get(), p->d_w_ends.get());
+                });
 }
 
 int msd_pos_snapshot(msd_pos *p, msd_aircraft *out, size_t cap, int on_device, size_t *n)
 {
     if (!p || !p->table || !n || (!out && cap > 0))
         return -EINVAL;
-    *n = (size_t)p->live;
-    if (p->live > cap) {
-        snprintf(p->err, sizeof p->err, "%llu aircraft do not fit %zu entries", (unsigned long long)p->live, cap);
-        return -ENOSPC;
-    }
-    if (p->live == 0)
-        return 0;
-    POS_HIP(p, hipSetDevice(p->device));
-    const msd_pos_table t = p->tab[p->cur];
-    const int rc = snapshot_buffers(p);
-    if (rc)
-        return rc;
-    if (!on_device && p->live > p->cap_snap) {
-        release(p->d_snap);
-        p->cap_snap = 0;
-        POS_HIP(p, hipMalloc(&p->d_snap, p->live * sizeof(msd_aircraft)));
-        p->cap_snap = (size_t)p->live;
-    }
-    msd_aircraft *dst = on_device ? out : p->d_snap;
-    msd_pos_launch_snapshot(p->stream, t, (uint32_t)p->live, snapshot_key_bits(p), p->s_idx[0], p->s_idx[1], p->s_hist, dst);
-    POS_HIP(p, hipGetLastError());
-    if (!on_device)
-        POS_HIP(p, hipMemcpyAsync(out, p->d_snap, p->live * sizeof(msd_aircraft), hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    return 0;
+    return read_out(p, p->d_snap, out, cap, on_device, n, [&](uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist, msd_aircraft *dst) {
+        msd_pos_launch_snapshot(p->stream, p->tab[p->cur], (uint32_t)p->live, snapshot_key_bits(p), idx_a, idx_b, hist, dst);
+    });
 }
 
 int msd_pos_modeac_enable(msd_pos *p)
 {
     if (!p || !p->table)
         return -EINVAL;
-    if (p->d_ac)
+    if (p->d_ac.get())
         return 0;
     POS_HIP(p, hipSetDevice(p->device));
     uint16_t c_to_a[MSD_MODEAC_CODES];
     msd_modeac_build_c_to_a(c_to_a);
-    const size_t ac_bytes = sizeof(uint32_t) * MSD_MODEAC_WORDS * p->nrx;
-    uint32_t *ac = nullptr;
-    uint16_t *d_c_to_a = nullptr;
-    msd_modeac_code *codes = nullptr;
-    uint8_t *hits[2] = {nullptr, nullptr};
+    const size_t ac_words = (size_t)MSD_MODEAC_WORDS * p->nrx;
+    dev<uint32_t> ac;
+    dev<uint16_t> d_c_to_a;
+    dev<msd_modeac_code> codes;
+    dev<uint8_t> hits[2];
     const auto build = [&]() -> int {
-        POS_HIP(p, hipMalloc(&ac, ac_bytes));
-        POS_HIP(p, hipMalloc(&d_c_to_a, sizeof c_to_a));
-        POS_HIP(p, hipMalloc(&codes, sizeof(msd_modeac_code) * MSD_MODEAC_CODES));
+        POS_HIP(p, ac.reserve(ac_words));
+        POS_HIP(p, d_c_to_a.reserve(MSD_MODEAC_CODES));
+        POS_HIP(p, codes.reserve(MSD_MODEAC_CODES));
         for (int k = 0; k < 2; ++k)
-            POS_HIP(p, hipMalloc(&hits[k], 2u * (size_t)p->tab[k].cap));
-        POS_HIP(p, hipMemsetAsync(ac, 0, ac_bytes, p->stream));
+            POS_HIP(p, hits[k].reserve(2u * (size_t)p->tab[k].cap));
+        POS_HIP(p, hipMemsetAsync(ac.get(), 0, sizeof(uint32_t) * ac_words, p->stream));
         for (int k = 0; k < 2; ++k) /* the aircraft the table has already start without hits */
-            POS_HIP(p, hipMemsetAsync(hits[k], 0, 2u * (size_t)p->tab[k].cap, p->stream));
-        POS_HIP(p, hipMemcpyAsync(d_c_to_a, c_to_a, sizeof c_to_a, hipMemcpyHostToDevice, p->stream));
+            POS_HIP(p, hipMemsetAsync(hits[k].get(), 0, 2u * (size_t)p->tab[k].cap, p->stream));
+        POS_HIP(p, hipMemcpyAsync(d_c_to_a.get(), c_to_a, sizeof c_to_a, hipMemcpyHostToDevice, p->stream));
         POS_HIP(p, hipStreamSynchronize(p->stream));
         return 0;
     };
     const int rc = build();
     if (rc) { /* the tracker stays as it was */
         (void)hipGetLastError();
-        release(ac), release(d_c_to_a), release(codes), release(hits[0]), release(hits[1]);
         return rc;
     }
-    p->d_ac = ac;
-    p->d_c_to_a = d_c_to_a;
-    p->d_codes = codes;
-    p->tab[0].hits = hits[0];
-    p->tab[1].hits = hits[1];
+    p->d_ac = std::move(ac);
+    p->d_c_to_a = std::move(d_c_to_a);
+    p->d_codes = std::move(codes);
+    p->hits[0] = std::move(hits[0]);
+    p->hits[1] = std::move(hits[1]);
+    point_tables(p);
     return 0;
 }
 
 int msd_pos_modeac_match(msd_pos *p, uint64_t now_ms, uint64_t message_now_ms)
 {
-    if (!p || !p->d_ac)
+    if (!p || !p->d_ac.get())
         return -EINVAL;
     POS_HIP(p, hipSetDevice(p->device));
-    msd_pos_launch_modeac_match(p->stream, p->tab[p->cur], p->nrx, now_ms, message_now_ms, p->d_c_to_a, p->d_ac);
+    msd_pos_launch_modeac_match(p->stream, p->tab[p->cur], p->nrx, now_ms, message_now_ms, p->d_c_to_a.get(), p->d_ac.get());
     POS_HIP(p, hipGetLastError());
     POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
@@ -910,47 +802,25 @@ int msd_pos_modeac_match(msd_pos *p, uint64_t now_ms, uint64_t message_now_ms)
 
 int msd_pos_modeac_codes(msd_pos *p, uint32_t receiver, msd_modeac_code *out, int on_device)
 {
-    if (!p || !p->d_ac || receiver >= p->nrx || !out)
+    if (!p || !p->d_ac.get() || receiver >= p->nrx || !out)
         return -EINVAL;
     POS_HIP(p, hipSetDevice(p->device));
-    msd_modeac_code *dst = on_device ? out : p->d_codes;
-    msd_pos_launch_modeac_codes(p->stream, p->d_ac + (size_t)receiver * MSD_MODEAC_WORDS, dst);
+    msd_modeac_code *dst = on_device ? out : p->d_codes.get();
+    msd_pos_launch_modeac_codes(p->stream, p->d_ac.get() + (size_t)receiver * MSD_MODEAC_WORDS, dst);
     POS_HIP(p, hipGetLastError());
     if (!on_device)
-        POS_HIP(p, hipMemcpyAsync(out, p->d_codes, sizeof(msd_modeac_code) * MSD_MODEAC_CODES, hipMemcpyDeviceToHost, p->stream));
+        POS_HIP(p, hipMemcpyAsync(out, dst, sizeof(msd_modeac_code) * MSD_MODEAC_CODES, hipMemcpyDeviceToHost, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     return 0;
 }
 
 int msd_pos_modeac_hits(msd_pos *p, msd_modeac_hit *out, size_t cap, int on_device, size_t *n)
 {
-    if (!p || !p->d_ac || !n || (!out && cap > 0))
+    if (!p || !p->d_ac.get() || !n || (!out && cap > 0))
         return -EINVAL;
-    *n = (size_t)p->live;
-    if (p->live > cap) {
-        snprintf(p->err, sizeof p->err, "%llu aircraft do not fit %zu entries", (unsigned long long)p->live, cap);
-        return -ENOSPC;
-    }
-    if (p->live == 0)
-        return 0;
-    POS_HIP(p, hipSetDevice(p->device));
-    const int rc = snapshot_buffers(p);
-    if (rc)
-        return rc;
-    if (!on_device && p->live > p->cap_hits_out) {
-        release(p->d_hits_out);
-        p->cap_hits_out = 0;
-        POS_HIP(p, hipMalloc(&p->d_hits_out, p->live * sizeof(msd_modeac_hit)));
-        p->cap_hits_out = (size_t)p->live;
-    }
-    msd_modeac_hit *dst = on_device ? out : p->d_hits_out;
-    msd_pos_launch_modeac_hits(p->stream, p->tab[p->cur], (uint32_t)p->live, snapshot_key_bits(p), p->s_idx[0], p->s_idx[1],
-                               p->s_hist, dst);
-    POS_HIP(p, hipGetLastError());
-    if (!on_device)
-        POS_HIP(p, hipMemcpyAsync(out, p->d_hits_out, p->live * sizeof(msd_modeac_hit), hipMemcpyDeviceToHost, p->stream));
-    POS_HIP(p, hipStreamSynchronize(p->stream));
-    return 0;
+    return read_out(p, p->d_hits_out, out, cap, on_device, n, [&](uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist, msd_modeac_hit *dst) {
+        msd_pos_launch_modeac_hits(p->stream, p->tab[p->cur], (uint32_t)p->live, snapshot_key_bits(p), idx_a, idx_b, hist, dst);
+    });
 }
 
 int msd_aircraft_valid(const msd_aircraft *a, int member, uint64_t now_ms)
@@ -964,10 +834,10 @@ int msd_pos_expire(msd_pos *p, uint64_t now_ms)
         return -EINVAL;
     POS_HIP(p, hipSetDevice(p->device));
     uint32_t ctl[MSD_POS_CTL_N] = {};
-    POS_HIP(p, hipMemsetAsync(p->d_ctl, 0, sizeof ctl, p->stream));
-    msd_pos_launch_expire(p->stream, p->tab[p->cur], now_ms, p->d_ctl);
+    POS_HIP(p, hipMemsetAsync(p->d_ctl.get(), 0, sizeof ctl, p->stream));
+    msd_pos_launch_expire(p->stream, p->tab[p->cur], now_ms, p->d_ctl.get());
     POS_HIP(p, hipGetLastError());
-    POS_HIP(p, hipMemcpyAsync(ctl, p->d_ctl, sizeof ctl, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipMemcpyAsync(ctl, p->d_ctl.get(), sizeof ctl, hipMemcpyDeviceToHost, p->stream));
     POS_HIP(p, hipStreamSynchronize(p->stream));
     if (!ctl[MSD_POS_CTL_REMOVED])
         return 0;
@@ -976,8 +846,8 @@ int msd_pos_expire(msd_pos *p, uint64_t now_ms)
     msd_pos_launch_fill(p->stream, p->tab[other].keys, p->tab[other].cap);
     msd_pos_launch_rebuild(p->stream, p->tab[p->cur], p->tab[other]);
     POS_HIP(p, hipGetLastError());
-    if (p->d_pb_table) {
-        msd_pb_launch_move(p->stream, p->tab[p->cur], p->pb_state[p->cur], p->tab[other], p->pb_state[other]);
+    if (p->pb) {
+        msd_pb_launch_move(p->stream, p->tab[p->cur], p->pb_state[p->cur].get(), p->tab[other], p->pb_state[other].get());
         POS_HIP(p, hipGetLastError());
     }
     POS_HIP(p, hipStreamSynchronize(p->stream));
@@ -992,7 +862,7 @@ int msd_pos_get_stats(const msd_pos *p, msd_pos_stats *st)
         return -EINVAL;
     unsigned long long d[MSD_POS_DSTATS];
     if (hipSetDevice(p->device) != hipSuccess ||
-        hipMemcpy(d, p->d_stats, sizeof d, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(d, p->d_stats.get(), sizeof d, hipMemcpyDeviceToHost) != hipSuccess)
         return -EIO;
     memcpy(st, d, sizeof(uint64_t) * MSD_PC_N);
     st->aircraft = p->live;

@@ -1,5 +1,7 @@
-/* msd_pos.h -- what msd_pos.cpp (the C-ABI of the position tracker) launches from msd_pos_kernels.hip.  Every function
- * queues kernels on `stream` and returns; all pointers are device memory. */
+/* msd_pos.h -- what msd_pos.cpp (the C-ABI of the position tracker) launches from msd_pos_kernels.hip and from its four
+ * writers (msd_reduce_kernels.hip, msd_sbs_kernels.hip, msd_pb_kernels.hip, msd_vrs_kernels.hip).  Every function queues
+ * kernels on `stream` and returns; all pointers are device memory.  The tables and the call structs are raw pointers
+ * because kernels take them by value; msd_pos.cpp owns what they point into. */
 #ifndef MSD_POS_H
 #define MSD_POS_H
 
@@ -91,13 +93,20 @@ void msd_pb_launch_move(hipStream_t stream, msd_pos_table from, const uint64_t *
  * ceil(items / 256) + 1 words -- bytes, written, with position, TIS-B --, the workgroups' offsets and then the total; rx:
  * nrx rows.  store: the bytes to out (device memory, as many as block_sums' first total says), and every written
  * aircraft's shadow into state */
-void msd_pb_launch_lengths(hipStream_t stream, msd_pos_table t, const uint64_t *state, const uint32_t *idx, uint32_t live,
-                           uint32_t nrx, uint64_t now_ms, const uint64_t *messages_total, const uint16_t *track_table,
-                           uint32_t *first, uint32_t *items, uint64_t *shadow, uint16_t *lens, uint32_t *within,
-                           uint32_t *cwithin, uint32_t *block_sums, msd_pb_receiver *rx);
-void msd_pb_launch_store(hipStream_t stream, msd_pos_table t, uint64_t *state, const uint32_t *idx, uint32_t live, uint32_t nrx,
-                         uint64_t now_ms, const uint64_t *messages_total, const uint16_t *track_table, const uint32_t *items,
-                         const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off, uint8_t *out);
+typedef struct msd_pb_call {
+    msd_pos_table t;
+    uint64_t *state;                /* the written state, per slot */
+    const uint32_t *idx;            /* the ordered slots */
+    const uint32_t *items;
+    const uint64_t *messages_total; /* per receiver, or NULL */
+    const uint16_t *track_table;
+    uint64_t now_ms;
+    uint32_t nitems, nrx;
+} msd_pb_call;
+void msd_pb_launch_lengths(hipStream_t stream, msd_pb_call c, uint32_t live, uint32_t *first, uint32_t *items, uint64_t *shadow,
+                           uint16_t *lens, uint32_t *within, uint32_t *cwithin, uint32_t *block_sums, msd_pb_receiver *rx);
+void msd_pb_launch_store(hipStream_t stream, msd_pb_call c, const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off,
+                         uint8_t *out);
 /* VRS output (msd_vrs_kernels.hip).  The items of a call are, per receiver, a head, its live aircraft and a tail, in
  * stream order (live + 2 * nrx of them; idx: the ordered slots).  select: first[0 .. nrx], items[], and per item lens
  * (an aircraft's without its comma; 0: not selected) and swithin (the selected aircraft before it inside its workgroup of

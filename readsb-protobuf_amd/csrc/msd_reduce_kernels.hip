@@ -4,7 +4,7 @@
  * msd_pos_reduce_wire (msd_pos.cpp): n records and their verdict bytes -> one dense stream of the records that pass the
  * delivery conditions, in record order.  The three steps of msd_wire_encode (msd_wire_kernels.hip) with the verdict in
  * front: msd_reduce_len_kernel leaves a length per record -- 0 for one that stays behind -- and a sum per workgroup of
- * 256, msd_reduce_scan_kernel turns the sums into offsets (one workgroup), msd_reduce_store_kernel encodes into LDS and
+ * 256, scan_kernel (msd_wire_store_impl.h) turns the sums into offsets (one workgroup), msd_reduce_store_kernel encodes into LDS and
  * stores through wire_store_run as whole-wavefront runs of aligned dwords.  No place is handed out by an atomic: a
  * record's offset is a prefix sum, so the stream is the same on every run.
  */
@@ -13,7 +13,7 @@
 
 namespace {
 
-using namespace msd_wire_store; /* WT, IMAGE_WORDS, block_scan, block_sums_scan, image_at, wire_store_run */
+using namespace msd_wire_store; /* WT, IMAGE_WORDS, block_scan, scan_kernel, image_at, wire_store_run */
 
 /* mode_s.c:2164-2172 and net_io.c:1282: the verdict says forward, and the aircraft has been seen twice unless
  * --net-verbatim or --net-only; msd_wire_source adds net_io.c:1278's correctedbits < 2 unless --net-verbatim */
@@ -40,13 +40,6 @@ __global__ void __launch_bounds__(WT) msd_reduce_len_kernel(const msd_message *m
     (void)block_scan(len, part, total);
     if (threadIdx.x == 0)
         block_sums[blockIdx.x] = total;
-}
-
-/* block_sums[0 .. nblocks) -> their exclusive prefix in place, block_sums[nblocks] = the stream's length.  One workgroup. */
-__global__ void __launch_bounds__(WT) msd_reduce_scan_kernel(uint32_t *block_sums, uint32_t nblocks)
-{
-    __shared__ uint32_t part[4];
-    block_sums_scan(block_sums, nblocks, part);
 }
 
 __global__ void __launch_bounds__(WT) msd_reduce_store_kernel(const msd_message *msgs, uint32_t n, uint32_t flags,
@@ -79,7 +72,7 @@ void msd_reduce_launch_lengths(hipStream_t stream, const msd_message *msgs, cons
 {
     const uint32_t nblocks = (n + WT - 1u) / WT;
     msd_reduce_len_kernel<<<nblocks, WT, 0, stream>>>(msgs, forward, n, flags, lens, block_sums);
-    msd_reduce_scan_kernel<<<1, WT, 0, stream>>>(block_sums, nblocks);
+    scan_kernel<><<<1, WT, 0, stream>>>(block_sums, nblocks);
 }
 
 void msd_reduce_launch_store(hipStream_t stream, const msd_message *msgs, uint32_t n, uint32_t flags, const uint8_t *lens,

@@ -4,7 +4,7 @@
  * msd_pos_sbs_wire (msd_pos.cpp): n records, their fields and their rows -> one dense stream of the lines of the records
  * that pass the delivery conditions, in record order.  The three steps of msd_reduce_kernels.hip with text in place of
  * frames: msd_sbs_len_kernel leaves a length per record -- 0 for one that writes nothing -- and a sum per workgroup of
- * 256, msd_sbs_scan_kernel turns the sums into offsets (one workgroup), msd_sbs_store_kernel has every lane format its
+ * 256, scan_kernel (msd_wire_store_impl.h) turns the sums into offsets (one workgroup), msd_sbs_store_kernel has every lane format its
  * record into the LDS image and stores the image through wire_store_run as whole-wavefront runs of aligned dwords.  No
  * place is handed out by an atomic: a record's offset is a prefix sum, so the stream is the same on every run.
  * Both kernels run msd_sbs_line (msd_sbs_impl.h): the length kernel with no destination, so that a length is by
@@ -19,7 +19,7 @@
 
 namespace {
 
-using namespace msd_wire_store; /* WT, block_scan, block_sums_scan, image_at, wire_store_run */
+using namespace msd_wire_store; /* WT, block_scan, scan_kernel, image_at, wire_store_run */
 
 static_assert(MSD_SBS_MAX <= 255, "a line's length is kept in a byte");
 /* the image starts at the destination's offset in its dword; behind the tile's 256 longest lines there is room for one
@@ -46,13 +46,6 @@ msd_sbs_len_kernel(const msd_message *msgs, const msd_fields *fields, const msd_
     (void)block_scan(len, part, total);
     if (threadIdx.x == 0)
         block_sums[blockIdx.x] = total;
-}
-
-/* block_sums[0 .. nblocks) -> their exclusive prefix in place, block_sums[nblocks] = the stream's length.  One workgroup. */
-__global__ void __launch_bounds__(WT) msd_sbs_scan_kernel(uint32_t *block_sums, uint32_t nblocks)
-{
-    __shared__ uint32_t part[4];
-    block_sums_scan(block_sums, nblocks, part);
 }
 
 __global__ void __launch_bounds__(WT)
@@ -86,7 +79,7 @@ void msd_sbs_launch_lengths(hipStream_t stream, const msd_message *msgs, const m
 {
     const uint32_t nblocks = (n + WT - 1u) / WT;
     msd_sbs_len_kernel<<<nblocks, WT, 0, stream>>>(msgs, fields, trk, n, opt, track_table, lens, block_sums);
-    msd_sbs_scan_kernel<<<1, WT, 0, stream>>>(block_sums, nblocks);
+    scan_kernel<><<<1, WT, 0, stream>>>(block_sums, nblocks);
 }
 
 void msd_sbs_launch_store(hipStream_t stream, const msd_message *msgs, const msd_fields *fields, const msd_sbs_track *trk,

@@ -12,67 +12,38 @@
  * document, so an aircraft's length depends on whether any aircraft between its receiver's head and itself was selected.
  * That is a difference of two prefix counts, and a count across workgroups exists only after a scan; so there are two
  * length passes:
- *   msd_vrs_items_kernel   first[] by a binary search per receiver, the items by a scatter per aircraft
+ *   items_kernel<2>        first[] by a binary search per receiver, the items by a scatter per aircraft (msd_items_impl.h)
  *   msd_vrs_select_kernel  one lane per item.  An aircraft's lane reads its entry once, where it lies, decides selection
  *                          and leaves the object's length without a comma (0: not written); per item the selected
  *                          aircraft before it inside its workgroup, per workgroup their sum
- *   msd_vrs_scan_kernel    the sums into offsets (one workgroup)
+ *   scan_kernel            the sums into offsets (one workgroup; msd_wire_store_impl.h)
  *   msd_vrs_len_kernel     one lane per item: selected before me minus selected before my receiver's head says whether the
  *                          comma is there (bit 15 of the length); the bytes before the item inside its workgroup, per
  *                          workgroup their sum.  Of the table it reads a selected aircraft's key alone
- *   msd_vrs_scan_kernel    again, over the bytes
+ *   scan_kernel            again, over the bytes
  *   msd_vrs_rx_kernel      one lane per receiver: its row from the prefixes at its head's item and at the next head's
- *   msd_vrs_store_kernel   lanes write into an LDS image, wire_store_run stores it as whole-wavefront runs of aligned dwords
+ *   msd_vrs_store_kernel   lanes write into an LDS image, tiled_store (msd_items_impl.h) stores it as whole-wavefront runs of
+ *                          aligned dwords
  * Both object passes run msd_vrs_aircraft (msd_vrs_impl.h), the select kernel with no destination: a length is by
  * construction what the store kernel writes.  No kernel changes the table: the call is stateless.
  * The image.  An object is at most MSD_VRS_AIRCRAFT_MAX = 418 bytes, three more than an aircraft.pb entry, and the
  * image still holds what pb's does: VRS_TILE = 128 items, 53.9 KB, three workgroups, twelve wavefronts, per CU of 160 KB
  * (3 x 53 952 = 161 856 of 163 840 bytes) -- the pb store kernel's occupancy.  A workgroup keeps the writers' 256
- * threads (block_scan and wire_store_run are built on them) and fills and stores the image twice, lanes 0-127 then lanes
- * 128-255; all 256 threads store both times.
+ * threads (block_scan and wire_store_run are built on them) and fills and stores the image twice (tiled_store).
  */
 #include "msd_pos.h"
 #include "msd_vrs_impl.h"
-#include "msd_wire_store_impl.h"
+#include "msd_items_impl.h"
 
 namespace {
 
-using namespace msd_wire_store; /* WT, block_scan, block_sums_scan, image_at, wire_store_run */
+using namespace msd_items; /* HEAD, TAIL, items_kernel, tiled_store; of msd_wire_store: WT, block_scan, scan_kernel */
 
 constexpr uint32_t VRS_TILE = MSD_VRS_TILE;
-constexpr uint32_t VRS_HEAD = 0x80000000u; /* an item that is a receiver's head; the low bits are the receiver */
-constexpr uint32_t VRS_TAIL = 0x40000000u; /* its tail */
 constexpr uint32_t VRS_COMMA = 0x8000u;    /* in a length: the object has its comma; the low bits include it */
-static_assert(WT == 2u * VRS_TILE, "a workgroup fills the image twice");
 static_assert(MSD_VRS_HEAD_LEN <= MSD_VRS_AIRCRAFT_MAX && MSD_VRS_AIRCRAFT_MAX < VRS_COMMA, "an item is at most an object");
 /* the image starts at the destination's offset in its dword; behind the tile's longest items there is room for one more */
 constexpr uint32_t VRS_IMAGE_WORDS = (VRS_TILE * MSD_VRS_AIRCRAFT_MAX + MSD_VRS_AIRCRAFT_MAX + 3u) / 4u + 2u;
-
-__global__ void __launch_bounds__(WT)
-msd_vrs_items_kernel(const uint64_t *keys, const uint32_t *idx, uint32_t live, uint32_t nrx, uint32_t *first, uint32_t *items)
-{
-    const uint32_t g = blockIdx.x * WT + threadIdx.x;
-    if (g <= nrx) { /* the first place whose receiver is g or above; first[nrx] = live */
-        uint32_t lo = 0, hi = live;
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2u;
-            if ((keys[idx[mid]] >> 25) < g)
-                lo = mid + 1u;
-            else
-                hi = mid;
-        }
-        first[g] = lo;
-        if (g < nrx)
-            items[lo + 2u * g] = VRS_HEAD | g;
-        if (g > 0)
-            items[lo + 2u * g - 1u] = VRS_TAIL | (g - 1u);
-    }
-    if (g < live) {
-        const uint64_t r = keys[idx[g]] >> 25;
-        if (r < nrx) /* (every key's receiver is: msd_pos_update refuses any other) */
-            items[g + 2u * (uint32_t)r + 1u] = g;
-    }
-}
 
 __global__ void __launch_bounds__(WT)
 msd_vrs_select_kernel(msd_vrs_call c, uint16_t *lens, uint16_t *swithin, uint32_t *sel_sums)
@@ -82,9 +53,9 @@ msd_vrs_select_kernel(msd_vrs_call c, uint16_t *lens, uint16_t *swithin, uint32_
     uint32_t len = 0, selected = 0;
     if (i < c.nitems) {
         const uint32_t item = c.items[i];
-        if (item & VRS_HEAD) {
+        if (item & HEAD) {
             len = MSD_VRS_HEAD_LEN;
-        } else if (item & VRS_TAIL) {
+        } else if (item & TAIL) {
             len = MSD_VRS_TAIL_LEN;
         } else {
             const uint32_t s = c.idx[item];
@@ -105,13 +76,6 @@ msd_vrs_select_kernel(msd_vrs_call c, uint16_t *lens, uint16_t *swithin, uint32_
         sel_sums[blockIdx.x] = total;
 }
 
-/* sums[0 .. nblocks) -> their exclusive prefix in place, sums[nblocks] = their sum */
-__global__ void __launch_bounds__(WT) msd_vrs_scan_kernel(uint32_t *sums, uint32_t nblocks)
-{
-    __shared__ uint32_t part[4];
-    block_sums_scan(sums, nblocks, part);
-}
-
 /* the selected aircraft in front of item i (i == nitems: all of them) */
 __device__ __forceinline__ uint32_t vrs_selected_before(uint32_t i, uint32_t nitems, const uint16_t *swithin, const uint32_t *sel_sums,
                                                          uint32_t nblocks)
@@ -129,7 +93,7 @@ msd_vrs_len_kernel(msd_vrs_call c, uint16_t *lens, const uint16_t *swithin, cons
     if (i < c.nitems) {
         len = lens[i];
         const uint32_t item = c.items[i];
-        if (len && !(item & (VRS_HEAD | VRS_TAIL))) {
+        if (len && !(item & (HEAD | TAIL))) {
             const uint32_t r = (uint32_t)(c.t.keys[c.idx[item]] >> 25);
             const uint32_t head = c.first[r] + 2u * r;
             if (vrs_selected_before(i, c.nitems, swithin, sel_sums, nblocks) !=
@@ -167,39 +131,24 @@ __global__ void __launch_bounds__(WT)
 msd_vrs_store_kernel(msd_vrs_call c, const uint16_t *lens, const uint32_t *block_off, uint8_t *out)
 {
     __shared__ uint32_t part[4];
-    __shared__ uint32_t half; /* the bytes of the workgroup's first VRS_TILE items */
+    __shared__ uint32_t half;
     __shared__ uint32_t image[VRS_IMAGE_WORDS];
-    const uint32_t i = blockIdx.x * WT + threadIdx.x;
-    const uint32_t coded = i < c.nitems ? lens[i] : 0u;
-    const uint32_t len = coded & (VRS_COMMA - 1u);
-    uint32_t total;
-    const uint32_t off = block_scan(len, part, total);
-    if (threadIdx.x == VRS_TILE)
-        half = off;
-    __syncthreads();
-    const uint32_t first_bytes = half;
-    uint8_t *const dst0 = out + block_off[blockIdx.x];
-    for (uint32_t round = 0; round < 2u; ++round) {
-        uint8_t *const dst = round ? dst0 + first_bytes : dst0;
-        const uint32_t run = round ? total - first_bytes : first_bytes;
-        if (threadIdx.x / VRS_TILE == round && len) { /* (a length above 0: a head, a tail, a selected aircraft) */
-            uint8_t *at = image_at(image, dst, round ? off - first_bytes : off);
-            const uint32_t item = c.items[i];
-            if (item & VRS_HEAD) {
-                (void)msd_vrs_head_text(at);
-            } else if (item & VRS_TAIL) {
-                (void)msd_vrs_tail_text(at);
-            } else {
-                const uint32_t s = c.idx[item];
-                msd_vrs_head h;
-                msd_vrs_head_of_state(c.t.keys[s], &c.t.st[s], &h);
-                (void)msd_vrs_aircraft(&h, &c.t.trk[s], c.now_ms, (coded & VRS_COMMA) != 0, c.track_table, at);
-            }
+    const uint32_t me = blockIdx.x * WT + threadIdx.x;
+    const uint32_t coded = me < c.nitems ? lens[me] : 0u;
+    /* (a length above 0: a head, a tail, a selected aircraft) */
+    tiled_store<VRS_TILE>(coded & (VRS_COMMA - 1u), out, block_off, part, half, image, [&](uint32_t i, uint8_t *at) {
+        const uint32_t item = c.items[i];
+        if (item & HEAD) {
+            (void)msd_vrs_head_text(at);
+        } else if (item & TAIL) {
+            (void)msd_vrs_tail_text(at);
+        } else {
+            const uint32_t s = c.idx[item];
+            msd_vrs_head h;
+            msd_vrs_head_of_state(c.t.keys[s], &c.t.st[s], &h);
+            (void)msd_vrs_aircraft(&h, &c.t.trk[s], c.now_ms, (coded & VRS_COMMA) != 0, c.track_table, at);
         }
-        __syncthreads();
-        wire_store_run(dst, image, run);
-        __syncthreads();
-    }
+    });
 }
 
 } // namespace
@@ -209,11 +158,11 @@ void msd_vrs_launch_lengths(hipStream_t stream, msd_vrs_call c, uint32_t live, u
 {
     const uint32_t nblocks = (c.nitems + WT - 1u) / WT;
     const uint32_t most = live > c.nrx + 1u ? live : c.nrx + 1u;
-    msd_vrs_items_kernel<<<(most + WT - 1u) / WT, WT, 0, stream>>>(c.t.keys, c.idx, live, c.nrx, first, items);
+    items_kernel<2><<<(most + WT - 1u) / WT, WT, 0, stream>>>(c.t.keys, c.idx, live, c.nrx, first, items);
     msd_vrs_select_kernel<<<nblocks, WT, 0, stream>>>(c, lens, swithin, sel_sums);
-    msd_vrs_scan_kernel<<<1, WT, 0, stream>>>(sel_sums, nblocks);
+    scan_kernel<><<<1, WT, 0, stream>>>(sel_sums, nblocks);
     msd_vrs_len_kernel<<<nblocks, WT, 0, stream>>>(c, lens, swithin, sel_sums, within, byte_sums, nblocks);
-    msd_vrs_scan_kernel<<<1, WT, 0, stream>>>(byte_sums, nblocks);
+    scan_kernel<><<<1, WT, 0, stream>>>(byte_sums, nblocks);
     msd_vrs_rx_kernel<<<(c.nrx + WT - 1u) / WT, WT, 0, stream>>>(first, c.nrx, c.nitems, swithin, sel_sums, within, byte_sums, nblocks, rx);
 }
 

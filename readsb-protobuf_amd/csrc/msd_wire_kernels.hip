@@ -2,7 +2,7 @@
  * msd_wire_kernels.hip -- Beast frames and AVR lines written on the GPU (msd_wire_impl.h encodes one message).
  *
  *   msd_wire_encode (msd_capi.cpp): n records -> one dense stream in record order.  msd_wire_len_kernel leaves a
- *   length per record and a sum per workgroup of 256, msd_wire_scan_kernel turns the sums into offsets (one
+ *   length per record and a sum per workgroup of 256, scan_kernel (msd_wire_store_impl.h) turns the sums into offsets (one
  *   workgroup), msd_wire_store_kernel encodes and stores.
  *
  *   receiver groups (msd_group.cpp): one workgroup per buffer of a call builds the buffer's messages the way
@@ -22,7 +22,7 @@
 
 namespace {
 
-using namespace msd_wire_store; /* WT, IMAGE_WORDS, block_scan, block_sums_scan, image_at, wire_store_run */
+using namespace msd_wire_store; /* WT, IMAGE_WORDS, block_scan, scan_kernel, image_at, wire_store_run */
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* msd_wire_encode */
@@ -42,13 +42,6 @@ __global__ void __launch_bounds__(WT) msd_wire_len_kernel(const msd_message *msg
     (void)block_scan(len, part, total);
     if (threadIdx.x == 0)
         block_sums[blockIdx.x] = total;
-}
-
-/* block_sums[0 .. nblocks) -> their exclusive prefix in place, block_sums[nblocks] = the stream's length.  One workgroup. */
-__global__ void __launch_bounds__(WT) msd_wire_scan_kernel(uint32_t *block_sums, uint32_t nblocks)
-{
-    __shared__ uint32_t part[4];
-    block_sums_scan(block_sums, nblocks, part);
 }
 
 __global__ void __launch_bounds__(WT) msd_wire_store_kernel(const msd_message *msgs, uint32_t n, int format, int verbatim,
@@ -177,7 +170,7 @@ extern "C" int msd_launch_wire_lengths(const msd_message *d_msgs, uint32_t n, in
     const uint32_t nblocks = (n + WT - 1) / WT;
     hipLaunchKernelGGL(msd_wire_len_kernel, dim3(nblocks), dim3(WT), 0, stream, d_msgs, n, format, verbatim, d_lens,
                        d_block_sums);
-    hipLaunchKernelGGL(msd_wire_scan_kernel, dim3(1), dim3(WT), 0, stream, d_block_sums, nblocks);
+    hipLaunchKernelGGL(scan_kernel<>, dim3(1), dim3(WT), 0, stream, d_block_sums, nblocks);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -1,7 +1,8 @@
 /* msd_wire_store_impl.h -- how the wire kernels lay a stream out and store it: the workgroup scan over the messages'
  * lengths, the scan over the workgroups' sums, and the LDS image of up to 256 messages that leaves as whole-wavefront
  * runs of consecutive aligned dwords (the destination may be host memory, where a store per message byte would cost a
- * PCIe write each).  Shared by msd_wire_kernels.hip and msd_group_remote_out_kernels.hip.  Device code only. */
+ * PCIe write each).  Shared by msd_wire_kernels.hip, msd_group_remote_out_kernels.hip and the position tracker's four
+ * writers (msd_reduce_kernels.hip, msd_sbs_kernels.hip, msd_pb_kernels.hip, msd_vrs_kernels.hip).  Device code only. */
 #ifndef MSD_WIRE_STORE_IMPL_H
 #define MSD_WIRE_STORE_IMPL_H
 
@@ -40,7 +41,7 @@ __device__ inline uint32_t block_scan(uint32_t v, uint32_t *part, uint32_t &tota
 }
 
 /* block_sums[0 .. nblocks) -> their exclusive prefix in place, block_sums[nblocks] = the stream's length.  The body of
- * a kernel of one workgroup. */
+ * scan_kernel. */
 __device__ inline void block_sums_scan(uint32_t *block_sums, uint32_t nblocks, uint32_t *part)
 {
     uint32_t run = 0;
@@ -55,6 +56,15 @@ __device__ inline void block_sums_scan(uint32_t *block_sums, uint32_t nblocks, u
     }
     if (threadIdx.x == 0)
         block_sums[nblocks] = run;
+}
+
+/* The scan step of every writer, one workgroup: each of ARRAYS consecutive arrays of nblocks + 1 words, as block_sums_scan
+ * leaves it. */
+template <uint32_t ARRAYS = 1> __global__ void __launch_bounds__(WT) scan_kernel(uint32_t *block_sums, uint32_t nblocks)
+{
+    __shared__ uint32_t part[4];
+    for (uint32_t q = 0; q < ARRAYS; ++q)
+        block_sums_scan(block_sums + q * (nblocks + 1u), nblocks, part);
 }
 
 /* Where thread t's bytes go in the image of a run that will be stored at dst: the image mirrors the destination's
