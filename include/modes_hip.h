@@ -850,8 +850,9 @@ int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, co
  * aircraft, with decoded_nic / decoded_rc, are kept by a tracker made with msd_pos_create_table ("the aircraft table"
  * below); a table tracker can also match the Mode A/C replies against its aircraft ("Mode A/C matching" below) and thin
  * the feed to readsb's reduced Beast output ("Reduced Beast output" below), write the SBS output ("SBS output" below) and
- * write aircraft.pb, the AircraftsUpdate protobuf, from the table ("aircraft.pb" below).
- * Not built: the declination, the polar range, SBS input and MLAT positions.
+ * write aircraft.pb, the AircraftsUpdate protobuf, from the table ("aircraft.pb" below); either kind of tracker can keep
+ * a->meta.distance, the polar range and the longest distance per receiver ("Receiver range" below).
+ * Not built: the declination, SBS input and MLAT positions.
  *
  * What is exact.  The coordinates: double + - * / floor fmod in the reference's order, nothing contracted; delivered
  * lat / lon are bit-identical to the reference's whenever the decisions are.
@@ -933,8 +934,8 @@ int msd_pos_get_stats(const msd_pos *p, msd_pos_stats *st);
  * :458-473).  accept_data's stale interval is 15 s for altitude_baro, squawk and airground and 60 s for the others; every
  * member expires 70 s after its update, so a member keeps `source` and `updated` only -- except altitude_geom, whose
  * validity combine_validity can make from two others and which keeps its stale and expiry times.
- * Not built: FATSV state, the declination (geomag_calc), the polar range, SBS and MLAT input (SBS output: "SBS output"
- * below).  modeA_hit / modeC_hit
+ * Not built: FATSV state, the declination (geomag_calc), SBS and MLAT input (SBS output: "SBS output" below; distance
+ * and the polar range: "Receiver range" below).  modeA_hit / modeC_hit
  * are kept beside the entry, not in it: "Mode A/C matching" below; so are the timers of accept_data's reduce_forward half:
  * "Reduced Beast output" below.
  *
@@ -1208,8 +1209,9 @@ int msd_pos_sbs_wire(msd_pos *p, const msd_message *msgs, const msd_fields *fiel
  * NUL, at most 8 bytes, if attached; nav_modes (150) with its six bools if attached (all false: B2 09 00); seen_pos (41)
  * if non-zero.  The state starts at 0 with the aircraft, moves with its slot, goes with removal and msd_pos_reset, is not
  * touched for an aircraft that is not selected, and is committed only by a call that returns 0.
- * Not written: distance (13), declination (46), wind_speed / wind_direction (47 / 48) and valid_source.wind (132).  They
- * need update_polar_range and geomag_calc, which are not built; a wind against a declination of 0 would be wrong.
+ * distance (13) is written, when non-zero, by a tracker that keeps the receiver range ("Receiver range" below) and by no
+ * other.  Not written: declination (46), wind_speed / wind_direction (47 / 48) and valid_source.wind (132).  They need
+ * geomag_calc, which is not built; a wind against a declination of 0 would be wrong.
  * CONTRACT, the table's: the device and the host object (msd_pos_host_pb_enable, msd_pos_host_aircraft_pb -- a plain
  * sequential encoder that shares no code with the device's) deliver the same stream, the same rows and the same written
  * state on every table on which they hold the same msd_aircraft bytes and min_rssi_margin_ulps is at least
@@ -1327,6 +1329,84 @@ int msd_pos_vrs_enable(msd_pos *p);
  * enabled, NULL, an unknown flag, reserved != 0, n_parts not a power of two in 1 .. 2048, part >= n_parts.  -E2BIG: the
  * table could hold more than 2^32 - 1 bytes of stream (above some 10 million aircraft). */
 int msd_pos_vrs(msd_pos *p, const msd_vrs_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_vrs_receiver *rx);
+
+/* ---- Receiver range: the last lines of updatePosition (track.c:683-686) -- a->meta.distance, the polar range of
+ * --stats-range (update_polar_range :281-308 with getBearing :238-250; Statistics.polar_range in stats.pb, the range
+ * outline on the map) and stats_current.longest_distance -- per receiver index, for either kind of tracker, on the device
+ * (DESIGN.md 4.10).
+ *
+ * The rule, for a record from which a position was decoded (msd_position.decoded), after lat / lon and the pos_reliable
+ * counters are updated: distance = 0; if pos_reliable_odd >= 1, pos_reliable_even >= 1 and the record's source is 7
+ * (ADS-B) and the record's receiver has a location: range = greatcircle(receiver, position) -- the function and the libm
+ * of the gates --; longest = range where range <= max_range_m (or max_range_m is 0) and range > longest; with
+ * MSD_RANGE_POLAR, bucket = (int)round(getBearing(receiver, position) / 5), 72 and more -> 0, and polar_range[bucket] =
+ * (uint32_t)range where it is smaller; distance = (uint32_t)range; `evaluated` counts these records.  A decoded record that
+ * is not ADS-B, or whose aircraft is not yet reliable (a receiver-relative decode after an expiry succeeds at 0 / 0), or
+ * whose receiver has no location, leaves distance 0 and touches nothing else.
+ * polar_range[b] ends as the maximum of (uint32_t)range over the bucket's records (the truncation is monotone), longest
+ * as a maximum of non-negative doubles: neither depends on the order in which the records are taken, and the device
+ * takes them one lane per record with integer atomic maxima, combined per wavefront first.  distance is per aircraft: the
+ * value left by its last decoded record in stream order.  It starts at 0 with the aircraft, moves with its slot, and goes
+ * with removal and msd_pos_reset.  Results do not depend on how a stream is cut into calls.
+ * aircraft.pb: on a tracker with both the range and aircraft.pb enabled, distance (13) is written when non-zero, between
+ * rssi (12) and air_ground (15), by the device's encoder and by the host object's; an entry can then reach
+ * MSD_PB_AIRCRAFT_MAX_RANGE bytes, the length prefix stays two bytes.  A tracker without the range writes the bytes it
+ * wrote before.
+ *
+ * CONTRACT.  The device and the host object (msd_pos_host_range_*) deliver the same msd_range_receiver bytes and the same
+ * distances on every stream on which (1) they deliver the same msd_position records, (2) the host object's
+ * min_range_margin_m is at least MSD_RANGE_MARGIN_M -- the smallest |range - nearest integer| over every evaluated range
+ * (multiples of 1852 are integers, so longest_nm is covered) and |range - max_range_m| where the receiver has a limit --,
+ * and (3) with MSD_RANGE_POLAR its min_bearing_margin_deg is at least MSD_RANGE_BEARING_MARGIN_DEG: the smallest distance
+ * of getBearing's result from an edge 2.5 + 5k, counted as 0 for a record whose range is below 1 m (where the bearing is
+ * ill-conditioned).  Both margins are +infinity when nothing was evaluated, and start again with msd_pos_reset.  The
+ * device reports its own margins, computed with its own libm; they need not equal the host's.  Where the figures come
+ * from: glibc's doubles against 80-bit evaluation over 4.8 M positions from 1 m to 800 km around receivers at 0.5, 52 and
+ * 78 degrees latitude are off by at most 5.6e-6 m (greatcircle) and 7.7e-8 degrees (getBearing, range >= 1 m): the
+ * constants are about 180 and 130 times those.  Nobody has measured the device library; the bound derived for it in
+ * DESIGN.md 4.10 from its documented 4 ulp for sin, cos and acos and 6 ulp for atan2 is 3.6e-5 m for a receiver at 78
+ * degrees (growing towards the poles about as 1 / cos(latitude): the law of cosines is at its worst 0.001 rad of longitude
+ * from the receiver) and 8.8e-7 degrees at 1 m (falling with 1 / range) -- both below a tenth of the constants, for
+ * receivers up to 85.7 degrees of latitude. ---- */
+#define MSD_RANGE_BUCKETS 72u                 /* POLAR_RANGE_BUCKETS, stats.h:124-125 */
+#define MSD_RANGE_POLAR 1u                    /* enable flag: --stats-range; without it only distance and longest are kept */
+#define MSD_RANGE_TAKE_LONGEST 1u             /* read flag: zero `longest` after reading (the caller rotates stats_current) */
+#define MSD_RANGE_MARGIN_M 1e-3               /* the gates' contract figure: same function, same libm */
+#define MSD_RANGE_BEARING_MARGIN_DEG 1e-5
+#define MSD_PB_AIRCRAFT_MAX_RANGE 421         /* MSD_PB_AIRCRAFT_MAX (stays 415) + tag 0x68 + a 5-byte varint */
+#define MSD_RANGE_PB_ENTRY_MAX 10             /* 32 08 + 08 47 + 10 and a 5-byte varint */
+typedef struct msd_range_receiver {           /* 304 bytes, no implicit padding */
+    uint32_t polar_range[MSD_RANGE_BUCKETS];  /* metres; Modes.stats_range.polar_range */
+    uint32_t longest_m;                       /* (uint32_t)longest_distance             net_io.c:2249 */
+    uint32_t longest_nm;                      /* (uint32_t)(longest_distance / 1852.0)  net_io.c:2250 */
+    uint64_t evaluated;                       /* ranges computed for this receiver since creation / reset */
+} msd_range_receiver;
+typedef struct msd_range_margins { double min_range_margin_m, min_bearing_margin_deg; } msd_range_margins;
+/* Either kind of tracker.  flags: 0 or MSD_RANGE_POLAR; -EINVAL for any other bit.  A second call returns 0 and changes
+ * nothing (its flags are not looked at beyond that check); -ENOMEM leaves the tracker as it was.  Allocates 4 bytes per
+ * slot, twice, 304 bytes per receiver and one byte per record of a call; the aircraft the table already has start at
+ * distance 0.  From then on every update call runs the range instantiation of the position walk, which leaves one code
+ * byte per record, and the range kernel.  msd_pos_set_receiver keeps the receiver's arrays, as handle_radarcape_position
+ * does.  msd_pos_reset zeroes everything and leaves the tracker enabled.  A call that fails with -ENOSPC or -EINVAL
+ * changes nothing.  A tracker that never calls this allocates and launches exactly what it did before. */
+int msd_pos_range_enable(msd_pos *p, uint32_t flags);
+/* Receivers first .. first + count - 1 into the host array out.  longest_m and longest_nm are derived on the device
+ * from the device's own double, which is never delivered.  flags: 0 or MSD_RANGE_TAKE_LONGEST.  -EINVAL: not enabled, an
+ * unknown flag, a range of receivers that is not within 0 .. receivers, NULL with count > 0. */
+int msd_pos_range_read(msd_pos *p, uint32_t first, uint32_t count, msd_range_receiver *out, uint32_t flags);
+/* One distance per live aircraft in msd_pos_snapshot's (receiver, addr) order, into device memory (on_device = 1) or host
+ * memory; *n is their number, also under -ENOSPC (cap is too small, nothing was written).  -EINVAL: not enabled, NULL. */
+int msd_pos_range_distances(msd_pos *p, uint32_t *out, size_t cap, int on_device, size_t *n);
+int msd_pos_range_margins(const msd_pos *p, msd_range_margins *m);
+/* Statistics.polar_range (readsb.proto:271, field 6: map<uint32, uint32>) of every receiver index 0 .. receivers-1 in
+ * ascending order, as protobuf-c's statistics__pack writes what generateStatsProtoBuf builds (net_io.c:2297-2305): 72
+ * entries in bucket order, each the tag 0x32, a length, key (08 <bucket>) and value (10 <varint metres>), either left out
+ * when 0 -- an untouched bucket 0 is 32 00.  One dense stream in the host array out, written on the device with the
+ * writers' three steps (lengths, scan, store); end: a host array of `receivers` end offsets, or NULL.  A caller appends a
+ * receiver's part behind its own fields 1-5 (the counters and their rotation are host bookkeeping) to get stats.pb.
+ * -ENOSPC: cap is too small, *out_len is the size needed, nothing was written and the call can be repeated.  -EINVAL:
+ * not enabled, enabled without MSD_RANGE_POLAR, NULL. */
+int msd_pos_range_pb(msd_pos *p, uint8_t *out, size_t cap, size_t *out_len, uint64_t *end);
 
 #ifdef __cplusplus
 }

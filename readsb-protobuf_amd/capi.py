@@ -244,6 +244,7 @@ EXPORTS = [
     "msd_pos_reduce_enable", "msd_pos_update_reduce", "msd_pos_reduce_wire",
     "msd_pos_sbs_enable", "msd_pos_update_sbs", "msd_pos_sbs_wire", "msd_pos_pb_enable", "msd_pos_aircraft_pb",
     "msd_pos_vrs_enable", "msd_pos_vrs",
+    "msd_pos_range_enable", "msd_pos_range_read", "msd_pos_range_distances", "msd_pos_range_margins", "msd_pos_range_pb",
 ]
 
 _lib = None
@@ -1137,6 +1138,15 @@ PB_RSSI_MARGIN_ULPS = 8.0
 VRS_RECEIVER_DTYPE = np.dtype([("end", "<u8"), ("aircraft", "<u4"), ("reserved", "<u4")])
 assert VRS_RECEIVER_DTYPE.itemsize == 16
 VRS_AIRCRAFT_MAX = 418
+# the receiver range: a receiver's row of msd_pos_range_read (msd_range_receiver), the enable and read flags, and the two
+# margins on the host object under which the device and the host object may differ
+RANGE_BUCKETS = 72
+RANGE_RECEIVER_DTYPE = np.dtype([("polar_range", "<u4", (RANGE_BUCKETS,)), ("longest_m", "<u4"), ("longest_nm", "<u4"),
+                                 ("evaluated", "<u8")])
+assert RANGE_RECEIVER_DTYPE.itemsize == 304
+RANGE_POLAR, RANGE_TAKE_LONGEST = 1, 1
+RANGE_MARGIN_M, RANGE_BEARING_MARGIN_DEG = 1e-3, 1e-5
+PB_AIRCRAFT_MAX_RANGE, RANGE_PB_ENTRY_MAX = 421, 10
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmsd_host.so")
 
 
@@ -1151,6 +1161,10 @@ class PbOptions(C.Structure):
 class VrsOptions(C.Structure):
     _fields_ = [("now_ms", C.c_uint64), ("part", C.c_uint32), ("n_parts", C.c_uint32), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class RangeMargins(C.Structure):
+    _fields_ = [("min_range_margin_m", C.c_double), ("min_bearing_margin_deg", C.c_double)]
 
 
 class PosReceiver(C.Structure):
@@ -1196,8 +1210,14 @@ def _pos_lib(host):
                                               "create_table", "update_nicrc", "snapshot", "modeac_enable", "modeac_match",
                                               "modeac_codes", "modeac_hits", "reduce_enable", "update_reduce",
                                               "reduce_wire", "sbs_enable", "update_sbs", "sbs_wire", "pb_enable", "aircraft_pb",
-                                              "vrs_enable", "vrs")}
+                                              "vrs_enable", "vrs", "range_enable", "range_read", "range_distances",
+                                              "range_margins", "range_pb")}
         dev = [] if host else [C.c_int]
+        f["range_enable"].argtypes = [C.c_void_p, C.c_uint32]
+        f["range_read"].argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
+        f["range_distances"].argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + dev + [C.POINTER(C.c_size_t)]
+        f["range_margins"].argtypes = [C.c_void_p, C.POINTER(RangeMargins)]
+        f["range_pb"].argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
         f["pb_enable"].argtypes = [C.c_void_p]
         f["aircraft_pb"].argtypes = [C.c_void_p, C.POINTER(PbOptions), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                      C.c_void_p] + ([C.POINTER(C.c_double)] if host else [])
@@ -1254,7 +1274,7 @@ class PositionTracker:
     stream whose min_gate_margin_m on the twin stays above 1e-3 m."""
 
     def __init__(self, capacity=1 << 16, receivers=None, filter_persistence=0, device=0, host=False, table=False,
-                 modeac=False, reduce_interval_ms=None, sbs=False, pb=False, vrs=False):
+                 modeac=False, reduce_interval_ms=None, sbs=False, pb=False, vrs=False, range=False, polar=True):
         """table=True: msd_pos_create_table -- the tracker also keeps the aircraft table (update_nicrc, snapshot).
         modeac=True (a table tracker): msd_pos_modeac_enable -- it also counts Mode A/C replies and matches them against
         its aircraft (modeac_match, modeac_codes, modeac_hits).
@@ -1264,7 +1284,10 @@ class PositionTracker:
         readsb's SBS (BaseStation) lines from them.
         pb=True (a table tracker): msd_pos_pb_enable -- aircraft_pb writes every receiver's aircraft.pb from the table.
         vrs=True (a table tracker): msd_pos_vrs_enable -- vrs writes a part of every receiver's VRS JSON aircraft list
-        from the table."""
+        from the table.
+        range=True (either kind of tracker): msd_pos_range_enable -- it also keeps every aircraft's distance to its
+        receiver, every receiver's longest distance and, with polar=True (--stats-range), its polar range (range_read,
+        range_distances, range_margins)."""
         self.host, self.table = host, table
         self.nrx = len(receivers) if receivers is not None else 1
         self.L, self.f = _pos_lib(host)
@@ -1288,6 +1311,8 @@ class PositionTracker:
                 self.pb_enable()
             if vrs:
                 self.vrs_enable()
+            if range:
+                self.range_enable(RANGE_POLAR if polar else 0)
         except MsdError:
             self.close()
             raise
@@ -1457,6 +1482,72 @@ class PositionTracker:
         stream, rx = self.vrs_stream(now_ms, part, n_parts)
         ends = [0] + [int(e) for e in rx["end"]]
         return [stream[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
+    def range_enable(self, flags=RANGE_POLAR):
+        self._check(self.f["range_enable"](self.h, flags), "msd_pos_range_enable")
+
+    def range_read(self, first=0, count=None, take_longest=False, flags=None):
+        """Receivers first .. first + count - 1 (default: all from first) -> RANGE_RECEIVER_DTYPE array.  take_longest:
+        `longest` is zeroed behind the read."""
+        count = self.nrx - first if count is None else count
+        flags = (RANGE_TAKE_LONGEST if take_longest else 0) if flags is None else flags
+        out = np.zeros(max(count, 0), dtype=RANGE_RECEIVER_DTYPE)
+        self._check(self.f["range_read"](self.h, first, count, out.ctypes.data if len(out) else None, flags), "msd_pos_range_read")
+        return out
+
+    def range_distances(self, cap=None):
+        """The distance of every live aircraft, row j belonging to snapshot()'s row j -> uint32 array.  cap: the entries
+        offered (default: as many as are live); self.distances_count is *n of the last call."""
+        n = C.c_size_t(0)
+        dev = [] if self.host else [0]
+        if cap is None:
+            rc = self.f["range_distances"](self.h, None, 0, *dev, C.byref(n))
+            if rc not in (0, -errno.ENOSPC):
+                self._check(rc, "msd_pos_range_distances")
+            cap = n.value
+        out = np.zeros(cap, dtype=np.uint32)
+        rc = self.f["range_distances"](self.h, out.ctypes.data if cap else None, cap, *dev, C.byref(n))
+        self.distances_count = n.value
+        self.distances_out = out
+        self._check(rc, "msd_pos_range_distances")
+        return out[:n.value]
+
+    def range_distances_device(self, d_out, cap):
+        """The same into device memory of cap entries (a pointer); GPU tracker only -> the number written."""
+        assert not self.host
+        n = C.c_size_t(0)
+        self._check(self.f["range_distances"](self.h, d_out, cap, 1, C.byref(n)), "msd_pos_range_distances")
+        return n.value
+
+    def range_pb_stream(self, cap=None):
+        """msd_pos_range_pb -> (the stream of every receiver's Statistics.polar_range entries, uint64 end offsets).  cap:
+        the bytes offered (default: as many as are needed, asked for first); self.range_pb_needed is *out_len of the last
+        call."""
+        need = C.c_size_t(0)
+        if cap is None:
+            rc = self.f["range_pb"](self.h, None, 0, C.byref(need), None)
+            if rc not in (0, -errno.ENOSPC):
+                self._check(rc, "msd_pos_range_pb")
+            cap = need.value
+        out = np.zeros(cap, dtype=np.uint8)
+        end = np.zeros(self.nrx, dtype=np.uint64)
+        rc = self.f["range_pb"](self.h, out.ctypes.data if cap else None, cap, C.byref(need), end.ctypes.data)
+        self.range_pb_needed = need.value
+        self.range_pb_out = out
+        self._check(rc, "msd_pos_range_pb")
+        return out[:need.value].tobytes(), end
+
+    def range_pb(self):
+        """Every receiver's Statistics.polar_range entries -> a list of bytes, one per receiver index."""
+        stream, end = self.range_pb_stream()
+        ends = [0] + [int(e) for e in end]
+        return [stream[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
+    def range_margins(self):
+        """-> {min_range_margin_m, min_bearing_margin_deg}: the host object's are the contract's."""
+        m = RangeMargins()
+        self._check(self.f["range_margins"](self.h, C.byref(m)), "msd_pos_range_margins")
+        return {"min_range_margin_m": m.min_range_margin_m, "min_bearing_margin_deg": m.min_bearing_margin_deg}
 
     def reduce_timers(self, receiver, addr):
         """The twin's timers of one aircraft -> uint64 array of REDUCE_TIMERS (AC_MEMBERS order, then DF11), or None."""

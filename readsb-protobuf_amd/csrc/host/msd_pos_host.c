@@ -32,6 +32,13 @@ struct msd_pos_host {
     int sbs; /* SBS output (msd_pos_host_sbs_enable): the twin keeps nothing for it */
     uint64_t *pb_state; /* aircraft.pb (msd_pos_host_pb_enable), else NULL: the written state per slot */
     int vrs; /* VRS output (msd_pos_host_vrs_enable): the twin keeps nothing for it */
+    /* the receiver range (msd_pos_host_range_enable), else NULL: a distance per slot, per receiver 72 buckets, the longest
+     * distance and the ranges evaluated; the two margins of the contract */
+    uint32_t *dist, *polar;
+    double *longest;
+    uint64_t *evaluated;
+    int range_polar;
+    msd_range_margins rmargins;
 };
 
 int msd_cpr_host_airborne(int even_lat, int even_lon, int odd_lat, int odd_lon, int fflag, double *lat, double *lon)
@@ -71,6 +78,14 @@ static void clear(msd_pos_host *p)
         memset(p->next_reduce, 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->cap);
     if (p->pb_state)
         memset(p->pb_state, 0, sizeof(uint64_t) * p->cap);
+    if (p->dist) {
+        memset(p->dist, 0, sizeof(uint32_t) * p->cap);
+        memset(p->polar, 0, sizeof(uint32_t) * MSD_RANGE_BUCKETS * p->nrx);
+        memset(p->evaluated, 0, sizeof(uint64_t) * p->nrx);
+        for (uint32_t r = 0; r < p->nrx; ++r)
+            p->longest[r] = 0;
+        p->rmargins.min_range_margin_m = p->rmargins.min_bearing_margin_deg = INFINITY;
+    }
 }
 
 static int create(const msd_pos_config *cfg, msd_pos_host **out, int table)
@@ -113,6 +128,10 @@ void msd_pos_host_destroy(msd_pos_host *p)
 {
     if (!p)
         return;
+    free(p->dist);
+    free(p->polar);
+    free(p->longest);
+    free(p->evaluated);
     free(p->pb_state);
     free(p->next_reduce);
     free(p->ac);
@@ -162,11 +181,36 @@ static int64_t find_or_insert(msd_pos_host *p, uint64_t key, int *fresh)
                 memset(&p->next_reduce[(size_t)s * MSD_REDUCE_TIMERS], 0, sizeof(uint64_t) * MSD_REDUCE_TIMERS);
             if (p->pb_state)
                 p->pb_state[s] = 0;
+            if (p->dist)
+                p->dist[s] = 0;
             *fresh = 1;
             return s;
         }
     }
     return -1;
+}
+
+/* track.c:683-686 for one record the feed has taken (msd_pos_impl.h, "the receiver range"), in stream order */
+static void range_record(msd_pos_host *p, uint32_t s, uint32_t r, const msd_fields *f, const msd_position *o)
+{
+    const uint32_t code = msd_pos_range_code(&p->st[s], f, o);
+    if (!(code & MSD_RANGE_CODE_DECODED))
+        return;
+    p->dist[s] = 0;
+    if (!(code & MSD_RANGE_CODE_EVAL) || !p->rx[r].latlon_valid)
+        return;
+    msd_range_one e;
+    msd_pos_range_one(&p->rx[r], o->lat, o->lon, p->range_polar, &e);
+    p->evaluated[r]++;
+    if (e.longest && e.range > p->longest[r])
+        p->longest[r] = e.range;
+    if (p->range_polar && e.counts && p->polar[(size_t)r * MSD_RANGE_BUCKETS + e.bucket] < e.metres)
+        p->polar[(size_t)r * MSD_RANGE_BUCKETS + e.bucket] = e.metres;
+    p->dist[s] = e.metres;
+    if (e.range_margin < p->rmargins.min_range_margin_m)
+        p->rmargins.min_range_margin_m = e.range_margin;
+    if (p->range_polar && e.bearing_margin < p->rmargins.min_bearing_margin_deg)
+        p->rmargins.min_bearing_margin_deg = e.bearing_margin;
 }
 
 static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver, size_t n,
@@ -230,6 +274,8 @@ static int update(msd_pos_host *p, const msd_message *msgs, const msd_fields *fi
                      &out[i], &p->acc);
         if (want_sbs)
             msd_pos_sbs(&out[i], &p->acc, p->st[slot[i]].messages, &sbs[i]);
+        if (p->dist)
+            range_record(p, slot[i], receiver ? receiver[i] : 0u, &fields[i], &out[i]);
         int fwd = 0;
         if (p->trk)
             fwd = msd_trk_feed(&p->trk[slot[i]], msgs[i].sysTimestampMsg, &msgs[i], &fields[i], &out[i], &q,
@@ -675,7 +721,7 @@ static double pb_float_margin(double d)
 }
 
 /* AircraftMeta of one exported entry with its written state after this write -> body (at most 512 bytes) */
-static void pb_meta(const msd_aircraft *e, uint64_t state, pb_buf *b, double *margin)
+static void pb_meta(const msd_aircraft *e, uint64_t state, uint32_t distance, pb_buf *b, double *margin)
 {
     msd_aircraft_float fl;
     msd_aircraft_to_float(e, &fl);
@@ -705,6 +751,7 @@ static void pb_meta(const msd_aircraft *e, uint64_t state, pb_buf *b, double *ma
             *margin = m;
         pb_put_float(b, 12, (float)d);
     }
+    pb_put_u64(b, 13, distance); /* a->meta.distance: of a tracker that keeps the receiver range, 0 of any other */
     pb_put_i32(b, 15, e->air_ground);
     pb_put_i32(b, 20, e->alt_geom);
     pb_put_i32(b, 21, e->baro_rate);
@@ -796,7 +843,7 @@ int msd_pos_host_aircraft_pb(msd_pos_host *p, const msd_pb_options *opt, uint8_t
                 }
                 uint8_t body[512];
                 pb_buf b = {body, 0};
-                pb_meta(&e, state, &b, &margin);
+                pb_meta(&e, state, p->dist ? p->dist[s] : 0u, &b, &margin);
                 pb_put_bytes(&file, 15, &b, body);
                 row.aircraft++;
                 if (pass)
@@ -1113,6 +1160,100 @@ int msd_pos_host_modeac_hits(msd_pos_host *p, msd_modeac_hit *out, size_t cap, s
     return 0;
 }
 
+int msd_pos_host_range_enable(msd_pos_host *p, uint32_t flags)
+{
+    if (!p || (flags & ~MSD_RANGE_POLAR))
+        return -EINVAL;
+    if (p->dist)
+        return 0;
+    uint32_t *dist = calloc(p->cap, sizeof(uint32_t)); /* the aircraft the table already has start at distance 0 */
+    uint32_t *polar = calloc((size_t)p->nrx * MSD_RANGE_BUCKETS, sizeof(uint32_t));
+    double *longest = calloc(p->nrx, sizeof(double));
+    uint64_t *evaluated = calloc(p->nrx, sizeof(uint64_t));
+    if (!dist || !polar || !longest || !evaluated) {
+        free(dist);
+        free(polar);
+        free(longest);
+        free(evaluated);
+        return -ENOMEM;
+    }
+    p->dist = dist;
+    p->polar = polar;
+    p->longest = longest;
+    p->evaluated = evaluated;
+    p->range_polar = (flags & MSD_RANGE_POLAR) != 0;
+    p->rmargins.min_range_margin_m = p->rmargins.min_bearing_margin_deg = INFINITY;
+    return 0;
+}
+
+int msd_pos_host_range_read(msd_pos_host *p, uint32_t first, uint32_t count, msd_range_receiver *out, uint32_t flags)
+{
+    if (!p || !p->dist || (flags & ~MSD_RANGE_TAKE_LONGEST) || first > p->nrx || count > p->nrx - first || (!out && count > 0))
+        return -EINVAL;
+    for (uint32_t k = 0; k < count; ++k) {
+        const uint32_t r = first + k;
+        memcpy(out[k].polar_range, &p->polar[(size_t)r * MSD_RANGE_BUCKETS], sizeof out[k].polar_range);
+        out[k].longest_m = (uint32_t)p->longest[r];             /* net_io.c:2249 */
+        out[k].longest_nm = (uint32_t)(p->longest[r] / 1852.0); /* net_io.c:2250 */
+        out[k].evaluated = p->evaluated[r];
+        if (flags & MSD_RANGE_TAKE_LONGEST)
+            p->longest[r] = 0;
+    }
+    return 0;
+}
+
+int msd_pos_host_range_distances(msd_pos_host *p, uint32_t *out, size_t cap, size_t *n)
+{
+    if (!p || !p->dist || !n || (!out && cap > 0))
+        return -EINVAL;
+    *n = (size_t)p->live;
+    if (p->live > cap)
+        return -ENOSPC;
+    if (p->live == 0)
+        return 0;
+    uint64_t *ks = ordered_slots(p);
+    if (!ks)
+        return -ENOMEM;
+    for (size_t j = 0; j < p->live; ++j)
+        out[j] = p->dist[ks[2 * j + 1]];
+    free(ks);
+    return 0;
+}
+
+/* Statistics.polar_range as statistics__pack writes it: pb_put_* over the 72 entries, receiver after receiver */
+int msd_pos_host_range_pb(msd_pos_host *p, uint8_t *out, size_t cap, size_t *out_len, uint64_t *end)
+{
+    if (!p || !p->dist || !p->range_polar || !out_len || (!out && cap > 0))
+        return -EINVAL;
+    *out_len = 0;
+    for (int pass = 0; pass < 2; ++pass) { /* the size first: a stream that does not fit leaves out and end alone */
+        pb_buf file = {pass ? out : NULL, 0};
+        for (uint32_t r = 0; r < p->nrx; ++r) {
+            for (uint32_t bucket = 0; bucket < MSD_RANGE_BUCKETS; ++bucket) {
+                uint8_t body[16];
+                pb_buf b = {body, 0};
+                pb_put_u64(&b, 1, bucket);
+                pb_put_u64(&b, 2, p->polar[(size_t)r * MSD_RANGE_BUCKETS + bucket]);
+                pb_put_bytes(&file, 6, &b, body);
+            }
+            if (pass && end)
+                end[r] = file.n;
+        }
+        *out_len = file.n;
+        if (file.n > cap)
+            return -ENOSPC;
+    }
+    return 0;
+}
+
+int msd_pos_host_range_margins(const msd_pos_host *p, msd_range_margins *m)
+{
+    if (!p || !p->dist || !m)
+        return -EINVAL;
+    *m = p->rmargins;
+    return 0;
+}
+
 int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
 {
     if (!p)
@@ -1137,7 +1278,10 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
     const size_t next_bytes = sizeof(uint64_t) * MSD_REDUCE_TIMERS * p->cap;
     uint64_t *next = p->next_reduce ? malloc(next_bytes) : NULL;
     uint64_t *pb = p->pb_state ? malloc(sizeof(uint64_t) * p->cap) : NULL;
-    if (!keys || !st || (p->trk && !trk) || (p->hits && !hits) || (p->next_reduce && !next) || (p->pb_state && !pb)) {
+    uint32_t *dist = p->dist ? malloc(sizeof(uint32_t) * p->cap) : NULL;
+    if (!keys || !st || (p->trk && !trk) || (p->hits && !hits) || (p->next_reduce && !next) || (p->pb_state && !pb) ||
+        (p->dist && !dist)) {
+        free(dist);
         free(pb);
         free(keys);
         free(st);
@@ -1150,6 +1294,10 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
         memcpy(next, p->next_reduce, next_bytes);
     if (pb)
         memcpy(pb, p->pb_state, sizeof(uint64_t) * p->cap);
+    if (dist) { /* a removed aircraft's distance goes with it */
+        memcpy(dist, p->dist, sizeof(uint32_t) * p->cap);
+        memset(p->dist, 0, sizeof(uint32_t) * p->cap);
+    }
     if (hits)
         memcpy(hits, p->hits, 2u * (size_t)p->cap);
     if (trk)
@@ -1174,8 +1322,11 @@ int msd_pos_host_expire(msd_pos_host *p, uint64_t now_ms)
                        sizeof(uint64_t) * MSD_REDUCE_TIMERS);
             if (pb)
                 p->pb_state[d] = pb[s];
+            if (dist)
+                p->dist[d] = dist[s];
         }
     p->live -= removed;
+    free(dist);
     free(pb);
     free(keys);
     free(st);

@@ -57,6 +57,13 @@ int msd_pos_host_aircraft_pb(msd_pos_host *p, const msd_pb_options *opt, uint8_t
 int msd_pos_host_vrs_enable(msd_pos_host *p);
 int msd_pos_host_vrs(msd_pos_host *p, const msd_vrs_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_vrs_receiver *rx);
 size_t msd_pos_host_vrs_object(const msd_aircraft *a, uint64_t now_ms, int comma, char *out);
+/* the receiver range (modes_hip.h, "Receiver range"): msd_pos_range_* on the host -- msd_pos_impl.h's per-record function
+ * with the host's libm, record after record in stream order.  Its margins are the contract's */
+int msd_pos_host_range_enable(msd_pos_host *p, uint32_t flags);
+int msd_pos_host_range_read(msd_pos_host *p, uint32_t first, uint32_t count, msd_range_receiver *out, uint32_t flags);
+int msd_pos_host_range_distances(msd_pos_host *p, uint32_t *out, size_t cap, size_t *n);
+int msd_pos_host_range_margins(const msd_pos_host *p, msd_range_margins *m);
+int msd_pos_host_range_pb(msd_pos_host *p, uint8_t *out, size_t cap, size_t *out_len, uint64_t *end);
 /* for tests: the MSD_AC_N + 1 timers of one aircraft (the members' in MSD_AC_* order, then the DF11 timer) into out;
  * -ENOENT: no such aircraft */
 int msd_pos_host_reduce_timers(const msd_pos_host *p, uint32_t receiver, uint32_t addr, uint64_t *out);

@@ -194,6 +194,40 @@ static int write_aircraft_pb(int want_stats)
     return bad;
 }
 
+/* --stats-range: after the last message, receiver 0's longest distance and polar range (msd_pos_range_read) as
+ * "range longest_m,M,longest_nm,NM,evaluated,N" and 72 lines "range-bucket B,METRES" (bucket B: bearings around 5 B
+ * degrees); --stats-range-pb FILE: the same buckets as Statistics.polar_range entries (msd_pos_range_pb) */
+static int g_stats_range;
+static const char *g_range_pb_path;
+static int write_range(FILE *to, int want_stats)
+{
+    msd_range_receiver row;
+    int rc = msd_pos_range_read(g_pos, 0, 1, &row, 0);
+    if (rc) {
+        fprintf(stderr, "msd_pos_range_read: %s (%d)\n", msd_pos_last_error(g_pos), rc);
+        return 1;
+    }
+    fprintf(to, "range longest_m,%u,longest_nm,%u,evaluated,%" PRIu64 "\n", row.longest_m, row.longest_nm, row.evaluated);
+    for (unsigned b = 0; b < MSD_RANGE_BUCKETS; ++b)
+        fprintf(to, "range-bucket %u,%u\n", b, row.polar_range[b]);
+    if (!g_range_pb_path)
+        return 0;
+    uint8_t bytes[MSD_RANGE_BUCKETS * MSD_RANGE_PB_ENTRY_MAX];
+    size_t len = 0;
+    rc = msd_pos_range_pb(g_pos, bytes, sizeof bytes, &len, NULL);
+    FILE *out = rc ? NULL : fopen(g_range_pb_path, "wb");
+    int bad = !out;
+    if (out) {
+        bad = fwrite(bytes, 1, len, out) != len;
+        bad |= fclose(out) != 0;
+    }
+    if (bad)
+        fprintf(stderr, "--stats-range-pb %s: %s (%d)\n", g_range_pb_path, rc ? msd_pos_last_error(g_pos) : "cannot write", rc);
+    else if (want_stats)
+        fprintf(stderr, "polar_range bytes,%zu\n", len);
+    return bad;
+}
+
 /* --vrs-out: after the last message, receiver 0's VRS documents for parts 0 .. g_vrs_parts - 1, one after the other, at
  * now_ms = the last message's time (msd_pos_vrs: the size first, then the bytes) */
 static const char *g_vrs_path;
@@ -529,6 +563,8 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--aircraft-pb") && next) { g_pb_path = next; ++i; }
         else if (!strcmp(a, "--vrs-out") && next) { g_vrs_path = next; ++i; }
         else if (!strcmp(a, "--vrs-parts") && next) { g_vrs_parts = (uint32_t)strtoul(next, NULL, 10); ++i; }
+        else if (!strcmp(a, "--stats-range")) g_stats_range = 1; /* readsb.c:564: Modes.stats_polar_range */
+        else if (!strcmp(a, "--stats-range-pb") && next) { g_range_pb_path = next; ++i; }
         else if (!strcmp(a, "--gnss")) gnss = 1; /* readsb.c: Modes.use_gnss */
         else if (!strcmp(a, "--utc-offset") && next) { utc_offset_s = atof(next); ++i; }
         else if (!strcmp(a, "--clock-start-ms") && next) { g_clock_start_ms = strtoull(next, NULL, 10); ++i; }
@@ -556,7 +592,8 @@ int main(int argc, char **argv)
         } else {
             fprintf(stderr, "usage: msd_replay --ifile F [--iformat uc8|sc16|sc16q11] [--fix|--no-fix|--aggressive] [--dcfilter] "
                             "[--preamble-threshold N] [--modeac] [--mlat] [--net-raw|--beast|--no-output] [--net-verbatim] [--stats] [--timing] [--throttle] [--path fused|magbuf] "
-                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] [--aircraft [--match-modeac] "
+                            "[--device N] [--sc16q11-table-bits N] [--positions [--lat DEG --lon DEG] [--max-range NM] "
+                            "[--stats-range [--stats-range-pb FILE]] [--aircraft [--match-modeac] "
                             "[--beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]] "
                             "[--sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]] [--aircraft-pb FILE] "
                             "[--vrs-out FILE [--vrs-parts N]]] [--clock-start-ms N]]\n"
@@ -565,6 +602,9 @@ int main(int argc, char **argv)
                             "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
                             "       receiver's location (both, or neither); --max-range: the absolute maximum range in nautical miles, 0 = none.\n"
                             "       Also with --beast-in and --avr-in; not with --net-raw, --beast or --no-output.\n"
+                            "       --stats-range (with --positions --lat --lon): readsb's polar range, kept on the GPU; after the last message\n"
+                            "       \"range longest_m,M,longest_nm,NM,evaluated,N\" and 72 lines \"range-bucket B,METRES\"; --aircraft-pb then\n"
+                            "       carries every aircraft's distance.  --stats-range-pb FILE: the buckets as Statistics.polar_range entries.\n"
                             "       --aircraft (with --positions): after the last message one line per tracked aircraft,\n"
                             "       \"aircraft ADDR,messages,callsign,squawk,altitude_baro,gs,lat,lon\", a member empty when it is not valid at the\n"
                             "       last message's time.  --clock-start-ms: milliseconds added to every message's time in front of the tracker.\n"
@@ -607,6 +647,14 @@ int main(int argc, char **argv)
     }
     if (g_vrs_path && !want_aircraft) {
         fprintf(stderr, "--vrs-out goes with --positions --aircraft\n");
+        return 2;
+    }
+    if (g_range_pb_path && !g_stats_range) {
+        fprintf(stderr, "--stats-range-pb goes with --stats-range\n");
+        return 2;
+    }
+    if (g_stats_range && !(want_positions && have_lat && have_lon)) {
+        fprintf(stderr, "--stats-range goes with --positions --lat --lon\n");
         return 2;
     }
     if (g_vrs_parts == 0 || g_vrs_parts > 2048 || (g_vrs_parts & (g_vrs_parts - 1)) != 0) {
@@ -688,6 +736,11 @@ int main(int argc, char **argv)
             msd_pos_destroy(g_pos);
             return 1;
         }
+        if (g_stats_range && msd_pos_range_enable(g_pos, MSD_RANGE_POLAR) != 0) {
+            fprintf(stderr, "--stats-range: %s\n", msd_pos_last_error(g_pos));
+            msd_pos_destroy(g_pos);
+            return 1;
+        }
         if (g_vrs_path && msd_pos_vrs_enable(g_pos) != 0) {
             fprintf(stderr, "--vrs-out %s: %s\n", g_vrs_path, msd_pos_last_error(g_pos));
             msd_pos_destroy(g_pos);
@@ -699,6 +752,8 @@ int main(int argc, char **argv)
         const int rc = avr_in ? run_remote_in(avr_in, 1, avr_chunk, now_ms, &rx, want_stats)
                               : run_remote_in(beast_in, 0, beast_chunk, now_ms, &rx, want_stats);
         if (want_aircraft && !rc && (print_aircraft(stdout) || (g_match_modeac && print_modeac(stdout))))
+            g_pos_failed = 1;
+        if (g_stats_range && !rc && write_range(stdout, want_stats))
             g_pos_failed = 1;
         if (g_reduce_out && reduce_finish(want_stats))
             g_pos_failed = 1;
@@ -751,6 +806,8 @@ int main(int argc, char **argv)
     }
     msd_ifileClose();
     if (want_aircraft && (print_aircraft(stdout) || (g_match_modeac && print_modeac(stdout))))
+        g_pos_failed = 1;
+    if (g_stats_range && write_range(stdout, want_stats))
         g_pos_failed = 1;
     if (g_reduce_out && reduce_finish(want_stats))
         g_pos_failed = 1;

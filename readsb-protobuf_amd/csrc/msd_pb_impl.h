@@ -138,6 +138,7 @@ typedef struct msd_pb_head {
     uint32_t addr, gs, ias, tas;
     uint8_t gs_source, ias_source, tas_source, position_source;
     int8_t adsb_version;
+    uint32_t distance; /* a->meta.distance of a tracker that keeps the receiver range; 0 of any other: whoever has one sets it */
 } msd_pb_head;
 
 MSD_HD void msd_pb_head_of_state(uint64_t key, const msd_pos_aircraft *p, msd_pb_head *h)
@@ -156,6 +157,7 @@ MSD_HD void msd_pb_head_of_state(uint64_t key, const msd_pos_aircraft *p, msd_pb
     h->tas_source = p->src[MSD_PV_TAS];
     h->position_source = p->src[MSD_PV_POSITION];
     h->adsb_version = p->version[0];
+    h->distance = 0;
 }
 
 MSD_HD void msd_pb_head_of_entry(const msd_aircraft *a, msd_pb_head *h)
@@ -174,6 +176,7 @@ MSD_HD void msd_pb_head_of_entry(const msd_aircraft *a, msd_pb_head *h)
     h->tas_source = a->source[MSD_AC_TAS];
     h->position_source = a->source[MSD_AC_POSITION];
     h->adsb_version = a->adsb_version;
+    h->distance = 0;
 }
 
 /* net_io.c:2011 in integers: the aircraft is written */
@@ -277,7 +280,7 @@ MSD_HD void msd_pb_body(msd_pb_w *w, const msd_pb_head *h, const msd_trk_aircraf
     msd_pb_uint(w, 10, h->messages);
     msd_pb_uint(w, 11, h->seen);
     msd_pb_float(w, 12, msd_pb_rssi(t));
-    /* 13 distance: not written */
+    msd_pb_uint(w, 13, h->distance);
     msd_pb_int32(w, 15, t->air_ground);
     msd_pb_int32(w, 20, t->alt_geom);
     msd_pb_int32(w, 21, t->baro_rate);
@@ -351,6 +354,20 @@ MSD_HD uint32_t msd_pb_aircraft(const msd_pb_head *h, const msd_trk_aircraft *t,
     if (!out)
         return w.n + c.n;
     msd_pb_body(&w, h, t, state, track_table);
+    return w.n;
+}
+
+/* One entry of Statistics.polar_range (modes_hip.h "Receiver range", msd_pos_range_pb): tag 0x32, length, key and value,
+ * either left out when 0 -> its length, at most MSD_RANGE_PB_ENTRY_MAX.  out == NULL: the length alone. */
+MSD_HD uint32_t msd_range_pb_entry(uint32_t bucket, uint32_t metres, uint8_t *out)
+{
+    msd_pb_w c = {0, 0}, w = {out, 0};
+    msd_pb_uint(&c, 1, bucket);
+    msd_pb_uint(&c, 2, metres);
+    msd_pb_byte(&w, 0x32);
+    msd_pb_byte(&w, c.n); /* at most 8 */
+    msd_pb_uint(&w, 1, bucket);
+    msd_pb_uint(&w, 2, metres);
     return w.n;
 }
 

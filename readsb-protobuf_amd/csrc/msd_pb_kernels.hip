@@ -20,6 +20,9 @@
  *                        its buffer launches it, so a refused call moves no state.
  * Both encoding kernels run msd_pb_aircraft / msd_pb_header (msd_pb_impl.h), the length kernel with no destination: a
  * length is by construction what the store kernel writes.
+ * A tracker that keeps the receiver range hands over its distances (c.dist): the entry then has distance (13) and can be
+ * MSD_PB_AIRCRAFT_MAX_RANGE = 421 bytes long, and the store kernel's instantiation with the larger image runs; a tracker
+ * without runs the one it always ran.
  * The image.  An entry is at most MSD_PB_AIRCRAFT_MAX = 415 bytes; 256 of them are 106 KB, one workgroup per CU of 160 KB.
  * The image therefore holds PB_TILE = 128 items, 53.6 KB: three workgroups, twelve wavefronts, per CU.  A workgroup keeps
  * the writers' 256 threads (block_scan and wire_store_run are built on them) and fills and stores the image twice
@@ -39,7 +42,10 @@ using namespace msd_items; /* HEAD, items_kernel, tiled_store; of msd_wire_store
 constexpr uint32_t PB_TILE = MSD_PB_TILE;
 static_assert(MSD_PB_HEADER_MAX <= MSD_PB_AIRCRAFT_MAX, "an item is at most an aircraft entry");
 /* the image starts at the destination's offset in its dword; behind the tile's longest items there is room for one more */
-constexpr uint32_t PB_IMAGE_WORDS = (PB_TILE * MSD_PB_AIRCRAFT_MAX + MSD_PB_AIRCRAFT_MAX + 3u) / 4u + 2u;
+constexpr uint32_t image_words(uint32_t entry_max)
+{
+    return (PB_TILE * entry_max + entry_max + 3u) / 4u + 2u;
+}
 
 __global__ void __launch_bounds__(WT)
 msd_pb_len_kernel(msd_pb_call c, uint64_t *shadow, uint16_t *lens, uint32_t *within, uint32_t *cwithin, uint32_t *block_sums,
@@ -57,6 +63,8 @@ msd_pb_len_kernel(msd_pb_call c, uint64_t *shadow, uint16_t *lens, uint32_t *wit
             const uint32_t s = c.idx[item];
             msd_pb_head h;
             msd_pb_head_of_state(c.t.keys[s], &c.t.st[s], &h);
+            if (c.dist)
+                h.distance = c.dist[s];
             uint64_t st = c.state[s];
             if (msd_pb_selected(&h, c.now_ms)) {
                 const msd_trk_aircraft *a = &c.t.trk[s];
@@ -116,12 +124,13 @@ msd_pb_rx_kernel(const uint32_t *first, uint32_t nrx, uint32_t nitems, const uin
     rx[r] = row;
 }
 
+template <uint32_t ENTRY_MAX>
 __global__ void __launch_bounds__(WT)
 msd_pb_store_kernel(msd_pb_call c, const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off, uint8_t *out)
 {
     __shared__ uint32_t part[4];
     __shared__ uint32_t half;
-    __shared__ uint32_t image[PB_IMAGE_WORDS];
+    __shared__ uint32_t image[image_words(ENTRY_MAX)];
     const uint32_t me = blockIdx.x * WT + threadIdx.x;
     /* (a length above 0: a head with something to say, a selected aircraft) */
     tiled_store<PB_TILE>(me < c.nitems ? lens[me] : 0u, out, block_off, part, half, image, [&](uint32_t i, uint8_t *at) {
@@ -134,6 +143,8 @@ msd_pb_store_kernel(msd_pb_call c, const uint64_t *shadow, const uint16_t *lens,
             const uint64_t st = shadow[i];
             msd_pb_head h;
             msd_pb_head_of_state(c.t.keys[s], &c.t.st[s], &h);
+            if (ENTRY_MAX > MSD_PB_AIRCRAFT_MAX)
+                h.distance = c.dist[s];
             (void)msd_pb_aircraft(&h, &c.t.trk[s], st, c.track_table, at);
             c.state[s] = st;
         }
@@ -196,5 +207,8 @@ void msd_pb_launch_lengths(hipStream_t stream, msd_pb_call c, uint32_t live, uin
 void msd_pb_launch_store(hipStream_t stream, msd_pb_call c, const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off,
                          uint8_t *out)
 {
-    msd_pb_store_kernel<<<(c.nitems + WT - 1u) / WT, WT, 0, stream>>>(c, shadow, lens, block_off, out);
+    if (c.dist)
+        msd_pb_store_kernel<MSD_PB_AIRCRAFT_MAX_RANGE><<<(c.nitems + WT - 1u) / WT, WT, 0, stream>>>(c, shadow, lens, block_off, out);
+    else
+        msd_pb_store_kernel<MSD_PB_AIRCRAFT_MAX><<<(c.nitems + WT - 1u) / WT, WT, 0, stream>>>(c, shadow, lens, block_off, out);
 }

@@ -1,6 +1,6 @@
 /* msd_pos.cpp -- C-ABI of the position tracker (modes_hip.h "positions"): the object, its device memory (msd_devbuf.h:
  * every buffer is an owning array, freed with the object) and the order in which a call queues the kernels of
- * msd_pos_kernels.hip and of the four writers.  The writers share emit(), host input is staged by stage(), the two
+ * msd_pos_kernels.hip and of the five writers.  The writers share emit(), host input is staged by stage(), the two
  * read-outs of the table share read_out(). */
 #include <errno.h>
 #include <math.h>
@@ -90,6 +90,18 @@ struct msd_pos {
     dev<msd_vrs_receiver> d_vrs_rx;
     dev<uint32_t> d_vrs_items, d_vrs_within, d_vrs_sel, d_vrs_block;
     dev<uint16_t> d_vrs_lens, d_vrs_swithin;
+    /* the receiver range (msd_pos_range_enable): tab[k].dist, the receivers' rows, the two margins' bits, the code byte
+     * per record of a call, and the buffers the two read-out calls hand to the host */
+    bool range = false, range_polar = false, range_combine = true, range_timing = false;
+    hipEvent_t range_ev[2] = {nullptr, nullptr}; /* with range_timing: around the range kernel (scripts/range_rate.py) */
+    float range_ms = 0;
+    dev<uint32_t> dist[2];
+    dev<msd_range_state> d_rng;
+    dev<unsigned long long> d_rmargins;
+    dev<uint8_t> d_rcode;
+    dev<msd_range_receiver> d_rng_out;
+    dev<uint32_t> d_dist_out;
+    dev<unsigned long long> d_rng_end;
     char err[256] = "";
 };
 
@@ -117,7 +129,23 @@ void point_tables(msd_pos *p)
         p->tab[k].trk = p->trk[k].get();
         p->tab[k].hits = p->hits[k].get();
         p->tab[k].next_reduce = p->next_reduce[k].get();
+        p->tab[k].dist = p->dist[k].get();
     }
+}
+
+/* the receiver range as a new tracker has it: no distance, empty rows, no margin */
+int range_clear(msd_pos *p, uint32_t *const dist[2], msd_range_state *rng, unsigned long long *margins)
+{
+    unsigned long long inf[2];
+    const double d = INFINITY;
+    memcpy(&inf[0], &d, sizeof d);
+    inf[1] = inf[0];
+    for (int k = 0; k < 2; ++k)
+        POS_HIP(p, hipMemsetAsync(dist[k], 0, sizeof(uint32_t) * p->tab[k].cap, p->stream));
+    POS_HIP(p, hipMemsetAsync(rng, 0, sizeof(msd_range_state) * p->nrx, p->stream));
+    POS_HIP(p, hipMemcpyAsync(margins, inf, sizeof inf, hipMemcpyHostToDevice, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream)); /* inf leaves the stack */
+    return 0;
 }
 
 int clear(msd_pos *p)
@@ -139,6 +167,12 @@ int clear(msd_pos *p)
     if (p->pb)
         for (int k = 0; k < 2; ++k)
             POS_HIP(p, hipMemsetAsync(p->pb_state[k].get(), 0, sizeof(uint64_t) * p->tab[k].cap, p->stream));
+    if (p->range) {
+        uint32_t *const dist[2] = {p->dist[0].get(), p->dist[1].get()};
+        const int rc = range_clear(p, dist, p->d_rng.get(), p->d_rmargins.get());
+        if (rc)
+            return rc;
+    }
     POS_HIP(p, hipStreamSynchronize(p->stream));
     p->live = 0;
     return 0;
@@ -161,6 +195,8 @@ int reserve(msd_pos *p, size_t n, bool want_sbs)
         POS_HIP(p, p->d_forward.reserve(n));
     if (want_sbs)
         POS_HIP(p, p->d_sbs.reserve(n));
+    if (p->range)
+        POS_HIP(p, p->d_rcode.reserve(n));
     return 0;
 }
 
@@ -382,6 +418,9 @@ void msd_pos_destroy(msd_pos *p)
     const hipStream_t stream = p->stream;
     if (stream)
         (void)hipStreamSynchronize(stream);
+    for (hipEvent_t e : p->range_ev)
+        if (e)
+            (void)hipEventDestroy(e);
     delete p; /* every buffer, behind the stream's last work and before the stream goes */
     if (stream)
         (void)hipStreamDestroy(stream);
@@ -441,6 +480,7 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
     msd_position *const d_out = p->d_out.get();
     msd_pos_nicrc *const d_nicrc = p->d_nicrc.get();
     msd_sbs_track *const d_sbs = p->d_sbs.get();
+    uint8_t *const d_rcode = p->range ? p->d_rcode.get() : nullptr;
     uint32_t ctl[MSD_POS_CTL_N] = {};
     POS_HIP(p, hipMemsetAsync(d_ctl, 0, sizeof ctl, p->stream));
     msd_pos_launch_find(p->stream, t, msgs, fields, receiver, p->nrx, (uint32_t)n, d_slot, d_fresh, d_out, d_ctl);
@@ -470,12 +510,28 @@ static int update(msd_pos *p, const msd_message *msgs, const msd_fields *fields,
         POS_HIP(p, hipMemsetAsync(d_forward, 0, n, p->stream));
     if (want_sbs) /* and its row; no other call makes rows */
         POS_HIP(p, hipMemsetAsync(d_sbs, 0, n * sizeof(msd_sbs_track), p->stream));
+    if (d_rcode) /* and its range code: the range kernel passes it by */
+        POS_HIP(p, hipMemsetAsync(d_rcode, 0, n, p->stream));
     for (size_t base = 0; base < n; base += MSD_POS_PIECE) {
         const size_t m = n - base < MSD_POS_PIECE ? n - base : MSD_POS_PIECE;
         msd_pos_launch_piece(p->stream, t, msgs, fields, receiver, p->d_rx.get(), p->fp, (uint32_t)base, (uint32_t)m, d_slot,
                              p->d_idx[0].get(), p->d_idx[1].get(), p->d_hist.get(), d_out, p->d_stats.get(), d_nicrc,
-                             p->reduce_interval, d_forward, want_sbs ? d_sbs : nullptr);
+                             p->reduce_interval, d_forward, want_sbs ? d_sbs : nullptr, d_rcode);
         POS_HIP(p, hipGetLastError());
+        if (d_rcode) { /* behind the piece's walk, piece after piece: an aircraft's last decoded record of the call wins */
+            if (p->range_timing)
+                POS_HIP(p, hipEventRecord(p->range_ev[0], p->stream));
+            msd_pos_launch_range(p->stream, t, d_out, receiver, p->d_rx.get(), d_slot, d_rcode, (uint32_t)base, (uint32_t)m,
+                                 p->range_polar, p->range_combine, p->d_rng.get(), p->d_rmargins.get());
+            POS_HIP(p, hipGetLastError());
+            if (p->range_timing) { /* a measuring run: the piece's kernel alone, waited for */
+                float ms = 0;
+                POS_HIP(p, hipEventRecord(p->range_ev[1], p->stream));
+                POS_HIP(p, hipEventSynchronize(p->range_ev[1]));
+                POS_HIP(p, hipEventElapsedTime(&ms, p->range_ev[0], p->range_ev[1]));
+                p->range_ms = base ? p->range_ms + ms : ms;
+            }
+        }
     }
     POS_HIP(p, hipMemcpyAsync(out, d_out, n * sizeof(msd_position), hipMemcpyDeviceToHost, p->stream));
     if (want_nicrc)
@@ -647,7 +703,7 @@ int msd_pos_aircraft_pb(msd_pos *p, const msd_pb_options *opt, uint8_t *out, siz
     if (!p || !p->pb || !out_len || !msd_pb_options_ok(opt) || (!out && cap > 0))
         return -EINVAL;
     *out_len = 0;
-    if (p->live * MSD_PB_AIRCRAFT_MAX + (uint64_t)p->nrx * MSD_PB_HEADER_MAX > 0xFFFFFFFFull) {
+    if (p->live * (p->range ? MSD_PB_AIRCRAFT_MAX_RANGE : MSD_PB_AIRCRAFT_MAX) + (uint64_t)p->nrx * MSD_PB_HEADER_MAX > 0xFFFFFFFFull) {
         snprintf(p->err, sizeof p->err, "%llu aircraft could take more than 2^32 - 1 bytes", (unsigned long long)p->live);
         return -E2BIG;
     }
@@ -667,7 +723,8 @@ int msd_pos_aircraft_pb(msd_pos *p, const msd_pb_options *opt, uint8_t *out, siz
                                   p->stream));
         d_total = p->d_pb_total.get();
     }
-    const msd_pb_call c = {p->tab[p->cur], p->pb_state[p->cur].get(), ordered_slots(p, live), p->d_pb_items.get(), d_total,
+    const msd_pb_call c = {p->tab[p->cur], p->pb_state[p->cur].get(), p->tab[p->cur].dist, ordered_slots(p, live),
+                           p->d_pb_items.get(), d_total,
                            p->d_trunc_table.get(), opt->now_ms, (uint32_t)nitems, p->nrx};
     msd_pb_launch_lengths(p->stream, c, live, p->d_pb_first.get(), p->d_pb_items.get(), p->d_pb_shadow.get(), p->d_pb_lens.get(),
                           p->d_pb_within.get(), p->d_pb_cwithin.get(), p->d_pb_block.get(), p->d_pb_rx.get());
@@ -823,6 +880,121 @@ int msd_pos_modeac_hits(msd_pos *p, msd_modeac_hit *out, size_t cap, int on_devi
     });
 }
 
+int msd_pos_range_enable(msd_pos *p, uint32_t flags)
+{
+    if (!p || (flags & ~MSD_RANGE_POLAR))
+        return -EINVAL;
+    if (p->range)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    dev<uint32_t> dist[2];
+    dev<msd_range_state> rng;
+    dev<unsigned long long> margins;
+    const auto build = [&]() -> int {
+        for (int k = 0; k < 2; ++k) /* the aircraft the table already has start at distance 0 */
+            POS_HIP(p, dist[k].reserve(p->tab[k].cap));
+        POS_HIP(p, rng.reserve(p->nrx));
+        POS_HIP(p, margins.reserve(2));
+        uint32_t *const d[2] = {dist[0].get(), dist[1].get()};
+        return range_clear(p, d, rng.get(), margins.get());
+    };
+    const int rc = build();
+    if (rc) { /* the tracker stays as it was */
+        (void)hipGetLastError();
+        return rc;
+    }
+    p->dist[0] = std::move(dist[0]);
+    p->dist[1] = std::move(dist[1]);
+    p->d_rng = std::move(rng);
+    p->d_rmargins = std::move(margins);
+    point_tables(p);
+    p->range_polar = (flags & MSD_RANGE_POLAR) != 0;
+    p->range = true;
+    return 0;
+}
+
+/* for scripts/range_rate.py (declared in msd_pos.h, not in modes_hip.h): the range kernel with (1, the default) or without
+ * (0) the per-wavefront reduction in front of its atomics -- the results are the same --, and with events around it whose
+ * interval msd_pos_range_kernel_ms hands over: the last call's range kernels, in ms */
+int msd_pos_range_measure(msd_pos *p, int combine, int timing)
+{
+    if (!p || !p->range)
+        return -EINVAL;
+    POS_HIP(p, hipSetDevice(p->device));
+    if (timing && !p->range_ev[0]) {
+        POS_HIP(p, hipEventCreate(&p->range_ev[0]));
+        POS_HIP(p, hipEventCreate(&p->range_ev[1]));
+    }
+    p->range_combine = combine != 0;
+    p->range_timing = timing != 0;
+    return 0;
+}
+
+int msd_pos_range_kernel_ms(const msd_pos *p, float *ms)
+{
+    if (!p || !p->range || !ms)
+        return -EINVAL;
+    *ms = p->range_ms;
+    return 0;
+}
+
+int msd_pos_range_read(msd_pos *p, uint32_t first, uint32_t count, msd_range_receiver *out, uint32_t flags)
+{
+    if (!p || !p->range || (flags & ~MSD_RANGE_TAKE_LONGEST) || first > p->nrx || count > p->nrx - first || (!out && count > 0))
+        return -EINVAL;
+    if (count == 0)
+        return 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    POS_HIP(p, p->d_rng_out.reserve(count));
+    msd_pos_launch_range_read(p->stream, p->d_rng.get(), first, count, (flags & MSD_RANGE_TAKE_LONGEST) != 0, p->d_rng_out.get());
+    POS_HIP(p, hipGetLastError());
+    POS_HIP(p, hipMemcpyAsync(out, p->d_rng_out.get(), sizeof(msd_range_receiver) * count, hipMemcpyDeviceToHost, p->stream));
+    POS_HIP(p, hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int msd_pos_range_distances(msd_pos *p, uint32_t *out, size_t cap, int on_device, size_t *n)
+{
+    if (!p || !p->range || !n || (!out && cap > 0))
+        return -EINVAL;
+    return read_out(p, p->d_dist_out, out, cap, on_device, n, [&](uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist, uint32_t *dst) {
+        msd_pos_launch_range_distances(p->stream, p->tab[p->cur], (uint32_t)p->live, snapshot_key_bits(p), idx_a, idx_b, hist, dst);
+    });
+}
+
+int msd_pos_range_pb(msd_pos *p, uint8_t *out, size_t cap, size_t *out_len, uint64_t *end)
+{
+    if (!p || !p->range || !p->range_polar || !out_len || (!out && cap > 0))
+        return -EINVAL;
+    *out_len = 0;
+    POS_HIP(p, hipSetDevice(p->device));
+    const size_t n = (size_t)p->nrx * MSD_RANGE_BUCKETS; /* at most 65536 * 72 entries of at most 10 bytes */
+    const uint32_t nblocks = (uint32_t)((n + 255u) / 256u);
+    POS_HIP(p, p->d_w_lens.reserve(n));
+    POS_HIP(p, p->d_w_block.reserve(nblocks + 1u));
+    POS_HIP(p, p->d_rng_end.reserve(p->nrx));
+    msd_range_pb_launch_lengths(p->stream, p->d_rng.get(), p->nrx, p->d_w_lens.get(), p->d_w_block.get());
+    POS_HIP(p, hipGetLastError());
+    return emit(p, p->d_w_block.get(), nblocks, "polar range", out, cap, out_len, end, p->d_rng_end.get(),
+                sizeof(uint64_t) * p->nrx, [&](uint32_t) {
+                    msd_range_pb_launch_store(p->stream, p->d_rng.get(), p->nrx, p->d_w_lens.get(), p->d_w_block.get(),
+                                              p->d_w_out.get(), p->d_rng_end.get());
+                });
+}
+
+int msd_pos_range_margins(const msd_pos *p, msd_range_margins *m)
+{
+    if (!p || !p->range || !m)
+        return -EINVAL;
+    unsigned long long d[2];
+    if (hipSetDevice(p->device) != hipSuccess ||
+        hipMemcpy(d, p->d_rmargins.get(), sizeof d, hipMemcpyDeviceToHost) != hipSuccess)
+        return -EIO;
+    memcpy(&m->min_range_margin_m, &d[0], sizeof(double));
+    memcpy(&m->min_bearing_margin_deg, &d[1], sizeof(double));
+    return 0;
+}
+
 int msd_aircraft_valid(const msd_aircraft *a, int member, uint64_t now_ms)
 {
     return a && member >= 0 && member < MSD_AC_N && msd_trk_valid(a, member, now_ms);
@@ -843,6 +1015,8 @@ int msd_pos_expire(msd_pos *p, uint64_t now_ms)
         return 0;
     /* linear probing has no holes to leave: the survivors are inserted again into the other, empty table */
     const int other = p->cur ^ 1;
+    if (p->range) /* a removed aircraft's distance goes with it */
+        POS_HIP(p, hipMemsetAsync(p->tab[other].dist, 0, sizeof(uint32_t) * p->tab[other].cap, p->stream));
     msd_pos_launch_fill(p->stream, p->tab[other].keys, p->tab[other].cap);
     msd_pos_launch_rebuild(p->stream, p->tab[p->cur], p->tab[other]);
     POS_HIP(p, hipGetLastError());

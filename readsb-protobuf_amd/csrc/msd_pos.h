@@ -1,5 +1,5 @@
-/* msd_pos.h -- what msd_pos.cpp (the C-ABI of the position tracker) launches from msd_pos_kernels.hip and from its four
- * writers (msd_reduce_kernels.hip, msd_sbs_kernels.hip, msd_pb_kernels.hip, msd_vrs_kernels.hip).  Every function queues
+/* msd_pos.h -- what msd_pos.cpp (the C-ABI of the position tracker) launches from msd_pos_kernels.hip and from its five
+ * writers (msd_reduce_kernels.hip, msd_sbs_kernels.hip, msd_pb_kernels.hip, msd_vrs_kernels.hip, msd_range_kernels.hip).  Every function queues
  * kernels on `stream` and returns; all pointers are device memory.  The tables and the call structs are raw pointers
  * because kernels take them by value; msd_pos.cpp owns what they point into. */
 #ifndef MSD_POS_H
@@ -23,6 +23,7 @@ typedef struct msd_pos_table {
     msd_trk_aircraft *trk; /* cap entries of a table tracker (msd_pos_create_table), else NULL */
     uint8_t *hits;         /* 2 * cap bytes {modeA_hit, modeC_hit} of a tracker that matches Mode A/C replies, else NULL */
     uint64_t *next_reduce; /* MSD_REDUCE_TIMERS * cap timers of a tracker that reduces (msd_trk_reduce), else NULL */
+    uint32_t *dist;        /* cap distances (a->meta.distance) of a tracker with the receiver range, else NULL */
     uint32_t cap;          /* a power of two */
 } msd_pos_table;
 
@@ -37,12 +38,39 @@ void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t
  * 256 * ceil(n / MSD_POS_TILE) words.  With t.trk, step 5: the table walk over the same grouped order, which reads the
  * out[] of step 3 and writes nicrc[] (n entries from base).  With t.next_reduce, the reduce instantiations of both walks:
  * forward[] (as out[], zeroed by the caller) gets every walked record's verdict byte, reduce_interval is in ms.  With sbs
- * (as out[], zeroed by the caller; a table tracker), the SBS instantiations: every walked record's row */
+ * (as out[], zeroed by the caller; a table tracker), the SBS instantiations: every walked record's row.  With rcode (as
+ * out[], zeroed by the caller; a tracker with the receiver range), the range instantiation of the position walk: every
+ * walked record's msd_pos_range_code, MSD_RANGE_CODE_LAST on each aircraft's last decoded record of the piece */
 void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
                           const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
                           uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
                           msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc, uint32_t reduce_interval,
-                          uint8_t *forward, msd_sbs_track *sbs);
+                          uint8_t *forward, msd_sbs_track *sbs, uint8_t *rcode);
+/* The receiver range (msd_pos_impl.h, "the receiver range").  Per receiver, 304 bytes that are msd_range_receiver's with
+ * the double's bits where longest_m / longest_nm will be; margins: the bits of the two smallest margins.
+ * range: one lane per record of the piece base .. base + n, behind the piece's walk: the maxima into rng[receiver],
+ * combined per wavefront first when `combine`, and t.dist[slot] from the records that carry MSD_RANGE_CODE_LAST.
+ * read: rows first .. first + count as msd_range_receiver into out, `take` zeroing longest behind it.
+ * distances: the snapshot's ordering passes, then out[j] = the distance of the aircraft in the j-th slot */
+typedef struct msd_range_state {
+    uint32_t polar[MSD_RANGE_BUCKETS];
+    unsigned long long longest_bits, evaluated;
+} msd_range_state;
+void msd_pos_launch_range(hipStream_t stream, msd_pos_table t, const msd_position *out, const uint32_t *receiver,
+                          const msd_pos_receiver *rx, const uint32_t *slot, const uint8_t *rcode, uint32_t base, uint32_t n,
+                          int polar, int combine, msd_range_state *rng, unsigned long long *margins);
+void msd_pos_launch_range_read(hipStream_t stream, msd_range_state *rng, uint32_t first, uint32_t count, int take,
+                               msd_range_receiver *out);
+void msd_pos_launch_range_distances(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
+                                    uint32_t *idx_b, uint32_t *hist, uint32_t *out);
+#ifdef __cplusplus
+extern "C" {
+#endif
+int msd_pos_range_measure(msd_pos *p, int combine, int timing); /* msd_pos.cpp; for scripts/range_rate.py */
+int msd_pos_range_kernel_ms(const msd_pos *p, float *ms);
+#ifdef __cplusplus
+}
+#endif
 /* expiry: marks and counts the aircraft to remove (ctl[MSD_POS_CTL_REMOVED]); rebuild inserts the others into `to` */
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl);
 void msd_pos_launch_rebuild(hipStream_t stream, msd_pos_table from, msd_pos_table to);
@@ -96,6 +124,7 @@ void msd_pb_launch_move(hipStream_t stream, msd_pos_table from, const uint64_t *
 typedef struct msd_pb_call {
     msd_pos_table t;
     uint64_t *state;                /* the written state, per slot */
+    const uint32_t *dist;           /* the distances of a tracker that keeps the receiver range, per slot; else NULL */
     const uint32_t *idx;            /* the ordered slots */
     const uint32_t *items;
     const uint64_t *messages_total; /* per receiver, or NULL */
@@ -107,6 +136,11 @@ void msd_pb_launch_lengths(hipStream_t stream, msd_pb_call c, uint32_t live, uin
                            uint16_t *lens, uint32_t *within, uint32_t *cwithin, uint32_t *block_sums, msd_pb_receiver *rx);
 void msd_pb_launch_store(hipStream_t stream, msd_pb_call c, const uint64_t *shadow, const uint16_t *lens, const uint32_t *block_off,
                          uint8_t *out);
+/* Statistics.polar_range (msd_range_kernels.hip): the 72 entries of receivers 0 .. nrx - 1, dense and in order; lengths
+ * and store as the reduced output's over the nrx * 72 entries; end[r]: receiver r's end offset */
+void msd_range_pb_launch_lengths(hipStream_t stream, const msd_range_state *rng, uint32_t nrx, uint8_t *lens, uint32_t *block_sums);
+void msd_range_pb_launch_store(hipStream_t stream, const msd_range_state *rng, uint32_t nrx, const uint8_t *lens,
+                               const uint32_t *block_off, uint8_t *out, unsigned long long *end);
 /* VRS output (msd_vrs_kernels.hip).  The items of a call are, per receiver, a head, its live aircraft and a tail, in
  * stream order (live + 2 * nrx of them; idx: the ordered slots).  select: first[0 .. nrx], items[], and per item lens
  * (an aircraft's without its comma; 0: not selected) and swithin (the selected aircraft before it inside its workgroup of

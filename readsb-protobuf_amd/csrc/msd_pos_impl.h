@@ -3,21 +3,24 @@
  * Restated from track.c / track.h:
  *   accept_data :170-196 (its reduce_forward half is msd_trk_impl.h's: msd_pos_acc.accepted tells it which of the six
  *   members a record's feed accepted), trackDataValid track.h:217-219, trackDataAge :229-235,
- *   greatcircle :260-279, speed_check :313-369, doGlobalCPR :371-446, doLocalCPR :448-542, updatePosition :551-688 up to
- *   the assignment of a->meta.lat/lon, the part of trackUpdateFromMessage that reaches them -- seen / messages
+ *   getBearing :238-250, greatcircle :260-279, update_polar_range :281-308, speed_check :313-369, doGlobalCPR :371-446,
+ *   doLocalCPR :448-542, updatePosition :551-688 (the declination, :676-681, left out; :683-686 is "the receiver range" at
+ *   the end of this file), the part of trackUpdateFromMessage that reaches them -- seen / messages
  *   :1024-1025, the per-source versions :1032-1075, the gs / ias / tas stores :1222-1235, the CPR stores :1313-1329,
  *   :1381-1383 -- and the part of trackRemoveStaleAircraft :1494-1570 that concerns these members.
- * Not here: geomag_calc, update_polar_range, SBS and MLAT input (the SBS output's text is msd_sbs_impl.h).  NIC / Rc and the other members of struct aircraft are
- * msd_trk_impl.h's, for a tracker with the aircraft table.
+ * Not here: geomag_calc, SBS and MLAT input (the SBS output's text is msd_sbs_impl.h).  NIC / Rc and the other members of
+ * struct aircraft are msd_trk_impl.h's, for a tracker with the aircraft table.
  *
  * Every validity of the six kept members has stale_interval 60 s and expire_interval 70 s (track.c:113-115,132-134), so
  * the state keeps `source` and `updated` and derives stale = updated + 60000, expires = updated + 70000: accept_data is
  * the only place that sets a source other than SOURCE_INVALID, and it sets all three together.
  *
  * The coordinates are msd_cpr_impl.h's and exact.  greatcircle's sin / cos / acos / atan2 are the libm of whoever
- * compiles this: its distances are never delivered, they feed three comparisons (--max-range, the local range limit, the
- * speed check), and msd_pos_acc.margin keeps the smallest |distance - limit| seen so that a caller can tell whether a
- * stream came close enough to a gate for two libms to decide it differently (modes_hip.h, msd_pos_update). */
+ * compiles this: its distances feed three comparisons (--max-range, the local range limit, the speed check), and
+ * msd_pos_acc.margin keeps the smallest |distance - limit| seen so that a caller can tell whether a stream came close
+ * enough to a gate for two libms to decide it differently (modes_hip.h, msd_pos_update).  The receiver range delivers a
+ * distance truncated to metres and a bearing rounded to a bucket, and keeps two margins of its own for the same purpose
+ * (modes_hip.h, "Receiver range"). */
 #ifndef MSD_POS_IMPL_H
 #define MSD_POS_IMPL_H
 
@@ -449,6 +452,79 @@ MSD_HD int msd_pos_expire_one(msd_pos_aircraft *a, uint64_t now)
         a->reliable_even = 0;
     }
     return 0;
+}
+
+/* ---- the receiver range: the last lines of updatePosition (track.c:683-686) with update_polar_range (:281-308) and
+ * getBearing (:238-250).  For a record whose msd_pos_update_position returned location_result >= 0, after lat / lon and
+ * the pos_reliable counters are updated:
+ *     a->meta.distance = 0                                                              :683
+ *     if pos_reliable_odd >= 1 && pos_reliable_even >= 1 && mm->source == SOURCE_ADSB   :684
+ *         a->meta.distance = update_polar_range(new_lat, new_lon)                       :685
+ * update_polar_range: 0 without a receiver location (:285); range = greatcircle(receiver, position) (:288);
+ * longest_distance = range where range is within --max-range (or there is none) and longer (:290-292); with
+ * --stats-range, bucket = (int)round(getBearing / 5), 72 and more -> 0 (:296-300), polar_range[bucket] = (uint32_t)range
+ * where polar_range[bucket] < range (:302-304); -> (uint32_t)range (:307).
+ * The serial walk does none of the trigonometry: it leaves msd_pos_range_code per record, and msd_pos_range_one is
+ * evaluated by one lane per record afterwards (msd_pos_range_kernel), by the host object in stream order.  Both results are
+ * maxima -- of (uint32_t)range, which is monotone in range, and of non-negative doubles -- so the order does not matter. */
+#define MSD_RANGE_CODE_DECODED 1u /* location_result >= 0: the record sets a->meta.distance (:683) */
+#define MSD_RANGE_CODE_EVAL 2u    /* and :684 holds: update_polar_range is called */
+#define MSD_RANGE_CODE_LAST 4u    /* the aircraft's last decoded record of the call (of the piece): it leaves the distance */
+
+/* a: the aircraft after msd_pos_feed took the record, o: what the feed delivered for it.  A receiver-relative decode can
+ * succeed at pos_reliable 0 / 0 (after an expiry): decoded, not evaluated. */
+MSD_HD uint32_t msd_pos_range_code(const msd_pos_aircraft *a, const msd_fields *f, const msd_position *o)
+{
+    if (!o->decoded)
+        return 0;
+    return MSD_RANGE_CODE_DECODED | (a->reliable_odd >= 1 && a->reliable_even >= 1 && f->source == 7 ? MSD_RANGE_CODE_EVAL : 0u);
+}
+
+MSD_HD double msd_pos_bearing(double lat0, double lon0, double lat1, double lon1) /* getBearing, track.c:238-250: [0, 360] */
+{
+    lat0 = lat0 * MSD_POS_PI / 180.0;
+    lon0 = lon0 * MSD_POS_PI / 180.0;
+    lat1 = lat1 * MSD_POS_PI / 180.0;
+    lon1 = lon1 * MSD_POS_PI / 180.0;
+    const double dlon = lon1 - lon0;
+    const double x = cos(lat0) * sin(dlon);
+    const double y = cos(lat1) * sin(lat0) - sin(lat1) * cos(lat0) * cos(dlon);
+    const double b = atan2(x, y);
+    const double bearing = 180 / MSD_POS_PI * b;
+    return bearing + 180;
+}
+
+typedef struct msd_range_one {
+    double range;          /* greatcircle(receiver, position) */
+    double range_margin;   /* min(|range - nearest integer|, |range - max_range_m| with a limit) */
+    double bearing_margin; /* with the polar range: the bearing's distance from the nearest edge 2.5 + 5k; 0 below 1 m */
+    uint32_t metres;       /* (uint32_t)range: update_polar_range's return value */
+    uint32_t bucket;       /* with the polar range: 0 .. 71 */
+    uint32_t counts;       /* range is a number: it takes part in the maxima (a NaN compares false in :290 and :302) */
+    uint32_t longest;      /* :290's first half: within --max-range, or there is none */
+} msd_range_one;
+
+/* update_polar_range's arithmetic for one position and a receiver with a location */
+MSD_HD void msd_pos_range_one(const msd_pos_receiver *rx, double lat, double lon, int polar, msd_range_one *e)
+{
+    const double range = msd_pos_greatcircle(rx->lat, rx->lon, lat, lon);
+    e->range = range;
+    e->counts = range >= 0;
+    e->metres = e->counts ? (uint32_t)range : 0u;
+    e->longest = e->counts && (range <= rx->max_range_m || rx->max_range_m == 0);
+    e->range_margin = e->counts ? fabs(range - floor(range + 0.5)) : 0;
+    if (rx->max_range_m != 0 && !(fabs(range - rx->max_range_m) >= e->range_margin))
+        e->range_margin = fabs(range - rx->max_range_m);
+    e->bucket = 0;
+    e->bearing_margin = INFINITY;
+    if (polar) {
+        const double q = msd_pos_bearing(rx->lat, rx->lon, lat, lon) / 5;
+        int bucket = (int)round(q);
+        if (bucket >= (int)MSD_RANGE_BUCKETS || bucket < 0)
+            bucket = 0;
+        e->bucket = (uint32_t)bucket;
+        e->bearing_margin = range >= 1 ? 5 * fabs(q - floor(q) - 0.5) : 0;
+    }
 }
 
 #endif

@@ -25,6 +25,10 @@
  * msd_pos_update_sbs (modes_hip.h "SBS output") runs the SBS instantiations of the two walks, which leave one row per
  * record: step 3 everything it knows, step 5 the aircraft's geometric delta.  No other call runs them.  The text writer
  * is msd_sbs_kernels.hip.
+ * A tracker that keeps the receiver range (modes_hip.h "Receiver range") runs the range instantiation of step 3, which
+ * leaves one code byte per record, and behind each piece 6. msd_pos_range_kernel, one lane per record: greatcircle and
+ * getBearing for the records the walk marked, integer atomic maxima into the receivers' rows, and the aircraft's distance
+ * from its last decoded record.  The writer of Statistics.polar_range is msd_range_kernels.hip.
  * Wave64 throughout: ballots are 64 bits wide and a workgroup of 256 threads is four waves.  The walk is double
  * precision arithmetic with long dependent chains and divergent branches per aircraft; its rate comes from the number of
  * aircraft in flight, not from the vector width.
@@ -92,6 +96,8 @@ msd_pos_find_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
             if (t.next_reduce)
                 for (uint32_t k = 0; k < MSD_REDUCE_TIMERS; ++k)
                     t.next_reduce[(size_t)s * MSD_REDUCE_TIMERS + k] = 0;
+            if (t.dist)
+                t.dist[s] = 0;
             atomicAdd(&ctl[MSD_POS_CTL_INSERTED], 1u);
         }
     }
@@ -107,8 +113,11 @@ msd_pos_find_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
 __global__ void __launch_bounds__(NT) msd_pos_rollback_kernel(msd_pos_table t, const uint32_t *slot, const uint8_t *fresh, uint32_t n)
 {
     const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    if (i < n && fresh[i])
+    if (i < n && fresh[i]) {
         t.keys[slot[i]] = MSD_POS_EMPTY;
+        if (t.dist)
+            t.dist[slot[i]] = 0;
+    }
 }
 
 /* ---- one counting pass over the piece's n indices: digit = (slot >> shift) & 255 ---- */
@@ -217,12 +226,15 @@ msd_pos_scatter_kernel(const uint32_t *idx_in, Digit digit, uint32_t n, const ui
  * forward[i] what the table walk's rule needs of this one: the members msd_pos_feed accepted and whether the aircraft has
  * been seen twice; a tracker that does not runs the instantiation without it.  SBS: the call is msd_pos_update_sbs, and
  * the walk leaves the record's row in sbs[i] -- all of it but the geometric delta, which the table walk adds; every other
- * call runs the instantiation without it. */
-template <bool REDUCE, bool SBS>
+ * call runs the instantiation without it.  RANGE: the tracker keeps the receiver range, and the walk leaves the record's
+ * msd_pos_range_code in rcode[i] -- two comparisons, no arithmetic: the trigonometry is msd_pos_range_kernel's -- and marks
+ * the aircraft's last decoded record; a tracker that does not runs the instantiation without it. */
+template <bool REDUCE, bool SBS, bool RANGE>
 __global__ void __launch_bounds__(NT)
 msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *fields, const uint32_t *receiver,
                     const msd_pos_receiver *rx, int filter_persistence, uint32_t base, uint32_t n, const uint32_t *slot,
-                    const uint32_t *idx, msd_position *out, unsigned long long *dstats, uint8_t *forward, msd_sbs_track *sbs)
+                    const uint32_t *idx, msd_position *out, unsigned long long *dstats, uint8_t *forward, msd_sbs_track *sbs,
+                    uint8_t *rcode)
 {
     const uint32_t j = blockIdx.x * NT + threadIdx.x;
     if (j >= n)
@@ -233,6 +245,7 @@ msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
     msd_pos_aircraft a = t.st[s];
     msd_pos_acc acc = {};
     acc.margin = INFINITY;
+    uint32_t last = UINT32_MAX, last_code = 0;
     for (uint32_t k = j; k < n; ++k) {
         const uint32_t i = base + element(idx, k);
         if (slot[i] != s)
@@ -251,7 +264,17 @@ msd_pos_walk_kernel(msd_pos_table t, const msd_message *msgs, const msd_fields *
             msd_pos_sbs(&o, &acc, a.messages, &row);
             sbs[i] = row;
         }
+        if (RANGE) {
+            const uint32_t code = msd_pos_range_code(&a, &f, &o);
+            rcode[i] = (uint8_t)code;
+            if (code) {
+                last = i;
+                last_code = code;
+            }
+        }
     }
+    if (RANGE && last != UINT32_MAX)
+        rcode[last] = (uint8_t)(last_code | MSD_RANGE_CODE_LAST);
     t.st[s] = a;
     for (int c = 0; c < MSD_PC_N; ++c)
         if (acc.c[c])
@@ -338,6 +361,8 @@ __global__ void __launch_bounds__(NT) msd_pos_rebuild_kernel(msd_pos_table from,
     if (from.next_reduce)
         for (uint32_t k = 0; k < MSD_REDUCE_TIMERS; ++k)
             to.next_reduce[(size_t)d * MSD_REDUCE_TIMERS + k] = from.next_reduce[(size_t)s * MSD_REDUCE_TIMERS + k];
+    if (from.dist)
+        to.dist[d] = from.dist[s];
 }
 
 /* snapshot: entry j of the output is the aircraft in slot idx[j] */
@@ -449,6 +474,162 @@ __global__ void __launch_bounds__(NT) msd_modeac_gather_kernel(msd_pos_table t, 
     }
 }
 
+/* ---- the receiver range (msd_pos_impl.h, "the receiver range") ---- */
+/* One lane per record of the piece, behind the piece's walk: the records the walk marked MSD_RANGE_CODE_EVAL compute
+ * greatcircle and getBearing -- some 300 double operations that no lane waits on another for -- and add to their
+ * receiver's maxima; the record marked MSD_RANGE_CODE_LAST stores its aircraft's distance.  The maxima are integer atomics
+ * (a non-negative double orders as its bits), so arrival order does not matter.  A call's records often share a receiver
+ * and, with one aircraft or a stream of them along one airway, a bucket: COMBINE reduces the lanes of a wave that have
+ * the same word first, as msd_modeac_count_kernel does -- the first pending lane's word is broadcast, the lanes with the
+ * same word take the maximum among themselves with six butterfly steps and leave, and the first issues one atomic --,
+ * while a group has at least COMBINE_MIN lanes and for at most RANGE_ROUNDS rounds; the lanes still pending issue their
+ * own.  The margins are two minima over the whole wave and one atomic each.  Without COMBINE every lane issues its own
+ * five atomics: scripts/range_rate.py measures both.  The whole wave runs every loop: their conditions are ballots'. */
+constexpr int RANGE_ROUNDS = 4;
+
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
+{
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned long long o = __shfl_xor(v, m);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
+{
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned long long o = __shfl_xor(v, m);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+template <bool COMBINE>
+__global__ void __launch_bounds__(NT)
+msd_pos_range_kernel(msd_pos_table t, const msd_position *out, const uint32_t *receiver, const msd_pos_receiver *rx,
+                     const uint32_t *slot, const uint8_t *rcode, uint32_t base, uint32_t n, int polar, msd_range_state *rng,
+                     unsigned long long *margins)
+{
+    const uint32_t j = blockIdx.x * NT + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t i = base + j;
+    const uint32_t code = j < n ? rcode[i] : 0u; /* 0 for a record the walk never saw: the caller zeroed the array */
+    const unsigned long long inf = (unsigned long long)__double_as_longlong(INFINITY);
+    bool eval = false;
+    uint32_t r = 0;
+    msd_range_one e = {};
+    if (code & MSD_RANGE_CODE_EVAL) {
+        r = receiver ? receiver[i] : 0u; /* below nrx: the find step has refused a call with any other */
+        const msd_pos_receiver x = rx[r];
+        if (x.latlon_valid) { /* track.c:285 */
+            const msd_position o = out[i];
+            msd_pos_range_one(&x, o.lat, o.lon, polar, &e);
+            eval = true;
+        }
+    }
+    if (code & MSD_RANGE_CODE_LAST) /* a walked record: its slot is below cap */
+        t.dist[slot[i]] = eval ? e.metres : 0u;
+    const unsigned long long lbits = eval && e.longest ? (unsigned long long)__double_as_longlong(e.range) : 0ull;
+    const unsigned long long rm = eval ? (unsigned long long)__double_as_longlong(e.range_margin) : inf;
+    const unsigned long long bm = eval && polar ? (unsigned long long)__double_as_longlong(e.bearing_margin) : inf;
+    const bool pol = eval && polar && e.counts;
+    const uint32_t word = r * MSD_RANGE_BUCKETS + e.bucket; /* receivers <= 65536: below 2^23 */
+    if (!COMBINE) {
+        if (eval) {
+            atomicAdd(&rng[r].evaluated, 1ull);
+            if (lbits)
+                atomicMax(&rng[r].longest_bits, lbits);
+            atomicMin(&margins[0], rm);
+            if (polar)
+                atomicMin(&margins[1], bm);
+        }
+        if (pol)
+            atomicMax(&rng[r].polar[e.bucket], e.metres);
+        return;
+    }
+    if (!__ballot(eval)) /* the whole wave */
+        return;
+    const unsigned long long wrm = wave_min(rm), wbm = wave_min(bm);
+    if (lane == 0) {
+        if (wrm < inf)
+            atomicMin(&margins[0], wrm);
+        if (wbm < inf)
+            atomicMin(&margins[1], wbm);
+    }
+    bool pending = eval; /* longest and evaluated: the word is the receiver */
+    for (int round = 0; round < RANGE_ROUNDS; ++round) {
+        const unsigned long long left = __ballot(pending);
+        if (!left)
+            break;
+        const int first = __ffsll((long long)left) - 1;
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)r, first);
+        const bool same = pending && r == r0;
+        const int peers = __popcll(__ballot(same));
+        const unsigned long long best = wave_max(same ? lbits : 0ull);
+        if ((int)lane == first) {
+            atomicAdd(&rng[r0].evaluated, (unsigned long long)peers);
+            if (best)
+                atomicMax(&rng[r0].longest_bits, best);
+        }
+        pending = pending && !same;
+        if (peers < COMBINE_MIN)
+            break;
+    }
+    if (pending) {
+        atomicAdd(&rng[r].evaluated, 1ull);
+        if (lbits)
+            atomicMax(&rng[r].longest_bits, lbits);
+    }
+    pending = pol; /* the polar range: the word is (receiver, bucket) */
+    for (int round = 0; round < RANGE_ROUNDS; ++round) {
+        const unsigned long long left = __ballot(pending);
+        if (!left)
+            break;
+        const int first = __ffsll((long long)left) - 1;
+        const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)word, first);
+        const bool same = pending && word == w0;
+        const int peers = __popcll(__ballot(same));
+        const uint32_t best = (uint32_t)wave_max(same ? (unsigned long long)e.metres : 0ull);
+        if ((int)lane == first && best)
+            atomicMax(&rng[w0 / MSD_RANGE_BUCKETS].polar[w0 % MSD_RANGE_BUCKETS], best);
+        pending = pending && !same;
+        if (peers < COMBINE_MIN)
+            break;
+    }
+    if (pending && e.metres)
+        atomicMax(&rng[r].polar[e.bucket], e.metres);
+}
+
+/* one lane per receiver: its row as msd_range_receiver; longest_m / longest_nm from the device's own double */
+__global__ void __launch_bounds__(NT)
+msd_pos_range_read_kernel(msd_range_state *rng, uint32_t first, uint32_t count, int take, msd_range_receiver *out)
+{
+    const uint32_t k = blockIdx.x * NT + threadIdx.x;
+    if (k >= count)
+        return;
+    msd_range_state *const s = &rng[first + k];
+    msd_range_receiver *const row = &out[k];
+    for (uint32_t b = 0; b < MSD_RANGE_BUCKETS; ++b)
+        row->polar_range[b] = s->polar[b];
+    const double longest = __longlong_as_double((long long)s->longest_bits);
+    row->longest_m = (uint32_t)longest;               /* net_io.c:2249 */
+    row->longest_nm = (uint32_t)(longest / 1852.0);   /* net_io.c:2250 */
+    row->evaluated = s->evaluated;
+    if (take)
+        s->longest_bits = 0;
+}
+
+/* entry j of the output is the distance of the aircraft in slot idx[j]: msd_trk_gather_kernel's row j */
+__global__ void __launch_bounds__(NT) msd_pos_range_gather_kernel(msd_pos_table t, const uint32_t *idx, uint32_t live, uint32_t *out)
+{
+    const uint32_t j = blockIdx.x * NT + threadIdx.x;
+    if (j >= live)
+        return;
+    const uint32_t s = idx[j];
+    out[j] = s < t.cap ? t.dist[s] : 0u;
+}
+
 /* one stable counting pass over n elements */
 template <typename Digit>
 void counting_pass(hipStream_t stream, const uint32_t *in, Digit digit, uint32_t n, uint32_t *hist, uint32_t *out)
@@ -483,16 +664,31 @@ void msd_pos_launch_rollback(hipStream_t stream, msd_pos_table t, const uint32_t
     msd_pos_rollback_kernel<<<blocks(n), NT, 0, stream>>>(t, slot, fresh, n);
 }
 
+/* step 3 with or without the range codes */
+template <bool REDUCE, bool SBS>
+static void pos_walk(hipStream_t stream, uint32_t tiles, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
+                     const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base, uint32_t n,
+                     const uint32_t *slot, const uint32_t *in, msd_position *out, unsigned long long *dstats, uint8_t *forward,
+                     msd_sbs_track *sbs, uint8_t *rcode)
+{
+    if (rcode)
+        msd_pos_walk_kernel<REDUCE, SBS, true><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n,
+                                                                         slot, in, out, dstats, forward, sbs, rcode);
+    else
+        msd_pos_walk_kernel<REDUCE, SBS, false><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base,
+                                                                          n, slot, in, out, dstats, forward, sbs, nullptr);
+}
+
 /* steps 3 to 5 over the grouped order `in` */
 template <bool SBS>
 static void walks(hipStream_t stream, uint32_t tiles, msd_pos_table t, const msd_message *msgs, const msd_fields *fields,
                   const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base, uint32_t n,
                   const uint32_t *slot, const uint32_t *in, msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc,
-                  uint32_t reduce_interval, uint8_t *forward, msd_sbs_track *sbs)
+                  uint32_t reduce_interval, uint8_t *forward, msd_sbs_track *sbs, uint8_t *rcode)
 {
     if (t.next_reduce) { /* (a table tracker: msd_pos_reduce_enable refuses any other) */
-        msd_pos_walk_kernel<true, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot,
-                                                                 in, out, dstats, forward, sbs);
+        pos_walk<true, SBS>(stream, tiles, t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out, dstats,
+                            forward, sbs, rcode);
         if (t.hits)
             msd_trk_walk_kernel<true, true, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc,
                                                                            reduce_interval, forward, sbs);
@@ -501,8 +697,8 @@ static void walks(hipStream_t stream, uint32_t tiles, msd_pos_table t, const msd
                                                                             reduce_interval, forward, sbs);
         return;
     }
-    msd_pos_walk_kernel<false, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in,
-                                                              out, dstats, nullptr, sbs);
+    pos_walk<false, SBS>(stream, tiles, t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out, dstats, nullptr,
+                         sbs, rcode);
     if (t.trk && t.hits)
         msd_trk_walk_kernel<true, false, SBS><<<tiles, NT, 0, stream>>>(t, msgs, fields, base, n, slot, in, out, nicrc, 0u, nullptr,
                                                                         sbs);
@@ -515,7 +711,7 @@ void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message
                           const uint32_t *receiver, const msd_pos_receiver *rx, int filter_persistence, uint32_t base,
                           uint32_t n, const uint32_t *slot, uint32_t *idx_a, uint32_t *idx_b, uint32_t *hist,
                           msd_position *out, unsigned long long *dstats, msd_pos_nicrc *nicrc, uint32_t reduce_interval,
-                          uint8_t *forward, msd_sbs_track *sbs)
+                          uint8_t *forward, msd_sbs_track *sbs, uint8_t *rcode)
 {
     const uint32_t tiles = blocks(n);
     /* slots run from 0 to cap inclusive (cap = skipped) */
@@ -532,10 +728,10 @@ void msd_pos_launch_piece(hipStream_t stream, msd_pos_table t, const msd_message
     }
     if (sbs) /* msd_pos_update_sbs: the instantiations that leave the rows (a table tracker: msd_pos_sbs_enable refuses any other) */
         walks<true>(stream, tiles, t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out, dstats, nicrc,
-                    reduce_interval, forward, sbs);
+                    reduce_interval, forward, sbs, rcode);
     else
         walks<false>(stream, tiles, t, msgs, fields, receiver, rx, filter_persistence, base, n, slot, in, out, dstats, nicrc,
-                     reduce_interval, forward, nullptr);
+                     reduce_interval, forward, nullptr, rcode);
 }
 
 void msd_pos_launch_expire(hipStream_t stream, msd_pos_table t, uint64_t now_ms, uint32_t *ctl)
@@ -601,4 +797,27 @@ void msd_pos_launch_modeac_hits(hipStream_t stream, msd_pos_table t, uint32_t li
 {
     const uint32_t *idx = ordered_slots(stream, t, live, key_bits, idx_a, idx_b, hist);
     msd_modeac_gather_kernel<<<blocks(live), NT, 0, stream>>>(t, idx, live, out);
+}
+
+void msd_pos_launch_range(hipStream_t stream, msd_pos_table t, const msd_position *out, const uint32_t *receiver,
+                          const msd_pos_receiver *rx, const uint32_t *slot, const uint8_t *rcode, uint32_t base, uint32_t n,
+                          int polar, int combine, msd_range_state *rng, unsigned long long *margins)
+{
+    if (combine)
+        msd_pos_range_kernel<true><<<blocks(n), NT, 0, stream>>>(t, out, receiver, rx, slot, rcode, base, n, polar, rng, margins);
+    else
+        msd_pos_range_kernel<false><<<blocks(n), NT, 0, stream>>>(t, out, receiver, rx, slot, rcode, base, n, polar, rng, margins);
+}
+
+void msd_pos_launch_range_read(hipStream_t stream, msd_range_state *rng, uint32_t first, uint32_t count, int take,
+                               msd_range_receiver *out)
+{
+    msd_pos_range_read_kernel<<<blocks(count), NT, 0, stream>>>(rng, first, count, take, out);
+}
+
+void msd_pos_launch_range_distances(hipStream_t stream, msd_pos_table t, uint32_t live, uint32_t key_bits, uint32_t *idx_a,
+                                    uint32_t *idx_b, uint32_t *hist, uint32_t *out)
+{
+    const uint32_t *idx = ordered_slots(stream, t, live, key_bits, idx_a, idx_b, hist);
+    msd_pos_range_gather_kernel<<<blocks(live), NT, 0, stream>>>(t, idx, live, out);
 }

@@ -8,7 +8,8 @@
  *   msd_pos_feed does (seen / messages, gs / ias / tas, the CPR halves and updatePosition), the NIC / Rc of doGlobalCPR
  *   :378-379 and doLocalCPR :458-473 with updatePosition's stores :667-674, and trackRemoveStaleAircraft's EXPIRE list
  *   :1520-1563 for these members.
- * Not here: FATSV state, geomag_calc, update_polar_range, SBS and MLAT input.  The SBS output takes the aircraft's
+ * Not here: FATSV state, geomag_calc, SBS and MLAT input (a->meta.distance and update_polar_range are msd_pos_impl.h's,
+ * "the receiver range", kept beside the table, not in it).  The SBS output takes the aircraft's
  * geom_delta and its validity from the entry after a record's feed (msd_trk_sbs below); its text is msd_sbs_impl.h.
  * trackMatchAC is msd_modeac_impl.h; of modeA_hit / modeC_hit this file has the two resets (:1096-1102, :1154-1156).
  *

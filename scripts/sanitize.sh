@@ -37,7 +37,7 @@ asan) SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omi
 tsan) SAN="-fsanitize=thread -fno-omit-frame-pointer"; CC=/opt/rocm/lib/llvm/bin/clang; CXX=/opt/rocm/lib/llvm/bin/clang++ ;;
 *) echo "usage: $0 asan|tsan OUTDIR" >&2; exit 2 ;;
 esac
-test -f msd_kernels.o -a -f msd_dc_kernels.o -a -f msd_resolve_kernels.o -a -f msd_frames_kernels.o -a -f msd_wire_kernels.o -a -f msd_avr_kernels.o -a -f msd_group_beast_kernels.o -a -f msd_group_avr_kernels.o -a -f msd_group_remote_out_kernels.o -a -f msd_pos_kernels.o -a -f msd_reduce_kernels.o -a -f msd_sbs_kernels.o -a -f msd_pb_kernels.o -a -f msd_vrs_kernels.o -a -f msd_capi.o -a -f msd_batch.o -a -f msd_collect.o -a -f msd_group.o -a -f msd_frames.o || { echo "run build.sh first (the HIP objects are reused)" >&2; exit 1; }
+test -f msd_kernels.o -a -f msd_dc_kernels.o -a -f msd_resolve_kernels.o -a -f msd_frames_kernels.o -a -f msd_wire_kernels.o -a -f msd_avr_kernels.o -a -f msd_group_beast_kernels.o -a -f msd_group_avr_kernels.o -a -f msd_group_remote_out_kernels.o -a -f msd_pos_kernels.o -a -f msd_reduce_kernels.o -a -f msd_sbs_kernels.o -a -f msd_pb_kernels.o -a -f msd_vrs_kernels.o -a -f msd_range_kernels.o -a -f msd_capi.o -a -f msd_batch.o -a -f msd_collect.o -a -f msd_group.o -a -f msd_frames.o || { echo "run build.sh first (the HIP objects are reused)" >&2; exit 1; }
 INC="-I. -I../../include -Ihost"
 CF="-std=c11 -O1 -g -Wall -Wextra -fPIC $SAN $INC"
 $CC $CF -ffp-contract=off -c msd_tables.c -o "$OUT/msd_tables.o"
@@ -60,7 +60,7 @@ CAPI_OBJ="$CAPI_OBJ $OUT/msd_frames.o $OUT/msd_group.o $OUT/msd_group_remote.o $
 # (the sanitizer runtime comes from LD_PRELOAD or from the instrumented executable: the shared objects leave it undefined)
 # (the wire writers are in both libraries, as in build.sh)
 $CC $CF -c host/msd_wire.c -o "$OUT/msd_wire.o"
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmodes_hip.so" msd_kernels.o msd_dc_kernels.o msd_resolve_kernels.o msd_frames_kernels.o msd_wire_kernels.o msd_avr_kernels.o msd_group_beast_kernels.o msd_group_avr_kernels.o msd_group_remote_out_kernels.o msd_pos_kernels.o msd_reduce_kernels.o msd_sbs_kernels.o msd_pb_kernels.o msd_vrs_kernels.o $CAPI_OBJ \
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmodes_hip.so" msd_kernels.o msd_dc_kernels.o msd_resolve_kernels.o msd_frames_kernels.o msd_wire_kernels.o msd_avr_kernels.o msd_group_beast_kernels.o msd_group_avr_kernels.o msd_group_remote_out_kernels.o msd_pos_kernels.o msd_reduce_kernels.o msd_sbs_kernels.o msd_pb_kernels.o msd_vrs_kernels.o msd_range_kernels.o $CAPI_OBJ \
     "$OUT/msd_tables.o" "$OUT/msd_resolve.o" "$OUT/msd_fields.o" "$OUT/msd_magbuf.o" "$OUT/msd_wire.o" -lm -lpthread
 for f in msd_fifo msd_sdr_ifile msd_converter msd_demod; do
     $CC $CF -c host/$f.c -o "$OUT/$f.o"
