@@ -49,7 +49,7 @@ class Builder(acs.Builder):
 
 
 NAMES = ["threshold", "seen_5000", "squawk_expired", "two_on_one_squawk", "own_mode_c", "negative_altitudes", "c_plus_one",
-         "ageing", "mode_a_hit_reset", "mode_c_hit_reset", "expiry_rebuild", "two_receivers", "spi"]
+         "ageing", "mode_a_hit_reset", "mode_c_hit_reset", "expiry_rebuild", "two_receivers", "spi", "mode_c_outside_the_table"]
 
 
 def scenarios(pkg):
@@ -226,6 +226,23 @@ def scenarios(pkg):
         c = obs[-1]["codes"][0]
         assert tuple(c[idx(0x1200)]) == (4, 4, 0x1C0001, 10) and int(c["count"].sum()) == 4
     S["spi"] = ([None], [b.step(), ("match", T0 + 1000, T0 + 1000)], check)
+
+    # altitudes whose C, C + 1 or C - 1 lies outside modeCToATable (modeCToModeA's range test, mode_ac.c:93-98).
+    # -1400 ft: C = (-1400 + 49) / 100 = -13 has no code, C - 1 = -14 is below the table, C + 1 = -12 is -1200 ft: a reply
+    # there matches.  408 300 ft: C = 4083 is the first index past the table, C + 1 is further out, C - 1 = 4082 is the
+    # table's last entry and has no code: replies under squawk 0000 -- what a careless lookup would return -- match nobody
+    low = code_of_feet(-1200)
+    b = B()
+    b.alt(T0, 0x1D0001, -1400).alt(T0, 0x1D0002, 408300, rx=1)
+    b.reply(T0 + 10, low, n=4).reply(T0 + 10, 0x0000, n=4).reply(T0 + 10, low, rx=1, n=4).reply(T0 + 10, 0x0000, rx=1, n=4)
+
+    def check(obs):
+        assert obs[-1]["hits"] == {(0, 0x1D0001): (0, 1), (1, 0x1D0002): (0, 0)}
+        c = obs[-1]["codes"]
+        assert tuple(c[0][idx(low)]) == (4, 4, 0x1D0001, 10) and tuple(c[0][0]) == (4, 4, 0, 0)
+        assert tuple(c[1][idx(low)]) == (4, 4, 0, 0) and tuple(c[1][0]) == (4, 4, 0, 0)
+        assert int(obs[-1]["snap"][(1, 0x1D0002)]["alt_baro"]) == 408300
+    S["mode_c_outside_the_table"] = ([None, None], [b.step(), ("match", T0 + 1000, T0 + 1000)], check)
     return S
 
 

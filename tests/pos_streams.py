@@ -151,19 +151,177 @@ def scenarios(pkg):
     b.pos(T0 + 900000, 0x900001, 47.2, 8.2, 0)
     steps += [b.step()]
     S["expiry_and_ttl"] = ([None], 0, steps)
+
+    # accept_data's refusals for the six members msd_pos_feed accepts (refusal_family below)
+    b = B()
+    refusal_family(b)
+    S["refusals"] = ([None, dict(HOME, max_range_m=150 * NM)], 0, [b.step()])
+
+    # the speed check of a surface target.  Without any valid speed: 100 kt x 4 / 3 = 133 kt = 68.42 m/s; the position
+    # is 30 s old, so the limit is 100 m + 31 s x 68.42 m/s = 2221 m: 1800 m north passes, 2350 m fails (with the
+    # airborne default of 700 kt, clamped to the surface's 150 kt, the limit were 2492 m and it would pass).  With gs
+    # valid -- movement 48 is 24.5 kt, stored as 24 --: 24 x 4 / 3 = 32 kt = 16.46 m/s, the position is 60 s old (the
+    # pairing window of a slow target is 50 s): 100 m + 61 s x 16.46 m/s = 1104 m: 850 m passes, 1350 m fails
+    b = B()
+    for k, (mov, gap, north) in enumerate(((0, 30000, 1800.0), (0, 30000, 2350.0), (48, 60000, 850.0), (48, 60000, 1350.0))):
+        a = 0x220000 + k
+        b.pos(T0, a, 52.3, 4.76, 0, surface=True, movement=mov).pos(T0 + 400, a, 52.3, 4.76, 1, surface=True, movement=mov)
+        b.pos(T0 + 400 + gap, a, 52.3 + north / M_PER_DEG, 4.76, 0, surface=True, movement=mov)
+    S["surface_speed_check"] = ([HOME], 0, [b.step()])
+
+    # the surface movement codes at the steps of the table's upper half (mode_s.c:216-259): 93 is 69.5 kt, 94 71 kt,
+    # 108 99 kt, 109 102.5 kt, 123 172.5 kt, 124 180 kt, 125 and 127 are 0 kt ("reserved") -- and 0 kt is a valid speed
+    # of at most 25 kt, so those two pair their halves across 40 s and the others do not
+    b = B()
+    for k, mov in enumerate(MOVEMENT_CODES):
+        a = 0x230000 + k
+        b.pos(T0, a, 52.3, 4.76, 0, surface=True, movement=mov).pos(T0 + 40000, a, 52.3, 4.76, 1, surface=True, movement=mov)
+    S["surface_movement_codes"] = ([HOME], 0, [b.step()])
+
+    # --max-range in the global decode: without a receiver location the limit is not applied (receiver 0); with one a
+    # pair 190 NM away is bad data and one 40 NM away is not (receiver 1; there single halves are tried relative to the
+    # receiver, within 100 NM: the far one fails, the near one decodes)
+    b = B()
+    b.pos(T0, 0x630000, 53.0, 9.0, 0, rx=0).pos(T0 + 300, 0x630000, 53.0, 9.0, 1, rx=0)
+    b.pos(T0, 0x630001, 53.0, 9.0, 0, rx=1).pos(T0 + 300, 0x630001, 53.0, 9.0, 1, rx=1)
+    b.pos(T0, 0x630002, 52.5, 5.0, 0, rx=1).pos(T0 + 300, 0x630002, 52.5, 5.0, 1, rx=1)
+    S["global_max_range"] = ([dict(max_range_m=100 * NM), dict(HOME, max_range_m=100 * NM)], 0, [b.step()])
+
+    # a negative --max-range is not "none": doLocalCPR takes it for a limit below 180 NM, and `range_limit > 0` then
+    # leaves the range check out: the single half decodes relative to the receiver
+    b = B()
+    b.pos(T0, 0x640000, 52.5, 5.0, 0)
+    S["negative_max_range"] = ([dict(HOME, max_range_m=-1.0)], 0, [b.step()])
+
+    # the speed check is for sources no better than the position's.  A and B have a TIS-B position at 50 N 8 E; 20 s
+    # later (too late to pair with the first halves) an even half from 52 N -- 222 km away, beyond the 100 NM of a decode
+    # relative to the aircraft: -1 -- and its odd half, a global pair: from ADS-B it is taken unchecked (A), from TIS-B
+    # it is 222 km in 20 s and bad data (B).  C and D the same for the local decode, 50.5 N, 56 km away, where 933 kt
+    # allow 10.4 km: ADS-B taken (C), TIS-B refused (D)
+    b = B()
+    for k, (src, lat, pair_) in enumerate(((ip.ADSB, 52.0, True), (ip.TISB, 52.0, True), (ip.ADSB, 50.5, False), (ip.TISB, 50.5, False))):
+        a = 0x650000 + k
+        b.pos(T0, a, 50.0, 8.0, 0, source=ip.TISB).pos(T0 + 400, a, 50.0, 8.0, 1, source=ip.TISB)
+        b.pos(T0 + 20000, a, lat, 8.0, 0, source=src)
+        if pair_:
+            b.pos(T0 + 20400, a, lat, 8.0, 1, source=src)
+    S["higher_source_skips_speed_check"] = ([None], 0, [b.step()])
+
+    # pos_reliable_odd and _even part ways: three global decodes on odd halves make 3 / 1 (A) and one more on an even half
+    # 3 / 2 (B); bad data then costs one each: 2 / 0 takes A's position away (and both counters), 2 / 1 leaves B's
+    b = B()
+    for k, a in enumerate((0x410001, 0x410002)):
+        b.pos(T0, a, 50.0, 8.0, 0)
+        for j in range(3):
+            b.pos(T0 + 400 * (j + 1), a, 50.0, 8.0, 1)
+        if k:
+            b.pos(T0 + 1600, a, 50.0, 8.0, 0)
+        b.pos(T0 + 2000, a, 40.0, 20.0, 0)
+    S["reliable_sides"] = ([None], 8, [b.step()])
+
+    # the global airborne decode refuses a pair of which only the odd half's latitude is out of range (cpr.c:188-196).
+    # Even YZ = 0, odd YZ = 99328 = 131072 x 97 / 128: j = floor(-60 x 97 / 128 + 0.5) = floor(-44.97) = -45, so the even
+    # latitude is 6 x (15 + 0) = 90 exactly -- in range -- and the odd one 360 / 59 x (14 + 97 / 128) = 90.048: bad data.
+    # Odd YZ = 31744 = 131072 x 31 / 128: j = -15, the even latitude is 6 x 45 = 270 -> -90, in range, the odd one
+    # 360 / 59 x (44 + 31 / 128) = 269.95, which is below 270 and stays: bad data
+    b = B()
+    b.raw(T0, 0x420001, 0, 0, 0).raw(T0 + 400, 0x420001, 99328, 0, 1)
+    b.raw(T0, 0x420002, 0, 0, 0).raw(T0 + 400, 0x420002, 31744, 0, 1)
+    S["odd_latitude_alone_out_of_range"] = ([None], 0, [b.step()])
     return S
 
 
-def mixed_stream(pkg, n=2000, seed=7):
+# What the later scenarios are named for, derived by hand in their comments: the rows' results and the counters that tell.
+# test_positions_model.py asserts them on the host twin, test_gpu_positions.py on the device.
+KNOWN = {
+    "surface_speed_check": ([-1, 0, 1] + [-1, 0, -1] + [-1, 0, 1] + [-1, 0, -1], dict(cpr_local_speed_checks=2, cpr_surface=12)),
+    "surface_movement_codes": ([-1, -1] * 6 + [-1, 0] * 2, dict(cpr_global_ok=2)),
+    "global_max_range": ([-1, 0] + [-1, -2] + [2, 0], dict(cpr_global_range_checks=1, cpr_local_range_checks=1)),
+    "negative_max_range": ([2], dict(cpr_local_range_checks=0, cpr_local_receiver_relative=1)),
+    "higher_source_skips_speed_check": ([-1, 0, -1, 0] + [-1, 0, -1, -2] + [-1, 0, 1] + [-1, 0, -1],
+                                        dict(cpr_global_speed_checks=1, cpr_local_speed_checks=1, cpr_local_range_checks=2)),
+    "reliable_sides": ([-1, 0, 0, 0, -2] + [-1, 0, 0, 0, 0, -2], dict(cpr_global_bad=2)),
+    "odd_latitude_alone_out_of_range": ([-1, -2, -1, -2], dict(cpr_global_bad=2, cpr_global_range_checks=0, cpr_global_speed_checks=0)),
+}
+
+
+def known(name, out, st):
+    results, counters = KNOWN[name] if name != "refusals" else ([x for case in REFUSAL_RESULTS for x in case], dict(
+        cpr_local_receiver_relative=5, cpr_local_aircraft_relative=1, cpr_global_skipped=1, cpr_global_ok=1, cpr_local_speed_checks=0))
+    assert [int(x) for x in out["result"]] == results, name
+    assert {k: st[k] for k in counters} == counters, name
+
+
+M_PER_DEG = 6371e3 * np.pi / 180  # greatcircle's metres per degree of latitude
+MOVEMENT_CODES = (93, 94, 108, 109, 123, 124, 125, 127)
+MOVEMENT_GS = (69, 71, 99, 102, 172, 180, 0, 0)  # (uint32) of the knots above: what the table keeps as gs
+# refusal_family: per member the address of its five aircraft's first, what the ADS-B record at T0 and the others carry
+# (value A, value B), and what tells them apart in the table entry
+REFUSAL_MEMBERS = ("gs", "ias", "tas", "cpr_even", "cpr_odd", "position")
+REFUSAL_CASES = (("inside", 1000, False), ("last_ms", 59999, False), ("first_ms_outside", 60000, True), ("older", -1, False),
+                 ("equal_source", 1000, True))
+
+
+def refusal_addr(member, case):
+    return 0xA00000 + 0x100 * REFUSAL_MEMBERS.index(member) + case
+
+
+def refusal_family(b):
+    """accept_data (track.c:170-196) for gs, ias, tas, the CPR halves and the position, all stale after 60 s: per member
+    five aircraft with an ADS-B value at T0 and then one record each --
+      0. a lesser source 1 s later: refused;  1. the same 59 999 ms later: refused;  2. 60 000 ms later: accepted;
+      3. the same source, 1 ms before T0: older than `updated`, refused;  4. the same source 1 s later: accepted.
+    gs, ias, tas and the CPR halves are on receiver 0 (no location: a single half decodes nothing, -1, and a refused half
+    is NOT_TRIED); the position's aircraft are on receiver 1 (52 N 4 E, --max-range 150 NM): the odd half at T0 decodes
+    relative to the receiver (2), a TIS-B even half then decodes relative to the aircraft and the position's accept_data
+    decides (refused: -1, accepted: 1); the ADS-B even half pairs with the odd one: 1 ms older than the position it is
+    a good decode that is skipped (-2), 1 s later it is the position (0).  REFUSAL_RESULTS has the rows' results."""
+    lesser = dict(source=ip.MODE_S_CHECKED, msgtype=20)
+    for case, (_, dt, _) in enumerate(REFUSAL_CASES):
+        same = case >= 3
+        a = refusal_addr("gs", case)
+        b.vel(T0, a, 300, 400)  # 500 kt
+        b.vel(T0 + dt, a, 60, 80) if same else b.rec(T0 + dt, a, commb_valid=2, gs=100, **lesser)
+        a = refusal_addr("ias", case)
+        b.rec(T0, a, ias_valid=1, ias=250)
+        b.rec(T0 + dt, a, ias_valid=1, ias=180, **({} if same else lesser))
+        a = refusal_addr("tas", case)
+        b.rec(T0, a, tas_valid=1, tas=420)
+        b.rec(T0 + dt, a, tas_valid=1, tas=390, **({} if same else lesser))
+        for odd, member in ((0, "cpr_even"), (1, "cpr_odd")):
+            a = refusal_addr(member, case)
+            b.pos(T0, a, 51.5, 3.5, odd)
+            b.pos(T0 + dt, a, 51.6, 3.5, odd, source=ip.ADSB if same else ip.TISB)
+            if not same:
+                b.f[-1]["metype"] = 13  # the table tells by the NIC / Rc whether the half was stored
+        a = refusal_addr("position", case)
+        b.pos(T0, a, 52.5, 5.0, 1, rx=1)
+        b.pos(T0 + dt, a, 52.5, 5.0, 0, rx=1, source=ip.ADSB if same else ip.TISB)
+    return b
+
+
+#                   gs      ias       tas       cpr_even  cpr_odd   position     (first record, second record) per case
+REFUSAL_RESULTS = [[-3, -3, -3, -3, -3, -3, -1, -3, -1, -3, 2, -1],    # a lesser source inside the interval
+                   [-3, -3, -3, -3, -3, -3, -1, -3, -1, -3, 2, -1],    # at its last millisecond
+                   [-3, -3, -3, -3, -3, -3, -1, -1, -1, -1, 2, 1],     # at the first outside
+                   [-3, -3, -3, -3, -3, -3, -1, -3, -1, -3, 2, -2],    # older than `updated`
+                   [-3, -3, -3, -3, -3, -3, -1, -1, -1, -1, 2, 0]]     # an equal source
+
+
+def mixed_stream(pkg, n=2000, seed=7, aircraft=40, third_receiver=False, jitter=None):
     """n records of 40 aircraft on two receivers: straight flights with a position every 400 to 600 ms alternating even
     and odd, velocities, airspeeds, operational status, a few surface targets, jumps to implausible places, Mode A/C
-    records and address 0 in between; in time order.  -> (receivers, msgs, fields, receiver)."""
+    records and address 0 in between; in time order.  third_receiver: a third one, in Sydney, takes every third aircraft.
+    jitter(i) -> (dlat, dlon) moves the position that record i carries (range_streams.settle's way of keeping a margin).
+    -> (receivers, msgs, fields, receiver)."""
     rng = np.random.default_rng(seed)
     rxs = [dict(lat=52.0, lon=4.0, latlon_valid=1, max_range_m=300 * NM), dict(lat=48.0, lon=11.0, latlon_valid=1)]
+    if third_receiver:
+        rxs.append(dict(lat=-33.9, lon=151.2, latlon_valid=1, max_range_m=200 * NM))
     b = Builder(pkg)
     planes = []
-    for k in range(40):
-        r = k % 2
+    for k in range(aircraft):
+        r = k % len(rxs)
         planes.append(dict(addr=0x3C0000 + 97 * k + (1 << 24 if k % 13 == 0 else 0), rx=r, lat=rxs[r]["lat"] + rng.uniform(-1.5, 1.5),
                            lon=rxs[r]["lon"] + rng.uniform(-2, 2), vlat=rng.uniform(-2e-6, 2e-6), vlon=rng.uniform(-3e-6, 3e-6),
                            surface=k % 10 == 9, odd=int(rng.integers(0, 2)), source=ip.TISB if k % 13 == 0 else ip.ADSB))
@@ -182,6 +340,8 @@ def mixed_stream(pkg, n=2000, seed=7):
             if rng.uniform() < 0.04:
                 k = 0.1 if rng.uniform() < 0.5 else 1.0                          # bad data, near (speed) or far (range)
                 lat, lon = lat + k * rng.uniform(3, 6), lon - k * rng.uniform(3, 6)
+            if jitter:
+                lat, lon = lat + jitter(len(b.m))[0], lon + jitter(len(b.m))[1]
             b.pos(t, p["addr"], lat, lon, p["odd"], surface=p["surface"], movement=int(rng.integers(0, 60)) if p["surface"] else 0, **kw)
         elif u < 0.85:
             b.vel(t, p["addr"], int(p["vlon"] * 2.4e8), int(p["vlat"] * 3.6e8), **kw)

@@ -272,7 +272,58 @@ def _scenarios(pkg):
                     b.pos(T0 + 1000 * rep + 400 * half + k // 8, a, lat + 0.05 * d[0], lon + 0.05 * d[1], half)
         return [HOME], 0, [b.step()], True
     S["contention"] = settle("contention", contention)
+
+    # 12. --max-range nearer to a range than the next whole metre: the range margin is the distance to the limit.  The
+    # pair is decoded while the receiver has no limit (a global decode is held against --max-range, and that gate must stay
+    # 1 m away); then the limit is set 0.3 m beyond where the aircraft's even half will decode, 11 s later and so relative
+    # to the aircraft, which the limit does not gate: within the limit, 0.3 m from it and about 0.5 m from a whole metre
+    S["limit_beside_the_range"] = limit_beside_the_range(pkg)[0]
     return S
+
+
+def limit_beside_the_range(pkg):
+    """-> (scenario, the third record's range, the limit).  The place is searched for along a meridian: the aircraft sits
+    still, so what its halves decode to is known in advance."""
+    a = 0xA00071
+    for k in range(100000):
+        lat, lon = 52.3 + 1e-5 * k, 4.5
+        ye, xe = ip.cpr_encode(lat, lon, 0)
+        yo, xo = ip.cpr_encode(lat, lon, 1)
+        ranges, ok = [], True
+        for fflag in (1, 0):  # the pair's decode is the odd half's, the late half's its own
+            p = ip.decode_airborne(ye, xe, yo, xo, fflag)[1:]
+            rng = ip.greatcircle(HOME["lat"], HOME["lon"], *p)
+            ok = ok and edge_distance_ok(ir.get_bearing(HOME["lat"], HOME["lon"], *p))
+            ranges.append(rng)
+        frac = ranges[1] - math.floor(ranges[1])
+        if ok and 0.45 <= frac <= 0.55 and abs(ranges[0] - ir.c_round(ranges[0])) >= 0.35:  # the pair's own margin stays larger
+            break
+    else:
+        raise AssertionError("no such place")
+    limit = ranges[1] + 0.3
+    b = Builder(pkg)
+    pair(b, T0, a, lat, lon)
+    steps = [b.step(), ("set_receiver", 0, dict(HOME, max_range_m=limit))]
+    b.pos(T0 + 11400, a, lat, lon, 0)
+    steps += [b.step()]
+    return ([HOME], 0, steps, True), ranges[1], limit
+
+
+def edge_distance_ok(bearing):
+    return ir.edge_distance(bearing) >= 10 * BEARING_MARGIN
+
+
+def below_one_metre(pkg, polar=True):
+    """13. An aircraft 0.4 m from the receiver: the receiver is put 0.4 m south of where the pair decodes.  The range is
+    0 m, and below 1 m the bearing says nothing: the bearing margin is reported as 0, which is why this scenario is not
+    one of those the device is held to (the contract covers streams whose margins stay above its figures)."""
+    a, lat, lon = 0xA00081, 52.3, 4.5
+    ye, xe = ip.cpr_encode(lat, lon, 0)
+    yo, xo = ip.cpr_encode(lat, lon, 1)
+    plat, plon = ip.decode_airborne(ye, xe, yo, xo, 1)[1:]
+    b = Builder(pkg)
+    pair(b, T0, a, lat, lon)
+    return [dict(lat=plat - 0.4 / M_PER_DEG, lon=plon, latlon_valid=1)], 0, [b.step()], polar
 
 
 def bucket_wrap(pkg):
@@ -415,6 +466,9 @@ def known_answers(name, seen):
         assert seen[4][1] == [] and seen[4][0] == seen[3][0]                              # everything gone but the arrays
         assert seen[5][0] == [((0,) * 72, 0, 0, 0)] and seen[5][1] == []                  # reset
         assert seen[6][0][0][3] == 1 and seen[6][1][0] > 0                                # still enabled
+    elif name == "limit_beside_the_range":
+        assert seen[0][0][0][3] == 1 and seen[2][0][0][3] == 2 and seen[2][2][0][:2] == (1, 1)   # the late half: aircraft-relative
+        assert seen[2][0][0][1] == max(seen[0][1][0], seen[2][1][0])                             # within the limit: it counts
     elif name == "contention":
         (row,), dist = seen[0][0], seen[0][1]
         assert row[3] == 3584 and len(dist) == 512 and nonzero(row) == [max(dist)] and row[1] == max(dist)

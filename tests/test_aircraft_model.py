@@ -10,6 +10,8 @@ import pytest
 
 import aircraft_streams as acs
 import pos_streams as ps
+import range_streams as rs
+import whole_stack as ws
 
 
 @pytest.fixture(scope="module")
@@ -86,7 +88,8 @@ def test_cutting_does_not_matter(pkg, mixed, pieces):
     assert csnaps[-1].tobytes() == snaps[-1].tobytes()
 
 
-@pytest.mark.parametrize("name", ["gate_countdown", "derived_geom", "nic_relative_minimum", "heading_hrd_tah"])
+@pytest.mark.parametrize("name", ["gate_countdown", "derived_geom", "nic_relative_minimum", "heading_hrd_tah", "refusals",
+                                  "combine_single_source"])
 def test_cutting_does_not_matter_in_scenarios(pkg, scen, name):
     receivers, fp, steps, _ = scen[name]
     whole = twin(pkg, receivers, fp, steps)
@@ -94,6 +97,62 @@ def test_cutting_does_not_matter_in_scenarios(pkg, scen, name):
         cut = twin(pkg, receivers, fp, steps, pieces=pieces)
         assert cut[0].tobytes() == whole[0].tobytes() and cut[1].tobytes() == whole[1].tobytes()
         assert [s.tobytes() for s in cut[2]] == [s.tobytes() for s in whole[2]]
+
+
+# ---- the drawn stream through everything at once (whole_stack.py) ----
+@pytest.fixture(scope="module")
+def drawn(pkg):
+    receivers, m, f, r = acs.random_stream(pkg)
+    steps, now = ws.steps_of(m, f, r)
+    t = ws.tracker(pkg, receivers, True)
+    host = ws.run_library(t, steps, now)
+    t.close()
+    return receivers, (m, f, r), steps, now, host
+
+
+def test_drawn_stream_is_what_it_says(pkg, drawn):
+    receivers, (m, f, r), steps, now, host = drawn
+    tracked = (m["msgtype"] != 32) & (f["addr"] != 0)
+    assert len(m) == 4000 and len(receivers) == 3 and set(r.tolist()) == {0, 1, 2}
+    assert len(host["obs"][-1]["snap_raw"]) == 48 and len(set(f["addr"][tracked].tolist())) == 48
+    assert sorted(set(f["source"][tracked].tolist())) == list(range(8))
+    t = m["sysTimestampMsg"].astype(np.int64)
+    behind = np.maximum.accumulate(t) - t
+    assert 300 <= int((behind[tracked] > 400).sum()) <= 500 and 80000 < int(behind.max()) <= 90040  # one in ten, up to 90 s
+    assert int((m["msgtype"] == 32).sum()) > 100 and int((m["msgtype"] == 11).sum()) > 50 and int((f["addr"] == 0).sum()) > 20
+    # no gate, range or bearing where two libms could part, on the host object, with the figures of the range's tests
+    assert host["stats"]["min_gate_margin_m"] >= rs.GATE_MARGIN
+    assert host["margins"]["min_range_margin_m"] >= rs.RANGE_MARGIN and host["margins"]["min_bearing_margin_deg"] >= rs.BEARING_MARGIN
+    assert host["pb_margin"] >= pkg.capi.PB_RSSI_MARGIN_ULPS
+    # and the stream reaches the outputs: positions of every kind, hits, verdicts both ways, distances, text
+    st = host["stats"]
+    assert st["cpr_global_ok"] > 200 and st["cpr_local_aircraft_relative"] > 100 and st["cpr_global_bad"] > 10
+    assert int(host["nic"]["set"].sum()) > 400
+    hits = host["obs"][-1]["hits_raw"]
+    assert int(hits["mode_a_hit"].sum()) >= 3
+    assert 400 < int((host["fwd"] & 1).sum()) < 3600
+    assert sum(1 for d in host["obs"][-1]["range"][1] if d) >= 10 and all(row[3] > 50 for row in host["obs"][-1]["range"][0])
+    assert len(host["sbs_wire"][0]) > 100000 and all(len(x) > 200 for x in host["pb"]) and all(len(x) > 200 for x in host["vrs"])
+
+
+def test_drawn_stream_equals_the_second_readings(pkg, drawn):
+    """Rows, NIC / Rc, every step's snapshot, hits and codes, the verdicts and the reduced stream, the SBS rows and lines,
+    the range after every step, aircraft.pb with distances, the polar range and the VRS list: the host object's against
+    the second readings'.  The second reading of the table counts accept_data's verdicts: every member is accepted and
+    refused at least RANDOM_MIN times, so no member's rule can hide."""
+    receivers, _, steps, now, host = drawn
+    counting = ws.run_models(pkg, receivers, steps, now, host)
+    counts = {k: (counting.accepted.get(k, 0), counting.refused.get(k, 0)) for k in pkg.capi.AC_MEMBERS}
+    print("accepted, refused:", counts)
+    assert all(min(v) >= acs.RANDOM_MIN for v in counts.values()), {k: v for k, v in counts.items() if min(v) < acs.RANDOM_MIN}
+
+
+@pytest.mark.parametrize("pieces", [1, 64, 97])
+def test_drawn_stream_cut_into_calls(pkg, drawn, pieces):
+    receivers, _, steps, now, host = drawn
+    t = ws.tracker(pkg, receivers, True)
+    ws.same_bytes(ws.run_library(t, steps, now, pieces), host)
+    t.close()
 
 
 def test_positions_of_a_table_tracker_are_a_table_less_trackers(pkg):

@@ -14,6 +14,8 @@ import pytest
 import aircraft_streams as acs
 import indep_positions as ip
 import pos_streams as ps
+import range_streams as rs
+import whole_stack as ws
 
 pytestmark = pytest.mark.gpu
 T0 = ps.T0
@@ -55,8 +57,11 @@ def mixed(pkg):
 # ---- the rules ----
 @pytest.mark.parametrize("name", acs.NAMES)
 def test_scenario(pkg, torch_cuda, scen, name):
-    receivers, fp, steps, _ = scen[name]
-    same(run(pkg, False, 1024, receivers, fp, steps), run(pkg, True, 1024, receivers, fp, steps))
+    receivers, fp, steps, check = scen[name]
+    got = run(pkg, False, 1024, receivers, fp, steps)
+    same(got, run(pkg, True, 1024, receivers, fp, steps))
+    # the device's own result against the answer derived by hand: a rule wrong in the shared header fails here too
+    check([{int(e["addr"]): e for e in s} for s in got[2]], [(int(q["nic"]), int(q["rc"]), int(q["set"])) for q in got[1]])
 
 
 def test_mixed_stream(pkg, torch_cuda, mixed):
@@ -70,6 +75,38 @@ def test_cutting(pkg, torch_cuda, mixed, pieces):
     receivers, steps, want = mixed
     got = run(pkg, False, 1024, receivers, 0, steps, pieces, every_step=False)
     same(got, want)
+
+
+# ---- the drawn stream through everything at once (whole_stack.py): table, Mode A/C, verdicts, SBS, aircraft.pb, VRS, range ----
+@pytest.fixture(scope="module")
+def drawn(pkg):
+    receivers, m, f, r = acs.random_stream(pkg)
+    steps, now = ws.steps_of(m, f, r)
+    t = ws.tracker(pkg, receivers, True)
+    host = ws.run_library(t, steps, now)
+    t.close()
+    assert host["stats"]["min_gate_margin_m"] >= rs.GATE_MARGIN and host["pb_margin"] >= pkg.capi.PB_RSSI_MARGIN_ULPS
+    assert host["margins"]["min_range_margin_m"] >= rs.RANGE_MARGIN and host["margins"]["min_bearing_margin_deg"] >= rs.BEARING_MARGIN
+    return receivers, steps, now, host
+
+
+def test_drawn_stream(pkg, torch_cuda, drawn):
+    """Every byte the device delivers is the host object's, and after the last step equal to the second readings'."""
+    receivers, steps, now, host = drawn
+    t = ws.tracker(pkg, receivers, False)
+    got = ws.run_library(t, steps, now)
+    t.close()
+    ws.same_bytes(got, host)
+    ws.run_models(pkg, receivers, steps, now, got, margins=False)
+
+
+@pytest.mark.parametrize("pieces", [1, 64, 97])
+def test_drawn_stream_cut_into_calls(pkg, torch_cuda, drawn, pieces):
+    receivers, steps, now, host = drawn
+    t = ws.tracker(pkg, receivers, False)
+    got = ws.run_library(t, steps, now, pieces)
+    t.close()
+    ws.same_bytes(got, host)
 
 
 # ---- shapes of the walk ----

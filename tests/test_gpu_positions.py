@@ -138,10 +138,14 @@ def test_expiry_scenario(pkg, torch_cuda):
 
 
 @pytest.mark.parametrize("name", ["surface_windows", "global_failure", "receiver_relative", "speed_check", "backwards",
-                                  "clock_from_zero", "type_and_source_mismatch"])
+                                  "clock_from_zero", "type_and_source_mismatch", "refusals", "surface_speed_check",
+                                  "surface_movement_codes", "global_max_range", "negative_max_range",
+                                  "higher_source_skips_speed_check", "reliable_sides", "odd_latitude_alone_out_of_range"])
 def test_scenarios(pkg, torch_cuda, name):
     receivers, fp, steps = ps.scenarios(pkg)[name]
-    both(pkg, receivers, fp, steps)
+    g, st = both(pkg, receivers, fp, steps)
+    if name == "refusals" or name in ps.KNOWN:  # the device's own rows against the answers derived by hand
+        ps.known(name, g, st)
 
 
 def test_cutting_invariance(pkg, torch_cuda, mixed):

@@ -17,7 +17,13 @@ def scen(pkg):
 
 
 NAMES = ["pair_10s", "clock_from_zero", "surface_windows", "surface_version_and_no_reference", "type_and_source_mismatch",
-         "global_failure", "aircraft_relative", "receiver_relative", "speed_check", "backwards", "expiry_and_ttl"]
+         "global_failure", "aircraft_relative", "receiver_relative", "speed_check", "backwards", "expiry_and_ttl",
+         "refusals", "surface_speed_check", "surface_movement_codes", "global_max_range", "negative_max_range",
+         "higher_source_skips_speed_check", "reliable_sides", "odd_latitude_alone_out_of_range"]
+
+
+def test_scenario_list_is_complete(scen):
+    assert sorted(scen) == sorted(NAMES)
 
 
 def twin_run(pkg, receivers, fp, steps, pieces=None):
@@ -77,6 +83,33 @@ def test_the_scenarios_reach_what_they_are_named_for(pkg, scen):
     assert r == [-1, 0, -3, 0, -2] and st["cpr_global_skipped"] == 1 and st["cpr_global_bad"] == 0
     r, out, st = results(pkg, scen, "expiry_and_ttl")
     assert r == [-1, 0, -1, -3, -3] + [1, 0, -1] + [-1] and st["aircraft"] == 1
+    for name in ["refusals"] + sorted(ps.KNOWN):
+        r, out, st = results(pkg, scen, name)
+        ps.known(name, out, st)
+    r, out, st = results(pkg, scen, "refusals")
+    assert r == [x for case in ps.REFUSAL_RESULTS for x in case]
+    assert st["cpr_local_receiver_relative"] == 5 and st["cpr_local_aircraft_relative"] == 1 and st["cpr_global_skipped"] == 1
+    assert st["cpr_global_ok"] == 1 and st["cpr_local_speed_checks"] == 0 and st["cpr_local_range_checks"] == 0
+    r, out, st = results(pkg, scen, "surface_speed_check")
+    #           no speed: 1800 m, 2350 m    24 kt: 850 m, 1350 m
+    assert r == [-1, 0, 1] + [-1, 0, -1] + [-1, 0, 1] + [-1, 0, -1] and st["cpr_local_speed_checks"] == 2 and st["cpr_surface"] == 12
+    assert abs(out["lat"][2] - (52.3 + 1800.0 / ps.M_PER_DEG)) < 1e-4 and abs(out["lat"][8] - (52.3 + 850.0 / ps.M_PER_DEG)) < 1e-4
+    r, out, st = results(pkg, scen, "surface_movement_codes")
+    assert r == [-1, -1] * 6 + [-1, 0] * 2 and st["cpr_global_ok"] == 2
+    r, out, st = results(pkg, scen, "global_max_range")
+    #           no location    190 NM   40 NM
+    assert r == [-1, 0] + [-1, -2] + [2, 0] and st["cpr_global_range_checks"] == 1 and st["cpr_local_range_checks"] == 1
+    assert abs(out["lat"][1] - 53.0) < 1e-4 and abs(out["lon"][1] - 9.0) < 1e-4
+    r, out, st = results(pkg, scen, "negative_max_range")
+    assert r == [2] and st["cpr_local_range_checks"] == 0 and abs(out["lat"][0] - 52.5) < 1e-4 and abs(out["lon"][0] - 5.0) < 1e-4
+    r, out, st = results(pkg, scen, "higher_source_skips_speed_check")
+    assert r == [-1, 0, -1, 0] + [-1, 0, -1, -2] + [-1, 0, 1] + [-1, 0, -1]
+    assert st["cpr_global_speed_checks"] == 1 and st["cpr_local_speed_checks"] == 1 and st["cpr_local_range_checks"] == 2
+    assert abs(out["lat"][3] - 52.0) < 1e-4 and abs(out["lat"][10] - 50.5) < 1e-4
+    r, out, st = results(pkg, scen, "reliable_sides")
+    assert r == [-1, 0, 0, 0, -2] + [-1, 0, 0, 0, 0, -2] and st["cpr_global_bad"] == 2
+    r, out, st = results(pkg, scen, "odd_latitude_alone_out_of_range")
+    assert r == [-1, -2, -1, -2] and st["cpr_global_bad"] == 2 and st["cpr_global_range_checks"] == 0 and st["cpr_global_speed_checks"] == 0
     # the aircraft alive after each step: the one-message aircraft leaves after more than 60 s, the other after 10 min
     receivers, fp, steps = scen["expiry_and_ttl"]
     t = pkg.capi.PositionTracker(capacity=64, receivers=receivers, host=True)
@@ -86,6 +119,21 @@ def test_the_scenarios_reach_what_they_are_named_for(pkg, scen):
         alive.append(t.stats()["aircraft"])
     assert alive == [2, 2, 1, 1, 2, 1, 0, 0, 1]
     t.close()
+
+
+def test_create_refuses_every_configuration_the_check_names(pkg):
+    """msd_pos_config_ok: a capacity below 64, above 2^24 or not a power of two, no receiver or more than 65536, a
+    negative --filter-persistence, no configuration at all; and the bounds themselves are accepted"""
+    import ctypes as C
+    make = lambda **kw: pkg.capi.PositionTracker(host=True, **kw)  # noqa: E731
+    for kw in (dict(capacity=32), dict(capacity=1 << 25), dict(capacity=96), dict(capacity=64, receivers=[]),
+               dict(capacity=64, receivers=[None] * 65537), dict(capacity=64, filter_persistence=-1)):
+        with pytest.raises(pkg.MsdError):
+            make(**kw)
+    h = C.c_void_p()
+    assert pkg.capi._pos_lib(True)[1]["create"](None, C.byref(h)) == -22 and not h.value  # -EINVAL
+    for kw in (dict(capacity=64), dict(capacity=1 << 24, receivers=[None] * 65536)):
+        make(**kw).close()
 
 
 def test_margin_is_reported_and_resets(pkg, scen):

@@ -11,7 +11,7 @@ import indep_range as ir
 import range_streams as rs
 
 NAMES = ["one_pair", "no_location", "non_adsb", "relative_0_0", "longest_no_limit", "longest_limit", "three_receivers",
-         "three_receivers_no_polar", "out_and_back", "chain", "contention"]
+         "three_receivers_no_polar", "out_and_back", "chain", "contention", "limit_beside_the_range"]
 
 
 def host_tracker(pkg, scenario, capacity=1024, table=False):
@@ -51,6 +51,48 @@ def test_bucket_wrap_and_bucket_edge(pkg):
     assert aimed[0][0] < 2.5 and aimed[1][0] > 357.5 and 0.02 <= aimed[3][0] - aimed[2][0] <= 0.025
     polar = rows[0][0]
     assert sorted(k for k, v in enumerate(polar) if v) == [0, 18, 19] and rows[0][3] == 4
+
+
+def test_the_limit_beside_the_range_is_the_margin(pkg):
+    scenario, rng, limit = rs.limit_beside_the_range(pkg)
+    t = host_tracker(pkg, scenario)
+    rs.run(t, scenario[2])
+    m = assert_margins(t)
+    assert abs(m["min_range_margin_m"] - 0.3) < 1e-6 and 0.45 <= rng - math.floor(rng) <= 0.55 and limit - rng == m["min_range_margin_m"]
+    t.close()
+
+
+@pytest.mark.parametrize("polar", [True, False])
+def test_a_range_below_one_metre(pkg, polar):
+    """0.4 m from the receiver: distance 0, evaluated, and with the polar range a bearing margin of 0 -- the host object
+    says itself that the bucket of such a position is not covered by the contract; without it there is no bearing."""
+    scenario = rs.below_one_metre(pkg, polar)
+    t, m = host_tracker(pkg, scenario), rs.model(scenario)
+    got, want = rs.run(t, scenario[2]), rs.run(m, scenario[2])
+    assert got == want and t.range_margins() == m.range_margins()
+    (row,), (d,) = got[-1][0], got[-1][1]
+    assert d == 0 and row[1] == 0 and row[3] == 1 and not any(row[0])
+    margins = t.range_margins()
+    assert abs(margins["min_range_margin_m"] - 0.4) < 1e-3
+    assert margins["min_bearing_margin_deg"] == (0.0 if polar else math.inf)
+    assert t.stats()["min_gate_margin_m"] >= rs.GATE_MARGIN
+    t.close()
+
+
+def test_a_range_that_is_not_a_number(pkg):
+    """A receiver whose latitude is not a number: greatcircle gives NaN, which compares false in update_polar_range's two
+    tests (track.c:290, :302) -- the record is evaluated, the distance is 0, nothing becomes the longest -- and the host
+    object reports a range margin of 0: such a stream is outside the contract.  Host object only: the reference's
+    (uint32_t) of a NaN is undefined, so there is no second reading, and the device is not held to it."""
+    b = rs.Builder(pkg)
+    rs.pair(b, rs.T0, 0xA00091, 52.3, 4.5)
+    t = pkg.capi.PositionTracker(capacity=64, receivers=[dict(lat=math.nan, lon=4.0, latlon_valid=1)], host=True, range=True, polar=False)
+    out = t.update(*b.step()[1:])
+    assert [int(x) for x in out["result"]] == [-1, 0]
+    (row,) = rs.read_rows(t.range_read())
+    assert row == ((0,) * 72, 0, 0, 1) and list(t.range_distances()) == [0]
+    assert t.range_margins()["min_range_margin_m"] == 0.0
+    t.close()
 
 
 def test_cut_into_single_records(pkg):
