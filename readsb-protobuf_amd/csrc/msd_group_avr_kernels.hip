@@ -1,8 +1,9 @@
 /*
  * msd_group_avr_kernels.hip -- AVR raw text input for every receiver of a group call at once (msd_group_accept_avr;
- * DESIGN.md 4.9, "AVR text input per receiver").  The framing rule is the one of msd_avr_kernels.hip: a
- * line's start is a pure function of the MSD_AVR_LINE_MAX + 1 bytes in front of its '\n'.  Here a piece holds one
- * segment per entry, each starting on a span boundary, so a span and its '\n' belong to one receiver:
+ * DESIGN.md 4.9, "AVR text input per receiver").  The framing rule is the stream input's, from the one
+ * place that holds it for both, msd_avr_impl.h: a line's start is a pure function of the MSD_AVR_LINE_MAX + 1 bytes in
+ * front of its '\n'.  Here a piece holds one segment per entry, each starting on a span boundary, so a span and its '\n'
+ * belong to one receiver:
  *   msd_ga_layout_kernel  the piece: every segment's kept line, then its new bytes.
  *   msd_ga_count_kernel   one workgroup per span.  The window of msd_avr_count_kernel, with the look-back clipped at the
  *                         entry's s0 and nothing at or behind its s1; the discard flag is the entry's own.  Leaves the
@@ -13,12 +14,12 @@
  *   msd_ga_end_kernel     one wavefront per entry: the bytes behind its last '\n' to keep, or the discard flag.
  *   msd_ga_decode_kernel  the class of every record as msd_fr_records_decode_kernel classes it, one workgroup per span
  *                         with the entry's repair level and Mode A/C switch, counters in the entry's row.
- * The filter stage behind them is the Beast input's (msd_gb_launch_filter_records).  Window, the mask searches, line_at,
- * block_scan, hexval and put_record are msd_avr_kernels.hip's, line for line: that file's are in its unnamed namespace,
- * and it stays as it is.  The number of launches does not depend on the number of entries.
+ * The filter stage behind them is the Beast input's (msd_gb_launch_filter_records).  The number of launches
+ * does not depend on the number of entries.
  */
 #include <hip/hip_runtime.h>
 
+#include "msd_avr_impl.h"
 #include "msd_frames_impl.h"
 #include "msd_group_avr.h"
 
@@ -26,205 +27,7 @@ namespace {
 
 constexpr uint32_t CW = MSD_FR_CTR_WORDS;
 constexpr uint32_t LM = MSD_AVR_LINE_MAX;
-constexpr uint32_t AT = 256;                /* threads */
-constexpr uint32_t SPAN = MSD_AVR_SPAN;     /* bytes whose '\n' a workgroup owns */
-constexpr uint32_t LB = MSD_AVR_LOOKBACK;   /* bytes in front of them it classifies as well */
-constexpr uint32_t WIN = LB + SPAN;         /* the window, in LDS */
-constexpr uint32_t NW = WIN / 64;           /* mask words */
-constexpr uint32_t PER = SPAN / AT;         /* bytes whose '\n' a thread owns */
-constexpr int REACH = (int)MSD_AVR_LINE_MAX + 1; /* bytes in front of a '\n' that decide where its line starts */
-constexpr uint32_t MIN_LINE = 7;            /* "*XXXX;" and its '\n': the shortest line that yields a record */
-constexpr uint32_t MAX_RECS = 3;            /* ... so a thread's bytes end at most this many of them */
-static_assert(LB % 64 == 0 && LB >= (uint32_t)REACH, "the window must hold every byte a line start depends on");
-static_assert(SPAN % 64 == 0 && 64 % PER == 0 && PER <= 32, "a thread's bytes lie in one mask word");
-static_assert((PER - 1) / MIN_LINE + 1 <= MAX_RECS, "records per thread");
 static_assert(AT == (uint32_t)NT && SPAN == FT, "one workgroup per span, a span a tile of the filter stage");
-
-enum { L_LONG = 0, L_DROP = 1, L_REC = 2 };
-
-struct Window {
-    uint64_t nl[NW + 1], ws[NW + 1], nul[NW + 1], hex[NW + 1]; /* one word more, zero: two-word reads need no bound */
-    uint8_t ch[WIN];
-};
-
-/* bits [0, top] of a word */
-__device__ __forceinline__ uint64_t upto(int top)
-{
-    return (2ull << top) - 1ull;
-}
-
-/* the highest position in [lo, hi) whose bit is set (INV: clear), -1 if none */
-template <bool INV> __device__ int last_in(const uint64_t *m, int lo, int hi)
-{
-    if (hi <= lo)
-        return -1;
-    int k = (hi - 1) >> 6;
-    const int k0 = lo >> 6;
-    uint64_t w = (INV ? ~m[k] : m[k]) & upto((hi - 1) & 63);
-    for (;;) {
-        if (k == k0)
-            w &= ~0ull << (lo & 63);
-        if (w)
-            return k * 64 + 63 - __clzll((long long)w);
-        if (k == k0)
-            return -1;
-        --k;
-        w = INV ? ~m[k] : m[k];
-    }
-}
-
-/* the lowest such position */
-template <bool INV> __device__ int first_in(const uint64_t *m, int lo, int hi)
-{
-    if (hi <= lo)
-        return -1;
-    int k = lo >> 6;
-    const int k1 = (hi - 1) >> 6;
-    uint64_t w = (INV ? ~m[k] : m[k]) & (~0ull << (lo & 63));
-    for (;;) {
-        if (k == k1)
-            w &= upto((hi - 1) & 63);
-        if (w)
-            return k * 64 + __ffsll((unsigned long long)w) - 1;
-        if (k == k1)
-            return -1;
-        ++k;
-        w = INV ? ~m[k] : m[k];
-    }
-}
-
-/* cnt <= 32 mask bits from position start on */
-__device__ __forceinline__ uint32_t bits_at(const uint64_t *m, int start, int cnt)
-{
-    const int k = start >> 6, o = start & 63;
-    uint64_t v = m[k] >> o;
-    if (o)
-        v |= m[k + 1] << (64 - o);
-    return (uint32_t)v & (uint32_t)((1ull << cnt) - 1ull);
-}
-
-/* The line that the '\n' at window position r ends.  rmin: the window position of the piece's first byte.  For a line
- * that yields a record: a = where its text starts, skip = prefix and timestamp / signal digits, plen = payload digits. */
-__device__ int line_at(const Window &W, int r, int rmin, bool discard, int mode_ac, int &a, int &skip, int &plen)
-{
-    const bool reach = r - REACH >= rmin; /* REACH bytes of the piece lie in front of the '\n' */
-    const int j = last_in<false>(W.nl, reach ? r - REACH : rmin, r);
-    int s;
-    if (j >= 0)
-        s = j + 1;
-    else if (reach || discard) /* more than MSD_AVR_LINE_MAX bytes, in this piece or counting the ones before it */
-        return L_LONG;
-    else
-        s = rmin;
-    const int z = first_in<false>(W.nul, s, r);
-    const int e = z < 0 ? r : z; /* strlen */
-    const int bl = last_in<true>(W.ws, s, e);
-    if (bl < 0)
-        return L_DROP; /* empty, or white space only */
-    const int b = bl + 1;
-    a = first_in<true>(W.ws, s, b);
-    const int l = b - a;
-    if (W.ch[b - 1] != ';')
-        return L_DROP;
-    switch (W.ch[a]) {
-    case '<': skip = 15; break;
-    case '@':
-    case '%': skip = 13; break;
-    case '*':
-    case ':': skip = 1; break;
-    default: return L_DROP;
-    }
-    if (l < skip + 1)
-        return L_DROP;
-    plen = l - skip - 1;
-    if (plen != 4 && plen != 14 && plen != 28)
-        return L_DROP;
-    if (plen == 4 && !mode_ac)
-        return L_DROP;
-    if (bits_at(W.hex, a + skip, plen) != (uint32_t)((1ull << plen) - 1ull))
-        return L_DROP;
-    return L_REC;
-}
-
-/* the '\n' among the calling thread's bytes, bit i for window position first + i */
-__device__ __forceinline__ uint32_t my_newlines(const Window &W, int &first)
-{
-    const uint32_t off = threadIdx.x * PER;
-    first = (int)(LB + off);
-    return (uint32_t)(W.nl[(LB + off) >> 6] >> (off & 63u)) & ((1u << PER) - 1u);
-}
-
-/* exclusive prefix of v over the workgroup's 256 threads, and the total; `part`: 4 words of LDS */
-__device__ inline uint32_t block_scan(uint32_t v, uint32_t *part, uint32_t &total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d)
-            incl += up;
-    }
-    __syncthreads(); /* part may still be read from the call before */
-    if (lane == 63)
-        part[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4; ++w)
-        before += w < wave ? part[w] : 0u;
-    total = part[0] + part[1] + part[2] + part[3];
-    return before + incl - v;
-}
-
-/* hexval of msd_wire.c: -1 for anything else */
-__device__ __forceinline__ int hexval(uint32_t c)
-{
-    if (c - '0' < 10u)
-        return (int)(c - '0');
-    if ((c | 0x20u) - 'a' < 6u)
-        return (int)((c | 0x20u) - 'a') + 10;
-    return -1;
-}
-
-/* the record of the line whose text starts at window position a (msd_avr_parse_line behind its checks) */
-__device__ void put_record(const Window &W, int a, int skip, int plen, int keep_timestamp, msd_message &o)
-{
-    uint64_t ts = 0;
-    double level = 0.0;
-    if (skip > 1) {
-        if (bits_at(W.hex, a + 1, 12) == 0xfffu) /* a digit that is none: 0 */
-            for (int i = 1; i < 13; ++i)
-                ts = (ts << 4) | (uint64_t)hexval(W.ch[a + i]);
-        if (skip == 15) {
-            const int hi = hexval(W.ch[a + 13]), lo = hexval(W.ch[a + 14]);
-            level = (double)((hi * 16) | lo) / 255.0; /* net_io.c:1690-1691, whatever the digits are */
-            level *= level;
-        }
-    }
-    msd_message m;
-    m.timestampMsg = keep_timestamp ? ts : 0;
-    m.sysTimestampMsg = 0;
-    m.signalLevel = level;
-    m.addr = 0;
-    m.crc = 0;
-    m.score = 0;
-    m.msgtype = 0;
-    m.msgbits = (uint8_t)(4 * plen);
-    m.correctedbits = 0;
-    m.bestphase = 0;
-    const int p = a + skip;
-#pragma unroll
-    for (int j = 0; j < 14; ++j) {
-        uint8_t v = 0;
-        if (2 * j < plen)
-            v = (uint8_t)((hexval(W.ch[p + 2 * j]) << 4) | hexval(W.ch[p + 2 * j + 1]));
-        m.msg[j] = v;
-    }
-    m.iid = 0;
-    m.pad = 0;
-    o = m;
-}
 
 /* the piece: every segment's kept line, then its new bytes; one workgroup per span */
 __global__ void __launch_bounds__(AT) msd_ga_layout_kernel(const uint8_t *src, const msd_gb_entry *ent,
@@ -240,32 +43,19 @@ __global__ void __launch_bounds__(AT) msd_ga_layout_kernel(const uint8_t *src, c
     }
 }
 
-/* Window position r is piece position base + r.  Only bytes of the segment [s0, s1) get a class: the look-back of a
- * segment's first span is empty, and neither a '\n' nor text exists at or behind s1. */
-__device__ void classify(Window &W, const uint8_t *buf, uint32_t s0, uint32_t s1, int32_t base)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t c = wave; c < NW; c += AT / 64) {
-        const int32_t p = base + (int32_t)(c * 64 + lane);
+/* an entry's bytes for classify.  Only bytes of the segment [s0, s1) get a class: the look-back of a segment's first
+ * span is empty, and neither a '\n' nor text exists at or behind s1. */
+struct Segment {
+    const uint8_t *buf;
+    uint32_t s0, s1;
+    __device__ __forceinline__ uint32_t operator()(int32_t p) const
+    {
         uint32_t ch = 0xffu;
         if (p >= (int32_t)s0 && (uint32_t)p < s1)
             ch = buf[p];
-        W.ch[c * 64 + lane] = (uint8_t)ch;
-        const uint64_t m_nl = __ballot(ch == '\n');
-        const uint64_t m_ws = __ballot(ch == ' ' || ch - 9u <= 4u); /* space, 0x09..0x0D */
-        const uint64_t m_nul = __ballot(ch == 0u);
-        const uint64_t m_hex = __ballot(ch - '0' < 10u || (ch | 0x20u) - 'a' < 6u);
-        if (lane == 0) {
-            W.nl[c] = m_nl;
-            W.ws[c] = m_ws;
-            W.nul[c] = m_nul;
-            W.hex[c] = m_hex;
-        }
+        return ch;
     }
-    if (threadIdx.x == 0)
-        W.nl[NW] = W.ws[NW] = W.nul[NW] = W.hex[NW] = 0;
-    __syncthreads();
-}
+};
 
 /* the window of span t of entry E: its base, and the window position of the segment's first byte */
 __device__ __forceinline__ void span_window(uint32_t t, const msd_gb_entry &E, int32_t &base, int &rmin)
@@ -287,27 +77,15 @@ __global__ void __launch_bounds__(AT) msd_ga_count_kernel(const uint8_t *buf, co
     span_window(blockIdx.x, E, base, rmin);
     if (threadIdx.x < 4)
         tot[threadIdx.x] = 0;
-    classify(W, buf, E.s0, E.s1, base);
+    classify(W, Segment{buf, E.s0, E.s1}, base);
     const bool discard = (E.opt & MSD_GA_OPT_DISCARD) != 0;
     const int mode_ac = (E.opt & MSD_GB_OPT_MODEAC) ? 1 : 0;
-    int first;
-    uint32_t mine = my_newlines(W, first);
-    uint32_t c[3] = {0, 0, 0}, nlines = 0;
-    while (mine) {
-        const int bit = __ffs(mine) - 1;
-        mine &= mine - 1u;
-        int a, skip, plen;
-        const int kind = line_at(W, first + bit, rmin, discard, mode_ac, a, skip, plen);
-        c[0] += kind == L_LONG;
-        c[1] += kind == L_DROP;
-        c[2] += kind == L_REC;
-        ++nlines;
-    }
-    if (nlines) {
-        atomicAdd(&tot[3], nlines);
+    const Lines c = count_lines(W, base, rmin, discard, mode_ac); /* (c.end has no use here) */
+    if (c.n) {
+        atomicAdd(&tot[3], c.n);
         for (int k = 0; k < 3; ++k)
-            if (c[k])
-                atomicAdd(&tot[k], c[k]);
+            if (c.kind[k])
+                atomicAdd(&tot[k], c.kind[k]);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -328,41 +106,25 @@ __global__ void __launch_bounds__(AT) msd_ga_store_kernel(const uint8_t *buf, co
                                                          msd_message *rec, uint32_t *nodes)
 {
     __shared__ Window W;
-    __shared__ uint32_t part[4];
+    __shared__ uint32_t part[AT / 64];
     if (cnt[blockIdx.x + 1] == cnt[blockIdx.x]) /* no record ends here */
         return;
     const msd_gb_entry E = ent[tile_ent[blockIdx.x]];
     int32_t base;
     int rmin;
     span_window(blockIdx.x, E, base, rmin);
-    classify(W, buf, E.s0, E.s1, base);
+    classify(W, Segment{buf, E.s0, E.s1}, base);
     const bool discard = (E.opt & MSD_GA_OPT_DISCARD) != 0;
     const int mode_ac = (E.opt & MSD_GB_OPT_MODEAC) ? 1 : 0;
     const int keep = (E.opt & MSD_GA_OPT_KEEP_TS) ? 1 : 0;
-    int first;
-    uint32_t mine = my_newlines(W, first);
-    uint32_t d0 = 0, d1 = 0, d2 = 0, c = 0; /* a | skip << 16 | the '\n' among the thread's bytes << 20 | plen << 24 */
-    while (mine) {
-        const int bit = __ffs(mine) - 1;
-        mine &= mine - 1u;
-        int a, skip, plen;
-        if (line_at(W, first + bit, rmin, discard, mode_ac, a, skip, plen) != L_REC)
-            continue;
-        const uint32_t d = (uint32_t)a | ((uint32_t)skip << 16) | ((uint32_t)bit << 20) | ((uint32_t)plen << 24);
-        if (c == 0)
-            d0 = d;
-        else if (c == 1)
-            d1 = d;
-        else
-            d2 = d;
-        ++c;
-    }
+    const Records r = my_records(W, rmin, discard, mode_ac);
     uint32_t total;
-    const uint32_t rank = cnt[blockIdx.x] + block_scan(c, part, total);
-    for (uint32_t k = 0; k < c && k < MAX_RECS; ++k) {
-        const uint32_t d = k == 0 ? d0 : k == 1 ? d1 : d2;
-        put_record(W, (int)(d & 0xffffu), (int)((d >> 16) & 0xfu), (int)(d >> 24), keep, rec[rank + k]);
-        nodes[rank + k] = (uint32_t)(base + first + (int)((d >> 20) & 0xfu));
+    const uint32_t rank = cnt[blockIdx.x] + block_scan<AT>(r.n, part, total);
+#pragma unroll /* (three at most, as in msd_avr_store_kernel) */
+    for (uint32_t k = 0; k < r.n && k < MAX_RECS; ++k) {
+        const uint32_t d = r[k];
+        put_record(W, rec_a(d), rec_skip(d), rec_plen(d), keep, rec[rank + k]);
+        nodes[rank + k] = (uint32_t)(base + r.first + rec_bit(d));
     }
 }
 

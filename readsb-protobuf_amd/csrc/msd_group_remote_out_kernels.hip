@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(WT) msd_gro_len_kernel(const msd_message *out,
         lens[i] = (uint8_t)len;
     }
     uint32_t total;
-    (void)block_scan(len, part, total);
+    (void)block_scan<WT>(len, part, total);
     if (threadIdx.x == 0)
         block_sums[blockIdx.x] = total;
 }
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(WT) msd_gro_store_kernel(const msd_message *ou
     const bool mine = i < min(*count, bound);
     const uint32_t len = mine ? lens[i] : 0u;
     uint32_t total;
-    const uint32_t off = block_scan(len, part, total);
+    const uint32_t off = block_scan<WT>(len, part, total);
     uint8_t *dst = stream + block_off[blockIdx.x];
     if (mine) {
         starts[i] = block_off[blockIdx.x] + off;

@@ -57,7 +57,7 @@ __device__ __forceinline__ void tiled_store(uint32_t len, uint8_t *out, const ui
 {
     static_assert(WT == 2u * TILE, "a workgroup fills the image twice");
     uint32_t total;
-    const uint32_t off = block_scan(len, part, total);
+    const uint32_t off = block_scan<WT>(len, part, total);
     if (threadIdx.x == TILE)
         half = off; /* the bytes of the workgroup's first TILE items */
     __syncthreads();

@@ -79,8 +79,8 @@ msd_pb_len_kernel(msd_pb_call c, uint64_t *shadow, uint16_t *lens, uint32_t *wit
         lens[i] = (uint16_t)len;
     }
     uint32_t total, ctotal;
-    const uint32_t off = block_scan(len, part, total);
-    const uint32_t coff = block_scan(counts, part, ctotal);
+    const uint32_t off = block_scan<WT>(len, part, total);
+    const uint32_t coff = block_scan<WT>(counts, part, ctotal);
     if (i < c.nitems) {
         within[i] = off;
         cwithin[i] = coff;

@@ -29,7 +29,7 @@ msd_range_pb_len_kernel(const msd_range_state *rng, uint32_t n, uint8_t *lens, u
         lens[i] = (uint8_t)len;
     }
     uint32_t total;
-    (void)block_scan(len, part, total);
+    (void)block_scan<WT>(len, part, total);
     if (threadIdx.x == 0)
         block_sums[blockIdx.x] = total;
 }
@@ -43,7 +43,7 @@ msd_range_pb_store_kernel(const msd_range_state *rng, uint32_t n, const uint8_t 
     const uint32_t i = blockIdx.x * WT + threadIdx.x;
     const uint32_t len = i < n ? lens[i] : 0u;
     uint32_t total;
-    const uint32_t off = block_scan(len, part, total);
+    const uint32_t off = block_scan<WT>(len, part, total);
     uint8_t *dst = out + block_off[blockIdx.x];
     if (i < n) {
         const uint32_t r = i / MSD_RANGE_BUCKETS, b = i % MSD_RANGE_BUCKETS;

@@ -43,7 +43,7 @@ msd_sbs_len_kernel(const msd_message *msgs, const msd_fields *fields, const msd_
         lens[i] = (uint8_t)len;
     }
     uint32_t total;
-    (void)block_scan(len, part, total);
+    (void)block_scan<WT>(len, part, total);
     if (threadIdx.x == 0)
         block_sums[blockIdx.x] = total;
 }
@@ -57,7 +57,7 @@ msd_sbs_store_kernel(const msd_message *msgs, const msd_fields *fields, const ms
     const uint32_t i = blockIdx.x * WT + threadIdx.x;
     const uint32_t len = i < n ? lens[i] : 0u;
     uint32_t total;
-    const uint32_t off = block_scan(len, part, total);
+    const uint32_t off = block_scan<WT>(len, part, total);
     uint8_t *dst = out + block_off[blockIdx.x];
     if (i < n) {
         ends[i] = block_off[blockIdx.x] + off + len;

@@ -69,7 +69,7 @@ msd_vrs_select_kernel(msd_vrs_call c, uint16_t *lens, uint16_t *swithin, uint32_
         lens[i] = (uint16_t)len;
     }
     uint32_t total;
-    const uint32_t before = block_scan(selected, part, total);
+    const uint32_t before = block_scan<WT>(selected, part, total);
     if (i < c.nitems)
         swithin[i] = (uint16_t)before;
     if (threadIdx.x == 0)
@@ -104,7 +104,7 @@ msd_vrs_len_kernel(msd_vrs_call c, uint16_t *lens, const uint16_t *swithin, cons
         }
     }
     uint32_t total;
-    const uint32_t off = block_scan(len, part, total);
+    const uint32_t off = block_scan<WT>(len, part, total);
     if (i < c.nitems)
         within[i] = off;
     if (threadIdx.x == 0)

@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(WT) msd_wire_len_kernel(const msd_message *msg
         lens[i] = (uint8_t)len;
     }
     uint32_t total;
-    (void)block_scan(len, part, total);
+    (void)block_scan<WT>(len, part, total);
     if (threadIdx.x == 0)
         block_sums[blockIdx.x] = total;
 }
@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(WT) msd_wire_store_kernel(const msd_message *m
     const uint32_t i = blockIdx.x * WT + threadIdx.x;
     const uint32_t len = i < n ? lens[i] : 0u;
     uint32_t total;
-    const uint32_t off = block_scan(len, part, total);
+    const uint32_t off = block_scan<WT>(len, part, total);
     uint8_t *dst = out + block_off[blockIdx.x];
     if (i < n) {
         if (ends)
@@ -103,8 +103,8 @@ __global__ void __launch_bounds__(WT) msd_group_wire_count_kernel(const MsdResol
         fwd += len ? 1u : 0u;
     }
     uint32_t total_bytes, total_fwd;
-    (void)block_scan(bytes, part, total_bytes);
-    (void)block_scan(fwd, part, total_fwd);
+    (void)block_scan<WT>(bytes, part, total_bytes);
+    (void)block_scan<WT>(fwd, part, total_fwd);
     if (threadIdx.x == 0) {
         counts[2 * b] = total_bytes;
         counts[2 * b + 1] = total_fwd;
@@ -125,7 +125,7 @@ __global__ void __launch_bounds__(WT) msd_group_wire_kernel(const MsdResolvePara
     for (uint32_t i = threadIdx.x; i < b; i += WT)
         mine += (counts[2 * i] + 15u) & ~15u;
     uint32_t o;
-    (void)block_scan(mine, part, o);
+    (void)block_scan<WT>(mine, part, o);
     const uint32_t mybytes = counts[2 * b];
     const bool fits = (uint64_t)o + mybytes <= cap;
     if (threadIdx.x == 0) {
@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(WT) msd_group_wire_kernel(const MsdResolvePara
             len = msd_wire_length(src, format);
         }
         uint32_t total;
-        const uint32_t off = block_scan(len, part, total);
+        const uint32_t off = block_scan<WT>(len, part, total);
         uint8_t *dst = out + o + run;
         if (run + total > mybytes) /* (cannot happen: the counts come from the same arithmetic) */
             return;

@@ -1,13 +1,15 @@
 /* msd_wire_store_impl.h -- how the wire kernels lay a stream out and store it: the workgroup scan over the messages'
- * lengths, the scan over the workgroups' sums, and the LDS image of up to 256 messages that leaves as whole-wavefront
- * runs of consecutive aligned dwords (the destination may be host memory, where a store per message byte would cost a
- * PCIe write each).  Shared by msd_wire_kernels.hip, msd_group_remote_out_kernels.hip and the position tracker's four
- * writers (msd_reduce_kernels.hip, msd_sbs_kernels.hip, msd_pb_kernels.hip, msd_vrs_kernels.hip).  Device code only. */
+ * lengths and the scan over the workgroups' sums (msd_block_scan_impl.h), and the LDS image of up to 256 messages that
+ * leaves as whole-wavefront runs of consecutive aligned dwords (the destination may be host memory, where a store per
+ * message byte would cost a PCIe write each).  Shared by msd_wire_kernels.hip, msd_group_remote_out_kernels.hip and the
+ * position tracker's four writers (msd_reduce_kernels.hip, msd_sbs_kernels.hip, msd_pb_kernels.hip,
+ * msd_vrs_kernels.hip).  Device code only. */
 #ifndef MSD_WIRE_STORE_IMPL_H
 #define MSD_WIRE_STORE_IMPL_H
 
 #include <hip/hip_runtime.h>
 
+#include "msd_block_scan_impl.h"
 #include "msd_wire_impl.h"
 
 namespace msd_wire_store {
@@ -17,46 +19,9 @@ namespace msd_wire_store {
 constexpr uint32_t WT = 256;
 constexpr uint32_t IMAGE_WORDS = WT * MSD_WIRE_MAX / 4 + 2; /* the image starts at the destination's offset in its dword */
 
-/* exclusive prefix of v over the workgroup's 256 threads, and the total; `part`: 4 words of LDS */
-__device__ inline uint32_t block_scan(uint32_t v, uint32_t *part, uint32_t &total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d)
-            incl += up;
-    }
-    __syncthreads(); /* part may still be read from the call before */
-    if (lane == 63)
-        part[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4; ++w)
-        before += w < wave ? part[w] : 0u;
-    total = part[0] + part[1] + part[2] + part[3];
-    return before + incl - v;
-}
-
-/* block_sums[0 .. nblocks) -> their exclusive prefix in place, block_sums[nblocks] = the stream's length.  The body of
- * scan_kernel. */
-__device__ inline void block_sums_scan(uint32_t *block_sums, uint32_t nblocks, uint32_t *part)
-{
-    uint32_t run = 0;
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += WT) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t v = b < nblocks ? block_sums[b] : 0u;
-        uint32_t total;
-        const uint32_t before = block_scan(v, part, total);
-        if (b < nblocks)
-            block_sums[b] = run + before;
-        run += total;
-    }
-    if (threadIdx.x == 0)
-        block_sums[nblocks] = run;
-}
+/* the workgroup scan over the messages' lengths and the scan over the workgroups' sums; the writers call both at WT */
+using msd_block_scan::block_scan;
+using msd_block_scan::block_sums_scan;
 
 /* The scan step of every writer, one workgroup: each of ARRAYS consecutive arrays of nblocks + 1 words, as block_sums_scan
  * leaves it. */
@@ -64,7 +29,7 @@ template <uint32_t ARRAYS = 1> __global__ void __launch_bounds__(WT) scan_kernel
 {
     __shared__ uint32_t part[4];
     for (uint32_t q = 0; q < ARRAYS; ++q)
-        block_sums_scan(block_sums + q * (nblocks + 1u), nblocks, part);
+        block_sums_scan<WT>(block_sums + q * (nblocks + 1u), nblocks, part);
 }
 
 /* Where thread t's bytes go in the image of a run that will be stored at dst: the image mirrors the destination's
