@@ -1,6 +1,14 @@
 /* msd_block_scan_impl.h -- the exclusive prefix sum of one value per thread over a workgroup, by wavefront shuffles and
  * one LDS word per wavefront, and the scan of an array of workgroup sums built on it.  Used by the wire writers
- * (msd_wire_store_impl.h) and the AVR text input (msd_avr_impl.h).  Device code only. */
+ * (msd_wire_store_impl.h) and the AVR text input (msd_avr_impl.h).  Device code only.
+ *
+ * block_sums_scan walks the sums THREADS at a time and carries `run` from round to round: up to THREADS workgroups --
+ * 65 536 items at the writers' 256 -- the carry is never used, past that every offset rests on it.  The tests that hold
+ * the second and later rounds: tests/test_gpu_scan_check.py (scripts/micro/scan_check.hip: scan_kernel<1> and <4> alone,
+ * up to 65 537 sums, against a 64-bit host prefix, and block_scan twice on one `part`),
+ * test_bytes_and_ends_past_one_round_of_the_scan in tests/test_gpu_wire_encode.py, tests/test_gpu_writer_scale.py (the
+ * tracker's five writers), test_the_scan_past_one_round in tests/test_gpu_receiver_group_remote_wire.py, and
+ * test_a_call_longer_than_one_piece of the AVR input.  They are sized around THREADS = 256: change both together. */
 #ifndef MSD_BLOCK_SCAN_IMPL_H
 #define MSD_BLOCK_SCAN_IMPL_H
 

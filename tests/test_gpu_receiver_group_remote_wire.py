@@ -118,6 +118,43 @@ def test_lengths_and_the_scan(twin, kind, fmt):
     T.same_state(rng, 10)
 
 
+# 3b. the scan past one round: the wire kernels scan a piece's records, entry after entry, 256 sums a round
+# (block_sums_scan, msd_block_scan_impl.h), so past 65 536 records every record's start and every entry's range rest on
+# what the scan carries between its rounds.  One call, one piece, of 65 793 = 256 B + B + 1 accepted DF17 frames and one
+# record behind them.  An entry takes at most 1 MiB (MSD_GROUP_BEAST_ENTRY_MAX, MSD_GROUP_AVR_ENTRY_MAX), which is
+# fewer than 65 793 DF17 frames in either input, so three entries of 21 931 share them: the seams between the entries
+# lie inside workgroups, the seam between the rounds inside the third entry.  A few hundred frames built once, half of
+# them rich in 0x1A, are tiled -- no parity per record in Python.
+@pytest.mark.parametrize("kind,fmt", [("beast", WIRE_BEAST), ("avr", WIRE_AVR_MLAT)])
+def test_the_scan_past_one_round(pkg, twin, kind, fmt):
+    rng = random.Random(33)
+    each, tile = (B * B + B + 1) // 3, 300
+    sizes = [each, each, each, 1]
+    assert sum(sizes[:3]) == 256 * B + B + 1 and (sum(sizes) + B - 1) // B == 258
+    T = twin(len(sizes))
+
+    def items(r):
+        out = []
+        for k in range(tile):  # runs of five frames rich in 0x1A, then five without
+            dense = (k // 5) % 2 == 0
+            me = bytes([0x1A] * rng.randrange(1, 8)).ljust(7, b"\x33") if dense else b"\x20\x2C\xC3\x71\xC3\x2C\xE0"
+            body = pi(bytes([0x8D]) + (0x1A0000 + r).to_bytes(3, "big") + me)
+            out.append((body, rng.choice([0x1A1A1A1A1A1A, 0x1A331A331A33, 0x001A00001A00]) if dense else 0x112233445566 + k,
+                        0x1A if dense else 0x80))
+        return out
+
+    chunks = []
+    for r, n in enumerate(sizes):
+        some = items(r)
+        chunks.append((r, stream(kind, some) * (n // tile) + stream(kind, some[:n % tile])))
+    limit = pkg.capi.GROUP_BEAST_ENTRY_MAX if kind == "beast" else pkg.capi.GROUP_AVR_ENTRY_MAX
+    assert 23 * (B * B + B + 1) > limit >= max(len(b) for _, b in chunks)  # (23: the shortest Beast frame of a DF17)
+    want, got = T.wire(kind, chunks, 9, fmt, False, keep=True)
+    assert [len(m) for m in want] == sizes and [nm for _, _, nm in got] == sizes
+    assert all(len(b) > 23 * each for _, b, _ in got[:3]) and len(got[3][1]) >= 23
+    T.same_state(rng, 10)
+
+
 # 4. kept state across calls: a frame / line split between two calls of one receiver shows in the second call's entry
 # only, and another receiver that uses the same entry slot in between gets none of its bytes
 @pytest.mark.parametrize("kind", ["beast", "avr"])

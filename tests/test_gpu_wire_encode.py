@@ -1,7 +1,8 @@
 """msd_wire_encode: constructed message records as Beast frames and AVR lines written on the GPU, byte for byte against
 libmsd_host.so's msd_beast_frame_out / msd_avr_line_out called per record, and `ends` against the running sum of their
 lengths.  Every record count in NS -- so that frames straddle every wavefront and workgroup run -- in all three
-formats, with and without verbatim, from host and from device memory."""
+formats, with and without verbatim, from host and from device memory.  And, tiled from the same records, 65 536 to
+131 329 of them: past 256 workgroups the scan over their sums runs in rounds and every offset rests on its carry."""
 import ctypes as C
 import os
 
@@ -187,6 +188,69 @@ def test_bytes_and_ends(pkg, torch_cuda, pool, fmt, verbatim):
                     assert got[prev:prev + len(b)] == b, (what, i, part[i], got[prev:prev + len(b)].hex(), b.hex())
                     prev += len(b)
             assert got == b"".join(exp), what
+
+
+BIG_NS = (1 << 16, (1 << 16) + 1, 256 * 256 + 257, 2 * 256 * 256 + 257)  # 256, 257, 257 + a seam, 513 workgroups + a seam
+
+
+def tiled(pool, key, start, n):
+    """Records pool[(start + arange(n)) % len(pool)], the stream the host writers make of them and its ends -- put
+    together from the pool's per-record answers by index, no call per record."""
+    recs, want = pool
+    lens = np.array([len(b) for b in want[key]], dtype=np.int64)
+    blob = np.frombuffer(b"".join(want[key]), dtype=np.uint8)
+    begins = np.cumsum(lens) - lens
+    idx = (start + np.arange(n)) % len(recs)
+    ends = np.cumsum(lens[idx])
+    src = np.repeat(begins[idx] - (ends - lens[idx]), lens[idx]) + np.arange(ends[-1])
+    return np.ascontiguousarray(recs[idx]), blob[src], ends.astype(np.uint64), idx
+
+
+@pytest.mark.parametrize("fmt,verbatim", [(0, False), (2, True)])  # Beast plain, AVR-MLAT verbatim
+def test_bytes_and_ends_past_one_round_of_the_scan(pkg, torch_cuda, pool, fmt, verbatim):
+    """More than 256 workgroups of records: block_sums_scan (msd_block_scan_impl.h) then walks the workgroups' sums in
+    rounds of 256 and every offset, every end and the stream's length rest on what it carries from round to round --
+    one, two (by one record; by a workgroup and a record) and three rounds."""
+    dem = pkg.capi.Demodulator(fmt=pkg.capi.FMT_UC8, nfix_crc=2)
+    assert [(n + 255) // 256 for n in BIG_NS] == [256, 257, 258, 514]
+    for k, n in enumerate(BIG_NS):
+        part, exp, exp_ends, idx = tiled(pool, (fmt, verbatim), 101 * k + 3, n)
+        assert len(exp) == int(exp_ends[-1]) > 15 * n  # (a short Beast frame is 16 bytes; a few records have none)
+        dev = torch_cuda.from_numpy(part.view(np.uint8).reshape(-1)).cuda()
+        for on_device in (False, True):
+            got, ends = dem.encode_wire(dev if on_device else part, fmt, verbatim=verbatim, on_device=on_device)
+            what = (fmt, verbatim, n, on_device)
+            got = np.frombuffer(got, dtype=np.uint8)
+            assert len(ends) == n, what
+            wrong = np.flatnonzero(ends.astype(np.uint64) != exp_ends)
+            assert wrong.size == 0, (what, "ends: first at record", int(wrong[0]), int(ends[wrong[0]]), int(exp_ends[wrong[0]]))
+            m = min(len(got), len(exp))
+            wrong = np.flatnonzero(got[:m] != exp[:m])
+            if wrong.size:  # name the first record that differs
+                i = int(np.searchsorted(exp_ends, wrong[0], side="right"))
+                lo, hi = int(exp_ends[i - 1]) if i else 0, int(exp_ends[i])
+                assert False, (what, "record", i, "pool", int(idx[i]), got[lo:hi].tobytes().hex(), exp[lo:hi].tobytes().hex())
+            assert len(got) == len(exp), (what, len(got), len(exp))
+
+
+def test_one_byte_short_past_one_round_of_the_scan(pkg, torch_cuda, pool):
+    """-ENOSPC with the stream's length -- block_sums[nblocks], after two rounds -- and nothing written."""
+    capi = pkg.capi
+    n = BIG_NS[2]
+    part, exp, exp_ends, _ = tiled(pool, (0, False), 57, n)
+    dem = capi.Demodulator(fmt=capi.FMT_UC8, nfix_crc=2)
+    L = capi.lib()
+    used = C.c_size_t(12345)
+    out = np.full(len(exp) + 8, 0xAA, dtype=np.uint8)
+    ends = np.full(n, 0xAAAAAAAA, dtype=np.uint32)
+    call = lambda cap: L.msd_wire_encode(dem._h, part.ctypes.data, n, 0, 0, 0, out.ctypes.data, cap, C.byref(used),
+                                         ends.ctypes.data)
+    assert call(len(exp) - 1) == -28
+    assert used.value == len(exp) == int(exp_ends[-1])
+    assert (out == 0xAA).all() and (ends == 0xAAAAAAAA).all()
+    assert call(len(exp)) == 0 and used.value == len(exp)
+    assert np.array_equal(out[: len(exp)], exp) and (out[len(exp):] == 0xAA).all()
+    assert np.array_equal(ends.astype(np.uint64), exp_ends)
 
 
 def test_errors(pkg, torch_cuda, pool):
