@@ -850,7 +850,8 @@ int msd_group_accept_avr_wire(msd_group *g, const void *bytes, int on_device, co
  * aircraft, with decoded_nic / decoded_rc, are kept by a tracker made with msd_pos_create_table ("the aircraft table"
  * below); a table tracker can also match the Mode A/C replies against its aircraft ("Mode A/C matching" below) and thin
  * the feed to readsb's reduced Beast output ("Reduced Beast output" below), write the SBS output ("SBS output" below) and
- * write aircraft.pb, the AircraftsUpdate protobuf, from the table ("aircraft.pb" below); either kind of tracker can keep
+ * write aircraft.pb, the AircraftsUpdate protobuf, from the table ("aircraft.pb" below), the VRS aircraft list ("VRS
+ * output" below) and the history files ("history_N.pb" below; receiver.pb is msd_receiver_pb's); either kind of tracker can keep
  * a->meta.distance, the polar range and the longest distance per receiver ("Receiver range" below).
  * Not built: the declination, SBS input and MLAT positions.
  *
@@ -1329,6 +1330,75 @@ int msd_pos_vrs_enable(msd_pos *p);
  * enabled, NULL, an unknown flag, reserved != 0, n_parts not a power of two in 1 .. 2048, part >= n_parts.  -E2BIG: the
  * table could hold more than 2^32 - 1 bytes of stream (above some 10 million aircraft). */
 int msd_pos_vrs(msd_pos *p, const msd_vrs_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_vrs_receiver *rx);
+
+/* ---- history_N.pb: the files the web app draws its trails from at start-up -- the AircraftsUpdate message of
+ * readsb.proto with `history` entries alone, which generateHistoryProtoBuf (net_io.c:2086-2177) packs from the aircraft
+ * list every 30 s into a ring of 120 files (readsb.c:415-428) -- for a table tracker, one file per receiver index, written
+ * on the device from the table.  No enable call and no state: a call reads the table and changes nothing,
+ * aircraft.pb's written state included; its scratch is reserved by the first call.  A tracker that never calls it
+ * allocates and launches what it did before.  Which file of the ring a stream becomes is the caller's bookkeeping.
+ *
+ * A file.  Content and order are protobuf-c 1.3's aircrafts_update__pack: `now` (1) = now_ms / 1000, omitted when 0;
+ * `messages` (2) is never set; then one `history` (14) entry -- tag 0x72, a one-byte length, the AircraftHistory body --
+ * per selected aircraft.  With now_ms < 1000 a file without aircraft is zero bytes.
+ * Selection (net_io.c:2115-2124), in integers: aircraft.pb's rule -- written unless messages < 2 or now_ms > seen + 90000;
+ * one seen after now_ms is written -- and the position is valid: msd_aircraft_valid(a, MSD_AC_POSITION, now_ms).  The
+ * reference's trackDataValid reads whatever _messageNow last held, the time of the last message that reached the tracker;
+ * here it is now_ms, as in aircraft.pb and the VRS output.
+ * Order: ascending address within a receiver, msd_pos_snapshot's.  The reference walks its hash buckets; the order of a
+ * repeated field means nothing to a reader.  The same deliberate difference as in aircraft.pb.
+ * The body, in field order; a scalar is omitted when zero.  addr (1): a varint of the stored 25 bits,
+ * MSD_NON_ICAO_ADDRESS included.  alt_baro (5), an int32 (negative: a 10-byte varint): -9999 (INVALID_ALTITUDE) when
+ * airground is valid, its source is >= 4 (SOURCE_MODE_S_CHECKED) and air_ground is 1 (ground); else alt_baro when
+ * altitude_baro is valid and altitude_baro_reliable >= 3; else alt_geom when altitude_geom is valid -- by its own stale and
+ * expiry members --; else 0, that is absent.  "valid" is msd_aircraft_valid at now_ms.  lat (8), lon (9): the stored
+ * doubles, tags 0x41 / 0x49, omitted when 0 == value (-0.0 is omitted, NaN is written).
+ * CONTRACT, the table's: the device and the host object (msd_pos_host_history_pb -- a plain sequential encoder that shares
+ * no code with the device's) deliver the same stream and the same rows on every table on which they hold the same
+ * msd_aircraft bytes, whichever slots the aircraft occupy.  No libm function is involved: there is no margin. ---- */
+typedef struct msd_history_options { /* 16 bytes */
+    uint64_t now_ms;          /* mstime() of the write */
+    uint32_t flags, reserved; /* 0 */
+} msd_history_options;
+typedef struct msd_history_receiver { /* 16 bytes, no implicit padding */
+    uint64_t end;      /* the end offset of this receiver's file in the stream; it begins at the end before it */
+    uint32_t aircraft; /* aircraft written */
+    uint32_t reserved; /* 0 */
+} msd_history_receiver;
+/* the longest `history` entry: 1 tag + 1 length + 5 addr (25 bits) + 11 alt_baro (negative) + 9 lat + 9 lon */
+#define MSD_HISTORY_ENTRY_MAX 36
+/* The history file of every receiver index 0 .. receivers-1 in ascending order as one dense stream in the host array out;
+ * rx: a host array of `receivers` rows, or NULL.  An empty file repeats the end before it.
+ * -ENOSPC: cap is too small, *out_len is the size needed and nothing was written: the call can be repeated and gives the
+ * same bytes.  -EINVAL: a tracker without a table, NULL, an unknown flag, reserved != 0.  -E2BIG: the table could hold more
+ * than 2^32 - 1 bytes of stream (above some 119 million aircraft). */
+int msd_pos_history_pb(msd_pos *p, const msd_history_options *opt, uint8_t *out, size_t cap, size_t *out_len,
+                       msd_history_receiver *rx);
+
+/* ---- receiver.pb: the Receiver message of readsb.proto that generateReceiverProtoBuf (net_io.c:2342-2404) writes at
+ * start-up and after every history file until the ring has been full once -- what the web app loads first: the refresh
+ * period, the receiver's location and how many history files exist.  A dozen scalars, packed on the host; in
+ * libmodes_hip.so and libmsd_host.so alike.
+ * Bytes are protobuf-c 1.3's receiver__pack, fields in ascending order: version (1, a string; omitted when NULL or
+ * empty), refresh (2, float), latitude (3), longitude (4) (doubles), altitude (5), antenna_serial (6), antenna_flags (7),
+ * antenna_gps_sats (8), antenna_gps_hdop (9), antenna_reserved (14), history (15) (uint32); a scalar is omitted when zero
+ * (a float or double when 0 == value: -0.0 is omitted, NaN is written).  All-zero info gives zero bytes.
+ * location_accuracy is --rx-location-accuracy and is not itself written.  With 1 and a location that is not (0, 0),
+ * latitude and longitude are written as round(x * 100) / 100 (libm's round: ties away from zero), as the reference rounds
+ * them.  Any other value writes them as given -- 0 too: the reference does not remove the location from the file there,
+ * and neither does this call. ---- */
+typedef struct msd_receiver_info { /* 64 bytes, no implicit padding */
+    const char *version;          /* NUL-terminated, or NULL */
+    double latitude, longitude;
+    float refresh;                /* Modes.output_interval in ms */
+    uint32_t altitude, antenna_serial, antenna_flags, antenna_gps_sats, antenna_gps_hdop, antenna_reserved;
+    uint32_t history;             /* history files that exist: aircraft_history_next + 1 */
+    int32_t location_accuracy;
+    uint32_t reserved;            /* 0 */
+} msd_receiver_info;
+/* The message into out -> 0 and *out_len.  -ENOSPC: cap is too small, *out_len is the size needed, nothing was written.
+ * -EINVAL: NULL info or out_len, NULL out with cap > 0, reserved != 0. */
+int msd_receiver_pb(const msd_receiver_info *info, uint8_t *out, size_t cap, size_t *out_len);
 
 /* ---- Receiver range: the last lines of updatePosition (track.c:683-686) -- a->meta.distance, the polar range of
  * --stats-range (update_polar_range :281-308 with getBearing :238-250; Statistics.polar_range in stats.pb, the range

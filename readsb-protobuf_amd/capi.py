@@ -243,7 +243,7 @@ EXPORTS = [
     "msd_pos_modeac_enable", "msd_pos_modeac_match", "msd_pos_modeac_codes", "msd_pos_modeac_hits", "msd_mode_c_to_a",
     "msd_pos_reduce_enable", "msd_pos_update_reduce", "msd_pos_reduce_wire",
     "msd_pos_sbs_enable", "msd_pos_update_sbs", "msd_pos_sbs_wire", "msd_pos_pb_enable", "msd_pos_aircraft_pb",
-    "msd_pos_vrs_enable", "msd_pos_vrs",
+    "msd_pos_vrs_enable", "msd_pos_vrs", "msd_pos_history_pb", "msd_receiver_pb",
     "msd_pos_range_enable", "msd_pos_range_read", "msd_pos_range_distances", "msd_pos_range_margins", "msd_pos_range_pb",
 ]
 
@@ -1138,6 +1138,10 @@ PB_RSSI_MARGIN_ULPS = 8.0
 VRS_RECEIVER_DTYPE = np.dtype([("end", "<u8"), ("aircraft", "<u4"), ("reserved", "<u4")])
 assert VRS_RECEIVER_DTYPE.itemsize == 16
 VRS_AIRCRAFT_MAX = 418
+# history_N.pb: a receiver's row of msd_pos_history_pb (msd_history_receiver) and the longest `history` entry
+HISTORY_RECEIVER_DTYPE = np.dtype([("end", "<u8"), ("aircraft", "<u4"), ("reserved", "<u4")])
+assert HISTORY_RECEIVER_DTYPE.itemsize == 16
+HISTORY_ENTRY_MAX = 36
 # the receiver range: a receiver's row of msd_pos_range_read (msd_range_receiver), the enable and read flags, and the two
 # margins on the host object under which the device and the host object may differ
 RANGE_BUCKETS = 72
@@ -1161,6 +1165,20 @@ class PbOptions(C.Structure):
 class VrsOptions(C.Structure):
     _fields_ = [("now_ms", C.c_uint64), ("part", C.c_uint32), ("n_parts", C.c_uint32), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class HistoryOptions(C.Structure):
+    _fields_ = [("now_ms", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HistoryReceiver(C.Structure):
+    _fields_ = [("end", C.c_uint64), ("aircraft", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ReceiverInfo(C.Structure):
+    _fields_ = [("version", C.c_char_p), ("latitude", C.c_double), ("longitude", C.c_double), ("refresh", C.c_float)] + [
+        (k, C.c_uint32) for k in ("altitude", "antenna_serial", "antenna_flags", "antenna_gps_sats", "antenna_gps_hdop",
+                                  "antenna_reserved", "history")] + [("location_accuracy", C.c_int32), ("reserved", C.c_uint32)]
 
 
 class RangeMargins(C.Structure):
@@ -1210,7 +1228,7 @@ def _pos_lib(host):
                                               "create_table", "update_nicrc", "snapshot", "modeac_enable", "modeac_match",
                                               "modeac_codes", "modeac_hits", "reduce_enable", "update_reduce",
                                               "reduce_wire", "sbs_enable", "update_sbs", "sbs_wire", "pb_enable", "aircraft_pb",
-                                              "vrs_enable", "vrs", "range_enable", "range_read", "range_distances",
+                                              "vrs_enable", "vrs", "history_pb", "range_enable", "range_read", "range_distances",
                                               "range_margins", "range_pb")}
         dev = [] if host else [C.c_int]
         f["range_enable"].argtypes = [C.c_void_p, C.c_uint32]
@@ -1223,6 +1241,8 @@ def _pos_lib(host):
                                      C.c_void_p] + ([C.POINTER(C.c_double)] if host else [])
         f["vrs_enable"].argtypes = [C.c_void_p]
         f["vrs"].argtypes = [C.c_void_p, C.POINTER(VrsOptions), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+        f["history_pb"].argtypes = [C.c_void_p, C.POINTER(HistoryOptions), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                    C.c_void_p]
         f["sbs_enable"].argtypes = [C.c_void_p]
         f["update_sbs"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [C.c_void_p] * 4
         f["sbs_wire"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + dev + [
@@ -1256,6 +1276,8 @@ def _pos_lib(host):
             L.msd_pos_host_home_slot.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
             L.msd_pos_host_vrs_object.restype = C.c_size_t
             L.msd_pos_host_vrs_object.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+            L.msd_pos_host_history_entry.restype = C.c_size_t
+            L.msd_pos_host_history_entry.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
             L.msd_pos_host_reduce_timers.restype = C.c_int
             L.msd_pos_host_reduce_timers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             for name, n_ref, n_int in (("airborne", 0, 5), ("surface", 2, 5), ("relative", 2, 4)):
@@ -1483,6 +1505,31 @@ class PositionTracker:
         ends = [0] + [int(e) for e in rx["end"]]
         return [stream[a:b] for a, b in zip(ends[:-1], ends[1:])]
 
+    def history_pb_stream(self, now_ms, cap=None, flags=0, reserved=0, rx=True):
+        """msd_pos_history_pb -> (the stream of every receiver's history file, HISTORY_RECEIVER_DTYPE array).  cap: the
+        bytes offered (default: as many as are needed, asked for first); self.history_needed is *out_len of the last
+        call.  rx=False: the call gets no array for the rows, and None comes back in their place."""
+        opt = HistoryOptions(now_ms=now_ms, flags=flags, reserved=reserved)
+        need = C.c_size_t(0)
+        if cap is None:
+            rc = self.f["history_pb"](self.h, C.byref(opt), None, 0, C.byref(need), None)
+            if rc not in (0, -errno.ENOSPC):
+                self._check(rc, "msd_pos_history_pb")
+            cap = need.value
+        out = np.zeros(cap, dtype=np.uint8)
+        rows = np.zeros(self.nrx, dtype=HISTORY_RECEIVER_DTYPE) if rx else None
+        rc = self.f["history_pb"](self.h, C.byref(opt), out.ctypes.data if cap else None, cap, C.byref(need),
+                                  rows.ctypes.data if rx else None)
+        self.history_needed = need.value
+        self._check(rc, "msd_pos_history_pb")
+        return out[:need.value].tobytes(), rows
+
+    def history_pb(self, now_ms):
+        """Every receiver's history file at now_ms -> a list of bytes, one file per receiver index."""
+        stream, rx = self.history_pb_stream(now_ms)
+        ends = [0] + [int(e) for e in rx["end"]]
+        return [stream[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
     def range_enable(self, flags=RANGE_POLAR):
         self._check(self.f["range_enable"](self.h, flags), "msd_pos_range_enable")
 
@@ -1681,6 +1728,35 @@ class PositionTracker:
         st = PosStats()
         self._check(self.f["get_stats"](self.h, C.byref(st)), "msd_pos_get_stats")
         return st.as_dict()
+
+
+def receiver_pb(host=False, cap=None, **info):
+    """msd_receiver_pb: the bytes of receiver.pb for info's members (msd_receiver_info's names; version a str, bytes or
+    None).  host=True: libmsd_host.so's copy of the function.  cap: the bytes offered (default: as many as are needed,
+    asked for first); receiver_pb.needed is *out_len of the last call."""
+    L = C.CDLL(HOST_LIB_PATH) if host else lib()
+    L.msd_receiver_pb.restype = C.c_int
+    L.msd_receiver_pb.argtypes = [C.POINTER(ReceiverInfo), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    version = info.pop("version", None)
+    ri = ReceiverInfo(version=version.encode() if isinstance(version, str) else version, **info)
+    need = C.c_size_t(0)
+
+    def check(rc):
+        if rc != 0:
+            err = MsdError(f"msd_receiver_pb failed: {rc} ({os.strerror(-rc)})")
+            err.code = rc
+            raise err
+
+    if cap is None:
+        rc = L.msd_receiver_pb(C.byref(ri), None, 0, C.byref(need))
+        if rc != -errno.ENOSPC:
+            check(rc)
+        cap = need.value
+    out = np.zeros(cap, dtype=np.uint8)
+    rc = L.msd_receiver_pb(C.byref(ri), out.ctypes.data if cap else None, cap, C.byref(need))
+    receiver_pb.needed = need.value
+    check(rc)
+    return out[:need.value].tobytes()
 
 
 def cpr_host(kind, *args):

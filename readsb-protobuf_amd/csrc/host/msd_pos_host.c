@@ -1040,6 +1040,72 @@ int msd_pos_host_vrs(msd_pos_host *p, const msd_vrs_options *opt, uint8_t *out, 
     return 0;
 }
 
+/* ---- the history_N.pb writer: generateHistoryProtoBuf (net_io.c:2086-2177) and protobuf-c 1.3's pack as a plain
+ * sequential encoder over the exported entries, with aircraft.pb's pb_put_* above.  The yardstick of the device's writer
+ * (msd_history_impl.h): nothing of that file is used here. ---- */
+size_t msd_pos_host_history_entry(const msd_aircraft *a, uint64_t now, uint8_t *out)
+{
+    uint8_t body[MSD_HISTORY_ENTRY_MAX];
+    pb_buf b = {body, 0}, e = {out, 0};
+    int32_t alt = 0;
+    if (msd_aircraft_valid(a, MSD_AC_AIRGROUND, now) && a->source[MSD_AC_AIRGROUND] >= 4 /* SOURCE_MODE_S_CHECKED */ &&
+        a->air_ground == 1 /* AG_GROUND */)
+        alt = -9999; /* INVALID_ALTITUDE */
+    else if (msd_aircraft_valid(a, MSD_AC_ALTITUDE_BARO, now) && a->altitude_baro_reliable >= 3)
+        alt = a->alt_baro;
+    else if (msd_aircraft_valid(a, MSD_AC_ALTITUDE_GEOM, now))
+        alt = a->alt_geom;
+    pb_put_u64(&b, 1, a->addr & 0x1FFFFFFu);
+    pb_put_i32(&b, 5, alt);
+    pb_put_double(&b, 8, a->lat);
+    pb_put_double(&b, 9, a->lon);
+    pb_put_bytes(&e, 14, &b, body);
+    return e.n;
+}
+
+int msd_pos_host_history_pb(msd_pos_host *p, const msd_history_options *opt, uint8_t *out, size_t cap, size_t *out_len,
+                            msd_history_receiver *rx)
+{
+    if (!p || !p->trk || !out_len || !opt || opt->flags != 0 || opt->reserved != 0 || (!out && cap > 0))
+        return -EINVAL;
+    *out_len = 0;
+    uint64_t *ks = NULL;
+    if (p->live && !(ks = ordered_slots(p)))
+        return -ENOMEM;
+    const uint64_t now = opt->now_ms;
+    for (int pass = 0; pass < 2; ++pass) { /* the size first: a stream that does not fit leaves out alone */
+        pb_buf file = {pass ? out : NULL, 0};
+        size_t j = 0;
+        for (uint32_t r = 0; r < p->nrx; ++r) {
+            msd_history_receiver row = {0, 0, 0};
+            pb_put_u64(&file, 1, now / 1000);
+            for (; j < p->live && (ks[2 * j] >> 25) == r; ++j) {
+                const uint64_t s = ks[2 * j + 1];
+                msd_aircraft e;
+                msd_trk_export(ks[2 * j], &p->st[s], &p->trk[s], &e);
+                if (e.messages < 2 || (now > e.seen && now - e.seen > 90000)) /* net_io.c:2115 */
+                    continue;
+                if (!msd_aircraft_valid(&e, MSD_AC_POSITION, now)) /* :2122 */
+                    continue;
+                uint8_t entry[MSD_HISTORY_ENTRY_MAX];
+                const size_t k = msd_pos_host_history_entry(&e, now, entry);
+                pb_put(&file, entry, k);
+                row.aircraft++;
+            }
+            row.end = file.n;
+            if (pass && rx)
+                rx[r] = row;
+        }
+        *out_len = file.n;
+        if (file.n > cap) {
+            free(ks);
+            return -ENOSPC;
+        }
+    }
+    free(ks);
+    return 0;
+}
+
 int msd_pos_host_reduce_timers(const msd_pos_host *p, uint32_t receiver, uint32_t addr, uint64_t *out)
 {
     if (!p || !p->next_reduce || !out)

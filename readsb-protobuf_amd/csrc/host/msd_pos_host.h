@@ -57,6 +57,15 @@ int msd_pos_host_aircraft_pb(msd_pos_host *p, const msd_pb_options *opt, uint8_t
 int msd_pos_host_vrs_enable(msd_pos_host *p);
 int msd_pos_host_vrs(msd_pos_host *p, const msd_vrs_options *opt, uint8_t *out, size_t cap, size_t *out_len, msd_vrs_receiver *rx);
 size_t msd_pos_host_vrs_object(const msd_aircraft *a, uint64_t now_ms, int comma, char *out);
+/* history_N.pb (modes_hip.h, "history_N.pb"): msd_pos_history_pb on the host -- a plain sequential encoder over
+ * msd_pos_host_snapshot's entries that shares no code with the device's (msd_history_impl.h), the yardstick of the device's
+ * writer.  No enable and no state, as on the device; -EINVAL without a table.  CONTRACT: the device and this object deliver
+ * the same stream and the same rows on every table on which they hold the same msd_aircraft bytes; no libm function is
+ * called on either side, so there is no margin.  msd_pos_host_history_entry: one entry's `history` element at now_ms into
+ * out (MSD_HISTORY_ENTRY_MAX bytes at least, or NULL) -> its length; it does not look at selection */
+int msd_pos_host_history_pb(msd_pos_host *p, const msd_history_options *opt, uint8_t *out, size_t cap, size_t *out_len,
+                            msd_history_receiver *rx);
+size_t msd_pos_host_history_entry(const msd_aircraft *a, uint64_t now_ms, uint8_t *out);
 /* the receiver range (modes_hip.h, "Receiver range"): msd_pos_range_* on the host -- msd_pos_impl.h's per-record function
  * with the host's libm, record after record in stream order.  Its margins are the contract's */
 int msd_pos_host_range_enable(msd_pos_host *p, uint32_t flags);

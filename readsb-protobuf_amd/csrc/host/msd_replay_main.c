@@ -31,6 +31,11 @@
  * port 30003) output to FILE (msd_pos_update_sbs, msd_pos_sbs_wire): one MSG line per message the tracker knows the
  * aircraft of.  A replay has no wall clock: fields 9-10 repeat the message's own time (MSD_SBS_NOW_IS_RECEIVED), so the
  * file is the same on every run.  Works beside --beast-reduce-out.
+ * `--positions --aircraft --write-output DIR [--write-output-every SECONDS]` keeps receiver 0's output directory as readsb's
+ * --write-output does (readsb.c:410-428), on the message clock: receiver.pb (msd_receiver_pb) at the start and after every
+ * history file until the ring of 120 has been full once, aircraft.pb every SECONDS (default 1, at least 0.1) and once more
+ * after the last message, history_N.pb (msd_pos_history_pb) every 30 s; msd_pos_expire once per second.  Every file is
+ * written under a temporary name in DIR and renamed.
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -39,6 +44,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <unistd.h>
 
 #include "modes_hip_readsb.h"
 #include "msd_wire.h"
@@ -266,6 +272,116 @@ static int write_vrs(int want_stats)
     return bad;
 }
 
+/* --write-output DIR: readsb's output directory for receiver 0, driven by the message clock (backgroundTasks,
+ * readsb.c:410-428).  Before the message with time t reaches the tracker: t >= next_full writes aircraft.pb at now_ms = t
+ * with `messages` = the messages delivered so far; t >= next_history writes history_<next>.pb at now_ms = t and, until the
+ * ring has been full once, receiver.pb with history = next + 1.  receiver.pb is also written when the directory is set up,
+ * with history = 1 as the reference's start-up call leaves it */
+#define OUT_HISTORY_SIZE 120u      /* HISTORY_SIZE */
+#define OUT_HISTORY_INTERVAL 30000 /* HISTORY_INTERVAL, ms */
+static const char *g_out_dir;
+static uint64_t g_out_interval = 1000; /* Modes.output_interval */
+static uint64_t g_next_full, g_next_history;
+static uint32_t g_history_next;
+static int g_history_full;
+static msd_receiver_info g_receiver_info;
+static unsigned g_out_files[3]; /* aircraft.pb, history files, receiver.pb written */
+
+/* bytes -> DIR/name by way of DIR/name.XXXXXX, as the reference's writers do */
+static int out_file(const char *name, const uint8_t *bytes, size_t len)
+{
+    char tmp[4096], path[4096];
+    if (snprintf(tmp, sizeof tmp, "%s/%s.XXXXXX", g_out_dir, name) >= (int)sizeof tmp ||
+        snprintf(path, sizeof path, "%s/%s", g_out_dir, name) >= (int)sizeof path)
+        return 1;
+    const int fd = mkstemp(tmp);
+    if (fd < 0)
+        return 1;
+    size_t done = 0;
+    while (done < len) {
+        const ssize_t k = write(fd, bytes + done, len - done);
+        if (k <= 0)
+            break;
+        done += (size_t)k;
+    }
+    if (close(fd) != 0 || done != len || rename(tmp, path) != 0) {
+        unlink(tmp);
+        return 1;
+    }
+    return 0;
+}
+
+static int out_receiver_pb(uint32_t history)
+{
+    uint8_t bytes[512];
+    size_t len = 0;
+    g_receiver_info.history = history;
+    const int rc = msd_receiver_pb(&g_receiver_info, bytes, sizeof bytes, &len);
+    if (rc || out_file("receiver.pb", bytes, len)) {
+        fprintf(stderr, "--write-output %s: receiver.pb: %s (%d)\n", g_out_dir, rc ? "msd_receiver_pb" : "cannot write", rc);
+        return 1;
+    }
+    g_out_files[2]++;
+    return 0;
+}
+
+/* aircraft.pb (history < 0) or history_<history>.pb at now_ms: the size first, then the bytes */
+static int out_table_pb(uint64_t now_ms, int history)
+{
+    const uint64_t total = g_count;
+    msd_pb_options po;
+    msd_history_options ho;
+    memset(&po, 0, sizeof po);
+    memset(&ho, 0, sizeof ho);
+    po.now_ms = ho.now_ms = now_ms;
+    po.messages_total = &total;
+    char name[32] = "aircraft.pb";
+    if (history >= 0)
+        snprintf(name, sizeof name, "history_%d.pb", history);
+    size_t len = 0;
+    int rc = history < 0 ? msd_pos_aircraft_pb(g_pos, &po, NULL, 0, &len, NULL) : msd_pos_history_pb(g_pos, &ho, NULL, 0, &len, NULL);
+    uint8_t *bytes = rc == -ENOSPC ? malloc(len) : NULL;
+    if (rc == -ENOSPC && bytes)
+        rc = history < 0 ? msd_pos_aircraft_pb(g_pos, &po, bytes, len, &len, NULL) : msd_pos_history_pb(g_pos, &ho, bytes, len, &len, NULL);
+    const int bad = rc != 0 || out_file(name, bytes, len);
+    if (bad)
+        fprintf(stderr, "--write-output %s: %s: %s (%d)\n", g_out_dir, name, rc ? msd_pos_last_error(g_pos) : "cannot write", rc);
+    else
+        g_out_files[history >= 0]++;
+    free(bytes);
+    return bad;
+}
+
+static void out_tick(uint64_t t)
+{
+    if (t >= g_next_full) {
+        if (out_table_pb(t, -1))
+            g_pos_failed = 1;
+        g_next_full = t + g_out_interval;
+    }
+    if (t >= g_next_history) {
+        if (out_table_pb(t, (int)g_history_next))
+            g_pos_failed = 1;
+        if (!g_history_full) {
+            if (out_receiver_pb(g_history_next + 1u))
+                g_pos_failed = 1;
+            if (g_history_next == OUT_HISTORY_SIZE - 1u)
+                g_history_full = 1;
+        }
+        g_history_next = (g_history_next + 1u) % OUT_HISTORY_SIZE;
+        g_next_history = t + OUT_HISTORY_INTERVAL;
+    }
+}
+
+/* after the last message: one more aircraft.pb at that message's time, and with --stats what was written */
+static int out_finish(int want_stats)
+{
+    const int bad = out_table_pb(g_last_ms, -1);
+    if (want_stats)
+        fprintf(stderr, "write-output aircraft_pb,%u,history,%u,receiver_pb,%u\n", g_out_files[0], g_out_files[1], g_out_files[2]);
+    return bad;
+}
+
 static void print_raw_positions(const msd_message *mm, void *user)
 {
     FILE *out = user;
@@ -282,9 +398,9 @@ static void print_raw_positions(const msd_message *mm, void *user)
         fprintf(out, "%02x", mm->msg[j]);
     fputc(';', out);
     msd_decode_fields(mm, NULL, &f);
-    if (g_match_modeac && tm.sysTimestampMsg >= g_next_update) { /* trackRemoveStaleAircraft, then trackMatchAC */
+    if ((g_match_modeac || g_out_dir) && tm.sysTimestampMsg >= g_next_update) { /* trackRemoveStaleAircraft, then trackMatchAC */
         int prc = msd_pos_expire(g_pos, tm.sysTimestampMsg);
-        if (!prc)
+        if (!prc && g_match_modeac)
             prc = msd_pos_modeac_match(g_pos, tm.sysTimestampMsg, g_last_tracked_ms);
         if (prc) {
             fprintf(stderr, "msd_pos_modeac_match: %s (%d)\n", msd_pos_last_error(g_pos), prc);
@@ -292,6 +408,8 @@ static void print_raw_positions(const msd_message *mm, void *user)
         }
         g_next_update = tm.sysTimestampMsg + 1000;
     }
+    if (g_out_dir)
+        out_tick(tm.sysTimestampMsg);
     if (mm->msgtype != 32 && f.addr != 0)
         g_last_tracked_ms = tm.sysTimestampMsg;
     uint8_t forward = 0;
@@ -562,6 +680,13 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--sbs-out") && next) { sbs_path = next; ++i; }
         else if (!strcmp(a, "--aircraft-pb") && next) { g_pb_path = next; ++i; }
         else if (!strcmp(a, "--vrs-out") && next) { g_vrs_path = next; ++i; }
+        else if (!strcmp(a, "--write-output") && next) { g_out_dir = next; ++i; } /* readsb.c: Modes.output_dir */
+        else if (!strcmp(a, "--write-output-every") && next) { /* readsb.c:577-579 */
+            g_out_interval = (uint64_t)(1000 * atof(next));
+            if (g_out_interval < 100)
+                g_out_interval = 100;
+            ++i;
+        }
         else if (!strcmp(a, "--vrs-parts") && next) { g_vrs_parts = (uint32_t)strtoul(next, NULL, 10); ++i; }
         else if (!strcmp(a, "--stats-range")) g_stats_range = 1; /* readsb.c:564: Modes.stats_polar_range */
         else if (!strcmp(a, "--stats-range-pb") && next) { g_range_pb_path = next; ++i; }
@@ -596,7 +721,7 @@ int main(int argc, char **argv)
                             "[--stats-range [--stats-range-pb FILE]] [--aircraft [--match-modeac] "
                             "[--beast-reduce-out FILE [--beast-reduce-interval SECONDS] [--net-only]] "
                             "[--sbs-out FILE [--gnss] [--utc-offset SECONDS] [--net-only]] [--aircraft-pb FILE] "
-                            "[--vrs-out FILE [--vrs-parts N]]] [--clock-start-ms N]]\n"
+                            "[--vrs-out FILE [--vrs-parts N]] [--write-output DIR [--write-output-every SECONDS]]] [--clock-start-ms N]]\n"
                             "       --positions: the --raw lines, with \"lat,lon\" behind the ';' of every message from which readsb's tracker\n"
                             "       would have decoded a position (CPR global and local, its range and speed checks; the coordinates are exact, the\n"
                             "       checks' distances use the GPU's sin / cos / acos / atan2: modes_hip.h, msd_pos_update).  --lat / --lon: the\n"
@@ -619,6 +744,10 @@ int main(int argc, char **argv)
                             "       --vrs-out FILE (with --aircraft): after the last message, readsb's VRS JSON aircraft list of the table,\n"
                             "       written on the GPU: the documents of parts 0 .. N-1 one after the other (--vrs-parts N, a power of two up to\n"
                             "       2048, default 8 as readsb sends them); now = the last message's time.\n"
+                            "       --write-output DIR (with --aircraft): readsb's output directory for the web app, on the message clock:\n"
+                            "       receiver.pb at the start and after every history file until 120 exist, aircraft.pb every --write-output-every\n"
+                            "       seconds (default 1, at least 0.1) and after the last message, history_N.pb every 30 s, written on the GPU; the\n"
+                            "       tracker's once-per-second expiry runs too.  Each file goes to a temporary name in DIR and is renamed.\n"
                             "       --sbs-out FILE (with --aircraft): readsb's SBS (BaseStation) output to FILE, one MSG line per message of a\n"
                             "       tracked aircraft; --gnss: geometric altitudes and rates first, marked H; --utc-offset: the zone the dates\n"
                             "       are written in, seconds east of UTC (default 0, at most a day); the \"now\" of fields 9-10 is the message's own time.\n"
@@ -647,6 +776,10 @@ int main(int argc, char **argv)
     }
     if (g_vrs_path && !want_aircraft) {
         fprintf(stderr, "--vrs-out goes with --positions --aircraft\n");
+        return 2;
+    }
+    if (g_out_dir && !want_aircraft) {
+        fprintf(stderr, "--write-output goes with --positions --aircraft\n");
         return 2;
     }
     if (g_range_pb_path && !g_stats_range) {
@@ -736,6 +869,18 @@ int main(int argc, char **argv)
             msd_pos_destroy(g_pos);
             return 1;
         }
+        if (g_out_dir) {
+            g_receiver_info.version = "msd_replay (readsb-protobuf_amd)";
+            g_receiver_info.refresh = (float)(1.0 * (double)g_out_interval);
+            g_receiver_info.latitude = have_lat ? home.lat : 0.0;
+            g_receiver_info.longitude = have_lat ? home.lon : 0.0;
+            g_receiver_info.location_accuracy = 2; /* readsb.c:170 */
+            if (msd_pos_pb_enable(g_pos) != 0 || out_receiver_pb(1)) {
+                fprintf(stderr, "--write-output %s: %s\n", g_out_dir, msd_pos_last_error(g_pos));
+                msd_pos_destroy(g_pos);
+                return 1;
+            }
+        }
         if (g_stats_range && msd_pos_range_enable(g_pos, MSD_RANGE_POLAR) != 0) {
             fprintf(stderr, "--stats-range: %s\n", msd_pos_last_error(g_pos));
             msd_pos_destroy(g_pos);
@@ -762,6 +907,8 @@ int main(int argc, char **argv)
         if (g_pb_path && !rc && write_aircraft_pb(want_stats))
             g_pos_failed = 1;
         if (g_vrs_path && !rc && write_vrs(want_stats))
+            g_pos_failed = 1;
+        if (g_out_dir && !rc && out_finish(want_stats))
             g_pos_failed = 1;
         msd_pos_destroy(g_pos);
         return rc ? rc : g_pos_failed;
@@ -816,6 +963,8 @@ int main(int argc, char **argv)
     if (g_pb_path && write_aircraft_pb(want_stats))
         g_pos_failed = 1;
     if (g_vrs_path && write_vrs(want_stats))
+        g_pos_failed = 1;
+    if (g_out_dir && out_finish(want_stats))
         g_pos_failed = 1;
     msd_pos_destroy(g_pos);
     return g_pos_failed ? 1 : 0;

@@ -1,6 +1,6 @@
 /* msd_pos.cpp -- C-ABI of the position tracker (modes_hip.h "positions"): the object, its device memory (msd_devbuf.h:
  * every buffer is an owning array, freed with the object) and the order in which a call queues the kernels of
- * msd_pos_kernels.hip and of the five writers.  The writers share emit(), host input is staged by stage(), the two
+ * msd_pos_kernels.hip and of the six writers.  The writers share emit(), host input is staged by stage(), the two
  * read-outs of the table share read_out(). */
 #include <errno.h>
 #include <math.h>
@@ -15,6 +15,7 @@
 #include "msd_devbuf.h"
 #include "msd_pb_impl.h"
 #include "msd_vrs_impl.h"
+#include "msd_history_impl.h"
 #include "msd_sbs_impl.h"
 
 template <typename T> using dev = msd_devbuf<T>;
@@ -90,6 +91,13 @@ struct msd_pos {
     dev<msd_vrs_receiver> d_vrs_rx;
     dev<uint32_t> d_vrs_items, d_vrs_within, d_vrs_sel, d_vrs_block;
     dev<uint16_t> d_vrs_lens, d_vrs_swithin;
+    /* history_N.pb (msd_pos_history_pb; no enable): the writer's buffers, made by the first call -- per receiver, per item
+     * (grown to the largest call seen); the stream is the reduced writer's */
+    dev<uint32_t> d_hist_first;
+    dev<msd_history_receiver> d_hist_rx;
+    dev<uint32_t> d_hist_items, d_hist_block;
+    dev<uint16_t> d_hist_within, d_hist_cwithin;
+    dev<uint8_t> d_hist_lens;
     /* the receiver range (msd_pos_range_enable): tab[k].dist, the receivers' rows, the two margins' bits, the code byte
      * per record of a call, and the buffers the two read-out calls hand to the host */
     bool range = false, range_polar = false, range_combine = true, range_timing = false;
@@ -695,6 +703,42 @@ int msd_pos_vrs(msd_pos *p, const msd_vrs_options *opt, uint8_t *out, size_t cap
     return emit(p, p->d_vrs_block.get(), nblocks, "VRS", out, cap, out_len, rx, p->d_vrs_rx.get(),
                 sizeof(msd_vrs_receiver) * p->nrx, [&](uint32_t) {
                     msd_vrs_launch_store(p->stream, c, p->d_vrs_lens.get(), p->d_vrs_block.get(), p->d_w_out.get());
+                });
+}
+
+int msd_pos_history_pb(msd_pos *p, const msd_history_options *opt, uint8_t *out, size_t cap, size_t *out_len,
+                       msd_history_receiver *rx)
+{
+    if (!p || !p->table || !out_len || !msd_history_options_ok(opt) || (!out && cap > 0))
+        return -EINVAL;
+    *out_len = 0;
+    if (p->live * MSD_HISTORY_ENTRY_MAX + (uint64_t)p->nrx * MSD_HISTORY_HEADER_MAX > 0xFFFFFFFFull) {
+        snprintf(p->err, sizeof p->err, "%llu aircraft could take more than 2^32 - 1 bytes", (unsigned long long)p->live);
+        return -E2BIG;
+    }
+    POS_HIP(p, hipSetDevice(p->device));
+    const uint32_t live = (uint32_t)p->live;
+    const size_t nitems = (size_t)live + p->nrx;
+    const uint32_t nblocks = (uint32_t)((nitems + 255u) / 256u);
+    const int rc = snapshot_buffers(p); /* there is no enable: the first call makes what the writer needs */
+    if (rc)
+        return rc;
+    POS_HIP(p, p->d_hist_first.reserve((size_t)p->nrx + 1u));
+    POS_HIP(p, p->d_hist_rx.reserve(p->nrx));
+    POS_HIP(p, p->d_hist_items.reserve(nitems));
+    POS_HIP(p, p->d_hist_within.reserve(nitems));
+    POS_HIP(p, p->d_hist_cwithin.reserve(nitems));
+    POS_HIP(p, p->d_hist_block.reserve(2u * ((size_t)nblocks + 1u)));
+    POS_HIP(p, p->d_hist_lens.reserve(nitems));
+    const msd_history_call c = {p->tab[p->cur], ordered_slots(p, live), p->d_hist_items.get(), opt->now_ms, (uint32_t)nitems,
+                                p->nrx};
+    msd_history_launch_lengths(p->stream, c, live, p->d_hist_first.get(), p->d_hist_items.get(), p->d_hist_lens.get(),
+                               p->d_hist_within.get(), p->d_hist_cwithin.get(), p->d_hist_block.get(), p->d_hist_rx.get());
+    POS_HIP(p, hipGetLastError());
+    return emit(p, p->d_hist_block.get(), nblocks, "history", out, cap, out_len, rx, p->d_hist_rx.get(),
+                sizeof(msd_history_receiver) * p->nrx, [&](uint32_t need) {
+                    if (need) /* (no byte: now_ms < 1000 and no aircraft was written) */
+                        msd_history_launch_store(p->stream, c, p->d_hist_lens.get(), p->d_hist_block.get(), p->d_w_out.get());
                 });
 }
 

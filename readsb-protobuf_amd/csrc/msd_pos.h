@@ -1,5 +1,6 @@
-/* msd_pos.h -- what msd_pos.cpp (the C-ABI of the position tracker) launches from msd_pos_kernels.hip and from its five
- * writers (msd_reduce_kernels.hip, msd_sbs_kernels.hip, msd_pb_kernels.hip, msd_vrs_kernels.hip, msd_range_kernels.hip).  Every function queues
+/* msd_pos.h -- what msd_pos.cpp (the C-ABI of the position tracker) launches from msd_pos_kernels.hip and from its six
+ * writers (msd_reduce_kernels.hip, msd_sbs_kernels.hip, msd_pb_kernels.hip, msd_vrs_kernels.hip, msd_range_kernels.hip,
+ * msd_history_kernels.hip).  Every function queues
  * kernels on `stream` and returns; all pointers are device memory.  The tables and the call structs are raw pointers
  * because kernels take them by value; msd_pos.cpp owns what they point into. */
 #ifndef MSD_POS_H
@@ -159,5 +160,21 @@ typedef struct msd_vrs_call {
 void msd_vrs_launch_lengths(hipStream_t stream, msd_vrs_call c, uint32_t live, uint32_t *first, uint32_t *items, uint16_t *lens,
                             uint16_t *swithin, uint32_t *within, uint32_t *sel_sums, uint32_t *byte_sums, msd_vrs_receiver *rx);
 void msd_vrs_launch_store(hipStream_t stream, msd_vrs_call c, const uint16_t *lens, const uint32_t *block_off, uint8_t *out);
+/* history_N.pb (msd_history_kernels.hip).  The items of a call are aircraft.pb's: the nrx file heads and the live aircraft
+ * in stream order (live + nrx of them; idx: the ordered slots).  lengths: first[0 .. nrx], items[], and per item lens (0:
+ * not written), within / cwithin (the exclusive prefixes inside its workgroup of 256: bytes, written aircraft);
+ * block_sums: two arrays of ceil(items / 256) + 1 words -- bytes, written --, the workgroups' offsets and then the total;
+ * rx: nrx rows.  store: the bytes to out (device memory, as many as block_sums' first total says).  Neither changes the
+ * table */
+typedef struct msd_history_call {
+    msd_pos_table t;
+    const uint32_t *idx; /* the ordered slots */
+    const uint32_t *items;
+    uint64_t now_ms;
+    uint32_t nitems, nrx;
+} msd_history_call;
+void msd_history_launch_lengths(hipStream_t stream, msd_history_call c, uint32_t live, uint32_t *first, uint32_t *items,
+                                uint8_t *lens, uint16_t *within, uint16_t *cwithin, uint32_t *block_sums, msd_history_receiver *rx);
+void msd_history_launch_store(hipStream_t stream, msd_history_call c, const uint8_t *lens, const uint32_t *block_off, uint8_t *out);
 
 #endif

@@ -20,6 +20,9 @@
 #                           asan only, run it as it is
 #   OUTDIR/vrs_units        tests/c/vrs_units.c: the VRS writer's printing and escaping (msd_vrs_impl.h, what the device
 #                           runs) against snprintf, and its objects against the host twin's; asan only, run it as it is
+#   OUTDIR/history_units    tests/c/history_units.c: the history_N.pb encoder (msd_history_impl.h, what the device runs) --
+#                           every varint length, length == bytes written, the longest entry -- and its entries against the
+#                           host twin's; asan only, run it as it is
 # Run the python tests against them with MSD_LIBMODES_HIP=OUTDIR/libmodes_hip.so and LD_PRELOAD=$(gcc -print-file-name=libasan.so)
 # (tests/test_sanitizers.py does).
 set -e
@@ -37,7 +40,7 @@ asan) SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omi
 tsan) SAN="-fsanitize=thread -fno-omit-frame-pointer"; CC=/opt/rocm/lib/llvm/bin/clang; CXX=/opt/rocm/lib/llvm/bin/clang++ ;;
 *) echo "usage: $0 asan|tsan OUTDIR" >&2; exit 2 ;;
 esac
-test -f msd_kernels.o -a -f msd_dc_kernels.o -a -f msd_resolve_kernels.o -a -f msd_frames_kernels.o -a -f msd_wire_kernels.o -a -f msd_avr_kernels.o -a -f msd_group_beast_kernels.o -a -f msd_group_avr_kernels.o -a -f msd_group_remote_out_kernels.o -a -f msd_pos_kernels.o -a -f msd_reduce_kernels.o -a -f msd_sbs_kernels.o -a -f msd_pb_kernels.o -a -f msd_vrs_kernels.o -a -f msd_range_kernels.o -a -f msd_capi.o -a -f msd_batch.o -a -f msd_collect.o -a -f msd_group.o -a -f msd_frames.o || { echo "run build.sh first (the HIP objects are reused)" >&2; exit 1; }
+test -f msd_kernels.o -a -f msd_dc_kernels.o -a -f msd_resolve_kernels.o -a -f msd_frames_kernels.o -a -f msd_wire_kernels.o -a -f msd_avr_kernels.o -a -f msd_group_beast_kernels.o -a -f msd_group_avr_kernels.o -a -f msd_group_remote_out_kernels.o -a -f msd_pos_kernels.o -a -f msd_reduce_kernels.o -a -f msd_sbs_kernels.o -a -f msd_pb_kernels.o -a -f msd_vrs_kernels.o -a -f msd_history_kernels.o -a -f msd_range_kernels.o -a -f msd_capi.o -a -f msd_batch.o -a -f msd_collect.o -a -f msd_group.o -a -f msd_frames.o || { echo "run build.sh first (the HIP objects are reused)" >&2; exit 1; }
 INC="-I. -I../../include -Ihost"
 CF="-std=c11 -O1 -g -Wall -Wextra -fPIC $SAN $INC"
 $CC $CF -ffp-contract=off -c msd_tables.c -o "$OUT/msd_tables.o"
@@ -60,13 +63,14 @@ CAPI_OBJ="$CAPI_OBJ $OUT/msd_frames.o $OUT/msd_group.o $OUT/msd_group_remote.o $
 # (the sanitizer runtime comes from LD_PRELOAD or from the instrumented executable: the shared objects leave it undefined)
 # (the wire writers are in both libraries, as in build.sh)
 $CC $CF -c host/msd_wire.c -o "$OUT/msd_wire.o"
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmodes_hip.so" msd_kernels.o msd_dc_kernels.o msd_resolve_kernels.o msd_frames_kernels.o msd_wire_kernels.o msd_avr_kernels.o msd_group_beast_kernels.o msd_group_avr_kernels.o msd_group_remote_out_kernels.o msd_pos_kernels.o msd_reduce_kernels.o msd_sbs_kernels.o msd_pb_kernels.o msd_vrs_kernels.o msd_range_kernels.o $CAPI_OBJ \
-    "$OUT/msd_tables.o" "$OUT/msd_resolve.o" "$OUT/msd_fields.o" "$OUT/msd_magbuf.o" "$OUT/msd_wire.o" -lm -lpthread
+$CC $CF -ffp-contract=off -c host/msd_receiver_pb.c -o "$OUT/msd_receiver_pb.o"
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmodes_hip.so" msd_kernels.o msd_dc_kernels.o msd_resolve_kernels.o msd_frames_kernels.o msd_wire_kernels.o msd_avr_kernels.o msd_group_beast_kernels.o msd_group_avr_kernels.o msd_group_remote_out_kernels.o msd_pos_kernels.o msd_reduce_kernels.o msd_sbs_kernels.o msd_pb_kernels.o msd_vrs_kernels.o msd_history_kernels.o msd_range_kernels.o $CAPI_OBJ \
+    "$OUT/msd_tables.o" "$OUT/msd_resolve.o" "$OUT/msd_fields.o" "$OUT/msd_magbuf.o" "$OUT/msd_wire.o" "$OUT/msd_receiver_pb.o" -lm -lpthread
 for f in msd_fifo msd_sdr_ifile msd_converter msd_demod; do
     $CC $CF -c host/$f.c -o "$OUT/$f.o"
 done
 $CC $CF -ffp-contract=off -c host/msd_pos_host.c -o "$OUT/msd_pos_host.o"
-$CC -shared -fPIC $SAN -o "$OUT/libmsd_host.so" "$OUT"/msd_pos_host.o "$OUT"/msd_fifo.o "$OUT"/msd_sdr_ifile.o "$OUT"/msd_wire.o "$OUT"/msd_converter.o "$OUT"/msd_demod.o \
+$CC -shared -fPIC $SAN -o "$OUT/libmsd_host.so" "$OUT"/msd_pos_host.o "$OUT"/msd_fifo.o "$OUT"/msd_sdr_ifile.o "$OUT"/msd_wire.o "$OUT"/msd_receiver_pb.o "$OUT"/msd_converter.o "$OUT"/msd_demod.o \
     -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
 $CC $CF host/msd_replay_main.c "$OUT"/msd_sdr_ifile.o "$OUT"/msd_fifo.o "$OUT"/msd_wire.o "$OUT"/msd_converter.o -o "$OUT/msd_replay" \
     -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
@@ -87,5 +91,7 @@ if [ "$MODE" = asan ]; then
         -o "$OUT/pb_units" -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
     $CC $CF -ffp-contract=off ../../tests/c/vrs_units.c "$OUT"/msd_pos_host.o \
         -o "$OUT/vrs_units" -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
+    $CC $CF -ffp-contract=off ../../tests/c/history_units.c "$OUT"/msd_pos_host.o \
+        -o "$OUT/history_units" -L"$OUT" -lmodes_hip -Wl,-rpath,'$ORIGIN' -lpthread -lm
 fi
 echo "sanitizer build ($MODE): $(ls "$OUT" | grep -v '\.o$' | tr '\n' ' ')"
