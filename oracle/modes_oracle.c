@@ -1781,9 +1781,15 @@ static void fields_mode_ac(orc_fields *mm, unsigned ModeA)
     }
 }
 
-/* the fields of one accepted Mode S message (msgtype 0..31), for known-answer tests */
+/* the fields of one accepted message, for known-answer tests: Mode S (msgtype 0..31), or a Mode A/C reply
+ * (msgtype 32) as the first of its buffer, with nothing carried */
 void orc_fields_of(const orc_message *mm, orc_fields *out)
 {
+    if (mm->msgtype == 32) {
+        memset(out, 0, sizeof *out);
+        fields_mode_ac(out, ((unsigned)mm->msg[0] << 8) | mm->msg[1]);
+        return;
+    }
     fields_mode_s(mm, out);
 }
 

@@ -16,6 +16,9 @@ percentages (lines executed, branches taken at least once).  Nothing is written 
     python scripts/stream_coverage.py -k random   passes further arguments to pytest
     python scripts/stream_coverage.py --writers   the device-only writers (msd_sbs / msd_vrs / msd_pb_impl.h) instead,
                                                   through tests/c/*_units.c and the records those programs make
+    python scripts/stream_coverage.py --fields    the field decoder (msd_fields_impl.h, compiled three times for the device
+                                                  and once for the host) instead: msd_fields.c alone, instrumented, fed the
+                                                  constructed families of tests/field_cases.py through msd_decode_fields
 """
 import argparse
 import os
@@ -133,13 +136,59 @@ def writers(tmp, extra):
             print("%s: no coverage data among %s" % (header, sorted(f for f in os.listdir(tmp) if f.endswith(".gcda"))))
 
 
+FIELDS_CHILD = """
+import ctypes, sys
+sys.path[:0] = [%(root)r, %(tests)r]
+import numpy as np
+import __graft_entry__ as g
+import field_cases as fc
+capi = g.load_package().capi
+lib = ctypes.CDLL(%(lib)r)
+lib.msd_decode_fields.restype = None
+out = np.zeros(1, dtype=capi.FIELDS_DTYPE)
+for letter in %(letters)r:
+    records, note = fc.build(capi.MESSAGE_DTYPE, letter)
+    records = np.ascontiguousarray(records)
+    for i in range(len(records)):
+        lib.msd_decode_fields(ctypes.c_void_p(records.ctypes.data + i * records.dtype.itemsize), None, ctypes.c_void_p(out.ctypes.data))
+    if letter == "f":  # and once as the replies of one buffer, each with the one before as its carry
+        carry = np.zeros(1, dtype=capi.FIELDS_DTYPE)
+        for i in range(len(records)):
+            lib.msd_decode_fields(ctypes.c_void_p(records.ctypes.data + i * records.dtype.itemsize),
+                                  ctypes.c_void_p(carry.ctypes.data) if i else None, ctypes.c_void_p(out.ctypes.data))
+            carry[:] = out
+    print("family %%s: %%d records -- %%s" %% (letter, len(records), note["what"]))
+"""
+
+
+def fields(tmp, letters):
+    """msd_fields.c alone, instrumented, as a library of its own; a child process sends the families' records through its
+    msd_decode_fields (the coverage data is written when that process ends)"""
+    must(["gcc"] + CFLAGS + ["-shared", os.path.join(CSRC, "msd_fields.c"), "-o", "libmsd_fields_cov.so", "-lpthread", "-lm"], cwd=tmp)
+    child = FIELDS_CHILD % dict(root=ROOT, tests=os.path.join(ROOT, "tests"), lib=os.path.join(tmp, "libmsd_fields_cov.so"),
+                                letters=letters or "abcdefg")
+    code, out = run([sys.executable, "-c", child], cwd=tmp, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
+    print(out.strip())
+    if code:
+        sys.exit("the child that feeds the families failed (%d)" % code)
+    gcda = [f for f in os.listdir(tmp) if f.endswith(".gcda")]
+    if not gcda:
+        sys.exit("the instrumented library wrote no coverage data")
+    report(gcov(tmp, gcda[0], ("msd_fields_impl.h",)), ("msd_fields_impl.h",))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--writers", action="store_true")
+    ap.add_argument("--fields", action="store_true")
+    ap.add_argument("--families", default="", help="with --fields: the letters of the families to send (default: all)")
     args, extra = ap.parse_known_args()
     with tempfile.TemporaryDirectory(prefix="stream_coverage_") as tmp:
         if args.writers:
             writers(tmp, extra)
+            return
+        if args.fields:
+            fields(tmp, args.families)
             return
         build_twin(tmp)
         run_tests(tmp, extra)
